@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: body-body interactions/sec of the all-pairs step at N = 2^20 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself (a torch.distributed.run child,
@@ -10,11 +10,19 @@ before this process touches a GPU) and relays rank 0's line; it exits non-zero i
 A "step" is one pass of the hot path (the forces of all N x N ordered body-body interactions + kick-drift
 update) over one synthetic Plummer-sphere state resident in HBM.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else this script measures or
+checks: the energy / replica sanity checks around the timed region, the extra legs (the other force mode, the general-mass
+path, the other body order, the reference's N = 20000, the peer-copy leg) and the CPU baseline; --no-cpu-baseline,
+--no-extra-legs and --no-sanity leave parts of it out again.
+--dump-outputs DIR writes what the timed path computed in its last step -- the state a caller downloads, in the caller's body
+order -- as DIR/positions.npy and DIR/velocities.npy (float32, (N, 4); above 64 MB in all, the same seeded sample of rows of
+both).  The inputs depend only on the arguments (a seeded Plummer sphere), so two builds can be compared output for output.
+
 * value     = N^2 * K / wall time of K steps (max over ranks, barrier + synchronize on both sides).
 * --force-mode pair_once (default): nbody::force_sym_kernel evaluates each unordered pair once and applies it to
               both bodies (the reference's own VERSION 3 idea, kernel.cu:703-774, without atomics); one_sided:
-              nbody::force_kernel_r4 evaluates every ordered interaction.  Both on 1..8 GPUs; at N = 1 the other mode
-              is timed too and reported in "other_force_mode".
+              nbody::force_kernel_r4 evaluates every ordered interaction.  Both on 1..8 GPUs; at N = 1 with --full the
+              other mode is timed too and reported in "other_force_mode".
 * roofline  = the dominant force kernel against the fp32 vector peak: 20 flop x the pair evaluations one
               launch EXECUTES / its HIP-event duration, measured in this run on the stream the kernel runs on.  For the
               pair-once kernel that is half the ordered interactions it accounts for -- no 2x credit (SURVEY.md 8d);
@@ -22,14 +30,15 @@ update) over one synthetic Plummer-sphere state resident in HBM.  Rank 0 prints 
               under their own names.  "traffic" is the HBM bytes per launch from the committed rocprofv3 PMC summary
               when one exists for this kernel and size, else null.
 * cpu_baseline = the CPU oracle's scalar all-pairs loop (a port; the reference has no CPU path), timed on this
-              host's cores on a row slab of the same workload (N = 1 run only).
+              host's cores on a row slab of the same workload (N = 1 run with --full only).
 Multi-GPU: total N is fixed, rows are sharded over the ranks => "scaling": "strong".  With the nccl backend (the product
 path) every per-step exchange runs inside the library (nbody_multi_*, csrc/nbody_multi.hip: RCCL all-gather or ring);
 torch.distributed carries the RCCL id at start-up, the barriers and the max over ranks of the elapsed time.  The line then
 carries "per_rank" (every rank's kernels, exchange times and host enqueue time per step, from the library's own events) and
-"peer_copy_leg" (the same job from one process with hipMemcpyPeerAsync instead of RCCL, run in a child process after the
-ranks are done).  A rank whose exchange does not arrive within --exchange-timeout seconds (60) prints ONE JSON line with
-"error" and exits non-zero.  --transport peer_copy runs that secondary measurement as the main one (no launcher, no RCCL).
+with --full "peer_copy_leg" (the same job from one process with hipMemcpyPeerAsync instead of RCCL, run in a child process
+after the ranks are done).  A rank whose exchange does not arrive within --exchange-timeout seconds (60) prints ONE JSON
+line with "error" and exits non-zero.  --transport peer_copy runs that secondary measurement as the main one (no launcher,
+no RCCL).
 """
 import argparse
 import glob
@@ -211,6 +220,21 @@ def committed_traffic(n, kernel):
     return best
 
 
+def dump_outputs(out_dir, state, limit_bytes=64 << 20):
+    """positions.npy and velocities.npy (float32, the caller's body order); above limit_bytes in all, the same rows of both,
+    drawn once with a fixed seed, so that two runs with the same arguments write the same bodies."""
+    pos, vel = state
+    rows = pos.shape[0]
+    if pos.nbytes + vel.nbytes > limit_bytes:
+        keep = limit_bytes // (pos.itemsize * pos.shape[1] + vel.itemsize * vel.shape[1])
+        idx = np.sort(np.random.default_rng(20240).choice(rows, size=keep, replace=False))
+        pos, vel = pos[idx], vel[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "positions.npy"), np.ascontiguousarray(pos, dtype=np.float32))
+    np.save(os.path.join(out_dir, "velocities.npy"), np.ascontiguousarray(vel, dtype=np.float32))
+    log(f"bench.py: wrote {pos.shape[0]} of {rows} bodies' positions and velocities to {out_dir}")
+
+
 def forwarded_args(argv):
     """The command line as the rank processes get it behind torch.distributed.run: argparse checks every "--x" on the line
     against the launcher's own options before it reaches the script's, and "--n" is an ambiguous prefix there ("--nnodes",
@@ -372,7 +396,13 @@ def main():
                          "reductions of this script (gloo = NBODY_RENDEZVOUS=gloo: rehearsals with several ranks on one GPU); "
                          "every per-step exchange is the library's own RCCL call")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sanity checks, the extra legs and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step to DIR/positions.npy and DIR/velocities.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra_legs = args.no_sanity = True
     mode = "pair_once" if args.force_mode == "symmetric" else args.force_mode
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -482,6 +512,10 @@ def main():
         local_tm = read_timing()
         tm = local_tm[0]
         (system if library_exchange else kernels).timing(False)
+        if args.dump_outputs:
+            final = system.download()          # collective with the library-owned exchange: every rank downloads
+            if rank == 0:
+                dump_outputs(args.dump_outputs, final)
         per_rank = [dict(rank=rank + i, **per_step(t, args.steps)) for i, t in enumerate(local_tm)]
         if distributed:
             gathered = [None] * world

@@ -68,3 +68,28 @@ def test_error_line_and_per_rank_shape():
     per = bench.per_step(tm, 20)
     assert per["force_ms"] == 20.0 and per["force_launches_per_step"] == 2.0 and per["host_enqueue_ms"] == 0.12
     assert per["column_sum_exchange_ms"] == 0.25 and per["pos_exchange_wait_ms"] == 0.02
+
+
+def test_dump_outputs_writes_float32_state_and_a_seeded_sample_above_the_limit(tmp_path):
+    """--dump-outputs: the whole state when it fits in the limit; above it, the same seeded rows of positions and velocities,
+    so that two runs with the same arguments write the same bodies."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    pos, vel = rng.standard_normal((1000, 4)).astype(np.float32), rng.standard_normal((1000, 4)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), (pos, vel))
+    p, v = np.load(tmp_path / "whole" / "positions.npy"), np.load(tmp_path / "whole" / "velocities.npy")
+    assert p.dtype == v.dtype == np.float32 and np.array_equal(p, pos) and np.array_equal(v, vel)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), (pos, vel), limit_bytes=8000)
+    p, v = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "a" / "velocities.npy")
+    assert p.shape == v.shape == (250, 4) and p.nbytes + v.nbytes <= 8000
+    rows = [int(np.flatnonzero((pos == r).all(axis=1))[0]) for r in p]
+    assert rows == sorted(rows) and np.array_equal(vel[rows], v)              # the same bodies in both arrays
+    assert np.array_equal(np.load(tmp_path / "b" / "positions.npy"), p)       # and the same sample every run
+
+
+def test_plain_run_options():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout

@@ -8,8 +8,6 @@ import pytest
 from n_body_problem_amd import datasets as ds
 from n_body_problem_amd import initial_conditions as ic
 
-REF_DATA = "/root/reference/main_project/data"
-
 
 def sample(n=37):
     pos, vel = ic.uniform_cube(n, seed=77, random_masses=True, speed=0.3)
@@ -59,23 +57,23 @@ def test_snapshot_round_trip(tmp_path):
         ds.load_snapshot(f)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's data files are not on this machine")
-def test_reference_files_known_answers():
+def test_reference_files_known_answers(golden_dir):
     """F4 of SURVEY.md 8c: galaxy_20K.bin parsed with the reference's structs equals its own CSV dump
-    (unused_files/tool.cpp wrote galaxy_20k.csv from that file)."""
-    pos, vel = ds.load_reference_dataset(0, REF_DATA)
+    (unused_files/tool.cpp wrote galaxy_20k.csv from that file; galaxy_20k_sample.csv holds its rows by index).  The
+    reference's data files are the committed fixtures of tests/golden, byte for byte (tests/golden/README.md)."""
+    pos, vel = ds.load_reference_dataset(0, golden_dir)
     assert pos.shape == (20000, 4)
-    rows = list(csv.reader(open(os.path.join(REF_DATA, "galaxy_20k.csv"))))[1:]
-    assert len(rows) == 20000
+    rows = {int(r[0]): r[1:] for r in list(csv.reader(open(os.path.join(golden_dir, "galaxy_20k_sample.csv"))))[1:]}
+    assert max(rows) == 19999                                  # the dump's last row: 20000 rows
     for i in (0, 1, 2, 2499, 2500, 19999):
         want = np.array([float(x) for x in rows[i][1:]])      # x,y,z,mass,vx,vy,vz,eps
         got = np.array([*pos[i, :3], pos[i, 3], *vel[i, :3], vel[i, 3]], dtype=np.float64)
         assert np.allclose(got, want, rtol=1e-5, atol=1e-12), i   # the CSV keeps 6 significant digits
-    p, v = ds.load_reference_dataset(3, REF_DATA)              # stars.dat: "z y x vz vy vx", mass 1
-    first = [float(x) for x in open(os.path.join(REF_DATA, "stars.dat")).readline().split()]
+    p, v = ds.load_reference_dataset(3, golden_dir)            # stars.dat: "z y x vz vy vx", mass 1
+    first = [float(x) for x in open(os.path.join(golden_dir, "stars.dat")).readline().split()]
     assert np.allclose(p[0, :3], first[2::-1], rtol=1e-6) and np.allclose(v[0, :3], first[5:2:-1], rtol=1e-6)
     assert p.shape[0] == 43802 and np.all(p[:, 3] == 1)      # 43837 lines, 35 records wrapped over two lines
-    p, v = ds.load_reference_dataset(5, REF_DATA)              # k17hp.snap through the .snap parser
+    p, v = ds.load_reference_dataset(5, golden_dir)            # k17hp.snap through the .snap parser
     assert p.shape == (10002, 4) and p[0, 3] == pytest.approx(2e-4)
     assert ic.padded_count(20000) == 20225                     # the count the reference hard-codes at kernel.cu:1130
 
@@ -98,8 +96,8 @@ def test_committed_galaxy_file_against_the_reference_csv_rows(golden_dir):
 
 def test_committed_k17hp_and_stars_fixtures(golden_dir):
     """The two further inputs of load_data that travel with the repo (tests/golden/README.md): k17hp.snap whole, the first
-    8192 records of stars.dat.  Known answers read off the files' own text; where the reference is on this machine, the
-    fixtures are its bytes / its tokens."""
+    8192 records of stars.dat.  Known answers read off the files' own text; the fixtures are the reference's bytes (the
+    sha256 of its files, tests/golden/README.md) and its tokens."""
     import hashlib
     p, v = ds.read_any(os.path.join(golden_dir, "k17hp.snap"))
     assert p.shape == (10002, 4) and np.all(p[:, 3] == np.float32(2e-4)) and np.isclose(p[:, 3].sum(dtype=np.float64), 2.0004, rtol=1e-6)
@@ -121,10 +119,8 @@ def test_committed_k17hp_and_stars_fixtures(golden_dir):
     assert np.array_equal(whole[:8192], p) and np.array_equal(wv[:8192], v)
     assert hashlib.sha256(open(os.path.join(golden_dir, "stars.dat"), "rb").read()).hexdigest() == \
         "836bb3b21b91c71343e49f612ff10c6e79091995d41d0f79df178dd4fd5b9556"
-    if os.path.isdir(REF_DATA):
-        sha = lambda f: hashlib.sha256(open(f, "rb").read()).hexdigest()
-        assert sha(os.path.join(golden_dir, "stars.dat")) == sha(os.path.join(REF_DATA, "stars.dat"))
-        assert sha(os.path.join(golden_dir, "k17hp.snap")) == sha(os.path.join(REF_DATA, "k17hp.snap"))
-        assert sha(os.path.join(golden_dir, "k17c.snap")) == sha(os.path.join(REF_DATA, "k17c.snap"))
-        full, _ = ds.read_dat(os.path.join(REF_DATA, "stars.dat"))
-        assert np.array_equal(full[:8192], p)
+    sha = lambda f: hashlib.sha256(open(os.path.join(golden_dir, f), "rb").read()).hexdigest()
+    assert sha("k17hp.snap") == "08dc01a7f747ea5dbeee762dc034d1685b6f86f1bd751b563af73e969d548b90"
+    assert sha("k17c.snap") == "bef342187cef739530ee93081a1ad8135b1e90be284d7f5dd798d1777dabeab5"
+    full, _ = ds.read_dat(os.path.join(golden_dir, "stars.dat"))
+    assert np.array_equal(full[:8192], p)

@@ -162,7 +162,7 @@ def test_bench_ranks_under_torchrun_with_the_rendezvous_on_gloo(fake_library):
     env = dict(os.environ, NBODY_AMD_LIBRARY=fake_library, NBODY_RENDEZVOUS="gloo", FAKE_RCCL_SLOT_MB="64")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--bodies",
-           "65536", "--single-device", "--no-extra-legs"]
+           "65536", "--single-device", "--full", "--no-extra-legs"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [json.loads(x) for x in res.stdout.splitlines() if x.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-4000:]
