@@ -456,6 +456,45 @@ nbody_ctx *nbody_multi_shard(nbody_multi *m, int local_index);
 float *nbody_multi_positions_device(nbody_multi *m, int local_index);
 float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
 
+/* ======== batched ensembles: many independent small systems, one launch (csrc/nbody_batch.hip) ========
+ * Everything above steps ONE system.  Below NBODY_BATCH_MAX_BODIES bodies one system cannot fill the GPU -- a 256- or
+ * 4096-body step is ~0.02 ms of almost pure launch overhead -- while ensemble users (realisations of a cluster, parameter
+ * sweeps, stability surveys, training data) want many such systems.  A nbody_batch steps B independent systems of up to
+ * max_bodies bodies each; system s has its own count n_s <= max_bodies (nbody_batch_set_counts; default: all max_bodies).
+ * Buffers: caller-owned device arrays of B x max_bodies float4, system s at [s * max_bodies, s * max_bodies + n_s):
+ * positions {x, y, z, mass}, velocities {vx, vy, vz, w} (w preserved), both updated in place.  Slots n_s .. max_bodies - 1
+ * are never read and never written; a system with n_s = 0 is left alone.  The handle owns the counts, the kick-drift-kick
+ * acceleration cache (B x max_bodies float4) and a stream.
+ * Kernel: one workgroup per system, its positions in LDS (64 KiB at 4096 bodies: two workgroups per CU), rows in registers;
+ * the k steps of a call run inside one launch with the state on chip (a long k is cut into launches of 128 steps: the same
+ * bits).  Numerics: the pair term and the update of nbody_step; each row sums its columns j = 0 .. n_s - 1 in ascending
+ * order in one fp32 chain per component, so a system's result depends on that system alone -- not on its slot, on B, on
+ * max_bodies or on the other systems -- and step_n(k) is k x step_n(1) bit for bit, both integrators.  No atomics.
+ * Softening: nbody_step's rule (0 allowed -- zero-distance pairs then contribute nothing --, 0 < eps < NBODY_MIN_SOFTENING
+ * rejected).  Integrators: nbody_set_integrator's; the KDK cache is forgotten on new counts, another softening, other
+ * buffers, another integrator or nbody_batch_invalidate_forces (new contents in the same buffers need that call).
+ * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
+ * [1, NBODY_BATCH_MAX_BODIES], counts outside [0, max_bodies], k < 0, a non-finite dt, the softening rule, NULL pointers.
+ * nbody_batch_step_n_on returns with the work complete, _async only enqueues (nbody_batch_sync waits).  Diagnostics are
+ * synchronous, per system, with the definitions of nbody_energy / nbody_momentum: out3B[3s..3s+2] = {kinetic, potential,
+ * total}, out4B[4s..4s+3] = {px, py, pz, mass}. */
+#define NBODY_BATCH_MAX_BODIES 4096
+typedef struct nbody_batch nbody_batch;
+int nbody_batch_create(nbody_batch **out, int device, int64_t n_systems, int64_t max_bodies);
+int nbody_batch_destroy(nbody_batch *b);
+const char *nbody_batch_last_error(const nbody_batch *b); /* b == NULL: last error of a failed create or a NULL handle */
+int nbody_batch_set_counts(nbody_batch *b, const int64_t *host_counts); /* n_systems values in [0, max_bodies] */
+int nbody_batch_set_integrator(nbody_batch *b, int integrator);
+int nbody_batch_invalidate_forces(nbody_batch *b);
+int nbody_batch_set_stream(nbody_batch *b, void *hip_stream); /* verbatim, as nbody_set_stream: NULL = the default stream */
+int nbody_batch_step_n_on(nbody_batch *b, float *d_positions_xyzm, float *d_velocities_xyzw, int k, float dt, float softening);
+int nbody_batch_step_n_async(nbody_batch *b, float *d_positions_xyzm, float *d_velocities_xyzw, int k, float dt,
+                             float softening);
+int nbody_batch_sync(nbody_batch *b);
+int nbody_batch_energy(nbody_batch *b, const float *d_positions_xyzm, const float *d_velocities_xyzw, float softening,
+                       double *out3B);
+int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const float *d_velocities_xyzw, double *out4B);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,4 +256,74 @@ private:
     std::int64_t n_ = 0;
 };
 
+// B independent systems of up to maxBodies (<= NBODY_BATCH_MAX_BODIES) bodies stepped together (nbody_batch_*): the state
+// lives in caller-owned device arrays of B x maxBodies float4, system s at [s * maxBodies, s * maxBodies + counts[s]).
+class Batch {
+public:
+    Batch() = default;
+    Batch(std::int64_t numSystems, std::int64_t maxBodies, int device = 0) { create(numSystems, maxBodies, device); }
+    Batch(const Batch &) = delete;
+    Batch &operator=(const Batch &) = delete;
+    ~Batch() { nbody_batch_destroy(b_); }
+
+    void create(std::int64_t numSystems, std::int64_t maxBodies, int device = 0)
+    {
+        nbody_batch_destroy(b_);
+        b_ = nullptr;
+        check(nbody_batch_create(&b_, device, numSystems, maxBodies), "nbody_batch_create");
+        systems_ = numSystems;
+        maxBodies_ = maxBodies;
+    }
+    void setCounts(const std::vector<std::int64_t> &counts)
+    {
+        if ((std::int64_t)counts.size() != systems_)
+            throw std::runtime_error("Batch::setCounts: one count per system");
+        check(nbody_batch_set_counts(b_, counts.data()), "nbody_batch_set_counts");
+    }
+    void kickDriftKick(bool on)
+    {
+        check(nbody_batch_set_integrator(b_, on ? NBODY_INTEGRATOR_KDK : NBODY_INTEGRATOR_KICK_DRIFT), "nbody_batch_set_integrator");
+    }
+    void invalidateForces() { check(nbody_batch_invalidate_forces(b_), "nbody_batch_invalidate_forces"); }
+    void setStream(void *hipStream) { check(nbody_batch_set_stream(b_, hipStream), "nbody_batch_set_stream"); }
+    // k steps on the device arrays; returns with the work complete (stepNAsync: enqueued only, sync() waits)
+    void stepN(float *dPositions, float *dVelocities, int k, float dt = kTimeTick, float softening = kSofteningVersion3)
+    {
+        check(nbody_batch_step_n_on(b_, dPositions, dVelocities, k, dt, softening), "nbody_batch_step_n_on");
+    }
+    void stepNAsync(float *dPositions, float *dVelocities, int k, float dt = kTimeTick, float softening = kSofteningVersion3)
+    {
+        check(nbody_batch_step_n_async(b_, dPositions, dVelocities, k, dt, softening), "nbody_batch_step_n_async");
+    }
+    void sync() { check(nbody_batch_sync(b_), "nbody_batch_sync"); }
+    // per system {kinetic, potential, total} and {px, py, pz, mass}
+    std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
+    {
+        std::vector<double> e(3 * (size_t)systems_);
+        check(nbody_batch_energy(b_, dPositions, dVelocities, softening, e.data()), "nbody_batch_energy");
+        std::vector<System::Energy> out((size_t)systems_);
+        for (size_t s = 0; s < out.size(); ++s)
+            out[s] = {e[3 * s], e[3 * s + 1], e[3 * s + 2]};
+        return out;
+    }
+    std::vector<double> momentum(const float *dPositions, const float *dVelocities)
+    {
+        std::vector<double> p(4 * (size_t)systems_);
+        check(nbody_batch_momentum(b_, dPositions, dVelocities, p.data()), "nbody_batch_momentum");
+        return p;
+    }
+    std::int64_t numSystems() const { return systems_; }
+    std::int64_t maxBodies() const { return maxBodies_; }
+    nbody_batch *handle() { return b_; }
+
+private:
+    void check(int status, const char *what)
+    {
+        if (status != NBODY_OK)
+            throw std::runtime_error(std::string(what) + ": " + nbody_batch_last_error(b_) + " (" + nbody_status_string(status) + ")");
+    }
+    nbody_batch *b_ = nullptr;
+    std::int64_t systems_ = 0, maxBodies_ = 0;
+};
+
 }  // namespace nbody

@@ -121,6 +121,19 @@ _PROTOTYPES = {
     "nbody_multi_shard": (c_void_p, [c_void_p, c_int]),
     "nbody_multi_positions_device": (c_void_p, [c_void_p, c_int]),
     "nbody_multi_velocities_device": (c_void_p, [c_void_p, c_int]),
+    # batched ensembles (csrc/nbody_batch.hip)
+    "nbody_batch_create": (c_int, [POINTER(c_void_p), c_int, c_int64, c_int64]),
+    "nbody_batch_destroy": (c_int, [c_void_p]),
+    "nbody_batch_last_error": (c_char_p, [c_void_p]),
+    "nbody_batch_set_counts": (c_int, [c_void_p, POINTER(c_int64)]),
+    "nbody_batch_set_integrator": (c_int, [c_void_p, c_int]),
+    "nbody_batch_invalidate_forces": (c_int, [c_void_p]),
+    "nbody_batch_set_stream": (c_int, [c_void_p, c_void_p]),
+    "nbody_batch_step_n_on": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float]),
+    "nbody_batch_step_n_async": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float]),
+    "nbody_batch_sync": (c_int, [c_void_p]),
+    "nbody_batch_energy": (c_int, [c_void_p, c_void_p, c_void_p, c_float, POINTER(c_double)]),
+    "nbody_batch_momentum": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double)]),
 }
 
 

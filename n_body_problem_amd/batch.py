@@ -1,0 +1,172 @@
+"""Batched ensembles: many independent small systems stepped together, one launch per call (``nbody_batch_*`` of
+``include/nbody.h``, kernels in ``csrc/nbody_batch.hip``).
+
+One :class:`NBodySystem` below a few thousand bodies cannot fill the GPU: its step is ~0.02 ms of launch overhead.  A
+:class:`BatchedSystem` holds ``B`` systems of up to ``max_bodies`` (at most :data:`BATCH_MAX_BODIES`) bodies each -- system
+``s`` has ``counts[s]`` bodies -- and steps them all in one workgroup per system, ``k`` steps per launch.  A system's result
+depends on that system alone (its slot, ``B``, ``max_bodies`` and the other systems change no bit).  Device memory and the
+stream come from PyTorch-ROCm; the arithmetic is the HIP kernels'.  There is no CPU or PyTorch fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import NBodyError
+from .system import SOFTENING_VERSION3, TIME_TICK, _ptr, _torch
+
+#: NBODY_BATCH_MAX_BODIES: the largest system a batch holds (64 KiB of positions in LDS); larger ones belong to NBodySystem
+BATCH_MAX_BODIES = 4096
+INTEGRATORS = {"kick_drift": 0, "kdk": 1}
+
+
+def _check(lib, status: int, handle) -> None:
+    if status != _lib.NBODY_OK:
+        msg = lib.nbody_batch_last_error(handle) or b""
+        raise NBodyError(status, msg.decode("utf-8", "replace") or lib.nbody_status_string(status).decode())
+
+
+class BatchedSystem:
+    """``num_systems`` independent systems of up to ``max_bodies`` bodies on one GPU.
+
+    ``positions`` / ``velocities`` are ``(B, max_bodies, 4)`` float32 device tensors used by the kernels in place (zero
+    copy): ``positions[s, i] = {x, y, z, mass}``, ``velocities[s, i] = {vx, vy, vz, w}`` (``w`` preserved).  Slots
+    ``i >= counts[s]`` are never read or written.  ``integrator``: ``"kick_drift"`` (the reference's scheme) or ``"kdk"``
+    (velocity Verlet with the accelerations cached across calls).
+    """
+
+    def __init__(self, num_systems: int, max_bodies: int, device: int = 0, counts=None, integrator: str = "kick_drift"):
+        if integrator not in INTEGRATORS:
+            raise ValueError(f"integrator must be one of {tuple(INTEGRATORS)}")
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p(None)
+        h = ctypes.c_void_p(None)
+        _check(self._lib, self._lib.nbody_batch_create(ctypes.byref(h), int(device), int(num_systems), int(max_bodies)), None)
+        self._h = h
+        torch = _torch()
+        if not torch.cuda.is_available():
+            self.close()
+            raise NBodyError(_lib.NBODY_ERR_NO_DEVICE, "no HIP device visible to PyTorch; there is no CPU path")
+        self.num_systems, self.max_bodies = int(num_systems), int(max_bodies)
+        self.device = torch.device("cuda", int(device))
+        self.positions = torch.zeros((self.num_systems, self.max_bodies, 4), dtype=torch.float32, device=self.device)
+        self.velocities = torch.zeros_like(self.positions)
+        self._counts = np.full(self.num_systems, self.max_bodies, dtype=np.int64)
+        self.integrator = "kick_drift"
+        self.set_integrator(integrator)
+        if counts is not None:
+            self.set_counts(counts)
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.nbody_batch_destroy(self._h)
+            self._h = ctypes.c_void_p(None)
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _use_current_stream(self) -> None:
+        s = _torch().cuda.current_stream(self.device).cuda_stream
+        _check(self._lib, self._lib.nbody_batch_set_stream(self._h, ctypes.c_void_p(s)), self._h)
+
+    # -- configuration -----------------------------------------------------------------------
+    @property
+    def counts(self) -> np.ndarray:
+        """Bodies per system (a copy)."""
+        return self._counts.copy()
+
+    def set_counts(self, counts) -> None:
+        """``B`` body counts in ``[0, max_bodies]``; forgets the cached KDK accelerations."""
+        c = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+        if c.shape[0] != self.num_systems:
+            raise ValueError(f"expected {self.num_systems} counts, got {c.shape[0]}")
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_set_counts(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._h)
+        self._counts = c.copy()
+
+    def set_integrator(self, name: str) -> None:
+        if name not in INTEGRATORS:
+            raise ValueError(f"integrator must be one of {tuple(INTEGRATORS)}")
+        _check(self._lib, self._lib.nbody_batch_set_integrator(self._h, INTEGRATORS[name]), self._h)
+        self.integrator = name
+
+    def invalidate_forces(self) -> None:
+        """Forget the cached KDK accelerations (after editing ``positions`` in place)."""
+        _check(self._lib, self._lib.nbody_batch_invalidate_forces(self._h), self._h)
+
+    # -- state -------------------------------------------------------------------------------
+    def set_state(self, pos, vel, counts=None) -> None:
+        """Copy ``(B, n, 4)`` positions and velocities (numpy or torch, ``n <= max_bodies``) into slots ``[0, n)`` of every
+        system; ``counts`` (optional) sets the body counts first.  Every count must be at most ``n``.  Forgets the cached
+        KDK accelerations."""
+        torch = _torch()
+        p = torch.as_tensor(np.asarray(pos) if not isinstance(pos, torch.Tensor) else pos, dtype=torch.float32)
+        v = torch.as_tensor(np.asarray(vel) if not isinstance(vel, torch.Tensor) else vel, dtype=torch.float32)
+        if p.dim() != 3 or p.shape[0] != self.num_systems or p.shape[2] != 4 or p.shape[1] > self.max_bodies:
+            raise ValueError(f"positions must have shape ({self.num_systems}, n <= {self.max_bodies}, 4), got {tuple(p.shape)}")
+        if tuple(v.shape) != tuple(p.shape):
+            raise ValueError(f"velocities must have the shape of the positions {tuple(p.shape)}, got {tuple(v.shape)}")
+        if counts is not None:
+            self.set_counts(counts)
+        n = p.shape[1]
+        if int(self._counts.max(initial=0)) > n:
+            raise ValueError(f"a system has more bodies ({int(self._counts.max())}) than set_state provides ({n}): set_counts first")
+        self._use_current_stream()
+        self.positions[:, :n].copy_(p.to(self.device), non_blocking=False)
+        self.velocities[:, :n].copy_(v.to(self.device), non_blocking=False)
+        self.invalidate_forces()
+
+    def download(self):
+        """``(positions, velocities)`` as ``(B, max_bodies, 4)`` float32 numpy arrays (waits for the queued steps)."""
+        self._use_current_stream()
+        self.sync()
+        return self.positions.cpu().numpy(), self.velocities.cpu().numpy()
+
+    # -- stepping ----------------------------------------------------------------------------
+    def step_n(self, k: int, dt: float = TIME_TICK, softening: float = SOFTENING_VERSION3) -> None:
+        """``k`` steps of every system, enqueued on torch's current stream (one launch per 128 steps)."""
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_step_n_async(self._h, _ptr(self.positions), _ptr(self.velocities), int(k),
+                                                             float(dt), float(softening)), self._h)
+
+    def sync(self) -> None:
+        """Wait for the queued work and report a kernel failure."""
+        _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
+
+    # -- diagnostics -------------------------------------------------------------------------
+    def energy(self, softening: float) -> np.ndarray:
+        """``(B, 3)``: per system ``[kinetic, potential, total]`` (fp32 pair terms, fp64 sums; ``nbody_energy``'s definition)."""
+        self._use_current_stream()
+        out = np.zeros((self.num_systems, 3), dtype=np.float64)
+        _check(self._lib, self._lib.nbody_batch_energy(self._h, _ptr(self.positions), _ptr(self.velocities), float(softening),
+                                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), self._h)
+        return out
+
+    def momentum(self) -> np.ndarray:
+        """``(B, 4)``: per system ``[px, py, pz, mass]`` (fp64)."""
+        self._use_current_stream()
+        out = np.zeros((self.num_systems, 4), dtype=np.float64)
+        _check(self._lib, self._lib.nbody_batch_momentum(self._h, _ptr(self.positions), _ptr(self.velocities),
+                                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), self._h)
+        return out
+
+
+def interactions_per_step(counts) -> int:
+    """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention)."""
+    c = np.asarray(counts, dtype=np.int64)
+    return int((c * c).sum())
+
+
+__all__ = ["BatchedSystem", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

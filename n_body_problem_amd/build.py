@@ -13,7 +13,7 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
-SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip"]
+SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(PKG_DIR, "..", "include", "nbody.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
@@ -37,7 +37,8 @@ def is_stale() -> bool:
 
 #: per-source extra flags.  The force kernels are built without SLP vectorisation: v_pk_*_f32 buys nothing on gfx950
 #: (4 cycles for two lanes' worth) and the packing moves break their hand-ordered instruction phases.
-EXTRA_FLAGS = {"nbody_symmetric.hip": ["-fno-slp-vectorize"], "nbody_kernels.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"nbody_symmetric.hip": ["-fno-slp-vectorize"], "nbody_kernels.hip": ["-fno-slp-vectorize"],
+               "nbody_batch.hip": ["-fno-slp-vectorize"]}
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:

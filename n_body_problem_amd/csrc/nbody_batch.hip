@@ -1,0 +1,536 @@
+// nbody_batch.hip -- batched ensembles (include/nbody.h, nbody_batch_*): B independent systems of up to
+// NBODY_BATCH_MAX_BODIES bodies each, stepped together, ONE workgroup per system, k steps per launch with the system's
+// state resident on chip.  HBM is read at the start of a launch and written at its end; between the steps of a launch the
+// positions live in LDS (the column side, read by broadcast) and in registers (the row side, with velocities and
+// accelerations).
+//
+// Summation order (what makes every result a function of the system alone): row i of a system of n_b bodies sums its
+// columns j = 0 .. n_b - 1 in ascending order in ONE fp32 FMA chain per component, the self pair included (it adds exactly
+// 0 for eps > 0, and the guard drops it for eps = 0).  Neither the slot of the system, nor B, nor max_bodies (which picks
+// rows per lane and workgroup size), nor any other system changes a bit.  The pair term is the one of force_kernel
+// (nbody_kernels.hip): d = x_j - x_i, r^2 + eps^2 by an FMA chain, v_rsq_f32, s = (m_j inv) (inv inv), a = fma(d, s, a).
+// The update is update_kernel's: v <- (float)fma((double)a, (double)dt, (double)v), x <- (float)fma((double)v, ...).
+#include "../../include/nbody.h"
+#include "nbody_kernels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace nbody {
+namespace {
+
+static_assert(NBODY_BATCH_MAX_BODIES == 4096, "64 KiB of LDS per workgroup: two workgroups on a CU's 160 KiB");
+
+// Steps per launch at most: a long k is cut into launches of this many steps.  The state goes through HBM between them as
+// the same fp32 bits (the KDK accelerations through the handle's cache), so the cut changes nothing.
+constexpr int kBatchStepsPerLaunch = 128;
+
+// Workgroup shape for a capacity: rows per lane and threads.  Small systems keep a whole wave busy (one or two rows per
+// lane); from 129 bodies on four rows per lane feed on every broadcast LDS read, 64 threads per 256 bodies (4096 bodies:
+// 1024 threads, 16 waves).
+struct BatchShape {
+    int rpl, threads;
+};
+inline BatchShape batch_shape(int max_bodies)
+{
+    if (max_bodies <= 64)
+        return {1, 64};
+    if (max_bodies <= 128)
+        return {2, 64};
+    return {4, (max_bodies + 255) / 256 * 64};
+}
+
+// Accelerations of the lane's RPL rows from the n columns in LDS, ascending j, one chain per row and component.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void batch_forces(const float4 *sp, int n, const float4 (&x)[RPL], float eps2, float (&ax)[RPL],
+                                             float (&ay)[RPL], float (&az)[RPL])
+{
+#pragma unroll
+    for (int k = 0; k < RPL; ++k)
+        ax[k] = ay[k] = az[k] = 0.f;
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = sp[j];  // wave-uniform address: broadcast ds_read_b128
+#pragma unroll
+        for (int k = 0; k < RPL; ++k) {
+            const float dx = pj.x - x[k].x, dy = pj.y - x[k].y, dz = pj.z - x[k].z;
+            float r2 = __builtin_fmaf(dx, dx, eps2);
+            r2 = __builtin_fmaf(dy, dy, r2);
+            r2 = __builtin_fmaf(dz, dz, r2);
+            if (GUARD)  // eps == 0: a pair at zero distance (the self pair) contributes 0
+                r2 = guard_r2(r2);
+            const float inv = __builtin_amdgcn_rsqf(r2);
+            const float s = (pj.w * inv) * (inv * inv);
+            ax[k] = __builtin_fmaf(dx, s, ax[k]);
+            ay[k] = __builtin_fmaf(dy, s, ay[k]);
+            az[k] = __builtin_fmaf(dz, s, az[k]);
+        }
+    }
+}
+
+// kick v += a h, drift x += v h: fp64 FMA rounded to fp32, the arithmetic of update_kernel / kdk_kick_drift_kernel
+__device__ __forceinline__ void batch_kick(float4 &v, float ax, float ay, float az, double h)
+{
+    v.x = (float)__builtin_fma((double)ax, h, (double)v.x);
+    v.y = (float)__builtin_fma((double)ay, h, (double)v.y);
+    v.z = (float)__builtin_fma((double)az, h, (double)v.z);
+}
+__device__ __forceinline__ void batch_drift(float4 &x, const float4 &v, double h)
+{
+    x.x = (float)__builtin_fma((double)v.x, h, (double)x.x);
+    x.y = (float)__builtin_fma((double)v.y, h, (double)x.y);
+    x.z = (float)__builtin_fma((double)v.z, h, (double)x.z);
+}
+
+// One workgroup = system blockIdx.x.  Row r of the system is row k of lane t with r = k * blockDim.x + t.  Slots
+// r >= n_b are neither read nor written (their lanes compute on zeros and drop the result).
+// KDK: acc holds the accelerations at the current positions when have_acc, and receives them at the end.
+template <int RPL, bool GUARD, bool KDK>
+__global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *vel, float4 *acc, const int *counts,
+                                                          int max_bodies, int k, float dt, float eps2, int have_acc)
+{
+    extern __shared__ float4 sp[];  // the system's positions, max_bodies float4
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL], v[RPL];
+    float ax[RPL], ay[RPL], az[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        ax[q] = ay[q] = az[q] = 0.f;
+        if (r < n) {
+            x[q] = pos[base + r];
+            v[q] = vel[base + r];
+            sp[r] = x[q];
+            if (KDK && have_acc) {
+                const float4 a = acc[base + r];
+                ax[q] = a.x;
+                ay[q] = a.y;
+                az[q] = a.z;
+            }
+        }
+    }
+    __syncthreads();
+    const double h = (double)dt, hh = 0.5 * (double)dt;
+    if (KDK && !have_acc) {
+        batch_forces<RPL, GUARD>(sp, n, x, eps2, ax, ay, az);
+        __syncthreads();  // every lane is done reading before the first drift rewrites the positions
+    }
+    for (int s = 0; s < k; ++s) {
+        if (KDK) {
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                batch_kick(v[q], ax[q], ay[q], az[q], hh);
+                batch_drift(x[q], v[q], h);
+                const int r = q * T + tid;
+                if (r < n)
+                    sp[r] = x[q];
+            }
+            __syncthreads();
+            batch_forces<RPL, GUARD>(sp, n, x, eps2, ax, ay, az);
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                batch_kick(v[q], ax[q], ay[q], az[q], hh);
+        } else {
+            batch_forces<RPL, GUARD>(sp, n, x, eps2, ax, ay, az);
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                batch_kick(v[q], ax[q], ay[q], az[q], h);
+                batch_drift(x[q], v[q], h);
+                const int r = q * T + tid;
+                if (r < n)
+                    sp[r] = x[q];
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            pos[base + r] = x[q];  // .w (mass) unchanged
+            vel[base + r] = v[q];  // .w unchanged
+            if (KDK)
+                acc[base + r] = make_float4(ax[q], ay[q], az[q], 0.f);
+        }
+    }
+}
+
+template <int RPL, bool GUARD>
+void launch_step_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                     const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
+{
+    if (kdk)
+        hipLaunchKernelGGL((batch_step_kernel<RPL, GUARD, true>), grid, block, lds, stream, pos, vel, acc, counts, max_bodies,
+                           k, dt, eps2, have_acc);
+    else
+        hipLaunchKernelGGL((batch_step_kernel<RPL, GUARD, false>), grid, block, lds, stream, pos, vel, acc, counts, max_bodies,
+                           k, dt, eps2, have_acc);
+}
+
+hipError_t launch_batch_step(float4 *pos, float4 *vel, float4 *acc, const int *counts, int n_systems, int max_bodies, int k,
+                             float dt, float eps2, bool kdk, bool have_acc, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(eps2 > 0.f);
+    const int ha = have_acc ? 1 : 0;
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: launch_step_rpl<1, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    case 3: launch_step_rpl<1, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    case 4: launch_step_rpl<2, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    case 5: launch_step_rpl<2, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    case 8: launch_step_rpl<4, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    default: launch_step_rpl<4, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
+    }
+    return hipGetLastError();
+}
+
+// ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
+// nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
+constexpr int kDiagThreads = 256;
+constexpr int kDiagValues = 6;
+
+// POT = false: momentum and mass only (no pair loop).
+template <bool GUARD, bool POT>
+__global__ __launch_bounds__(kDiagThreads) void batch_diag_kernel(const float4 *pos, const float4 *vel, const int *counts,
+                                                                  int max_bodies, float eps2, double *out)
+{
+    extern __shared__ float4 sp[];
+    __shared__ double red[kDiagValues][kDiagThreads / 64];
+    const int n = counts[blockIdx.x];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    for (int j = tid; j < n; j += kDiagThreads)
+        sp[j] = pos[base + j];
+    __syncthreads();
+    double acc[kDiagValues] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += kDiagThreads) {
+        const float4 pi = sp[i];
+        const float4 w = vel[base + i];
+        double phi = 0.0;
+        for (int j = 0; j < (POT ? n : 0); ++j) {
+            const float4 pj = sp[j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, eps2)));
+            float inv = __builtin_amdgcn_rsqf(GUARD ? guard_r2(r2) : r2);
+            inv = j != i ? inv : 0.f;
+            phi += (double)(pj.w * inv);
+        }
+        acc[0] += 0.5 * (double)pi.w * ((double)w.x * w.x + (double)w.y * w.y + (double)w.z * w.z);
+        acc[1] += -0.5 * (double)pi.w * phi;
+        acc[2] += (double)pi.w * w.x;
+        acc[3] += (double)pi.w * w.y;
+        acc[4] += (double)pi.w * w.z;
+        acc[5] += (double)pi.w;
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int c = 0; c < kDiagValues; ++c) {
+        double s = acc[c];
+        for (int off = 32; off > 0; off >>= 1)
+            s += __shfl_down(s, off, 64);
+        if (lane == 0)
+            red[c][wave] = s;
+    }
+    __syncthreads();
+    if (tid < kDiagValues) {
+        double s = 0.0;
+        for (int q = 0; q < kDiagThreads / 64; ++q)
+            s += red[tid][q];
+        out[(size_t)blockIdx.x * kDiagValues + tid] = s;
+    }
+}
+
+hipError_t launch_batch_diag(const float4 *pos, const float4 *vel, const int *counts, int n_systems, int max_bodies,
+                             float eps2, bool potential, double *out, hipStream_t stream)
+{
+    const size_t lds = sizeof(float4) * (size_t)max_bodies;
+    if (!potential)
+        hipLaunchKernelGGL((batch_diag_kernel<false, false>), dim3(n_systems), dim3(kDiagThreads), lds, stream, pos, vel, counts,
+                           max_bodies, eps2, out);
+    else if (eps2 > 0.f)
+        hipLaunchKernelGGL((batch_diag_kernel<false, true>), dim3(n_systems), dim3(kDiagThreads), lds, stream, pos, vel, counts,
+                           max_bodies, eps2, out);
+    else
+        hipLaunchKernelGGL((batch_diag_kernel<true, true>), dim3(n_systems), dim3(kDiagThreads), lds, stream, pos, vel, counts,
+                           max_bodies, eps2, out);
+    return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace nbody
+
+using namespace nbody;
+
+// ---- the C ABI ----------------------------------------------------------------------------------------------------------
+
+struct nbody_batch {
+    int device = 0;
+    int64_t n_systems = 0, max_bodies = 0;
+    std::vector<int> counts;      // host copy of the per-system body counts
+    int *counts_dev = nullptr;    // [n_systems]
+    int integrator = NBODY_INTEGRATOR_KICK_DRIFT;
+    float4 *acc = nullptr;        // KDK: [n_systems][max_bodies] accelerations at the current positions (slots < n_b)
+    bool acc_valid = false;
+    const void *acc_pos = nullptr, *acc_vel = nullptr;  // the buffers and softening the cache belongs to
+    float acc_softening = 0.f;
+    double *diag_dev = nullptr;   // [n_systems][kDiagValues]
+    std::vector<double> diag_host;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;  // own_stream or the caller's (nbody_batch_set_stream)
+    std::string err;
+};
+
+static thread_local std::string g_batch_create_error;
+
+static int bfail(nbody_batch *b, int status, const std::string &msg)
+{
+    if (b)
+        b->err = msg;
+    else
+        g_batch_create_error = msg;
+    return status;
+}
+
+#define BATCH_TRY(b, call)                                                                                 \
+    do {                                                                                                   \
+        hipError_t e_ = (call);                                                                            \
+        if (e_ != hipSuccess)                                                                              \
+            return bfail((b), e_ == hipErrorOutOfMemory ? NBODY_ERR_ALLOC : NBODY_ERR_DEVICE,              \
+                         std::string(#call) + ": " + hipGetErrorString(e_));                               \
+    } while (0)
+
+// nbody_step's rule: finite, and 0 or at least NBODY_MIN_SOFTENING
+static bool softening_ok(float softening)
+{
+    return std::isfinite(softening) && softening >= 0.f && !(softening > 0.f && softening < NBODY_MIN_SOFTENING);
+}
+
+extern "C" {
+
+int nbody_batch_create(nbody_batch **out, int device, int64_t n_systems, int64_t max_bodies)
+{
+    if (!out)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: out is NULL");
+    *out = nullptr;
+    if (n_systems <= 0 || n_systems > ((int64_t)1 << 30))
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: n_systems out of range [1, 2^30]");
+    if (max_bodies <= 0 || max_bodies > NBODY_BATCH_MAX_BODIES)
+        return bfail(nullptr, NBODY_ERR_INVALID,
+                     "nbody_batch_create: max_bodies out of range [1, NBODY_BATCH_MAX_BODIES = 4096] (larger systems: nbody_create)");
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return bfail(nullptr, NBODY_ERR_NO_DEVICE,
+                     std::string("nbody_batch_create: no HIP device (") + hipGetErrorString(e) + "); this library has no CPU path");
+    if (device < 0 || device >= ndev)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: device index out of range");
+    BATCH_TRY(nullptr, hipSetDevice(device));
+    hipDeviceProp_t prop;
+    BATCH_TRY(nullptr, hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return bfail(nullptr, NBODY_ERR_NO_DEVICE,
+                     std::string("nbody_batch_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+    nbody_batch *b = new (std::nothrow) nbody_batch;
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_ALLOC, "nbody_batch_create: host allocation failed");
+    b->device = device;
+    b->n_systems = n_systems;
+    b->max_bodies = max_bodies;
+    b->counts.assign((size_t)n_systems, (int)max_bodies);
+    b->diag_host.resize((size_t)n_systems * kDiagValues);
+    hipError_t he = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
+    if (he == hipSuccess)
+        he = hipMalloc((void **)&b->counts_dev, sizeof(int) * (size_t)n_systems);
+    if (he == hipSuccess)
+        he = hipMalloc((void **)&b->diag_dev, sizeof(double) * b->diag_host.size());
+    if (he == hipSuccess)
+        he = hipMemcpy(b->counts_dev, b->counts.data(), sizeof(int) * (size_t)n_systems, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        const int rc = bfail(nullptr, he == hipErrorOutOfMemory ? NBODY_ERR_ALLOC : NBODY_ERR_DEVICE,
+                             std::string("nbody_batch_create: ") + hipGetErrorString(he));
+        nbody_batch_destroy(b);
+        return rc;
+    }
+    b->stream = b->own_stream;
+    *out = b;
+    return NBODY_OK;
+}
+
+int nbody_batch_destroy(nbody_batch *b)
+{
+    if (!b)
+        return NBODY_OK;
+    (void)hipSetDevice(b->device);
+    if (b->stream)
+        (void)hipStreamSynchronize(b->stream);
+    if (b->own_stream && b->own_stream != b->stream)
+        (void)hipStreamSynchronize(b->own_stream);
+    if (b->counts_dev) (void)hipFree(b->counts_dev);
+    if (b->acc) (void)hipFree(b->acc);
+    if (b->diag_dev) (void)hipFree(b->diag_dev);
+    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    delete b;
+    return NBODY_OK;
+}
+
+const char *nbody_batch_last_error(const nbody_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
+
+int nbody_batch_set_counts(nbody_batch *b, const int64_t *host_counts)
+{
+    if (!b || !host_counts)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_counts: NULL argument");
+    for (int64_t s = 0; s < b->n_systems; ++s)
+        if (host_counts[s] < 0 || host_counts[s] > b->max_bodies)
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_counts: count of system " + std::to_string(s) + " (" +
+                                                   std::to_string(host_counts[s]) + ") outside [0, max_bodies = " +
+                                                   std::to_string(b->max_bodies) + "]");
+    for (int64_t s = 0; s < b->n_systems; ++s)
+        b->counts[(size_t)s] = (int)host_counts[s];
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, hipMemcpyAsync(b->counts_dev, b->counts.data(), sizeof(int) * b->counts.size(), hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
+    b->acc_valid = false;
+    return NBODY_OK;
+}
+
+int nbody_batch_set_integrator(nbody_batch *b, int integrator)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_integrator: batch is NULL");
+    if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator");
+    if (integrator != b->integrator)
+        b->acc_valid = false;
+    b->integrator = integrator;
+    return NBODY_OK;
+}
+
+int nbody_batch_invalidate_forces(nbody_batch *b)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_invalidate_forces: batch is NULL");
+    b->acc_valid = false;
+    return NBODY_OK;
+}
+
+int nbody_batch_set_stream(nbody_batch *b, void *hip_stream)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_stream: batch is NULL");
+    b->stream = (hipStream_t)hip_stream;  // verbatim: NULL is the HIP default stream
+    return NBODY_OK;
+}
+
+int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, float dt, float softening)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_step_n: batch is NULL");
+    if (!d_pos || !d_vel)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: NULL buffer");
+    if (k < 0)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: k < 0");
+    if (!std::isfinite(dt))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: dt must be finite");
+    if (!softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
+                                           "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
+    if (k == 0)
+        return NBODY_OK;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK;
+    if (kdk) {
+        if (!b->acc)
+            BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * (size_t)b->n_systems * (size_t)b->max_bodies));
+        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening)
+            b->acc_valid = false;
+    }
+    const float eps2 = softening * softening;
+    for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
+        const int run = std::min(kBatchStepsPerLaunch, k - done);
+        BATCH_TRY(b, launch_batch_step(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->counts_dev,
+                                       (int)b->n_systems, (int)b->max_bodies, run, dt, eps2, kdk, kdk && b->acc_valid, b->stream));
+        if (kdk) {
+            b->acc_valid = true;
+            b->acc_pos = d_pos;
+            b->acc_vel = d_vel;
+            b->acc_softening = softening;
+        }
+    }
+    return NBODY_OK;
+}
+
+int nbody_batch_sync(nbody_batch *b)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_sync: batch is NULL");
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    BATCH_TRY(b, hipGetLastError());
+    return NBODY_OK;
+}
+
+int nbody_batch_step_n_on(nbody_batch *b, float *d_pos, float *d_vel, int k, float dt, float softening)
+{
+    const int rc = nbody_batch_step_n_async(b, d_pos, d_vel, k, dt, softening);
+    return rc != NBODY_OK ? rc : nbody_batch_sync(b);
+}
+
+static int batch_diag(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, bool potential)
+{
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, launch_batch_diag(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                   (int)b->n_systems, (int)b->max_bodies, softening * softening, potential, b->diag_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(b->diag_host.data(), b->diag_dev, sizeof(double) * b->diag_host.size(), hipMemcpyDeviceToHost,
+                                b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_energy(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, double *out3B)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_energy: batch is NULL");
+    if (!d_pos || !d_vel || !out3B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: NULL argument");
+    if (!softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    const int rc = batch_diag(b, d_pos, d_vel, softening, true);
+    if (rc != NBODY_OK)
+        return rc;
+    for (int64_t s = 0; s < b->n_systems; ++s) {
+        const double *d = &b->diag_host[(size_t)s * kDiagValues];
+        out3B[3 * s] = d[0];
+        out3B[3 * s + 1] = d[1];
+        out3B[3 * s + 2] = d[0] + d[1];
+    }
+    return NBODY_OK;
+}
+
+int nbody_batch_momentum(nbody_batch *b, const float *d_pos, const float *d_vel, double *out4B)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_momentum: batch is NULL");
+    if (!d_pos || !d_vel || !out4B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_momentum: NULL argument");
+    const int rc = batch_diag(b, d_pos, d_vel, 1.f, false);
+    if (rc != NBODY_OK)
+        return rc;
+    for (int64_t s = 0; s < b->n_systems; ++s)
+        for (int c = 0; c < 4; ++c)
+            out4B[4 * s + c] = b->diag_host[(size_t)s * kDiagValues + 2 + c];
+    return NBODY_OK;
+}
+
+}  // extern "C"
