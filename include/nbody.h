@@ -185,8 +185,10 @@ int nbody_update(nbody_ctx *ctx, float *d_positions_xyzm, float *d_velocities_xy
  *   / nbody_step_n follow the selected integrator; positions changed behind the library's back (a new buffer, an
  *   edit) need nbody_invalidate_forces.  A sharded host drives the pieces itself, because the drifted rows must be
  *   exchanged before the forces: forces + nbody_kdk_prepare once, then per step nbody_kdk_kick_drift -> exchange ->
- *   nbody_forces (+ _complement) -> nbody_kdk_kick. */
-enum { NBODY_INTEGRATOR_KICK_DRIFT = 0, NBODY_INTEGRATOR_KDK = 1 };
+ *   nbody_forces (+ _complement) -> nbody_kdk_kick.
+ * NBODY_INTEGRATOR_HERMITE: fourth-order Hermite predictor-corrector, for batched ensembles only
+ *   (nbody_batch_set_integrator, below); nbody_set_integrator and nbody_multi_create refuse it. */
+enum { NBODY_INTEGRATOR_KICK_DRIFT = 0, NBODY_INTEGRATOR_KDK = 1, NBODY_INTEGRATOR_HERMITE = 2 };
 int nbody_set_integrator(nbody_ctx *ctx, int integrator);
 /* Forgets the cached accelerations and every partial sum nbody_forces has produced since the last update. */
 int nbody_invalidate_forces(nbody_ctx *ctx);
@@ -464,15 +466,26 @@ float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
  * Buffers: caller-owned device arrays of B x max_bodies float4, system s at [s * max_bodies, s * max_bodies + n_s):
  * positions {x, y, z, mass}, velocities {vx, vy, vz, w} (w preserved), both updated in place.  Slots n_s .. max_bodies - 1
  * are never read and never written; a system with n_s = 0 is left alone.  The handle owns the counts, the kick-drift-kick
- * acceleration cache (B x max_bodies float4) and a stream.
- * Kernel: one workgroup per system, its positions in LDS (64 KiB at 4096 bodies: two workgroups per CU), rows in registers;
+ * acceleration cache (B x max_bodies float4; Hermite: a jerk cache beside it) and a stream.
+ * Kernel: one workgroup per system, its positions in LDS (64 KiB at 4096 bodies: two workgroups per CU; Hermite: predicted
+ * positions and velocities, 128 KiB, one workgroup per CU), rows in registers;
  * the k steps of a call run inside one launch with the state on chip (a long k is cut into launches of 128 steps: the same
  * bits).  Numerics: the pair term and the update of nbody_step; each row sums its columns j = 0 .. n_s - 1 in ascending
  * order in one fp32 chain per component, so a system's result depends on that system alone -- not on its slot, on B, on
- * max_bodies or on the other systems -- and step_n(k) is k x step_n(1) bit for bit, both integrators.  No atomics.
+ * max_bodies or on the other systems -- and step_n(k) is k x step_n(1) bit for bit, every integrator.  No atomics.
  * Softening: nbody_step's rule (0 allowed -- zero-distance pairs then contribute nothing --, 0 < eps < NBODY_MIN_SOFTENING
- * rejected).  Integrators: nbody_set_integrator's; the KDK cache is forgotten on new counts, another softening, other
- * buffers, another integrator or nbody_batch_invalidate_forces (new contents in the same buffers need that call).
+ * rejected).  Integrators: nbody_set_integrator's two and NBODY_INTEGRATOR_HERMITE, the batch's own: one fourth-order
+ * Hermite predict-evaluate-correct step per step, with accelerations a and jerks j (NBODY6, phiGPU, ph4), shared step h:
+ *   xp = x0 + v0 h + a0 h^2/2 + j0 h^3/6 ; vp = v0 + a0 h + j0 h^2/2 ; (a1, j1) = F(xp, vp), the one evaluation per step ;
+ *   v1 = v0 + (a0 + a1) h/2 + (j0 - j1) h^2/12 ; x1 = x0 + (v0 + v1) h/2 + (a0 - a1) h^2/12.
+ *   Pair term all fp32 (d = x_j - x_i, e = v_j - v_i, r^2 + eps^2 and inv = rsqrt as for the forces, inv2 = inv inv,
+ *   s = (m_j inv) inv2, rv = d.e by an FMA chain, c = (3 rv) inv2): a += d s, j += (e - c d) s, each an FMA; ascending j
+ *   as above, one fp32 chain per component of a and of j; eps = 0 drops zero-distance pairs from both.  Predictor and
+ *   corrector in fp64 from the fp32 operands, each result rounded once to fp32 (x1 uses the rounded v1).
+ *   KDK and Hermite keep a0 (and j0) in a handle-owned cache between calls (Hermite: a second B x max_bodies float4 array,
+ *   allocated on its first use); the cache is forgotten on new counts, another softening, other buffers, another integrator
+ *   or nbody_batch_invalidate_forces (new contents in the same buffers need that call).  Fixed, shared steps only: no
+ *   individual or adaptive time steps, no P(EC)^n iteration, no fp64 state.
  * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
  * [1, NBODY_BATCH_MAX_BODIES], counts outside [0, max_bodies], k < 0, a non-finite dt, the softening rule, NULL pointers.
  * nbody_batch_step_n_on returns with the work complete, _async only enqueues (nbody_batch_sync waits).  Diagnostics are

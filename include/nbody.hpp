@@ -284,6 +284,8 @@ public:
     {
         check(nbody_batch_set_integrator(b_, on ? NBODY_INTEGRATOR_KDK : NBODY_INTEGRATOR_KICK_DRIFT), "nbody_batch_set_integrator");
     }
+    // NBODY_INTEGRATOR_KICK_DRIFT, NBODY_INTEGRATOR_KDK or NBODY_INTEGRATOR_HERMITE (the batch's fourth-order scheme)
+    void setIntegrator(int integrator) { check(nbody_batch_set_integrator(b_, integrator), "nbody_batch_set_integrator"); }
     void invalidateForces() { check(nbody_batch_invalidate_forces(b_), "nbody_batch_invalidate_forces"); }
     void setStream(void *hipStream) { check(nbody_batch_set_stream(b_, hipStream), "nbody_batch_set_stream"); }
     // k steps on the device arrays; returns with the work complete (stepNAsync: enqueued only, sync() waits)

@@ -19,7 +19,7 @@ from .system import SOFTENING_VERSION3, TIME_TICK, _ptr, _torch
 
 #: NBODY_BATCH_MAX_BODIES: the largest system a batch holds (64 KiB of positions in LDS); larger ones belong to NBodySystem
 BATCH_MAX_BODIES = 4096
-INTEGRATORS = {"kick_drift": 0, "kdk": 1}
+INTEGRATORS = {"kick_drift": 0, "kdk": 1, "hermite": 2}
 
 
 def _check(lib, status: int, handle) -> None:
@@ -33,8 +33,11 @@ class BatchedSystem:
 
     ``positions`` / ``velocities`` are ``(B, max_bodies, 4)`` float32 device tensors used by the kernels in place (zero
     copy): ``positions[s, i] = {x, y, z, mass}``, ``velocities[s, i] = {vx, vy, vz, w}`` (``w`` preserved).  Slots
-    ``i >= counts[s]`` are never read or written.  ``integrator``: ``"kick_drift"`` (the reference's scheme) or ``"kdk"``
-    (velocity Verlet with the accelerations cached across calls).
+    ``i >= counts[s]`` are never read or written.  ``integrator``: ``"kick_drift"`` (the reference's scheme, first order),
+    ``"kdk"`` (velocity Verlet, second order, with the accelerations cached across calls) or ``"hermite"`` (the
+    fourth-order Hermite predictor-corrector of direct-summation codes such as NBODY6: one force-and-jerk evaluation per
+    step, about twice a force evaluation, with the accelerations and jerks cached across calls; ``nbody.h`` states the
+    scheme).  Every integrator uses a fixed step shared by all systems.
     """
 
     def __init__(self, num_systems: int, max_bodies: int, device: int = 0, counts=None, integrator: str = "kick_drift"):
@@ -88,7 +91,7 @@ class BatchedSystem:
         return self._counts.copy()
 
     def set_counts(self, counts) -> None:
-        """``B`` body counts in ``[0, max_bodies]``; forgets the cached KDK accelerations."""
+        """``B`` body counts in ``[0, max_bodies]``; forgets the cached accelerations (and Hermite jerks)."""
         c = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
         if c.shape[0] != self.num_systems:
             raise ValueError(f"expected {self.num_systems} counts, got {c.shape[0]}")
@@ -97,20 +100,22 @@ class BatchedSystem:
         self._counts = c.copy()
 
     def set_integrator(self, name: str) -> None:
+        """``"kick_drift"``, ``"kdk"`` or ``"hermite"``; a change forgets the cached accelerations (and jerks)."""
         if name not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {tuple(INTEGRATORS)}")
         _check(self._lib, self._lib.nbody_batch_set_integrator(self._h, INTEGRATORS[name]), self._h)
         self.integrator = name
 
     def invalidate_forces(self) -> None:
-        """Forget the cached KDK accelerations (after editing ``positions`` in place)."""
+        """Forget the cached accelerations of KDK and Hermite, and Hermite's jerks (after editing ``positions`` or
+        ``velocities`` in place: the next step evaluates them afresh)."""
         _check(self._lib, self._lib.nbody_batch_invalidate_forces(self._h), self._h)
 
     # -- state -------------------------------------------------------------------------------
     def set_state(self, pos, vel, counts=None) -> None:
         """Copy ``(B, n, 4)`` positions and velocities (numpy or torch, ``n <= max_bodies``) into slots ``[0, n)`` of every
         system; ``counts`` (optional) sets the body counts first.  Every count must be at most ``n``.  Forgets the cached
-        KDK accelerations."""
+        accelerations and jerks."""
         torch = _torch()
         p = torch.as_tensor(np.asarray(pos) if not isinstance(pos, torch.Tensor) else pos, dtype=torch.float32)
         v = torch.as_tensor(np.asarray(vel) if not isinstance(vel, torch.Tensor) else vel, dtype=torch.float32)

@@ -10,6 +10,8 @@
 // rows per lane and workgroup size), nor any other system changes a bit.  The pair term is the one of force_kernel
 // (nbody_kernels.hip): d = x_j - x_i, r^2 + eps^2 by an FMA chain, v_rsq_f32, s = (m_j inv) (inv inv), a = fma(d, s, a).
 // The update is update_kernel's: v <- (float)fma((double)a, (double)dt, (double)v), x <- (float)fma((double)v, ...).
+// Hermite (NBODY_INTEGRATOR_HERMITE) runs a sibling kernel, batch_hermite_kernel: the same order, with the jerk summed
+// beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
 #include "nbody_kernels.h"
 
@@ -165,6 +167,237 @@ __global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *v
     }
 }
 
+// ---- fourth-order Hermite: one predict-evaluate-correct (PEC) step per step, shared h ----
+//   xp = x0 + v0 h + a0 h^2/2 + j0 h^3/6          vp = v0 + a0 h + j0 h^2/2
+//   (a1, j1) = F(xp, vp)                           the one force evaluation of the step
+//   v1 = v0 + (a0 + a1) h/2 + (j0 - j1) h^2/12     x1 = x0 + (v0 + v1) h/2 + (a0 - a1) h^2/12
+// The column side lives in LDS, 32 B per body: body j's predicted {x, y, z, m} at sh[2j] and {vx, vy, vz, 0} at sh[2j + 1]
+// (128 KiB at 4096 bodies: one workgroup per CU, as the registers of a 1024-thread workgroup allow anyway).
+
+// Accelerations and jerks of G rows at their predicted state (xp, vp) from the n columns in LDS, ascending j, one fp32
+// chain per row and component.  Pair term: d = x_j - x_i, e = v_j - v_i, r^2 + eps^2 by batch_forces' FMA chain,
+// inv = v_rsq_f32, inv2 = inv inv, s = (m_j inv) inv2 (batch_forces' s), rv = fma(dz, ez, fma(dy, ey, dx ex)),
+// c = (3 rv) inv2; a = fma(d, s, a), j = fma(fma(-c, d, e), s, j).  27 VALU + 1 v_rsq_f32 per interaction.  GUARD: a
+// zero-distance pair has inv = 0, so s = c = 0 and it adds exactly 0 to a and j.
+template <int G, bool GUARD>
+__device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, const float3 (&xp)[G], const float3 (&vp)[G],
+                                                   float eps2, float3 (&a)[G], float3 (&jk)[G])
+{
+#pragma unroll
+    for (int k = 0; k < G; ++k)
+        a[k] = jk[k] = make_float3(0.f, 0.f, 0.f);
+#pragma unroll 1  // two rows of 27 VALU per column; unrolling would spill at RPL = 4
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = sh[2 * j];  // wave-uniform addresses: two broadcast ds_read_b128 per column
+        const float4 wj = sh[2 * j + 1];
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            const float dx = pj.x - xp[k].x, dy = pj.y - xp[k].y, dz = pj.z - xp[k].z;
+            const float ex = wj.x - vp[k].x, ey = wj.y - vp[k].y, ez = wj.z - vp[k].z;
+            float r2 = __builtin_fmaf(dx, dx, eps2);
+            r2 = __builtin_fmaf(dy, dy, r2);
+            r2 = __builtin_fmaf(dz, dz, r2);
+            if (GUARD)
+                r2 = guard_r2(r2);
+            const float inv = __builtin_amdgcn_rsqf(r2);
+            const float inv2 = inv * inv;
+            const float s = (pj.w * inv) * inv2;
+            const float rv = __builtin_fmaf(dz, ez, __builtin_fmaf(dy, ey, dx * ex));
+            const float c = (3.f * rv) * inv2;
+            a[k].x = __builtin_fmaf(dx, s, a[k].x);
+            a[k].y = __builtin_fmaf(dy, s, a[k].y);
+            a[k].z = __builtin_fmaf(dz, s, a[k].z);
+            jk[k].x = __builtin_fmaf(__builtin_fmaf(-c, dx, ex), s, jk[k].x);
+            jk[k].y = __builtin_fmaf(__builtin_fmaf(-c, dy, ey), s, jk[k].y);
+            jk[k].z = __builtin_fmaf(__builtin_fmaf(-c, dz, ez), s, jk[k].z);
+        }
+    }
+}
+
+// Predictor and corrector, per component in fp64 from the fp32 operands, each result rounded once to fp32
+// (h2 = h/2, h3 = h/3, h6 = h/6 in fp64):
+//   xp = x + h (v + h2 (a + h3 j))       vp = v + h (a + h2 j)
+//   v1 = v0 + h2 ((a0 + a1) + h6 (j0 - j1))       x1 = x0 + h2 ((v0 + v1) + h6 (a0 - a1)), v1 the rounded fp32 value
+// The predictor and the corrector both widen x0, v0, a0 and j0 to fp64; left alone, the compiler keeps the fp64 copies of
+// the predictor alive across the column loop for the corrector (twice the registers of the fp32 state: scratch at RPL = 4).
+// An empty asm statement after the prediction makes the fp32 values new ones, so they are widened again where used.
+__device__ __forceinline__ void renew_f32(float3 &u)
+{
+    asm volatile("" : "+v"(u.x), "+v"(u.y), "+v"(u.z));
+}
+
+struct HermiteSteps {
+    double h, h2, h3, h6;
+};
+__device__ __forceinline__ float hermite_predict_x(float x, float v, float a, float j, const HermiteSteps &t)
+{
+    return (float)__builtin_fma(t.h, __builtin_fma(t.h2, __builtin_fma(t.h3, (double)j, (double)a), (double)v), (double)x);
+}
+__device__ __forceinline__ float hermite_predict_v(float v, float a, float j, const HermiteSteps &t)
+{
+    return (float)__builtin_fma(t.h, __builtin_fma(t.h2, (double)j, (double)a), (double)v);
+}
+__device__ __forceinline__ void hermite_correct(float &x, float &v, float a0, float a1, float j0, float j1,
+                                                const HermiteSteps &t)
+{
+    const float v1 = (float)__builtin_fma(t.h2, __builtin_fma(t.h6, (double)j0 - (double)j1, (double)a0 + (double)a1),
+                                          (double)v);
+    x = (float)__builtin_fma(t.h2, __builtin_fma(t.h6, (double)a0 - (double)a1, (double)v + (double)v1), (double)x);
+    v = v1;
+}
+
+// Evaluate (a1, j1) for the lane's rows from the predicted state in LDS and, when CORRECT, apply the corrector; then
+// (a, j) = (a1, j1).  The rows go in groups of at most two, each group one pass over the columns with its own predicted
+// state reread from LDS: four rows at once (x0, v0, a0, j0 live beside the predicted state and the sums) would not fit
+// 128 VGPRs without scratch.  A group's corrector writes only registers, so the next group still reads the predicted state.
+template <int RPL, bool GUARD, bool CORRECT>
+__device__ __forceinline__ void hermite_evaluate(const float4 *sh, int n, int tid, int T, float eps2, float4 (&x)[RPL],
+                                                 float3 (&v)[RPL], float3 (&a)[RPL], float3 (&jk)[RPL], const HermiteSteps &t)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {  // xyz only: ds_read_b96
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+            }
+        }
+        batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i;
+            if (CORRECT) {
+                hermite_correct(x[q].x, v[q].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, t);
+                hermite_correct(x[q].y, v[q].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, t);
+                hermite_correct(x[q].z, v[q].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, t);
+            }
+            a[q] = a1[i];
+            jk[q] = j1[i];
+        }
+    }
+}
+
+// One workgroup = system blockIdx.x, rows as in batch_step_kernel.  acc / jerk hold a0 and j0 at the current state when
+// have_acc (otherwise they are evaluated first), and receive them at the end.  Slots r >= n_b are neither read nor written.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                             const int *counts, int max_bodies, int k, float dt, float eps2,
+                                                             int have_acc)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const double h = (double)dt;
+    const HermiteSteps t{h, 0.5 * h, h / 3.0, h / 6.0};
+    float4 x[RPL];  // {x, y, z, m}
+    float3 v[RPL], a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            if (have_acc) {
+                const float4 a0 = acc[base + r], j0 = jerk[base + r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!have_acc) {  // (a0, j0) at the current state
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                sh[2 * r] = x[q];
+                sh[2 * r + 1] = make_float4(v[q].x, v[q].y, v[q].z, 0.f);
+            }
+        }
+        __syncthreads();
+        hermite_evaluate<RPL, GUARD, false>(sh, n, tid, T, eps2, x, v, a, jk, t);
+        __syncthreads();  // every lane is done reading before the first prediction rewrites the columns
+    }
+    for (int s = 0; s < k; ++s) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                sh[2 * r] = make_float4(hermite_predict_x(x[q].x, v[q].x, a[q].x, jk[q].x, t),
+                                        hermite_predict_x(x[q].y, v[q].y, a[q].y, jk[q].y, t),
+                                        hermite_predict_x(x[q].z, v[q].z, a[q].z, jk[q].z, t), x[q].w);
+                sh[2 * r + 1] = make_float4(hermite_predict_v(v[q].x, a[q].x, jk[q].x, t),
+                                            hermite_predict_v(v[q].y, a[q].y, jk[q].y, t),
+                                            hermite_predict_v(v[q].z, a[q].z, jk[q].z, t), 0.f);
+            }
+            float3 xq = make_float3(x[q].x, x[q].y, x[q].z);
+            renew_f32(xq);
+            x[q] = make_float4(xq.x, xq.y, xq.z, x[q].w);
+            renew_f32(v[q]);
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        hermite_evaluate<RPL, GUARD, true>(sh, n, tid, T, eps2, x, v, a, jk, t);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            pos[base + r] = x[q];  // .w (mass) unchanged
+            float *w = reinterpret_cast<float *>(vel + base + r);
+            w[0] = v[q].x;  // .w left alone
+            w[1] = v[q].y;
+            w[2] = v[q].z;
+            acc[base + r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[base + r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_hermite_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                              float4 *jerk, const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
+{
+    // above the default 64 KiB of dynamic LDS from 2049 bodies on (128 KiB at 4096)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies,
+                       k, dt, eps2, have_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_hermite(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, int n_systems,
+                                int max_bodies, int k, float dt, float eps2, bool have_acc, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(eps2 > 0.f);
+    const int ha = have_acc ? 1 : 0;
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_hermite_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    case 3: return launch_hermite_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    case 4: return launch_hermite_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    case 5: return launch_hermite_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    case 8: return launch_hermite_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    default: return launch_hermite_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
+    }
+}
+
 template <int RPL, bool GUARD>
 void launch_step_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
                      const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
@@ -281,8 +514,10 @@ struct nbody_batch {
     std::vector<int> counts;      // host copy of the per-system body counts
     int *counts_dev = nullptr;    // [n_systems]
     int integrator = NBODY_INTEGRATOR_KICK_DRIFT;
-    float4 *acc = nullptr;        // KDK: [n_systems][max_bodies] accelerations at the current positions (slots < n_b)
+    float4 *acc = nullptr;        // KDK, Hermite: [n_systems][max_bodies] accelerations at the current state (slots < n_b)
+    float4 *jerk = nullptr;       // Hermite: [n_systems][max_bodies] jerks at the current state, allocated on first use
     bool acc_valid = false;
+    int acc_integrator = -1;      // the integrator that filled the cache
     const void *acc_pos = nullptr, *acc_vel = nullptr;  // the buffers and softening the cache belongs to
     float acc_softening = 0.f;
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
@@ -379,6 +614,7 @@ int nbody_batch_destroy(nbody_batch *b)
         (void)hipStreamSynchronize(b->own_stream);
     if (b->counts_dev) (void)hipFree(b->counts_dev);
     if (b->acc) (void)hipFree(b->acc);
+    if (b->jerk) (void)hipFree(b->jerk);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -409,8 +645,8 @@ int nbody_batch_set_integrator(nbody_batch *b, int integrator)
 {
     if (!b)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_integrator: batch is NULL");
-    if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator");
+    if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK && integrator != NBODY_INTEGRATOR_HERMITE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator (KICK_DRIFT = 0, KDK = 1, HERMITE = 2)");
     if (integrator != b->integrator)
         b->acc_valid = false;
     b->integrator = integrator;
@@ -449,19 +685,29 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
     if (k == 0)
         return NBODY_OK;
     BATCH_TRY(b, hipSetDevice(b->device));
-    const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK;
-    if (kdk) {
+    const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK, hermite = b->integrator == NBODY_INTEGRATOR_HERMITE;
+    const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
+    if (kdk || hermite) {
         if (!b->acc)
-            BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * (size_t)b->n_systems * (size_t)b->max_bodies));
-        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening)
+            BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
+        if (hermite && !b->jerk)
+            BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
+        // KDK's accelerations come without jerks: a cache is used only by the integrator that filled it
+        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening || b->acc_integrator != b->integrator)
             b->acc_valid = false;
     }
     const float eps2 = softening * softening;
     for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
         const int run = std::min(kBatchStepsPerLaunch, k - done);
-        BATCH_TRY(b, launch_batch_step(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->counts_dev,
-                                       (int)b->n_systems, (int)b->max_bodies, run, dt, eps2, kdk, kdk && b->acc_valid, b->stream));
-        if (kdk) {
+        float4 *pos = reinterpret_cast<float4 *>(d_pos), *vel = reinterpret_cast<float4 *>(d_vel);
+        if (hermite)
+            BATCH_TRY(b, launch_batch_hermite(pos, vel, b->acc, b->jerk, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run,
+                                              dt, eps2, b->acc_valid, b->stream));
+        else
+            BATCH_TRY(b, launch_batch_step(pos, vel, b->acc, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run, dt, eps2,
+                                           kdk, kdk && b->acc_valid, b->stream));
+        if (kdk || hermite) {
+            b->acc_integrator = b->integrator;
             b->acc_valid = true;
             b->acc_pos = d_pos;
             b->acc_vel = d_vel;

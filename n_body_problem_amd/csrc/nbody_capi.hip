@@ -1560,6 +1560,9 @@ static int ensure_acc(nbody_ctx *c)
 
 int nbody_set_integrator(nbody_ctx *c, int integrator)
 {
+    if (c && integrator == NBODY_INTEGRATOR_HERMITE)
+        return fail(c, NBODY_ERR_INVALID, "nbody_set_integrator: NBODY_INTEGRATOR_HERMITE exists for batched ensembles only "
+                                          "(nbody_batch_set_integrator)");
     if (!c || (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK))
         return fail(c, NBODY_ERR_INVALID, "nbody_set_integrator: unknown integrator");
     c->integrator = integrator;

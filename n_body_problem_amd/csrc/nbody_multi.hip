@@ -334,6 +334,9 @@ static int create_common(nbody_multi **out, const nbody_multi_config *cfg, int w
     *out = nullptr;
     if (!cfg)
         return mfail(nullptr, NBODY_ERR_INVALID, "nbody_multi_create: config is NULL");
+    if (cfg->integrator == NBODY_INTEGRATOR_HERMITE)
+        return mfail(nullptr, NBODY_ERR_INVALID, "nbody_multi_create: NBODY_INTEGRATOR_HERMITE exists for batched ensembles only "
+                                                 "(nbody_batch_set_integrator)");
     if ((cfg->body_order != NBODY_ORDER_GIVEN && cfg->body_order != NBODY_ORDER_MORTON) ||
         (cfg->integrator != NBODY_INTEGRATOR_KICK_DRIFT && cfg->integrator != NBODY_INTEGRATOR_KDK) ||
         (cfg->exchange != NBODY_EXCHANGE_ALLGATHER && cfg->exchange != NBODY_EXCHANGE_RING) ||

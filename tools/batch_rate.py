@@ -1,10 +1,12 @@
 """Batched ensembles against the status quo: B independent systems of n bodies stepped by one BatchedSystem, and the same
 systems stepped one NBodySystem each (timed on a subset, scaled to B).  One JSON line per (n, B, integrator):
-python tools/batch_rate.py [--cases 1024x1024 ...] [--integrators kick_drift kdk] [--repeats 5] [--subset 8]
+python tools/batch_rate.py [--cases 1024x1024 ...] [--integrators kick_drift kdk hermite] [--repeats 5] [--subset 8]
 
-Rates use the one-sided convention: n^2 ordered interactions per system and step, 20 flop each, against the 157.3 TFLOP/s
-fp32 vector peak.  Times are HIP events around step_n(k) after a warm-up, the median of repeats that alternate the batched
-and the status-quo measurement."""
+Rates use the one-sided convention: n^2 ordered interactions per system and step, against the 157.3 TFLOP/s fp32 vector
+peak at 20 flop per interaction for kick_drift and kdk (a force) and 60 flop per interaction for hermite (a force and a
+jerk, the convention of the Hermite GPU literature); the line names its convention.  Times are HIP events around
+step_n(k) after a warm-up, the median of repeats that alternate the batched and the status-quo measurement.  Hermite
+exists for batches only, so its lines have no status-quo figures."""
 import argparse
 import json
 import os
@@ -18,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import n_body_problem_amd as nb  # noqa: E402
 
 PEAK_FP32 = 157.3e12
-FLOP_PER_INTERACTION = 20
+FLOP_PER_INTERACTION = {"kick_drift": 20, "kdk": 20, "hermite": 60}
 CASES = [(64, 16384), (256, 4096), (1024, 1024), (4096, 256), (4096, 512)]
 
 ap = argparse.ArgumentParser()
@@ -62,7 +64,7 @@ for case in args.cases:
     for integrator in args.integrators:
         batch = nb.BatchedSystem(B, n, integrator=integrator)
         batch.set_state(P, V)
-        subset = min(args.subset, B)
+        subset = min(args.subset, B) if integrator != "hermite" else 0
         singles = []
         for s in range(subset):
             one = nb.NBodySystem(n)
@@ -86,19 +88,25 @@ for case in args.cases:
         tb, ts = [], []
         for _ in range(args.repeats):          # alternated
             tb.append(timed(run_batch) / k)
-            ts.append(timed(run_singles) / k_single * B / subset)
+            if singles:
+                ts.append(timed(run_singles) / k_single * B / subset)
         batch.sync()
         ms = statistics.median(tb)
-        ms_sq = statistics.median(ts)
         rate = inter / (ms * 1e-3)
-        print(json.dumps({
+        flop = FLOP_PER_INTERACTION[integrator]
+        line = {
             "n": n, "B": B, "integrator": integrator, "k": k, "ms_per_step": round(ms, 5),
             "ms_per_step_repeats": [round(x, 5) for x in tb],
             "interactions_per_s": float(f"{rate:.4g}"),
-            "frac_of_fp32_peak": round(FLOP_PER_INTERACTION * rate / PEAK_FP32, 4),
-            "status_quo_ms_per_step": round(ms_sq, 4), "status_quo_systems_timed": subset, "status_quo_k": k_single,
-            "status_quo_interactions_per_s": float(f"{inter / (ms_sq * 1e-3):.4g}"),
-            "speedup_vs_status_quo": round(ms_sq / ms, 1)}), flush=True)
+            "flop_per_interaction": flop,
+            "frac_of_fp32_peak": round(flop * rate / PEAK_FP32, 4)}
+        if ts:
+            ms_sq = statistics.median(ts)
+            line.update({
+                "status_quo_ms_per_step": round(ms_sq, 4), "status_quo_systems_timed": subset, "status_quo_k": k_single,
+                "status_quo_interactions_per_s": float(f"{inter / (ms_sq * 1e-3):.4g}"),
+                "speedup_vs_status_quo": round(ms_sq / ms, 1)})
+        print(json.dumps(line), flush=True)
         batch.close()
         for one in singles:
             one.close()
