@@ -14,6 +14,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 using namespace nbody;
@@ -37,17 +38,20 @@ struct nbody_ctx {
     // One force call = one or more parts: a part is a run of whole row groups whose tiles go in one launch and whose partial
     // sums are added up (on the auxiliary stream, beside the next part's tiles) as soon as that launch is over.  With more than
     // two parts the partial sums live in two buffer slots used in turn: the arrays hold two parts, not the whole pass.
-    struct SymPart {
+    struct SymPart {  // what the launches and the summation calls read of a part of the plan (SymPlanPart, nbody_sym_plan.h)
         int g0 = 0, g1 = 0;              // row groups [g0, g1)
-        int split_lo = 0, split_hi = 0;  // = row splits [split_lo, split_hi)
+        int split_lo = 0;                // their first own row split
         int64_t b0 = 0, rows = 0;        // = rows [b0, b0 + rows) of this context
-        int4 *tiles = nullptr;  // strips {R, first C, count, slot}
-        int2 *diag = nullptr;
+        const int4 *tiles = nullptr;     // strips {R, first C, count, slot}
+        const int2 *diag = nullptr;
         int n_tiles = 0, n_diag = 0;
-        size_t row_off = 0, col_off = 0;  // where the part's [n_splits/2+1][rows] and [splits][n_splits/2][split_len] arrays
-                                          // start in partials / col_partials, in 12-byte entries
+        size_t row_off = 0, col_off = 0;  // where its arrays start in partials / col_partials, in 12-byte entries
     };
-    struct SymPlan { std::vector<SymPart> parts; size_t row_entries = 0, col_entries = 0; };
+    struct SymPlan {
+        std::vector<SymPart> parts;
+        size_t row_entries = 0, col_entries = 0;
+        void *lists = nullptr;  // device: every part's strips, then every part's diagonal tiles
+    };
     std::map<std::tuple<int, int, bool>, SymPlan> sym_plans;  // per column range asked for
     const SymPart *pending = nullptr;  // the part of the last force call whose sums are still to be formed (the last one)
     std::vector<hipEvent_t> ev_tiles, ev_red;  // per part: tile launch over / its sums formed (the slot is free again)
@@ -748,7 +752,7 @@ static int resplit(nbody_ctx *c, int64_t split_len)
     return NBODY_OK;
 }
 
-static int sym_strip_len(const nbody_ctx *c);
+static int sym_strip_len(const nbody_ctx *c) { return nbody::sym_strip_len(c->n_splits, (int)c->split_len, c->strip_setting); }
 
 int nbody_set_force_mode(nbody_ctx *c, int mode)
 {
@@ -811,23 +815,6 @@ int nbody_set_force_mode(nbody_ctx *c, int mode)
     c->acc_valid = false;
     drop_step_graph(c);
     return NBODY_OK;
-}
-
-// Strips (SymArgs, nbody_kernels.h): from the 2048-body splits on -- N >= 2^20, where the partial sums are gigabytes -- a tile
-// workgroup takes four consecutive column splits of its row split and keeps the rows' sums in registers across them: a quarter
-// of the row-side partial sums (N = 2^20: 0.8 instead of 3.2 GB per pass; the column side keeps its 3.2 GB -- halving that as well
-// takes a workgroup that owns a whole CU, measured 7 % slower: profiles/r04_ab_whole_cu_workgroup.txt).  The blocks of four are
-// absolute and the number of splits must be a multiple of 8 x 4, so no strip straddles a summation group or a rank's column
-// chunk and which sums exist stays a function of (n_total, split_len) alone; other split counts keep single tiles.
-// Automatic: strips of FOUR column splits from 1024 splits on (N >= 2^21), of TWO below (N = 2^20).  A strip is one workgroup, and
-// a rank of eight's share of an N = 2^20 pass is only 4088 strips of four on 768 workgroup slots -- 5.3 rounds of 3.5 ms, six in
-// practice: 21.6 ms against 18.7 ms with single tiles and 20.0 ms with strips of two, while one GPU runs strips of two and of
-// four equally fast (146.2 ms; profiles/r04_shard_rate.txt).  A function of (n_total, split_len) only, like the split length:
-// the strips define the order of the row-side sums.
-static int sym_strip_len(const nbody_ctx *c)
-{
-    const int want = c->strip_setting ? c->strip_setting : (c->split_len >= 2048 ? (c->n_splits >= 1024 ? 4 : 2) : 1);
-    return want > 1 && c->n_splits % (kSymGroups * want) == 0 && c->split_len == 2048 ? want : 1;
 }
 
 int nbody_set_strip_len(nbody_ctx *c, int len)
@@ -1020,10 +1007,7 @@ int nbody_set_equal_mass_path(nbody_ctx *c, int on)
 static void free_sym_tiles(nbody_ctx *c)
 {
     for (auto &kv : c->sym_plans)
-        for (auto &p : kv.second.parts) {
-            if (p.tiles) (void)hipFree(p.tiles);
-            if (p.diag) (void)hipFree(p.diag);
-        }
+        if (kv.second.lists) (void)hipFree(kv.second.lists);
     c->sym_plans.clear();
     c->pending = nullptr;
     drop_step_graph(c);
@@ -1139,299 +1123,209 @@ static int ensure_sym_buffers(nbody_ctx *c, size_t row_entries, size_t col_entri
     return NBODY_OK;
 }
 
-static int forces_impl(nbody_ctx *c, const float *d_pos, int64_t col_lo, int64_t col_count, float softening,
-                       bool complement, const char *who)
+// The equal-mass flags once per step, by its first force call: a later call for other columns (the complement launch on a
+// second stream, the ring's chunks) would rewrite the same values under the kernels that read them
+static int ensure_split_flags(nbody_ctx *c, const float4 *pos)
 {
-    if (!c || (!d_pos && c->n_total))
-        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (!(softening >= 0.f) || !std::isfinite(softening))
-        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": softening must be finite and >= 0");
-    if (softening > 0.f && softening < NBODY_MIN_SOFTENING)
-        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": 0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass in the "
-                                                             "self pair); use 0 (zero-distance pairs then contribute nothing)");
-    if (col_lo < 0 || col_count < 0 || col_lo + col_count > c->n_total || col_lo % c->split_len != 0 ||
-        ((col_lo + col_count) % c->split_len != 0 && col_lo + col_count != c->n_total))
-        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": column range must be split-aligned and inside [0,n_total]");
-    if (c->row_count == 0 || c->n_total == 0)
-        return NBODY_OK;
-    const int first = (int)(col_lo / c->split_len);
-    const int count = (int)((col_count + c->split_len - 1) / c->split_len);
-    if (complement ? count == c->n_splits : count == 0)
-        return NBODY_OK;  // no column selected
-    if (c->force_mode == NBODY_FORCE_SYMMETRIC) {
-        // this context's tiles with a column split in the range asked for, cut into parts (cached per range)
-        const int S = c->n_splits, L = (int)c->split_len;
-        const int own_lo = (int)(c->row_lo / L), own_hi = (int)((c->row_lo + c->row_count + L - 1) / L);
-        const bool whole = c->row_lo == 0 && c->row_count == c->n_total && !complement && first == 0 && count == S;
-        if (!whole && c->pending && c->pending->g1 - c->pending->g0 != c->group_count)
-            for (int sp = 0; sp < S; ++sp)
-                if (c->split_done[(size_t)sp])
-                    return fail(c, NBODY_ERR_STATE, std::string(who) + ": a column range after a call for all columns in several "
-                                                                        "summation parts: the earlier parts are already summed");
-        const int SL = c->strip_len;
-        if (SL > 1 && (first % SL != 0 || ((first + count) % SL != 0 && first + count != S)))
-            return fail(c, NBODY_ERR_INVALID, std::string(who) + ": with strips of " + std::to_string(SL) + " column splits a column "
-                                                                  "range must start and end on a multiple of that many splits");
-        auto key = std::make_tuple(first, count, complement);
-        auto it = c->sym_plans.find(key);
-        if (it == c->sym_plans.end()) {
-            auto selected = [&](int C) { return (C >= first && C < first + count) != complement; };
-            // Launch order = L2 locality (speed only; every tile has its own outputs).  The tile of row split R and ring
-            // distance d has column split (R + d) mod S.  Blocks of 8 row splits x 8 distances touch 23 splits' bodies
-            // instead of 128; workgroups are dealt round-robin to the 8 XCDs (MI355X_MICROARCH.md), so block k's tiles
-            // take the launch slots congruent to k mod 8 and meet in one XCD's L2.
-            constexpr int kDiagInTilesMinStrip = 1;  // strips longer than this carry the diagonal tiles in the tile launch
-            const int B = 8;
-            auto list_rows = [&](int r_lo, int r_hi) {  // the strips with a row split in [r_lo, r_hi), in launch order
-                std::vector<int4> tiles;
-                std::vector<std::vector<int4>> per_xcd(8);
-                const int n_blocks = S / SL;  // SL = 1: a "block" is one column split, a strip one tile, its slot the ring distance
-                int k = 0;
-                for (int Rb = r_lo; Rb < r_hi; Rb += B)
-                    for (int jb = 0; jb <= n_blocks / 2 + 1; jb += B, ++k)
-                        for (int R = Rb; R < std::min(Rb + B, r_hi); ++R)
-                            for (int j = jb; j < std::min(jb + B, n_blocks / 2 + 2); ++j) {
-                                const int J = (((R + 1) % S) / SL + j) % n_blocks;  // the j-th block along the ring from R + 1
-                                int C0 = -1, cnt = 0;
-                                for (int C = J * SL; C < (J + 1) * SL; ++C)
-                                    if (selected(C) && sym_rows_side(R, C, S)) {
-                                        if (cnt == 0)
-                                            C0 = C;
-                                        ++cnt;
-                                    }
-                                // a block met twice along the ring (its head at the start of the half ring, its tail at the end)
-                                // cannot happen: the half ring is shorter than the ring by far more than a block
-                                if (cnt > 0)
-                                    per_xcd[(size_t)k % per_xcd.size()].push_back(make_int4(R, C0, cnt, sym_row_slot(R, C0, S, SL)));
-                            }
-                // Strips: the DIAGONAL tiles ride in the tile launch, as full squares of the hand-scheduled loops that keep their
-                // row side (slot 0) -- 512 one-tile workgroups more for the launch's tail at N = 2^20 instead of a compiler-scheduled
-                // launch beside it (0.4 % more pair evaluations; profiles/r04_strips_ab.txt)
-                if (SL > kDiagInTilesMinStrip)
-                    for (int R = r_lo; R < r_hi; ++R)
-                        if (selected(R))
-                            per_xcd[(size_t)R % per_xcd.size()].push_back(make_int4(R, R, 1, 0));
-                // whole strips first, the shorter ones of the band's edges behind them, longest first (the launch's tail is made
-                // of ever shorter workgroups: three-tile strips, then two, then one -- 145.4 against 145.9 ms per N = 2^20 step
-                // with the short ones in list order, profiles/r04_strips_ab.txt) -- inside each XCD's sequence, so that a block's
-                // strips keep meeting in one L2 (a partition of the interleaved list shifted the launch slots: 4.6 instead of 1.4 GB
-                // of fabric reads per N = 2^20 pass)
-                for (auto &seq : per_xcd)
-                    std::stable_sort(seq.begin(), seq.end(), [](const int4 &x, const int4 &y) { return x.z > y.z; });
-                for (size_t j = 0, more = 1; more; ++j) {
-                    more = 0;
-                    for (auto &seq : per_xcd)
-                        if (j < seq.size()) {
-                            tiles.push_back(seq[j]);
-                            more = 1;
-                        }
-                }
-                return tiles;
-            };
-            // Summation parts (one context that owns every row, all columns in one call, a system large enough for several
-            // launches): the canonical order is by row groups, so a part's sums can be formed as soon as its launch is over,
-            // on the auxiliary stream beside the next part's tiles, and nothing about the result changes.  What stays behind
-            // the force pass is the last part's share of the summation and the combination.  2 parts = 7 groups + 1 (one
-            // extra launch tail, the arrays hold the whole pass); 4 or 8 equal parts keep two parts' arrays.
-            const int n_groups = (S + c->group_splits - 1) / c->group_splits;
-            int K = c->sum_parts;
-            if (K == 0) {  // automatic: one launch is the fastest (profiles/r02_summation_parts_eight_rows.txt); more only for memory
-                // the column side and the row side (a strip's rows are summed in registers: 1 / strip_len of the entries)
-                const double pass_bytes = 6.0 * (double)c->n_total * (double)c->n_total / (double)L * (1.0 + 1.0 / (double)SL);
-                // 4 parts of 3 + 3 + 1 + 1 groups hold two slots of three groups = 3/4 of the pass; 8 equal parts a quarter
-                K = pass_bytes <= (double)NBODY_PARTIAL_SUM_BUDGET_BYTES ? 1 : 0.75 * pass_bytes <= (double)NBODY_PARTIAL_SUM_BUDGET_BYTES ? 4 : 8;
-            }
-            // below 32768 tiles (N = 2^18) an extra launch costs more than the summation it hides: the automatic choice takes
-            // one part there (an explicit nbody_set_summation_parts is honoured at every size)
-            const int64_t min_tiles = c->sum_parts == 0 ? 32768 : 0;
-            if (!whole || (int64_t)S * S / 2 < min_tiles || n_groups < 2)
-                K = 1;
-            else if (K > 2 && n_groups % K != 0)
-                K = 2;
-            nbody_ctx::SymPlan plan;
-            for (int p = 0; p < K; ++p) {
-                nbody_ctx::SymPart part;
-                if (K == 1) {
-                    part.g0 = c->group_lo;
-                    part.g1 = c->group_lo + c->group_count;
-                } else if (K == 2) {
-                    part.g0 = p ? n_groups - 1 : 0;
-                    part.g1 = p ? n_groups : n_groups - 1;
-                } else if (K == 4 && n_groups == 8) {
-                    // 3 + 3 + 1 + 1 groups: what stays behind the force pass is the LAST part's summation (its partial sums are
-                    // read back at HBM speed: 0.2 GB per group and per million bodies^2 / split_len), so the last part is one
-                    // group, not two -- update_ms 0.50 -> 0.3 ms at N = 2^20 -- and the two slots hold three groups each
-                    static const int cut[5] = {0, 3, 6, 7, 8};
-                    part.g0 = cut[p];
-                    part.g1 = cut[p + 1];
-                } else {
-                    part.g0 = p * (n_groups / K);
-                    part.g1 = (p + 1) * (n_groups / K);
-                }
-                part.split_lo = std::max(own_lo, part.g0 * c->group_splits);
-                part.split_hi = std::min(own_hi, part.g1 * c->group_splits);
-                part.b0 = (int64_t)part.split_lo * L - c->row_lo;
-                part.rows = std::min<int64_t>((int64_t)part.split_hi * L, c->row_lo + c->row_count) - (int64_t)part.split_lo * L;
-                const size_t row_need = (size_t)sym_row_slots(S, SL) * (size_t)part.rows;
-                const size_t col_need = (size_t)(part.split_hi - part.split_lo) * (size_t)(S / 2) * (size_t)L;
-                if (K > 2) {  // two slots used in turn
-                    plan.row_entries = std::max(plan.row_entries, 2 * row_need);
-                    plan.col_entries = std::max(plan.col_entries, 2 * col_need);
-                } else {
-                    part.row_off = plan.row_entries;
-                    part.col_off = plan.col_entries;
-                    plan.row_entries += row_need;
-                    plan.col_entries += col_need;
-                }
-                std::vector<int4> tiles = list_rows(part.split_lo, part.split_hi);
-                std::vector<int2> diag;
-                for (int R = part.split_lo; R < part.split_hi && SL <= kDiagInTilesMinStrip; ++R)
-                    if (selected(R))
-                        diag.push_back(make_int2(R, R));
-                HIP_TRY(c, hipSetDevice(c->device));
-                if (!tiles.empty()) {
-                    HIP_TRY(c, hipMalloc((void **)&part.tiles, sizeof(int4) * tiles.size()));
-                    HIP_TRY(c, hipMemcpy(part.tiles, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice));
-                }
-                if (!diag.empty()) {
-                    HIP_TRY(c, hipMalloc((void **)&part.diag, sizeof(int2) * diag.size()));
-                    HIP_TRY(c, hipMemcpy(part.diag, diag.data(), sizeof(int2) * diag.size(), hipMemcpyHostToDevice));
-                }
-                part.n_tiles = (int)tiles.size();
-                part.n_diag = (int)diag.size();
-                plan.parts.push_back(part);
-            }
-            if (K > 2)
-                for (int p = 0; p < K; ++p) {
-                    plan.parts[(size_t)p].row_off = (p & 1) * (plan.row_entries / 2);
-                    plan.parts[(size_t)p].col_off = (p & 1) * (plan.col_entries / 2);
-                }
-            it = c->sym_plans.emplace(key, std::move(plan)).first;
-        }
-        const nbody_ctx::SymPlan &plan = it->second;
-        {
-            int rc = ensure_sym_buffers(c, plan.row_entries, plan.col_entries);
-            if (rc != NBODY_OK)
-                return rc;
-        }
-        const int K = (int)plan.parts.size();
-        SymArgs sa;
-        sa.pos = reinterpret_cast<const float4 *>(d_pos);
-        sa.n_total = (int)c->n_total;
-        sa.split_len = L;
-        sa.eps2 = softening * softening;
-        sa.eps_pp = c->eps_pp;
-        sa.split_mass = c->split_mass;
-        // 3 (default): packed two-columns-per-step loops, eight rows per lane on every tile of splits of whole 1024 bodies -- one
-        // kernel holds the equal-mass loop (S8) and the loop for arbitrary masses (S9), allocated for three waves per SIMD, which
-        // costs the equal-mass loop 0.1 % against its own four-waves kernel (144.33 / 144.39 against 144.17 / 144.19 ms per
-        // N = 2^20 pass, profiles/r03_ab_packed3_equal_mass.txt) and gives every tile with arbitrary masses the eight-row loop
-        // (164.0 against 176.2 ms with the four-row loop, profiles/r03_ab_general_mass_eight_rows.txt).  The other arrangements
-        // stay reachable through nbody_set_rows_per_lane for A/B measurement in one process: 2 = round 2's (equal-mass tiles eight
-        // rows in a four-waves kernel, the others four rows), 4 = four rows per lane everywhere, 1 = the one-column loops.
-        sa.packed = sym_packed(c);
-        sa.equal_mass_path = c->equal_mass_path ? 1 : 0;
-        const bool quarter = sym_quarter_tiles(L, sa.eps2, sa.eps_pp, sa.packed);  // small systems: no flags, no diagonal launch
-        auto part_args = [&](const nbody_ctx::SymPart &p) {
-            sa.row_partials = reinterpret_cast<float3 *>(c->partials) + p.row_off;
-            sa.col_partials = c->col_partials + p.col_off;
-            sa.tiles = p.tiles;
-            sa.n_tiles = p.n_tiles;
-            sa.strip_len = c->strip_len;
-            sa.diag_tiles = p.diag;
-            sa.n_diag = p.n_diag;
-            sa.row_lo = (int)(c->row_lo + p.b0);
-            sa.row_count = (int)p.rows;
-        };
-        HIP_TRY(c, hipSetDevice(c->device));
-        // the equal-mass flags once per step, by its first force call: a later call for other columns (the complement launch on
-        // a second stream, the ring's chunks) would rewrite the same values under the kernels that read them
-        if (quarter) {
-            // the quarter-tile kernel reads the masses itself
-        } else if (!c->flags_valid) {
-            HIP_TRY(c, launch_split_mass(sa.pos, c->split_mass, sa.n_total, L, c->equal_mass_path, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev_flags, c->stream));
-            c->flags_valid = true;
-        } else {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_flags, 0));  // written on the stream of the step's first call
-        }
-        // The auxiliary stream, beside the tile launches: a part's diagonal tiles (pairs inside one split; their own slot of
-        // the row-side array: 0.56 ms at N = 2^20 that no longer stands between the tiles and the summation), and, once the
-        // part's tile launch is over, its column-side sums per group and the row-side sums of its rows.  With two slots the
-        // diagonal tiles of part p + 2 follow the sums of part p on this stream, and the tile launch of part p + 2 waits for
-        // them (they ran beside part p + 1's tiles).
-        // (small systems, one part: the tile launch serves the diagonal tiles and nothing runs beside it -- no fork, no join:
-        // an eagerly enqueued step at N = 1024 took 29 us with them against 18.5 us replayed as a graph)
-        const bool aux_idle = quarter && K == 1;
-        if (!aux_idle) {
-            HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-        }
-        auto diag_launch = [&](int p) -> int {
-            if (aux_idle)
-                return NBODY_OK;
-            part_args(plan.parts[(size_t)p]);
-            TimedLaunch t(c, &c->ev_aux, &c->aux_ms, &c->aux_launches, c->aux_stream, true);  // reported separately
-            HIP_TRY(c, launch_forces_symmetric_diag(sa, c->aux_stream));
-            return NBODY_OK;
-        };
-        for (int p = 0; p < std::min(K, 2); ++p)
-            if (int rc = diag_launch(p))
-                return rc;
-        // Two parts (7 groups + 1): the last part's tiles go on a stream of the LOWEST priority that does not wait for the first
-        // part's -- the dispatcher serves the first part's workgroups while it has any and fills their tail with the second
-        // part's, so the extra launch costs no tail, and the first part's summation (7/8 of it) runs beside the second part's
-        // tiles instead of behind the pass.
-        if (K == 2 && !c->tail_stream) {
-            int least = 0, greatest = 0;
-            HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIP_TRY(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, least));
-        }
-        for (int p = 0; p < K; ++p) {
-            const nbody_ctx::SymPart &part = plan.parts[(size_t)p];
-            hipStream_t ts = K == 2 && p == 1 ? c->tail_stream : c->stream;
-            if (ts != c->stream)
-                HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_fork, 0));  // the positions and the equal-mass flags are in place
-            if (K > 2 && p >= 2)
-                HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_red[(size_t)p - 2], 0));
-            part_args(part);
-            {
-                TimedLaunch t(c, &c->ev_force, &c->force_ms, &c->force_launches, ts, true);  // the dominant kernel alone
-                HIP_TRY(c, launch_forces_symmetric(sa, ts));
-            }
-            if (p == K - 1) {
-                if (ts != c->stream) {  // the last part's sums are formed on the context's stream
-                    HIP_TRY(c, hipEventRecord(c->ev_tiles[(size_t)p], ts));
-                    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_tiles[(size_t)p], 0));
-                }
-                break;
-            }
-            HIP_TRY(c, hipEventRecord(c->ev_tiles[(size_t)p], ts));
-            HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_tiles[(size_t)p], 0));
-            {
-                TimedLaunch t(c, &c->ev_aux, &c->aux_ms, &c->aux_launches, c->aux_stream, true);  // overlapped, like the diagonal
-                HIP_TRY(c, launch_sym_colparts(c->col_partials + part.col_off, c->colparts, (int)c->n_total, L, S, part.split_lo,
-                                               c->group_splits, part.g0, part.g1 - part.g0, c->aux_stream));
-                HIP_TRY(c, launch_sym_rowsum(reinterpret_cast<const float3 *>(c->partials) + part.row_off, c->rowsum + part.b0,
-                                             (int)(c->row_lo + part.b0), (int)part.rows, L, S, c->group_splits, (int)c->row_count,
-                                             c->strip_len, c->aux_stream));
-            }
-            HIP_TRY(c, hipEventRecord(c->ev_red[(size_t)p], c->aux_stream));
-            if (p + 2 < K)
-                if (int rc = diag_launch(p + 2))
-                    return rc;
-        }
-        if (!aux_idle) {
-            HIP_TRY(c, hipEventRecord(c->ev_join, c->aux_stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        }
-        c->pending = &plan.parts.back();
-        for (int s = 0; s < c->n_splits; ++s)
-            if ((s >= first && s < first + count) != complement)
-                c->split_done[(size_t)s] = 1;
-        c->sym_reduced = c->sym_rows_summed = false;
+    if (c->flags_valid) {
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_flags, 0));  // written on the stream of the step's first call
         return NBODY_OK;
     }
+    HIP_TRY(c, launch_split_mass(pos, c->split_mass, (int)c->n_total, (int)c->split_len, c->equal_mass_path, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_flags, c->stream));
+    c->flags_valid = true;
+    return NBODY_OK;
+}
+
+static void mark_splits_done(nbody_ctx *c, int first, int count, bool complement)
+{
+    for (int s = 0; s < c->n_splits; ++s)
+        if ((s >= first && s < first + count) != complement)
+            c->split_done[(size_t)s] = 1;
+}
+
+static_assert(sizeof(SymStrip) == sizeof(int4) && std::is_standard_layout<SymStrip>::value, "strips go to the device as int4");
+static_assert(sizeof(SymDiag) == sizeof(int2) && std::is_standard_layout<SymDiag>::value, "diagonal tiles go to the device as int2");
+
+// The plan of this context's force calls for one column range: built by the first such call (nbody_sym_plan.h) and uploaded
+// in one step -- ONE allocation holds every part's strips, then every part's diagonal tiles; nothing stays allocated when
+// that fails.
+static int sym_plan_for(nbody_ctx *c, int first, int count, bool complement, const nbody_ctx::SymPlan **out)
+{
+    const auto key = std::make_tuple(first, count, complement);
+    auto it = c->sym_plans.find(key);
+    if (it == c->sym_plans.end()) {
+        const SymHostPlan host = sym_build_plan({c->n_total, (int)c->split_len, c->n_splits, c->strip_len, c->row_lo, c->row_count,
+                                                 c->group_splits, c->group_lo, c->group_count, first, count, complement, c->sum_parts});
+        std::vector<char> bytes;
+        auto append = [&](const auto &v) { bytes.insert(bytes.end(), (const char *)v.data(), (const char *)(v.data() + v.size())); };
+        for (const SymPlanPart &hp : host.parts)
+            append(hp.strips);
+        const size_t diag_bytes = bytes.size();
+        for (const SymPlanPart &hp : host.parts)
+            append(hp.diag);
+        nbody_ctx::SymPlan plan;
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (!bytes.empty()) {
+            HIP_TRY(c, hipMalloc(&plan.lists, bytes.size()));
+            const hipError_t e = hipMemcpy(plan.lists, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(plan.lists);
+                return fail(c, NBODY_ERR_DEVICE, std::string("hipMemcpy(pair-once plan): ") + hipGetErrorString(e));
+            }
+        }
+        const int4 *tiles = static_cast<const int4 *>(plan.lists);
+        const int2 *diag = reinterpret_cast<const int2 *>(static_cast<const char *>(plan.lists) + diag_bytes);
+        for (const SymPlanPart &hp : host.parts) {
+            const int n_tiles = (int)hp.strips.size(), n_diag = (int)hp.diag.size();
+            plan.parts.push_back({hp.g0, hp.g1, hp.split_lo, hp.b0, hp.rows, n_tiles ? tiles : nullptr, n_diag ? diag : nullptr,
+                                  n_tiles, n_diag, hp.row_off, hp.col_off});
+            tiles += n_tiles;
+            diag += n_diag;
+        }
+        plan.row_entries = host.row_entries;
+        plan.col_entries = host.col_entries;
+        it = c->sym_plans.emplace(key, std::move(plan)).first;
+    }
+    *out = &it->second;
+    return NBODY_OK;
+}
+
+// Pair-once mode: this context's tiles with a column split in the range asked for, in the parts of the range's plan.
+static int sym_forces(nbody_ctx *c, const float4 *pos, int first, int count, bool complement, float softening, const char *who)
+{
+    const int S = c->n_splits, L = (int)c->split_len;
+    const bool whole = c->row_lo == 0 && c->row_count == c->n_total && !complement && first == 0 && count == S;
+    if (!whole && c->pending && c->pending->g1 - c->pending->g0 != c->group_count)
+        for (int sp = 0; sp < S; ++sp)
+            if (c->split_done[(size_t)sp])
+                return fail(c, NBODY_ERR_STATE, std::string(who) + ": a column range after a call for all columns in several "
+                                                                    "summation parts: the earlier parts are already summed");
+    const int SL = c->strip_len;
+    if (SL > 1 && (first % SL != 0 || ((first + count) % SL != 0 && first + count != S)))
+        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": with strips of " + std::to_string(SL) + " column splits a column "
+                                                              "range must start and end on a multiple of that many splits");
+    const nbody_ctx::SymPlan *found = nullptr;
+    if (int rc = sym_plan_for(c, first, count, complement, &found))
+        return rc;
+    const nbody_ctx::SymPlan &plan = *found;
+    {
+        int rc = ensure_sym_buffers(c, plan.row_entries, plan.col_entries);
+        if (rc != NBODY_OK)
+            return rc;
+    }
+    const int K = (int)plan.parts.size();
+    SymArgs sa;
+    sa.pos = pos;
+    sa.n_total = (int)c->n_total;
+    sa.split_len = L;
+    sa.eps2 = softening * softening;
+    sa.eps_pp = c->eps_pp;
+    sa.split_mass = c->split_mass;
+    // 3 (default): packed two-columns-per-step loops, eight rows per lane on every tile of splits of whole 1024 bodies -- one
+    // kernel holds the equal-mass loop (S8) and the loop for arbitrary masses (S9), allocated for three waves per SIMD, which
+    // costs the equal-mass loop 0.1 % against its own four-waves kernel (144.33 / 144.39 against 144.17 / 144.19 ms per
+    // N = 2^20 pass, profiles/r03_ab_packed3_equal_mass.txt) and gives every tile with arbitrary masses the eight-row loop
+    // (164.0 against 176.2 ms with the four-row loop, profiles/r03_ab_general_mass_eight_rows.txt).  The other arrangements
+    // stay reachable through nbody_set_rows_per_lane for A/B measurement in one process: 2 = round 2's (equal-mass tiles eight
+    // rows in a four-waves kernel, the others four rows), 4 = four rows per lane everywhere, 1 = the one-column loops.
+    sa.packed = sym_packed(c);
+    sa.equal_mass_path = c->equal_mass_path ? 1 : 0;
+    const bool quarter = sym_quarter_tiles(L, sa.eps2, sa.eps_pp, sa.packed);  // small systems: no flags, no diagonal launch
+    auto part_args = [&](const nbody_ctx::SymPart &p) {
+        sa.row_partials = reinterpret_cast<float3 *>(c->partials) + p.row_off;
+        sa.col_partials = c->col_partials + p.col_off;
+        sa.tiles = p.tiles;
+        sa.n_tiles = p.n_tiles;
+        sa.strip_len = c->strip_len;
+        sa.diag_tiles = p.diag;
+        sa.n_diag = p.n_diag;
+        sa.row_lo = (int)(c->row_lo + p.b0);
+        sa.row_count = (int)p.rows;
+    };
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!quarter)  // the quarter-tile kernel reads the masses itself
+        if (int rc = ensure_split_flags(c, sa.pos))
+            return rc;
+    // The auxiliary stream, beside the tile launches: a part's diagonal tiles (pairs inside one split; their own slot of
+    // the row-side array: 0.56 ms at N = 2^20 that no longer stands between the tiles and the summation), and, once the
+    // part's tile launch is over, its column-side sums per group and the row-side sums of its rows.  With two slots the
+    // diagonal tiles of part p + 2 follow the sums of part p on this stream, and the tile launch of part p + 2 waits for
+    // them (they ran beside part p + 1's tiles).
+    // (small systems, one part: the tile launch serves the diagonal tiles and nothing runs beside it -- no fork, no join:
+    // an eagerly enqueued step at N = 1024 took 29 us with them against 18.5 us replayed as a graph)
+    const bool aux_idle = quarter && K == 1;
+    if (!aux_idle) {
+        HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
+    }
+    auto diag_launch = [&](int p) -> int {
+        if (aux_idle)
+            return NBODY_OK;
+        part_args(plan.parts[(size_t)p]);
+        TimedLaunch t(c, &c->ev_aux, &c->aux_ms, &c->aux_launches, c->aux_stream, true);  // reported separately
+        HIP_TRY(c, launch_forces_symmetric_diag(sa, c->aux_stream));
+        return NBODY_OK;
+    };
+    for (int p = 0; p < std::min(K, 2); ++p)
+        if (int rc = diag_launch(p))
+            return rc;
+    // Two parts (7 groups + 1): the last part's tiles go on a stream of the LOWEST priority that does not wait for the first
+    // part's -- the dispatcher serves the first part's workgroups while it has any and fills their tail with the second
+    // part's, so the extra launch costs no tail, and the first part's summation (7/8 of it) runs beside the second part's
+    // tiles instead of behind the pass.
+    if (K == 2 && !c->tail_stream) {
+        int least = 0, greatest = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, least));
+    }
+    for (int p = 0; p < K; ++p) {
+        const nbody_ctx::SymPart &part = plan.parts[(size_t)p];
+        hipStream_t ts = K == 2 && p == 1 ? c->tail_stream : c->stream;
+        if (ts != c->stream)
+            HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_fork, 0));  // the positions and the equal-mass flags are in place
+        if (K > 2 && p >= 2)
+            HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_red[(size_t)p - 2], 0));
+        part_args(part);
+        {
+            TimedLaunch t(c, &c->ev_force, &c->force_ms, &c->force_launches, ts, true);  // the dominant kernel alone
+            HIP_TRY(c, launch_forces_symmetric(sa, ts));
+        }
+        if (p == K - 1) {
+            if (ts != c->stream) {  // the last part's sums are formed on the context's stream
+                HIP_TRY(c, hipEventRecord(c->ev_tiles[(size_t)p], ts));
+                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_tiles[(size_t)p], 0));
+            }
+            break;
+        }
+        HIP_TRY(c, hipEventRecord(c->ev_tiles[(size_t)p], ts));
+        HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_tiles[(size_t)p], 0));
+        {
+            TimedLaunch t(c, &c->ev_aux, &c->aux_ms, &c->aux_launches, c->aux_stream, true);  // overlapped, like the diagonal
+            HIP_TRY(c, launch_sym_colparts(c->col_partials + part.col_off, c->colparts, (int)c->n_total, L, S, part.split_lo,
+                                           c->group_splits, part.g0, part.g1 - part.g0, c->aux_stream));
+            HIP_TRY(c, launch_sym_rowsum(reinterpret_cast<const float3 *>(c->partials) + part.row_off, c->rowsum + part.b0,
+                                         (int)(c->row_lo + part.b0), (int)part.rows, L, S, c->group_splits, (int)c->row_count,
+                                         c->strip_len, c->aux_stream));
+        }
+        HIP_TRY(c, hipEventRecord(c->ev_red[(size_t)p], c->aux_stream));
+        if (p + 2 < K)
+            if (int rc = diag_launch(p + 2))
+                return rc;
+    }
+    if (!aux_idle) {
+        HIP_TRY(c, hipEventRecord(c->ev_join, c->aux_stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    }
+    c->pending = &plan.parts.back();
+    mark_splits_done(c, first, count, complement);
+    c->sym_reduced = c->sym_rows_summed = false;
+    return NBODY_OK;
+}
+
+// One-sided mode: every row of this context against the column splits asked for, in one launch.
+static int one_sided_forces(nbody_ctx *c, const float4 *pos, int first, int count, bool complement, float softening)
+{
     {
         int rc = ensure_partials(c);
         if (rc != NBODY_OK)
@@ -1439,7 +1333,7 @@ static int forces_impl(nbody_ctx *c, const float *d_pos, int64_t col_lo, int64_t
     }
     ForceArgs a;
     a.split_mass = c->split_mass;
-    a.pos = reinterpret_cast<const float4 *>(d_pos);
+    a.pos = pos;
     a.partials = c->partials;
     a.row_lo = (int)c->row_lo;
     a.row_count = (int)c->row_count;
@@ -1465,23 +1359,40 @@ static int forces_impl(nbody_ctx *c, const float *d_pos, int64_t col_lo, int64_t
     // the one-wave kernel forms the equal-mass flag of a split of one or two tiles itself (from the tile it holds and, for the
     // second, the masses in memory): no launch in front
     a.own_split_mass = rpl == 41 && a.split_len <= 2 * kTile && c->equal_mass_path;
-    if (!a.own_split_mass) {  // once per step, see the pair-once branch
-        if (!c->flags_valid) {
-            HIP_TRY(c, launch_split_mass(a.pos, c->split_mass, a.n_total, a.split_len, c->equal_mass_path, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev_flags, c->stream));
-            c->flags_valid = true;
-        } else {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_flags, 0));
-        }
-    }
+    if (!a.own_split_mass)
+        if (int rc = ensure_split_flags(c, a.pos))
+            return rc;
     {
         TimedLaunch t(c, &c->ev_force, &c->force_ms, &c->force_launches);
         HIP_TRY(c, launch_forces(a, rpl, c->stream));
     }
-    for (int s = 0; s < c->n_splits; ++s)
-        if ((s >= first && s < first + count) != complement)
-            c->split_done[(size_t)s] = 1;
+    mark_splits_done(c, first, count, complement);
     return NBODY_OK;
+}
+
+static int forces_impl(nbody_ctx *c, const float *d_pos, int64_t col_lo, int64_t col_count, float softening,
+                       bool complement, const char *who)
+{
+    if (!c || (!d_pos && c->n_total))
+        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (!(softening >= 0.f) || !std::isfinite(softening))
+        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": softening must be finite and >= 0");
+    if (softening > 0.f && softening < NBODY_MIN_SOFTENING)
+        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": 0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass in the "
+                                                             "self pair); use 0 (zero-distance pairs then contribute nothing)");
+    if (col_lo < 0 || col_count < 0 || col_lo + col_count > c->n_total || col_lo % c->split_len != 0 ||
+        ((col_lo + col_count) % c->split_len != 0 && col_lo + col_count != c->n_total))
+        return fail(c, NBODY_ERR_INVALID, std::string(who) + ": column range must be split-aligned and inside [0,n_total]");
+    if (c->row_count == 0 || c->n_total == 0)
+        return NBODY_OK;
+    const int first = (int)(col_lo / c->split_len);
+    const int count = (int)((col_count + c->split_len - 1) / c->split_len);
+    if (complement ? count == c->n_splits : count == 0)
+        return NBODY_OK;  // no column selected
+    const float4 *pos = reinterpret_cast<const float4 *>(d_pos);
+    if (c->force_mode == NBODY_FORCE_SYMMETRIC)
+        return sym_forces(c, pos, first, count, complement, softening, who);
+    return one_sided_forces(c, pos, first, count, complement, softening);
 }
 
 int nbody_forces(nbody_ctx *c, const float *d_pos, int64_t col_lo, int64_t col_count, float softening)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nbody_sym_plan.h"  // the pair-once geometry: sym_rows_side, sym_row_slot, kSymGroups
+
 namespace nbody {
 
 constexpr int kTile = 256;  // bodies per LDS tile == threads per workgroup (reference BLOCK_SIZE, kernel.cu:65)
@@ -35,43 +37,6 @@ struct ForceArgs {
     const float *split_mass;  // [n_splits]: the one mass of a split's bodies, or NaN (launch_split_mass)
     int own_split_mass;       // force_kernel_r4pk_w1, one-tile splits: the kernel forms that flag itself (nothing was launched)
 };
-
-// Pair-once kernel (nbody_symmetric.hip): one workgroup per ordered pair of splits (R, C), R's bodies as rows (one
-// context's own rows), C's bodies as columns; each unordered pair {R, C} is computed once, by the owner of the side
-// sym_rows_side() names.
-constexpr int kSymGroups = 8;  // the canonical summation: 8 groups of ceil(n_splits / 8) splits, see sym_finalize
-
-// True when the tile of the unordered split pair {R, C} (R != C) is computed with R's bodies as rows: the "forward
-// half" of the ring of S splits, so every split is the row side of (S - 1) / 2 tiles -- equal work for every rank that
-// owns equally many splits.  A pure function of (R, C, S): the summation kernels use it to know which partial sums exist.
-__host__ __device__ inline bool sym_rows_side(int R, int C, int S)
-{
-    int d = C - R;
-    if (d < 0)
-        d += S;
-    if (d == 0)
-        return false;
-    if (2 * d != S)
-        return 2 * d < S;
-    const int lo = R < C ? R : C;  // S even, opposite splits: alternate
-    return ((lo & 1) == 0) == (R == lo);
-}
-
-// Strips (round 4).  A workgroup takes `strip_len` = K consecutive column splits of one row split -- the splits C with equal
-// C / K that form a tile with R (K = 1: every tile alone, rounds 1-3) -- and keeps the rows' sums in registers across them: one
-// row-side partial sum per (row, strip) instead of per (row, tile).  The strip that holds column split C is slot
-// sym_row_slot(R, C) of the row split's array: the blocks of K splits are counted along the ring from the block of R + 1 (K = 1:
-// the ring distance of the tile, the layout of rounds 1-3); slot 0 is the diagonal tile.  Blocks are absolute (C / K), the
-// number of splits is a multiple of 8 K, so a strip never straddles a summation group or a rank's column chunk: which sums
-// exist and in which order they are added is a function of (n_total, split_len) only, as before.
-__host__ __device__ inline int sym_row_slot(int R, int C, int S, int K)
-{
-    int j = C / K - ((R + 1) % S) / K;
-    if (j < 0)
-        j += S / K;
-    return j + 1;
-}
-__host__ __device__ inline int sym_row_slots(int S, int K) { return K == 1 ? S / 2 + 1 : S / (2 * K) + 3; }
 
 struct SymArgs {
     const float4 *pos;     // all n_total bodies

@@ -46,7 +46,7 @@ def pair_once_geometry(num_bodies: int, world_size: int, split_len: int):
 
 
 def sym_rows_side(r: int, c: int, n_splits: int) -> bool:
-    """nbody::sym_rows_side (csrc/nbody_kernels.h): is the tile of the split pair {r, c} computed with r's bodies as rows?"""
+    """nbody::sym_rows_side (csrc/nbody_sym_plan.h): is the tile of the split pair {r, c} computed with r's bodies as rows?"""
     d = (c - r) % n_splits
     if d == 0:
         return False
