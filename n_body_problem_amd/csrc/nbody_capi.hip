@@ -135,15 +135,6 @@ static bool sym_fused_finish(const nbody_ctx *c)
            c->pending->row_off == 0 && c->pending->col_off == 0 && c->n_splits <= fused_max_splits && c->strip_len == 1;
 }
 
-// SymArgs::packed of the context's rows-per-lane setting (nbody_set_rows_per_lane)
-static int sym_packed(const nbody_ctx *c)
-{
-    int packed = c->rows_per_lane == 4 ? 1 : c->rows_per_lane == 2 ? 2 : c->rows_per_lane == 1 ? 0 : 3;
-    if (packed >= 2 && !c->equal_mass_path)
-        packed = 3;  // no tile can take the equal-mass loop
-    return packed;
-}
-
 // Partial sums consumed or forgotten: the next force call starts a new step (and recomputes the equal-mass flags).
 static void clear_split_done(nbody_ctx *c)
 {
@@ -188,70 +179,9 @@ const char *nbody_status_string(int s)
 
 const char *nbody_last_error(const nbody_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-int64_t nbody_default_split_len(int64_t n_total)
-{
-    // Columns per partial sum.  A function of n_total ONLY: split boundaries define the summation order, so
-    // they must not depend on the sharding.  n_total/128 rounded up to whole 256-body tiles, at most 8192
-    // (32 LDS tiles): 128 splits up to 2^20 bodies (79 at the reference's 20 000), n_total/8192 beyond.
-    // Many short splits keep the grid fine-grained -- at N = 65 536 a 256-column split measured 20 % faster
-    // than a 4096-column one, and 8 ranks sharing N = 2^20 still get 128 row tiles x 128 splits each -- at
-    // the price of 16 B x n_splits per row of partial sums (2 GiB at N = 2^20, ~0.4 % of the step time).
-    if (n_total <= 0)
-        return kTile;
-    // Small systems (one-wave workgroups of 256 rows x one split, section "small systems" of DESIGN.md): the pass takes
-    // ceil(waves / 1024) rounds on the chip's 1024 SIMDs, so 256-column splits leave the reference's own size -- 20 225 bodies:
-    // 80 x 80 = 6400 waves, 6.25 per SIMD -- waiting for the SIMDs that got seven (profiles/r03_pmc_small_n_one_sided.txt: 83 % of
-    // the large kernel's VALU share).  Where that decomposition needs three rounds or more the split length (a multiple of 64)
-    // is the one (a multiple of 64 from 256 to 512: the one-wave kernel stages such a split whole) that minimises rounds x
-    // length, rounds = ceil(rows-of-256 x splits / 1024), among the lengths that leave at least four rounds (four waves per
-    // SIMD to hide each other's latencies): 20 225 and 20 000 bodies get 64 splits of 320 columns -- 5120 waves, five per SIMD,
-    // 5 x 320 = 1600 columns per SIMD instead of 7 x 256 = 1792; measured 100.4 against 108.3 us per force pass, 0.108 against
-    // 0.116 ms per step (profiles/r04_small_n_split.txt).  256 stays wherever nothing is strictly better (shorter splits were
-    // tried: the partial sums they add cost the update more than the pass gains).  Still a function of n_total only.
-    constexpr int64_t kOneWaveKernelBodies = 32768;  // below it a one-sided workgroup is one wave (force_kernel_r4pk_w1)
-    const int64_t rb = (n_total + kTile - 1) / kTile;
-    if (n_total < kOneWaveKernelBodies && rb * rb > 2048) {
-        auto rounds = [&](int64_t L) { return ((n_total + L - 1) / L * rb + 1023) / 1024; };
-        int64_t best = kTile;
-        for (int64_t L = kTile + 64; L <= 2 * kTile; L += 64)
-            if (rounds(L) >= 4 && rounds(L) * L < rounds(best) * best)
-                best = L;
-        return best;
-    }
-    int64_t len = (n_total + 127) / 128;
-    len = (len + kTile - 1) / kTile * kTile;
-    return len > 8192 ? 8192 : len;
-}
+int64_t nbody_default_split_len(int64_t n_total) { return default_split_len(n_total); }
 
-int64_t nbody_pair_once_split_len(int64_t n_total)
-{
-    // 1024 = the eight-row kernel's rows per pass with two waves (four-row kernel: four waves): shorter splits idle waves,
-    // longer ones coarsen the grid (N = 131072 on one GPU 3.6 / 4.6 / 6.2 ms with 1024 / 2048 / 512).  One pass writes
-    // n_total^2 / split_len partial sums of 12 bytes into the two arrays: from N = 2^20 on the splits are 2048 bodies -- half
-    // the partial sums (6.4 GB per pass at N = 2^20, held in 4 summation parts of which two exist at a time: 3.2 GB) and
-    // 2.2 % less time per step than 1024-body splits in 8 parts at the same memory (156.0 against 159.5 ms, one GPU; one
-    // rank of 8: 19.7 against 20.0 ms; profiles/r02_split_len_auto_parts_sustained.txt, r02_shard_rate_eight_rows_split_len.txt);
-    // at N = 524288 one rank of 8 would lose 5 % to 2048 (a quarter of the tiles per rank), so 1024 stays below 2^20.
-    // The length doubles again where 16-byte entries (round 1's layout: the bound is kept) would pass 150 GB: 4096 from
-    // N = 2^23 (N = 2^22: 2048, 103 GB per pass, 26 GB held).  A function of n_total only: split boundaries define the
-    // summation order.
-    // Below that the splits shrink with the system (more, smaller tiles to fill the chip; one or two waves per workgroup):
-    // 256 bodies up to 65 535, 512 up to 131 071 -- measured per size with the round-3 kernels, one GPU
-    // (profiles/r03_split_len_mid_range.txt: N = 49 152: 0.436 / 0.479 / 0.544 ms per step with 256 / 512 / 1024; 65 536:
-    // 0.722 / 0.715 / 0.840; 98 304: 1.582 / 1.524 / 1.591; 131 072: 2.79 / 2.66 / 2.62).  768 is no length for the tile
-    // kernels (two waves cover 512 rows per pass: the second pass would run half empty and the equal-mass loops are off
-    // where a pass is partial -- N = 196 608 ran at 8.88 ms per step with it, 5.79 with 1024).
-    const double pairs16 = 16.0 * (double)n_total * (double)n_total;
-    if (n_total < 65536)
-        return kTile;
-    if (n_total < 131072)
-        return 2 * kTile;
-    int64_t len;
-    len = n_total >= ((int64_t)1 << 20) ? 2048 : 1024;
-    while (len < 4096 && pairs16 / (double)len > 150e9)
-        len *= 2;
-    return len;
-}
+int64_t nbody_pair_once_split_len(int64_t n_total) { return pair_once_split_len(n_total); }
 
 static int morton_order_impl(const float *xyzm, int64_t n, int64_t *perm);
 
@@ -1044,27 +974,6 @@ int nbody_set_rows_per_lane(nbody_ctx *c, int rpl)
     return NBODY_OK;
 }
 
-// Largest register blocking that still fills the chip evenly; 4 rows per lane (the hand-allocated kernel) is fastest
-// once there are enough workgroups.  With short splits (<= 512 columns: one or two LDS tiles per workgroup) a
-// workgroup is over quickly and what counts is how evenly the last ones spread: measured at the reference's N = 20 225
-// (split 256) 1 row per lane 0.145 ms, 2: 0.152, 4: 0.156; from N = 32 768 on 4 wins (tools/small_n.py).  Speed only:
-// each row's sum is the same FMA chain whatever the blocking.
-static int pick_rows_per_lane(const nbody_ctx *c, int split_count)
-{
-    if (c->rows_per_lane)
-        return c->rows_per_lane;
-    const bool short_splits = c->split_len <= 512;
-    const int64_t want[1] = {(short_splits ? 10LL : 4LL) * c->cu_count};
-    const int64_t blocks4 = (c->row_count + (int64_t)kTile * 4 - 1) / ((int64_t)kTile * 4) * split_count;
-    if (blocks4 >= want[0])
-        return 4;
-    // too few 1024-row workgroups: the same packed loop with one wave (256 rows) per workgroup -- at every size below (N =
-    // 4096 ... 20 225: 29 / 34 / 59 / 78 / 121 us per step against 42 / 38 / 73 / 89 / 137 with the compiler-allocated one-row
-    // kernel, profiles/r03_small_n_blocking*.txt).  Per-particle softening: the same two kernels with the softening term in
-    // the loop (N = 20 225: 0.165 ms per step with the compiler-allocated one-row kernel it used to take).
-    return 41;
-}
-
 // The partial-sum array of the one-sided mode (a mode switch may need a larger one).
 static int ensure_partials(nbody_ctx *c)
 {
@@ -1229,9 +1138,9 @@ static int sym_forces(nbody_ctx *c, const float4 *pos, int first, int count, boo
     // (164.0 against 176.2 ms with the four-row loop, profiles/r03_ab_general_mass_eight_rows.txt).  The other arrangements
     // stay reachable through nbody_set_rows_per_lane for A/B measurement in one process: 2 = round 2's (equal-mass tiles eight
     // rows in a four-waves kernel, the others four rows), 4 = four rows per lane everywhere, 1 = the one-column loops.
-    sa.packed = sym_packed(c);
+    sa.packed = sym_packed(c->rows_per_lane, c->equal_mass_path);
     sa.equal_mass_path = c->equal_mass_path ? 1 : 0;
-    const bool quarter = sym_quarter_tiles(L, sa.eps2, sa.eps_pp, sa.packed);  // small systems: no flags, no diagonal launch
+    const SymChoice tiles = sym_tile_choice(L, sa.eps2 > 0.f, sa.eps_pp != nullptr, sa.packed, c->strip_len);
     auto part_args = [&](const nbody_ctx::SymPart &p) {
         sa.row_partials = reinterpret_cast<float3 *>(c->partials) + p.row_off;
         sa.col_partials = c->col_partials + p.col_off;
@@ -1244,7 +1153,7 @@ static int sym_forces(nbody_ctx *c, const float4 *pos, int first, int count, boo
         sa.row_count = (int)p.rows;
     };
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!quarter)  // the quarter-tile kernel reads the masses itself
+    if (tiles.reads_flags())
         if (int rc = ensure_split_flags(c, sa.pos))
             return rc;
     // The auxiliary stream, beside the tile launches: a part's diagonal tiles (pairs inside one split; their own slot of
@@ -1254,7 +1163,7 @@ static int sym_forces(nbody_ctx *c, const float4 *pos, int first, int count, boo
     // them (they ran beside part p + 1's tiles).
     // (small systems, one part: the tile launch serves the diagonal tiles and nothing runs beside it -- no fork, no join:
     // an eagerly enqueued step at N = 1024 took 29 us with them against 18.5 us replayed as a graph)
-    const bool aux_idle = quarter && K == 1;
+    const bool aux_idle = tiles.serves_diag() && K == 1;
     if (!aux_idle) {
         HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
@@ -1355,16 +1264,15 @@ static int one_sided_forces(nbody_ctx *c, const float4 *pos, int first, int coun
     if (a.split_count <= 0)
         return NBODY_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int rpl = pick_rows_per_lane(c, a.split_count);
-    // the one-wave kernel forms the equal-mass flag of a split of one or two tiles itself (from the tile it holds and, for the
-    // second, the masses in memory): no launch in front
-    a.own_split_mass = rpl == 41 && a.split_len <= 2 * kTile && c->equal_mass_path;
+    const ForceChoice k = force_choice(c->rows_per_lane, a.split_len, c->row_count, a.split_count, c->cu_count, a.eps2 > 0.f,
+                                       a.eps_pp != nullptr, c->equal_mass_path);
+    a.own_split_mass = k.own_split_mass;
     if (!a.own_split_mass)
         if (int rc = ensure_split_flags(c, a.pos))
             return rc;
     {
         TimedLaunch t(c, &c->ev_force, &c->force_ms, &c->force_launches);
-        HIP_TRY(c, launch_forces(a, rpl, c->stream));
+        HIP_TRY(c, launch_forces(a, k, c->stream));
     }
     mark_splits_done(c, first, count, complement);
     return NBODY_OK;
@@ -1627,13 +1535,6 @@ int nbody_step(nbody_ctx *c, float *d_pos, float *d_vel, const float *d_masses, 
     return rc == NBODY_OK ? nbody_sync(c) : rc;
 }
 
-// Measured (tools/graph_ab.py, profiles/r02_graph_replay_ab.txt): a graph launch costs ~10 us more than three kernels
-// enqueued back to back, so the one-sided step (flags, forces, update) is FASTER eager at every size (N = 256: 29 against
-// 40 us per step; N = 20 225: 143 against 153); the pair-once step is seven launches on two streams with events between
-// them, and there the replay wins up to a few ten thousand bodies (N = 4096: 96 against 114 us; N = 20 225: 169 against
-// 190; N = 65 536: 801 against 788).  Automatic = pair-once mode, at most this many bodies, and a step of more than two kernels.
-constexpr int64_t kGraphAutoBodies = 32768;
-
 int nbody_set_graph_replay(nbody_ctx *c, int mode)
 {
     if (!c || mode < -1 || mode > 1)
@@ -1661,13 +1562,9 @@ int nbody_step_n_on(nbody_ctx *c, float *d_pos, float *d_vel, int k, float dt, f
     if (!c || k < 0)
         return fail(c, NBODY_ERR_INVALID, "nbody_step_n: bad argument");
     const bool whole = c->row_lo == 0 && c->row_count == c->n_total;
-    // (round 4: where the tile launch serves the diagonal tiles too -- sym_quarter_tiles, one part -- a pair-once step is two
-    // kernels on one stream, and those are faster enqueued eagerly as well: N = 1024: 12.5 against 18.5 us per step, 20 225:
-    // 85.9 against 91.4, profiles/r04_pair_once_small_n.txt)
-    const bool two_kernels = c->force_mode == NBODY_FORCE_SYMMETRIC && c->sum_parts <= 1 &&  // (kick-drift-kick: three, fused finish)
-                             sym_quarter_tiles((int)c->split_len, softening * softening, c->eps_pp, sym_packed(c));
-    const bool want = c->graph_replay == 1 || (c->graph_replay == -1 && c->force_mode == NBODY_FORCE_SYMMETRIC &&
-                                               c->n_total <= kGraphAutoBodies && !two_kernels);
+    const bool want = graph_replay_wanted(c->graph_replay, c->force_mode == NBODY_FORCE_SYMMETRIC, c->sum_parts, c->n_total,
+                                          sym_tile_choice((int)c->split_len, softening * softening > 0.f, c->eps_pp != nullptr,
+                                                          sym_packed(c->rows_per_lane, c->equal_mass_path), c->strip_len));
     const bool use_graph = want && whole && !c->timing && k >= 3 && c->n_total > 0;
     int s = 0;
     if (use_graph) {

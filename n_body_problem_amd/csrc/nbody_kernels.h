@@ -4,11 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nbody_sym_plan.h"  // the pair-once geometry: sym_rows_side, sym_row_slot, kSymGroups
+#include "nbody_launch_choice.h"  // which kernel a launch_forces* call runs: kTile, ForceChoice, sym_tile_choice
+#include "nbody_sym_plan.h"       // the pair-once geometry: sym_rows_side, sym_row_slot, kSymGroups
 
 namespace nbody {
-
-constexpr int kTile = 256;  // bodies per LDS tile == threads per workgroup (reference BLOCK_SIZE, kernel.cu:65)
 
 // Zero-distance guard of the eps == 0 kernel variants: a pair whose r^2 is below 2^-84 (closer than 2.3e-13: the self
 // pair, coincident bodies, and bodies that only rounding has moved apart) contributes exactly 0 for ANY finite mass --
@@ -64,20 +63,10 @@ struct SymArgs {
                               // per lane on equal-mass tiles of splits of whole 1024 bodies; 3 (default): eight rows per lane
                               // on every tile of such splits (one kernel, allocated for three waves per SIMD)
 };
-// Small systems (256- and 512-body splits, the packed loops; not per-particle softening with eps = 0, where a pair may meet at r^2 = 0
-// unguarded, and not per-particle softening at all with 512-body splits): the tiles AND the diagonal tiles are served by force_sym_quarter_kernel in ONE launch (launch_forces_symmetric),
-// which needs no split_mass flags.
-inline bool sym_quarter_tiles(int split_len, float eps2, const float *eps_pp, int packed)
-{
-    if (split_len == 512)  // eight waves per tile; per-particle softening keeps the eight-row loops (S10 / S12) of force_sym_kernel there
-        return packed >= 2 && !eps_pp;
-    return split_len == 256 && packed >= 2 && !(eps_pp && !(eps2 > 0.f));
-}
 // split_mass[s] for every split of the body set, from the masses now in pos (O(N); see split_mass_kernel)
 hipError_t launch_split_mass(const float4 *pos, float *split_mass, int n_total, int split_len, bool enabled, hipStream_t stream);
-hipError_t launch_forces_symmetric(const SymArgs &a, hipStream_t stream);       // the tiles (R != C); sym_quarter_tiles(): and the diagonal tiles
-hipError_t launch_forces_symmetric_diag(const SymArgs &a, hipStream_t stream);  // the diagonal tiles (sym_quarter_tiles(): nothing left to do)
-size_t symmetric_lds_bytes(int split_len);
+hipError_t launch_forces_symmetric(const SymArgs &a, hipStream_t stream);       // sym_tile_choice(): the tiles (R != C), perhaps the diagonal tiles too
+hipError_t launch_forces_symmetric_diag(const SymArgs &a, hipStream_t stream);  // sym_diag_choice(): the diagonal tiles, if any are left
 
 // colparts[g][c] = sum over the own splits R of group g (ascending, where the tile (R, C(c)) exists) of P_col[R][c],
 // for the own groups [group_lo, group_lo + group_count) and every body c.  colparts is [kSymGroups][n_total].
@@ -102,8 +91,8 @@ hipError_t launch_sym_finish_kick(const float3 *row_partials, const float3 *col_
                                   int split_len, int n_splits, int group_splits, float dt, bool kick, hipStream_t stream);
 
 // Partial accelerations of rows [row_lo,row_lo+row_count) from splits [split_first, split_first+split_count).
-// rows_per_lane in {1,2,4,8}.  eps2 == 0 selects the zero-distance-guarded variant.
-hipError_t launch_forces(const ForceArgs &a, int rows_per_lane, hipStream_t stream);
+// k: force_choice() of the context and of a.split_len, a.eps2 and a.eps_pp (eps2 == 0 selects the zero-distance-guarded variant).
+hipError_t launch_forces(const ForceArgs &a, const ForceChoice &k, hipStream_t stream);
 
 // Sum the partials of n_splits splits in ascending order and kick-drift rows of this context.
 hipError_t launch_update(float4 *pos_all, float4 *vel_rows, const float4 *partials, int row_lo, int row_count,

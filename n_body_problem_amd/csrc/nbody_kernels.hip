@@ -12,6 +12,7 @@
 // The kernel is VALU-bound; HBM traffic is the O(N) state plus the partials.
 #include "nbody_kernels.h"
 
+#include <algorithm>
 #include <type_traits>
 
 namespace nbody {
@@ -728,96 +729,35 @@ __global__ __launch_bounds__(64) void force_kernel_r4pk_w1(ForceArgs a)
     if (row_base + 192 < a.row_count) out[row_base + 192] = make_float4(ax23.y * sc, ay23.y * sc, az23.y * sc, 0.f);
 }
 
-template <int QT>
-static void launch_w1(const ForceArgs &a, dim3 grid, hipStream_t stream)
-{
-    if (a.eps_pp) {  // per-particle softening (a particle may have eps = 0: the guard stays on when eps = 0)
-        if (a.eps2 > 0.f)
-            hipLaunchKernelGGL((force_kernel_r4pk_w1<false, QT, true>), grid, dim3(64), 0, stream, a);
-        else
-            hipLaunchKernelGGL((force_kernel_r4pk_w1<true, QT, true>), grid, dim3(64), 0, stream, a);
-    } else if (a.eps2 > 0.f) {
-        hipLaunchKernelGGL((force_kernel_r4pk_w1<false, QT>), grid, dim3(64), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((force_kernel_r4pk_w1<true, QT>), grid, dim3(64), 0, stream, a);
-    }
-}
+// Every instantiation of the one-sided force kernels, once: ForceChoice (nbody_launch_choice.h) names one of these rows.
+using ForceKernel = void (*)(ForceArgs);
+struct ForceEntry { ForceFamily family; int targ[3]; ForceKernel kernel; };
+#define FORCE_ROW(kernel, ...) {ForceFamily::kernel, {__VA_ARGS__}, &kernel<__VA_ARGS__>}
+#define FORCE_ROWS_RPL(RPL) \
+    FORCE_ROW(force_kernel, RPL, false, false), FORCE_ROW(force_kernel, RPL, true, false), \
+    FORCE_ROW(force_kernel, RPL, false, true), FORCE_ROW(force_kernel, RPL, true, true)
+#define FORCE_ROWS_W1(QT) \
+    FORCE_ROW(force_kernel_r4pk_w1, false, QT, false), FORCE_ROW(force_kernel_r4pk_w1, true, QT, false), \
+    FORCE_ROW(force_kernel_r4pk_w1, false, QT, true), FORCE_ROW(force_kernel_r4pk_w1, true, QT, true)
+static const ForceEntry kForceKernels[] = {
+    FORCE_ROWS_RPL(1), FORCE_ROWS_RPL(2), FORCE_ROWS_RPL(4), FORCE_ROWS_RPL(8),
+    FORCE_ROW(force_kernel_r4, false), FORCE_ROW(force_kernel_r4, true),
+    FORCE_ROW(force_kernel_r4pk, false, false), FORCE_ROW(force_kernel_r4pk, true, false),
+    FORCE_ROW(force_kernel_r4pk, false, true), FORCE_ROW(force_kernel_r4pk, true, true),
+    FORCE_ROWS_W1(0), FORCE_ROWS_W1(4), FORCE_ROWS_W1(5), FORCE_ROWS_W1(6), FORCE_ROWS_W1(7), FORCE_ROWS_W1(8),
+};
 
-static hipError_t launch_forces_r4pk_w1(const ForceArgs &a, hipStream_t stream)
-{
-    dim3 grid((a.row_count + kTile - 1) / kTile, a.split_count, 1);
-    switch (a.split_len <= 2 * kTile ? (a.split_len + 63) / 64 : 0) {  // splits of up to 512 columns are staged whole
-    case 0: launch_w1<0>(a, grid, stream); break;
-    case 5: launch_w1<5>(a, grid, stream); break;
-    case 6: launch_w1<6>(a, grid, stream); break;
-    case 7: launch_w1<7>(a, grid, stream); break;
-    case 8: launch_w1<8>(a, grid, stream); break;
-    default: launch_w1<4>(a, grid, stream); break;  // 256 columns or fewer
-    }
-    return hipGetLastError();
-}
-
-static hipError_t launch_forces_r4pk(const ForceArgs &a, hipStream_t stream)
-{
-    dim3 grid((a.row_count + kTile * 4 - 1) / (kTile * 4), a.split_count, 1);
-    if (a.eps_pp) {
-        if (a.eps2 > 0.f)
-            hipLaunchKernelGGL((force_kernel_r4pk<false, true>), grid, dim3(kTile), 0, stream, a);
-        else
-            hipLaunchKernelGGL((force_kernel_r4pk<true, true>), grid, dim3(kTile), 0, stream, a);
-    } else if (a.eps2 > 0.f) {
-        hipLaunchKernelGGL((force_kernel_r4pk<false, false>), grid, dim3(kTile), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((force_kernel_r4pk<true, false>), grid, dim3(kTile), 0, stream, a);
-    }
-    return hipGetLastError();
-}
-
-template <int RPL>
-static hipError_t launch_forces_rpl(const ForceArgs &a, hipStream_t stream)
-{
-    const int rows_per_block = kTile * RPL;
-    dim3 grid((a.row_count + rows_per_block - 1) / rows_per_block, a.split_count, 1);
-    if (a.eps_pp) {  // per-particle softening: a particle may have eps = 0, so the guard stays on when eps = 0
-        if (a.eps2 > 0.f)
-            hipLaunchKernelGGL((force_kernel<RPL, false, true>), grid, dim3(kTile), 0, stream, a);
-        else
-            hipLaunchKernelGGL((force_kernel<RPL, true, true>), grid, dim3(kTile), 0, stream, a);
-        return hipGetLastError();
-    }
-    if (a.eps2 > 0.f)
-        hipLaunchKernelGGL((force_kernel<RPL, false>), grid, dim3(kTile), 0, stream, a);
-    else
-        hipLaunchKernelGGL((force_kernel<RPL, true>), grid, dim3(kTile), 0, stream, a);
-    return hipGetLastError();
-}
-
-static hipError_t launch_forces_r4_asm(const ForceArgs &a, hipStream_t stream)
-{
-    dim3 grid((a.row_count + kTile * 4 - 1) / (kTile * 4), a.split_count, 1);
-    if (a.eps2 > 0.f)
-        hipLaunchKernelGGL(force_kernel_r4<false>, grid, dim3(kTile), 0, stream, a);
-    else
-        hipLaunchKernelGGL(force_kernel_r4<true>, grid, dim3(kTile), 0, stream, a);
-    return hipGetLastError();
-}
-
-// rows_per_lane: 4 = the hand-allocated kernel (default), 41 = the same with one wave per workgroup (small systems), 1/2/8 and
-// -4 = the compiler-allocated template
-hipError_t launch_forces(const ForceArgs &a, int rows_per_lane, hipStream_t stream)
+hipError_t launch_forces(const ForceArgs &a, const ForceChoice &k, hipStream_t stream)
 {
     if (a.row_count <= 0 || a.split_count <= 0)
         return hipSuccess;
-    switch (rows_per_lane) {
-    case 1: return launch_forces_rpl<1>(a, stream);
-    case 2: return launch_forces_rpl<2>(a, stream);
-    case 4: return launch_forces_r4pk(a, stream);     // packed fp32 (default); per-particle softening: its own loop
-    case 40: return a.eps_pp ? launch_forces_rpl<4>(a, stream) : launch_forces_r4_asm(a, stream);  // one row per instruction
-    case 41: return launch_forces_r4pk_w1(a, stream);  // packed, one wave per workgroup
-    case -4: return launch_forces_rpl<4>(a, stream);
-    case 8: return launch_forces_rpl<8>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    for (const ForceEntry &e : kForceKernels)
+        if (e.family == k.family && std::equal(e.targ, e.targ + 3, k.targ)) {
+            const dim3 grid((a.row_count + k.rows_per_block - 1) / k.rows_per_block, a.split_count, 1);
+            hipLaunchKernelGGL(e.kernel, grid, dim3(k.threads), 0, stream, a);
+            return hipGetLastError();
+        }
+    return hipErrorInvalidValue;  // no such blocking
 }
 
 // The splits' partial sums of row r, added in ascending split order (one fp32 chain: the order defines the bits).  The

@@ -35,6 +35,7 @@
 // arbitrary masses.
 #include "nbody_kernels.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -44,7 +45,7 @@
 namespace nbody {
 
 // A tile's workgroup has W wave64 (W x 256 rows per pass): 4 for splits of 1024 bodies or more, fewer for the shorter
-// splits of small systems, so that no wave is left without rows (sym_waves()).
+// splits of small systems, so that no wave is left without rows (sym_tile_choice()).
 constexpr int kSymRows = 4;  // rows per lane
 constexpr int kSymStageFloatsPerWave = 512;  // per wave 2 KiB, 1 KiB-aligned: one 64-body group as float4[64] (or SoA, below)
 
@@ -1532,18 +1533,32 @@ __global__ __launch_bounds__(64 * W) void force_sym_general_kernel(SymArgs a)
 
 
 
-// waves per tile workgroup: W x 256 rows per pass must not exceed the split
-static int sym_waves(int split_len) { return split_len >= 1024 ? 4 : split_len >= 512 ? 2 : 1; }
+static_assert(kSymStageBytesPerWave == kSymStageFloatsPerWave * sizeof(float), "sym_lds_bytes() sizes the stages the kernels lay out");
 
-// the column-group stage, three column-sum arrays, and the per-wave eps_j^2 stage of the per-particle-softening variant
-size_t symmetric_lds_bytes(int split_len)
-{
-    const size_t w = (size_t)sym_waves(split_len);
-    return w * kSymStageFloatsPerWave * sizeof(float) + (size_t)split_len * 12 + w * 128 * sizeof(float);
-}
+// Every instantiation of the pair-once force kernels, once: SymChoice (nbody_launch_choice.h) names one of these rows.
+using SymKernel = void (*)(SymArgs);
+struct SymEntry { SymFamily family; int targ[4]; SymKernel kernel; };
+#define SYM_ROW(kernel, ...) {SymFamily::kernel, {__VA_ARGS__}, &kernel<__VA_ARGS__>}
+#define SYM_ROWS_TILE(W) \
+    SYM_ROW(force_sym_kernel, W, false, 0, 0), SYM_ROW(force_sym_kernel, W, true, 0, 0), SYM_ROW(force_sym_kernel, W, false, 4, 0)
+#define SYM_ROWS_GENERAL(W) \
+    SYM_ROW(force_sym_general_kernel, W, false, false, true), SYM_ROW(force_sym_general_kernel, W, false, true, true), \
+    SYM_ROW(force_sym_general_kernel, W, true, false, false), SYM_ROW(force_sym_general_kernel, W, true, true, false), \
+    SYM_ROW(force_sym_general_kernel, W, true, false, true), SYM_ROW(force_sym_general_kernel, W, true, true, true)
+static const SymEntry kSymKernels[] = {
+    SYM_ROW(force_sym_quarter_kernel, 0, 1), SYM_ROW(force_sym_quarter_kernel, 1, 1), SYM_ROW(force_sym_quarter_kernel, 2, 1),
+    SYM_ROW(force_sym_quarter_kernel, 0, 2), SYM_ROW(force_sym_quarter_kernel, 2, 2),
+    SYM_ROWS_TILE(1), SYM_ROWS_TILE(2), SYM_ROWS_TILE(4),
+    SYM_ROW(force_sym_kernel, 4, false, 0, 2), SYM_ROW(force_sym_kernel, 4, true, 0, 2), SYM_ROW(force_sym_kernel, 4, false, 4, 2),
+    SYM_ROW(force_sym_kernel, 2, false, 1, 0), SYM_ROW(force_sym_kernel, 4, false, 1, 0), SYM_ROW(force_sym_kernel, 4, false, 1, 2),
+    SYM_ROW(force_sym_kernel, 2, false, 2, 0), SYM_ROW(force_sym_kernel, 4, false, 2, 0),
+    SYM_ROW(force_sym_kernel, 2, false, 2, 1), SYM_ROW(force_sym_kernel, 4, false, 2, 1),
+    SYM_ROW(force_sym_kernel, 1, false, 3, 0), SYM_ROW(force_sym_kernel, 2, false, 3, 0), SYM_ROW(force_sym_kernel, 4, false, 3, 0),
+    SYM_ROW(force_sym_kernel, 1, false, 3, 1), SYM_ROW(force_sym_kernel, 2, false, 3, 1), SYM_ROW(force_sym_kernel, 4, false, 3, 1),
+    SYM_ROWS_GENERAL(1), SYM_ROWS_GENERAL(2), SYM_ROWS_GENERAL(4),
+};
 
-template <typename K>
-static hipError_t sym_launch(K kernel, int blocks, int waves, size_t lds, const SymArgs &a, hipStream_t stream)
+static hipError_t sym_launch(SymKernel kernel, int blocks, int waves, size_t lds, const SymArgs &a, hipStream_t stream)
 {
     if (blocks <= 0)
         return hipSuccess;
@@ -1569,119 +1584,31 @@ static hipError_t sym_launch(K kernel, int blocks, int waves, size_t lds, const 
     return hipGetLastError();
 }
 
-static size_t sym_lds_bytes_for(int waves, int split_len)
+static hipError_t sym_launch_choice(const SymChoice &k, int blocks, const SymArgs &a, hipStream_t stream)
 {
-    return (size_t)waves * kSymStageFloatsPerWave * sizeof(float) + (size_t)split_len * 12 + (size_t)waves * 128 * sizeof(float);
-}
-
-template <int W>
-static hipError_t sym_launch_tiles(const SymArgs &a, size_t lds, hipStream_t stream)
-{
-    if constexpr (W == 4) {
-        if (a.strip_len > 1) {  // the kernels that cannot keep a strip's rows in registers add its tiles' row sums in memory
-            if (a.eps_pp && a.eps2 > 0.f && a.packed >= 2)
-                return sym_launch(&force_sym_kernel<4, false, 4, 2>, a.n_tiles, 4, lds, a, stream);
-            if (a.eps_pp)
-                return a.eps2 > 0.f ? sym_launch(&force_sym_general_kernel<4, false, false, true>, a.n_tiles, 4, lds, a, stream)
-                                    : sym_launch(&force_sym_general_kernel<4, false, true, true>, a.n_tiles, 4, lds, a, stream);
-            return a.eps2 > 0.f ? sym_launch(&force_sym_kernel<4, false, 0, 2>, a.n_tiles, 4, lds, a, stream)
-                                : sym_launch(&force_sym_kernel<4, true, 0, 2>, a.n_tiles, 4, lds, a, stream);
+    for (const SymEntry &e : kSymKernels)
+        if (e.family == k.family && std::equal(e.targ, e.targ + 4, k.targ)) {
+            if (k.lds)
+                return sym_launch(e.kernel, blocks, k.waves, k.lds, a, stream);
+            // the quarter-tile kernels use no dynamic LDS: no attribute to set, and their steps are launch-bound (12.5 us at
+            // N = 1024, profiles/r04_pair_once_small_n.txt), so they pass by the cache above and its mutex
+            if (blocks > 0)
+                hipLaunchKernelGGL(e.kernel, dim3(blocks), dim3(k.threads()), 0, stream, a);
+            return hipGetLastError();
         }
-    }
-    // per-particle softening: the four-row loop S11 with eps > 0; with eps = 0 a particle may have eps_i = 0 too and the guarded,
-    // compiler-scheduled kernel runs (NBODY_SYM_PACKED=0 / rows_per_lane 4: that kernel always -- A/B, tests)
-    if (a.eps_pp && a.eps2 > 0.f && a.packed >= 2)
-        return sym_launch(&force_sym_kernel<W, false, 4>, a.n_tiles, W, lds, a, stream);
-    if (a.eps_pp)
-        return a.eps2 > 0.f ? sym_launch(&force_sym_general_kernel<W, false, false, true>, a.n_tiles, W, lds, a, stream)
-                            : sym_launch(&force_sym_general_kernel<W, false, true, true>, a.n_tiles, W, lds, a, stream);
-    return a.eps2 > 0.f ? sym_launch(&force_sym_kernel<W, false>, a.n_tiles, W, lds, a, stream)
-                        : sym_launch(&force_sym_kernel<W, true>, a.n_tiles, W, lds, a, stream);
-}
-
-template <int W>
-static hipError_t sym_launch_diag(const SymArgs &a, size_t lds, hipStream_t stream)
-{
-    if (a.eps_pp)
-        return a.eps2 > 0.f ? sym_launch(&force_sym_general_kernel<W, true, false, true>, a.n_diag, W, lds, a, stream)
-                            : sym_launch(&force_sym_general_kernel<W, true, true, true>, a.n_diag, W, lds, a, stream);
-    return a.eps2 > 0.f ? sym_launch(&force_sym_general_kernel<W, true, false, false>, a.n_diag, W, lds, a, stream)
-                        : sym_launch(&force_sym_general_kernel<W, true, true, false>, a.n_diag, W, lds, a, stream);
+    return hipErrorInvalidValue;  // a choice without an instantiation
 }
 
 hipError_t launch_forces_symmetric(const SymArgs &a, hipStream_t stream)
 {
-    if (sym_quarter_tiles(a.split_len, a.eps2, a.eps_pp, a.packed)) {  // small systems: tiles and diagonal tiles in one launch
-        if (a.n_tiles + a.n_diag > 0) {
-            const dim3 grid(a.n_tiles + a.n_diag);
-            const int loop = a.eps_pp ? 1 : a.eps2 > 0.f ? 0 : 2;
-            if (a.split_len == 256) {
-                if (loop == 1)
-                    hipLaunchKernelGGL((force_sym_quarter_kernel<1, 1>), grid, dim3(256), 0, stream, a);
-                else if (loop == 0)
-                    hipLaunchKernelGGL((force_sym_quarter_kernel<0, 1>), grid, dim3(256), 0, stream, a);
-                else
-                    hipLaunchKernelGGL((force_sym_quarter_kernel<2, 1>), grid, dim3(256), 0, stream, a);
-            } else {  // (sym_quarter_tiles: no per-particle softening here)
-                if (loop == 0)
-                    hipLaunchKernelGGL((force_sym_quarter_kernel<0, 2>), grid, dim3(512), 0, stream, a);
-                else
-                    hipLaunchKernelGGL((force_sym_quarter_kernel<2, 2>), grid, dim3(512), 0, stream, a);
-            }
-        }
-        return hipGetLastError();
-    }
-    // eight rows per lane for the equal-mass tiles (packed == 2): half the waves per split, 512 rows each
-    // (512-body splits, one wave per workgroup, measured 0.8 % slower than the four-row loop at N = 131072: multiples of
-    // 1024 only)
-    if (a.packed >= 2 && a.eps_pp && a.eps2 > 0.f && a.split_len % 512 == 0) {  // per-particle softening: the eight-row loop S10
-        const int w8 = a.split_len % 2048 == 0 ? 4 : a.split_len % 1024 == 0 ? 2 : 1;  // whole passes of 512 rows per wave
-        const size_t lds8 = sym_lds_bytes_for(w8, a.split_len);
-        if (a.split_len == 512 * w8)  // one pass: the rows stay in registers across a strip
-            return w8 == 4   ? sym_launch(&force_sym_kernel<4, false, 3, 1>, a.n_tiles, 4, lds8, a, stream)
-                   : w8 == 2 ? sym_launch(&force_sym_kernel<2, false, 3, 1>, a.n_tiles, 2, lds8, a, stream)
-                             : sym_launch(&force_sym_kernel<1, false, 3, 1>, a.n_tiles, 1, lds8, a, stream);
-        return w8 == 4   ? sym_launch(&force_sym_kernel<4, false, 3>, a.n_tiles, 4, lds8, a, stream)
-               : w8 == 2 ? sym_launch(&force_sym_kernel<2, false, 3>, a.n_tiles, 2, lds8, a, stream)
-                         : sym_launch(&force_sym_kernel<1, false, 3>, a.n_tiles, 1, lds8, a, stream);
-    }
-    if ((a.packed == 2 || a.packed == 3) && !a.eps_pp && a.eps2 > 0.f && a.split_len % 1024 == 0) {
-        const int w8 = a.split_len % 2048 == 0 ? 4 : 2;  // whole passes of 512 rows per wave
-        const size_t lds8 = sym_lds_bytes_for(w8, a.split_len);
-        if (a.packed == 3 && a.split_len == 512 * w8)  // both eight-row loops, one pass: the rows stay in registers across a strip
-            return w8 == 4 ? sym_launch(&force_sym_kernel<4, false, 2, 1>, a.n_tiles, 4, lds8, a, stream)
-                           : sym_launch(&force_sym_kernel<2, false, 2, 1>, a.n_tiles, 2, lds8, a, stream);
-        if (a.packed == 3)  // the eight-row loop for arbitrary masses too (three waves per SIMD)
-            return w8 == 4 ? sym_launch(&force_sym_kernel<4, false, 2>, a.n_tiles, 4, lds8, a, stream)
-                           : sym_launch(&force_sym_kernel<2, false, 2>, a.n_tiles, 2, lds8, a, stream);
-        if (a.strip_len > 1)  // strips exist with 2048-body splits only: four waves
-            return sym_launch(&force_sym_kernel<4, false, 1, 2>, a.n_tiles, 4, lds8, a, stream);
-        return w8 == 4 ? sym_launch(&force_sym_kernel<4, false, 1>, a.n_tiles, 4, lds8, a, stream)
-                       : sym_launch(&force_sym_kernel<2, false, 1>, a.n_tiles, 2, lds8, a, stream);
-    }
-    const size_t lds = symmetric_lds_bytes(a.split_len);
-    switch (sym_waves(a.split_len)) {
-    case 4: return sym_launch_tiles<4>(a, lds, stream);
-    case 2: return sym_launch_tiles<2>(a, lds, stream);
-    default: return sym_launch_tiles<1>(a, lds, stream);
-    }
+    const SymChoice k = sym_tile_choice(a.split_len, a.eps2 > 0.f, a.eps_pp != nullptr, a.packed, a.strip_len);
+    return sym_launch_choice(k, a.n_tiles + (k.serves_diag() ? a.n_diag : 0), a, stream);
 }
 
 hipError_t launch_forces_symmetric_diag(const SymArgs &a, hipStream_t stream)
 {
-    if (sym_quarter_tiles(a.split_len, a.eps2, a.eps_pp, a.packed))
-        return hipSuccess;  // served by the tile launch
-    // A diagonal workgroup must fit where a tile workgroup leaves: beside the two-wave tile kernels of 1024-body splits
-    // (three waves of ~165 registers per SIMD) a four-wave diagonal workgroup found room only in the launch's tail -- at N = 131 072
-    // the diagonal launch ended 85 us after the tiles and was the step's critical path (profiles/r04_diagonal_tiles.txt).
-    if (a.split_len == 1024)
-        return sym_launch_diag<2>(a, sym_lds_bytes_for(2, a.split_len), stream);
-    const size_t lds = symmetric_lds_bytes(a.split_len);
-    switch (sym_waves(a.split_len)) {
-    case 4: return sym_launch_diag<4>(a, lds, stream);
-    case 2: return sym_launch_diag<2>(a, lds, stream);
-    default: return sym_launch_diag<1>(a, lds, stream);
-    }
+    const SymChoice k = sym_diag_choice(a.split_len, a.eps2 > 0.f, a.eps_pp != nullptr, a.packed);
+    return k.family == SymFamily::none ? hipSuccess : sym_launch_choice(k, a.n_diag, a, stream);
 }
 
 // ---- the canonical summation of the pair-once partial sums (HBM-bound, O(N n_splits)) ------------------------------
