@@ -484,8 +484,10 @@ float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
  *   corrector in fp64 from the fp32 operands, each result rounded once to fp32 (x1 uses the rounded v1).
  *   KDK and Hermite keep a0 (and j0) in a handle-owned cache between calls (Hermite: a second B x max_bodies float4 array,
  *   allocated on its first use); the cache is forgotten on new counts, another softening, other buffers, another integrator
- *   or nbody_batch_invalidate_forces (new contents in the same buffers need that call).  Fixed, shared steps only: no
- *   individual or adaptive time steps, no P(EC)^n iteration, no fp64 state.
+ *   or nbody_batch_invalidate_forces (new contents in the same buffers need that call).  nbody_batch_step_n_* takes fixed,
+ *   shared steps; nbody_batch_evolve_on (nbody_batch_evolve.h, included below, which states the scheme) gives every system
+ *   its own adaptive step h = dt_max 2^-L from Aarseth's criterion and evolves all of them to a common time.  No
+ *   individual per-body time steps, no P(EC)^n iteration, no fp64 state.
  * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
  * [1, NBODY_BATCH_MAX_BODIES], counts outside [0, max_bodies], k < 0, a non-finite dt, the softening rule, NULL pointers.
  * nbody_batch_step_n_on returns with the work complete, _async only enqueues (nbody_batch_sync waits).  Diagnostics are
@@ -507,6 +509,9 @@ int nbody_batch_sync(nbody_batch *b);
 int nbody_batch_energy(nbody_batch *b, const float *d_positions_xyzm, const float *d_velocities_xyzw, float softening,
                        double *out3B);
 int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const float *d_velocities_xyzw, double *out4B);
+
+/* adaptive shared time steps for Hermite batches: the evolve-to-a-time entry points, declared in a header of their own */
+#include "nbody_batch_evolve.h"
 
 #ifdef __cplusplus
 }

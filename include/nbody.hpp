@@ -298,6 +298,26 @@ public:
         check(nbody_batch_step_n_async(b_, dPositions, dVelocities, k, dt, softening), "nbody_batch_step_n_async");
     }
     void sync() { check(nbody_batch_sync(b_), "nbody_batch_sync"); }
+    // Adaptive shared steps (NBODY_INTEGRATOR_HERMITE only, nbody_batch_evolve.h): every system advances by
+    // nIntervals x cfg.dt_max on its own step; returns with the work complete.  Throws when a system runs out of
+    // cfg.max_steps: evolveStats() then tells where each system stands, and the same call again continues.
+    struct EvolveStats {
+        std::vector<std::int64_t> steps, clamped, ticks;
+        std::vector<int> minLevel, maxLevel;
+    };
+    void evolve(float *dPositions, float *dVelocities, std::int64_t nIntervals, const nbody_batch_evolve_config &cfg)
+    {
+        check(nbody_batch_evolve_on(b_, dPositions, dVelocities, nIntervals, &cfg), "nbody_batch_evolve_on");
+    }
+    EvolveStats evolveStats()
+    {
+        EvolveStats s;
+        const size_t n = (size_t)systems_;
+        s.steps.resize(n), s.clamped.resize(n), s.ticks.resize(n), s.minLevel.resize(n), s.maxLevel.resize(n);
+        check(nbody_batch_evolve_stats(b_, s.steps.data(), s.minLevel.data(), s.maxLevel.data(), s.clamped.data(), s.ticks.data()),
+              "nbody_batch_evolve_stats");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

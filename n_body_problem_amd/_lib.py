@@ -137,6 +137,23 @@ _PROTOTYPES = {
 }
 
 
+class BatchEvolveConfig(ctypes.Structure):
+    """``nbody_batch_evolve_config`` of include/nbody_batch_evolve.h."""
+    _fields_ = [("dt_max", c_float), ("levels", c_int), ("eta", c_float), ("eta_start", c_float), ("softening", c_float),
+                ("max_steps", c_int)]
+
+
+#: the entry points of include/nbody_batch_evolve.h (adaptive shared steps for Hermite batches), which nbody.h includes
+_EVOLVE_PROTOTYPES = {
+    "nbody_batch_evolve_on": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(BatchEvolveConfig)]),
+    "nbody_batch_evolve_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int), POINTER(c_int), POINTER(c_int64),
+                                         POINTER(c_int64)]),
+    "nbody_batch_evolve_launch_steps": (c_int, [c_void_p, c_int]),
+}
+BATCH_EVOLVE_MAX_LEVELS = 20
+BATCH_EVOLVE_DEFAULT_MAX_STEPS = 1048576
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -161,7 +178,7 @@ def load() -> ctypes.CDLL:
         except ImportError:  # a torch-free host (ctypes only) uses the system runtime
             pass
         lib = ctypes.CDLL(path)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -170,7 +187,13 @@ def load() -> ctypes.CDLL:
 
 
 def exported_names():
+    """The entry points nbody.h itself declares."""
     return list(_PROTOTYPES)
+
+
+def evolve_names():
+    """The entry points of nbody_batch_evolve.h."""
+    return list(_EVOLVE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

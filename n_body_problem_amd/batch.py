@@ -37,7 +37,8 @@ class BatchedSystem:
     ``"kdk"`` (velocity Verlet, second order, with the accelerations cached across calls) or ``"hermite"`` (the
     fourth-order Hermite predictor-corrector of direct-summation codes such as NBODY6: one force-and-jerk evaluation per
     step, about twice a force evaluation, with the accelerations and jerks cached across calls; ``nbody.h`` states the
-    scheme).  Every integrator uses a fixed step shared by all systems.
+    scheme).  :meth:`step_n` takes a fixed step shared by all systems; :meth:`evolve` (Hermite only) gives every system
+    its own adaptive step and brings all of them to a common time.
     """
 
     def __init__(self, num_systems: int, max_bodies: int, device: int = 0, counts=None, integrator: str = "kick_drift"):
@@ -146,6 +147,36 @@ class BatchedSystem:
         _check(self._lib, self._lib.nbody_batch_step_n_async(self._h, _ptr(self.positions), _ptr(self.velocities), int(k),
                                                              float(dt), float(softening)), self._h)
 
+    def evolve(self, n_intervals: int, dt_max: float, levels: int = 12, eta: float = 0.01, eta_start: float = 0.01,
+               softening: float = SOFTENING_VERSION3, max_steps: int = 0) -> "EvolveResult":
+        """Advance every system by ``n_intervals * dt_max``, each on its own step ``dt_max * 2**-L`` (``0 <= L <= levels``)
+        chosen after every step from Aarseth's criterion with accuracy parameter ``eta`` (``eta_start``: the first step);
+        Hermite batches only, ``include/nbody_batch_evolve.h`` states the scheme.  Time is counted in integer ticks of
+        ``dt_max * 2**-levels``, so every system lands on the end time exactly.  ``max_steps`` bounds every system's steps
+        in this call (``0``: the library's default); when a system runs out, :class:`NBodyError` with
+        ``NBODY_ERR_STATE`` is raised, :meth:`evolve_stats` tells where each system stands, and the same call again
+        continues.  Returns with the work complete."""
+        self._use_current_stream()
+        cfg = _lib.BatchEvolveConfig(float(dt_max), int(levels), float(eta), float(eta_start), float(softening), int(max_steps))
+        _check(self._lib, self._lib.nbody_batch_evolve_on(self._h, _ptr(self.positions), _ptr(self.velocities), int(n_intervals),
+                                                          ctypes.byref(cfg)), self._h)
+        return self.evolve_stats()
+
+    def evolve_stats(self) -> "EvolveResult":
+        """Per-system figures of the last :meth:`evolve` call (also after one that ran out of steps)."""
+        B = self.num_systems
+        steps, clamped, ticks = (np.zeros(B, dtype=np.int64) for _ in range(3))
+        lo, hi = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        i64, i32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)
+        _check(self._lib, self._lib.nbody_batch_evolve_stats(self._h, steps.ctypes.data_as(i64), lo.ctypes.data_as(i32),
+                                                             hi.ctypes.data_as(i32), clamped.ctypes.data_as(i64),
+                                                             ticks.ctypes.data_as(i64)), self._h)
+        return EvolveResult(steps, lo, hi, clamped, ticks)
+
+    def set_evolve_launch_steps(self, steps_per_launch: int) -> None:
+        """Steps one launch of :meth:`evolve` takes per system at most (default 128); results do not depend on it."""
+        _check(self._lib, self._lib.nbody_batch_evolve_launch_steps(self._h, int(steps_per_launch)), self._h)
+
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
         _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
@@ -168,10 +199,23 @@ class BatchedSystem:
         return out
 
 
+class EvolveResult:
+    """What :meth:`BatchedSystem.evolve` did, per system (``(B,)`` arrays): ``steps`` taken, ``min_level`` and ``max_level``
+    stepped at, ``clamped`` steps (still longer than requested at the finest level) and the ``ticks`` reached, in units of
+    ``dt_max * 2**-levels`` (``n_intervals * 2**levels`` when finished)."""
+
+    def __init__(self, steps, min_level, max_level, clamped, ticks):
+        self.steps, self.min_level, self.max_level, self.clamped, self.ticks = steps, min_level, max_level, clamped, ticks
+
+    def __repr__(self):
+        return (f"EvolveResult(steps={self.steps.tolist()}, min_level={self.min_level.tolist()}, "
+                f"max_level={self.max_level.tolist()}, clamped={self.clamped.tolist()}, ticks={self.ticks.tolist()})")
+
+
 def interactions_per_step(counts) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention)."""
     c = np.asarray(counts, dtype=np.int64)
     return int((c * c).sum())
 
 
-__all__ = ["BatchedSystem", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

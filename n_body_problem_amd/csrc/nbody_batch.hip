@@ -398,6 +398,340 @@ hipError_t launch_batch_hermite(float4 *pos, float4 *vel, float4 *acc, float4 *j
     }
 }
 
+// ---- adaptive shared steps (include/nbody_batch_evolve.h): every system on its own step h = dt_max 2^-L, to a common tick.
+// A sibling of batch_hermite_kernel, which stays as it is: the step is its step (hermite_predict_*, batch_forces_jerks,
+// hermite_correct, the same row groups), followed by Aarseth's criterion per row in fp64, the largest level any row asks for
+// over the workgroup (the level of the smallest request) and the level rule, all workgroup-uniform.
+
+// Per system, in HBM between launches and calls.  steps, clamped, min_level and max_level are those of the current call.
+struct BatchEvolveState {
+    long long tick;  // in units of dt_max 2^-levels, from the start of the call
+    long long steps, clamped;
+    int level, min_level, max_level, pad;
+};
+
+struct BatchEvolveArgs {
+    // dt_max and what every step needs of it, formed once on the host in fp64: a level only scales them by a power of two,
+    // which is exact, so h / 3, 1 / h^2 ... are the values the division would give for h = dt_max 2^-L
+    double dt, dt_half, dt_third, dt_sixth, dt_six;  // dt_max, dt_max / 2, dt_max / 3, dt_max / 6, 6 dt_max
+    double dt2, inv_dt2, inv_dt3;                     // dt_max^2, 1 / dt_max^2, 1 / dt_max^3
+    double eta, eta_start2;  // eta_start^2
+    long long target, max_steps;
+    float eps2;
+    int levels, budget;  // steps per launch at most
+    int have_acc, have_level;
+    int new_call;    // first launch of a call: the call's counters start at 0
+    int reset_tick;  // ... and the tick too (not when the call resumes one that ran out of steps)
+};
+
+constexpr int kEvolveNoLevel = 1 << 30;
+
+// A value every lane holds, moved to scalar registers: the step constants must not cost vector registers.  The empty asm
+// statement pins the result there (the compiler otherwise folds the readfirstlane of a value it knows to be uniform and
+// keeps the fp64 constants in VGPRs).
+__device__ __forceinline__ int uniform_i32(int x)
+{
+    int s = __builtin_amdgcn_readfirstlane(x);
+    asm("" : "+s"(s));
+    return s;
+}
+__device__ __forceinline__ long long uniform_i64(long long x)
+{
+    const unsigned lo = (unsigned)uniform_i32((int)(unsigned)x);
+    const unsigned hi = (unsigned)uniform_i32((int)(unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double uniform_f64(double x) { return __longlong_as_double(uniform_i64(__double_as_longlong(x))); }
+
+__device__ __forceinline__ double pow2(int k) { return __longlong_as_double((long long)(1023 + k) << 52); }  // 2^k, |k| < 1023
+
+// The step constants of a level: h = dt_max 2^-level exactly, HermiteSteps as batch_hermite_kernel forms them from its h.
+struct EvolveSteps {
+    HermiteSteps t;
+    double ih2, ih3, h6;  // 1 / h^2, 1 / h^3, 6 h
+};
+__device__ __forceinline__ EvolveSteps evolve_steps(const BatchEvolveArgs &p, int level)
+{
+    const double s = pow2(-level);
+    EvolveSteps e;
+    e.t = HermiteSteps{uniform_f64(p.dt * s), uniform_f64(p.dt_half * s), uniform_f64(p.dt_third * s), uniform_f64(p.dt_sixth * s)};
+    e.ih2 = uniform_f64(p.inv_dt2 * pow2(2 * level));
+    e.ih3 = uniform_f64(p.inv_dt3 * pow2(3 * level));
+    e.h6 = uniform_f64(p.dt_six * s);
+    return e;
+}
+
+// Aarseth's criterion of one body from the accelerations and jerks at both ends of the step just taken (the header's
+// formulas): dt^2 = num / den with num = eta (|a1| |a2_1| + |j1|^2), den = |j1| |a3| + |a2_1|^2.  Nothing is divided: a step
+// of square h2 is too long for the body when h2 den > num (never for den = 0, the header's +inf).
+struct EvolveNorms {
+    double a1 = 0.0, a2 = 0.0, j1 = 0.0, a3 = 0.0;  // |a1|^2, |a2_1|^2, |j1|^2, |a3|^2, summed x, y, z
+};
+__device__ __forceinline__ void evolve_norms(EvolveNorms &s, float a0, float a1, float j0, float j1, const EvolveSteps &e)
+{
+    const double d = (double)a0 - (double)a1;
+    const double s2 = (-6.0 * d - e.t.h * (4.0 * (double)j0 + 2.0 * (double)j1)) * e.ih2;
+    const double s3 = (12.0 * d + e.h6 * ((double)j0 + (double)j1)) * e.ih3;
+    const double s21 = s2 + e.t.h * s3;
+    s.a1 += (double)a1 * (double)a1;
+    s.a2 += s21 * s21;
+    s.j1 += (double)j1 * (double)j1;
+    s.a3 += s3 * s3;
+}
+
+// The level a wave asks for so far, in scalar registers: the smallest L whose squared step dt_max^2 4^-L is too long for
+// none of the rows seen (at most `levels`; clamped: some row finds even that too long).  The system's request is the
+// minimum over its bodies; L is monotone in it, so the level of the minimum is the largest level any body asks for -- an
+// integer maximum, exact and free of order like the minimum, found without moving a double between lanes: one wave-wide
+// vote per level (evolve_raise), then a maximum over the waves' words in LDS (evolve_publish / evolve_collect).
+struct EvolveWant {
+    int level = 0;  // levels + 1: clamped at `levels`
+};
+__device__ __forceinline__ void evolve_raise(EvolveWant &w, bool valid, double num, double den, const BatchEvolveArgs &p)
+{
+    while (w.level <= p.levels && __any(valid && p.dt2 * pow2(-2 * w.level) * den > num))
+        ++w.level;
+}
+
+// hermite_evaluate<RPL, GUARD, true>, and the level the wave's rows ask for (rows r >= n ask for nothing).  x0 and v0 of
+// a group's rows are read from the state arrays before the group's column loop (which hides the latency) and the corrected
+// ones written back after it: held in registers for all four rows through both loops, as batch_hermite_kernel holds them,
+// they leave no room for the criterion.  Each row votes as soon as its criterion is formed: nothing of it is carried
+// across the next group's column loop.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ EvolveWant hermite_evaluate_request(const float4 *sh, int n, int tid, int T, float eps2, float4 *pos,
+                                                               float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL],
+                                                               const EvolveSteps &e, const BatchEvolveArgs &p)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+    EvolveWant want;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G], x[G], v[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = x[i] = v[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+                x[i] = *reinterpret_cast<const float3 *>(&pos[r]);
+                v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
+            }
+        }
+        batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
+            hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
+            hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            if (r < n) {  // x, y, z only: the masses and the velocities' w stay as they are
+                *reinterpret_cast<float3 *>(&pos[r]) = x[i];
+                *reinterpret_cast<float3 *>(&vel[r]) = v[i];
+            }
+            float3 a0 = a[q], j0 = jk[q];
+            renew_f32(a0);  // widened again below, one component at a time: the corrector's fp64 copies end here
+            renew_f32(j0);
+            renew_f32(a1[i]);
+            renew_f32(j1[i]);
+            a[q] = a1[i];
+            jk[q] = j1[i];
+            EvolveNorms s;
+            evolve_norms(s, a0.x, a1[i].x, j0.x, j1[i].x, e);
+            evolve_norms(s, a0.y, a1[i].y, j0.y, j1[i].y, e);
+            evolve_norms(s, a0.z, a1[i].z, j0.z, j1[i].z, e);
+            const double num = p.eta * (__builtin_sqrt(s.a1 * s.a2) + s.j1), den = __builtin_sqrt(s.j1 * s.a3) + s.a2;
+            evolve_raise(want, r < n, num, den, p);
+        }
+    }
+    return want;
+}
+
+// The workgroup's level from the waves': red[] holds one word per wave.  The caller's barrier lies between evolve_publish and
+// evolve_collect.  red[] is written between the two barriers of a step and read after the second, before the first
+// barrier of the next step: no barrier of its own.
+__device__ __forceinline__ void evolve_publish(int *red, const EvolveWant &w, int tid)
+{
+    if ((tid & 63) == 0)
+        red[uniform_i32(tid >> 6)] = w.level;
+}
+__device__ __forceinline__ EvolveWant evolve_collect(const int *red, int T)
+{
+    int m = red[0];
+    for (int w = 1; w < (T >> 6); ++w)
+        m = red[w] > m ? red[w] : m;
+    EvolveWant want;
+    want.level = uniform_i32(m);
+    return want;
+}
+
+// One workgroup = system blockIdx.x, rows and LDS as in batch_hermite_kernel.  The workgroup steps until its system is at
+// the target tick, the launch's budget is spent or the call's max_steps are; then it writes its state, the caches and
+// state[blockIdx.x], and counts itself in counters[0] if unfinished (counters[1]: unfinished and out of steps).
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_adaptive_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                      const int *counts, BatchEvolveState *state,
+                                                                      int *counters, int max_bodies, BatchEvolveArgs p)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    __shared__ int red[16];         // the waves' levels
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    // Registers hold the rows' accelerations and jerks only.  Positions and velocities stay in the state arrays between
+    // the steps: the predictor reads them, the corrector reads them again and writes them back (each lane its own rows, so
+    // program order is all the ordering needed); the masses stay in LDS (sh[2 r].w, written once: the predictor rewrites
+    // x, y, z only).  The same fp32 bits as in registers; per row and step two 16-byte reads and two 12-byte writes that
+    // the caches serve, beside 2 x n_b column reads.
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!p.have_acc) {  // (a0, j0) at the current state, which the columns hold
+        __syncthreads();
+        const HermiteSteps unused{0.0, 0.0, 0.0, 0.0};
+        float4 x4[RPL];  // not used without the corrector
+        float3 v3[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            x4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            v3[q] = make_float3(0.f, 0.f, 0.f);
+        }
+        hermite_evaluate<RPL, GUARD, false>(sh, n, tid, T, p.eps2, x4, v3, a, jk, unused);
+    }
+    if (!p.have_level) {  // the first step: dt = eta_start |a| / |j|, compared as squares
+        EvolveWant want;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+            const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+            evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);  // dt^2 = eta_start^2 |a|^2 / |j|^2
+        }
+        evolve_publish(red, want, tid);
+    }
+    __syncthreads();  // every lane is done reading before the first prediction rewrites the columns; red[] is complete
+    if (!p.have_level) {
+        const EvolveWant want = evolve_collect(red, T);
+        level = want.level > p.levels ? p.levels : want.level;
+        clamped += want.level > p.levels ? 1 : 0;
+    }
+    for (int run = 0; tick < p.target && run < p.budget && steps < p.max_steps; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        const EvolveWant mine = hermite_evaluate_request<RPL, GUARD>(sh, n, tid, T, p.eps2, pos, vel, a, jk, e, p);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick += 1ll << (p.levels - level);
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                               float4 *jerk, const int *counts, BatchEvolveState *state, int *counters, int max_bodies,
+                               const BatchEvolveArgs &p)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_adaptive_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_adaptive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
+                       counters, max_bodies, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_adaptive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, BatchEvolveState *state,
+                                 int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(p.eps2 > 0.f);
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_adaptive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    case 3: return launch_adaptive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    case 4: return launch_adaptive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    case 5: return launch_adaptive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    case 8: return launch_adaptive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    default: return launch_adaptive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    }
+}
+
 template <int RPL, bool GUARD>
 void launch_step_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
                      const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
@@ -520,6 +854,16 @@ struct nbody_batch {
     int acc_integrator = -1;      // the integrator that filled the cache
     const void *acc_pos = nullptr, *acc_vel = nullptr;  // the buffers and softening the cache belongs to
     float acc_softening = 0.f;
+    // nbody_batch_evolve_on: the per-system level and tick beside the caches, valid only while acc_valid
+    BatchEvolveState *evolve_state = nullptr;  // [n_systems]
+    int *evolve_counters = nullptr;            // {unfinished, unfinished and out of steps} of the last launch
+    std::vector<BatchEvolveState> evolve_host; // the last call's, for nbody_batch_evolve_stats
+    int64_t evolve_target = 0;
+    bool level_valid = false;                  // the levels belong to level_dt_max and level_levels
+    float level_dt_max = 0.f;
+    int level_levels = 0;
+    bool evolve_pending = false;               // the last call ran out of steps: systems sit at different ticks
+    int evolve_launch_steps = kBatchStepsPerLaunch;
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -615,6 +959,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->counts_dev) (void)hipFree(b->counts_dev);
     if (b->acc) (void)hipFree(b->acc);
     if (b->jerk) (void)hipFree(b->jerk);
+    if (b->evolve_state) (void)hipFree(b->evolve_state);
+    if (b->evolve_counters) (void)hipFree(b->evolve_counters);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -684,6 +1030,10 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
                                            "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
     if (k == 0)
         return NBODY_OK;
+    if (b->evolve_pending && b->acc_valid && b->integrator == NBODY_INTEGRATOR_HERMITE)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_step_n: the last nbody_batch_evolve_on ran out of steps and its systems sit at "
+                                         "different times: complete it, or nbody_batch_invalidate_forces to drop it");
+    b->level_valid = false;  // fixed steps leave the levels behind
     BATCH_TRY(b, hipSetDevice(b->device));
     const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK, hermite = b->integrator == NBODY_INTEGRATOR_HERMITE;
     const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
@@ -731,6 +1081,149 @@ int nbody_batch_step_n_on(nbody_batch *b, float *d_pos, float *d_vel, int k, flo
 {
     const int rc = nbody_batch_step_n_async(b, d_pos, d_vel, k, dt, softening);
     return rc != NBODY_OK ? rc : nbody_batch_sync(b);
+}
+
+int nbody_batch_evolve_launch_steps(nbody_batch *b, int steps_per_launch)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve_launch_steps: batch is NULL");
+    if (steps_per_launch < 1 || steps_per_launch > 4096)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve_launch_steps: steps_per_launch outside [1, 4096]");
+    b->evolve_launch_steps = steps_per_launch;
+    return NBODY_OK;
+}
+
+int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_intervals, const nbody_batch_evolve_config *cfg)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve: batch is NULL");
+    if (!d_pos || !d_vel || !cfg)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: NULL argument");
+    if (b->integrator != NBODY_INTEGRATOR_HERMITE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: adaptive steps need NBODY_INTEGRATOR_HERMITE "
+                                           "(nbody_batch_set_integrator): the criterion uses its accelerations and jerks");
+    if (cfg->levels < 0 || cfg->levels > NBODY_BATCH_EVOLVE_MAX_LEVELS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: levels outside [0, NBODY_BATCH_EVOLVE_MAX_LEVELS = 20]");
+    if (n_intervals < 0 || n_intervals >= ((int64_t)1 << (62 - cfg->levels)))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: n_intervals < 0 or n_intervals x 2^levels >= 2^62");
+    if (!std::isfinite(cfg->dt_max) || !(cfg->dt_max > 0.f))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: dt_max must be finite and positive");
+    if (!std::isfinite(cfg->eta) || !(cfg->eta > 0.f) || !std::isfinite(cfg->eta_start) || !(cfg->eta_start > 0.f))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: eta and eta_start must be finite and positive");
+    if (!softening_ok(cfg->softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
+                                           "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
+    const int64_t max_steps = cfg->max_steps > 0 ? cfg->max_steps : NBODY_BATCH_EVOLVE_DEFAULT_MAX_STEPS;
+    const int64_t target = n_intervals << cfg->levels;
+    if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != cfg->softening || b->acc_integrator != b->integrator)
+        b->acc_valid = false;
+    if (!b->acc_valid)
+        b->level_valid = b->evolve_pending = false;
+    const bool same_axis = b->level_valid && b->level_dt_max == cfg->dt_max && b->level_levels == cfg->levels;
+    const bool resume = b->evolve_pending;
+    if (resume) {
+        if (!same_axis)
+            return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: the last call ran out of steps; complete it with the same dt_max and "
+                                             "levels, or nbody_batch_invalidate_forces to drop it");
+        for (int64_t s = 0; s < b->n_systems; ++s)
+            if (b->counts[(size_t)s] > 0 && b->evolve_host[(size_t)s].tick > target)
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: n_intervals ends before the time system " + std::to_string(s) +
+                                                       " reached in the call this one resumes");
+    }
+    const size_t B = (size_t)b->n_systems;
+    if (b->evolve_host.size() != B)
+        b->evolve_host.assign(B, BatchEvolveState{0, 0, 0, 0, kEvolveNoLevel, -1, 0});
+    if (!resume)
+        for (BatchEvolveState &st : b->evolve_host)
+            st = BatchEvolveState{0, 0, 0, 0, kEvolveNoLevel, -1, 0};
+    b->evolve_target = target;
+    if (target == 0)
+        return NBODY_OK;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    const size_t slots = B * (size_t)b->max_bodies;
+    if (!b->acc)
+        BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
+    if (!b->jerk)
+        BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
+    if (!b->evolve_state) {
+        BATCH_TRY(b, hipMalloc((void **)&b->evolve_state, sizeof(BatchEvolveState) * B));
+        BATCH_TRY(b, hipMemsetAsync(b->evolve_state, 0, sizeof(BatchEvolveState) * B, b->stream));
+    }
+    if (!b->evolve_counters)
+        BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
+    BatchEvolveArgs p;
+    p.dt = (double)cfg->dt_max;
+    p.dt_half = 0.5 * p.dt;
+    p.dt_six = 6.0 * p.dt;
+    p.dt_third = p.dt / 3.0;
+    p.dt_sixth = p.dt / 6.0;
+    p.dt2 = p.dt * p.dt;
+    p.inv_dt2 = 1.0 / (p.dt * p.dt);
+    p.inv_dt3 = 1.0 / (p.dt * p.dt * p.dt);
+    p.eta = (double)cfg->eta;
+    p.eta_start2 = (double)cfg->eta_start * (double)cfg->eta_start;
+    p.target = target;
+    p.max_steps = max_steps;
+    p.eps2 = cfg->softening * cfg->softening;
+    p.levels = cfg->levels;
+    p.budget = b->evolve_launch_steps;
+    int counters[2] = {0, 0};
+    for (bool first = true;; first = false) {
+        p.have_acc = b->acc_valid ? 1 : 0;
+        p.have_level = !first || same_axis ? 1 : 0;
+        p.new_call = first ? 1 : 0;
+        p.reset_tick = first && !resume ? 1 : 0;
+        BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
+        BATCH_TRY(b, launch_batch_adaptive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
+                                           b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
+                                           p, b->stream));
+        b->acc_integrator = b->integrator;
+        b->acc_valid = b->level_valid = true;
+        b->acc_pos = d_pos;
+        b->acc_vel = d_vel;
+        b->acc_softening = cfg->softening;
+        b->level_dt_max = cfg->dt_max;
+        b->level_levels = cfg->levels;
+        b->evolve_pending = true;  // until every system is seen at the target
+        BATCH_TRY(b, hipMemcpyAsync(counters, b->evolve_counters, sizeof(counters), hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+        if (counters[0] == 0 || counters[0] == counters[1])
+            break;
+    }
+    BATCH_TRY(b, hipMemcpyAsync(b->evolve_host.data(), b->evolve_state, sizeof(BatchEvolveState) * B, hipMemcpyDeviceToHost, b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    for (size_t s = 0; s < B; ++s)
+        if (b->counts[s] <= 0)
+            b->evolve_host[s] = BatchEvolveState{target, 0, 0, 0, kEvolveNoLevel, -1, 0};
+    if (counters[0] == 0) {
+        b->evolve_pending = false;
+        return NBODY_OK;
+    }
+    size_t first_unfinished = 0;
+    while (first_unfinished < B && b->evolve_host[first_unfinished].tick >= target)
+        ++first_unfinished;
+    return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: system " + std::to_string(first_unfinished) + " is unfinished after max_steps = " +
+                                         std::to_string(max_steps) + " steps (tick " +
+                                         std::to_string(first_unfinished < B ? b->evolve_host[first_unfinished].tick : 0) + " of " +
+                                         std::to_string(target) + "); " + std::to_string(counters[0]) + " of " + std::to_string(B) +
+                                         " systems are unfinished; the same call again continues from here");
+}
+
+int nbody_batch_evolve_stats(nbody_batch *b, int64_t *steps, int *min_level, int *max_level, int64_t *clamped, int64_t *ticks)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve_stats: batch is NULL");
+    if (b->evolve_host.size() != (size_t)b->n_systems)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve_stats: no nbody_batch_evolve_on call yet");
+    for (size_t s = 0; s < b->evolve_host.size(); ++s) {
+        const BatchEvolveState &st = b->evolve_host[s];
+        if (steps) steps[s] = st.steps;
+        if (min_level) min_level[s] = st.steps > 0 ? st.min_level : 0;
+        if (max_level) max_level[s] = st.steps > 0 ? st.max_level : 0;
+        if (clamped) clamped[s] = st.clamped;
+        if (ticks) ticks[s] = st.tick;
+    }
+    return NBODY_OK;
 }
 
 static int batch_diag(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, bool potential)

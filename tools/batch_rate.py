@@ -6,7 +6,13 @@ Rates use the one-sided convention: n^2 ordered interactions per system and step
 peak at 20 flop per interaction for kick_drift and kdk (a force) and 60 flop per interaction for hermite (a force and a
 jerk, the convention of the Hermite GPU literature); the line names its convention.  Times are HIP events around
 step_n(k) after a warm-up, the median of repeats that alternate the batched and the status-quo measurement.  Hermite
-exists for batches only, so its lines have no status-quo figures."""
+exists for batches only, so its lines have no status-quo figures.
+
+--adaptive: instead, per case, one line with Hermite step_n(k, dt) against evolve(k, dt, levels=0) -- the same k steps of
+the same arithmetic through the adaptive kernel, so the difference is the cost of the step criterion, the workgroup minimum
+and the per-launch counter read -- alternated, medians; then one scattering-style line: 1024 Kepler pairs with
+eccentricities spread over 0 .. 0.99 in one batch, evolved one period (dt_max = period / 64, levels = 12, eta = 0.01,
+no softening): wall time, the distribution of the systems' step counts and the worst relative energy error."""
 import argparse
 import json
 import os
@@ -30,6 +36,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--subset", type=int, default=8, help="systems the status quo is timed on")
 ap.add_argument("--dt", type=float, default=1e-3)
 ap.add_argument("--eps", type=float, default=1e-2)
+ap.add_argument("--adaptive", action="store_true", help="Hermite step_n against evolve(levels=0), and a scattering case")
 args = ap.parse_args()
 
 
@@ -55,6 +62,82 @@ def ensemble(n, B):
             P[s, :, :3] += rng.normal(0, 1e-4, (n, 3)).astype(np.float32)
     return P, V
 
+
+def adaptive_lines():
+    import time
+    for case in args.cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        inter = B * n * n
+        k = int(min(400, max(10, 2e11 // inter)))
+        dt = float(np.float32(args.dt))
+        with nb.BatchedSystem(B, n, integrator="hermite") as batch:
+            batch.set_state(P, V)
+
+            def fixed():
+                batch.step_n(k, dt, args.eps)
+
+            def adaptive():
+                batch.evolve(k, dt, levels=0, softening=args.eps)
+
+            fixed()
+            adaptive()
+            torch.cuda.synchronize()
+            tf, ta = [], []
+            for _ in range(args.repeats):      # alternated
+                tf.append(timed(fixed) / k)
+                ta.append(timed(adaptive) / k)
+            mf, ma = statistics.median(tf), statistics.median(ta)
+        print(json.dumps({"n": n, "B": B, "k": k, "step_n_ms_per_step": round(mf, 5), "evolve_levels0_ms_per_step": round(ma, 5),
+                          "overhead": round(ma / mf - 1.0, 4), "step_n_repeats": [round(x, 5) for x in tf],
+                          "evolve_repeats": [round(x, 5) for x in ta]}), flush=True)
+    B = 1024
+    ecc = np.linspace(0.0, 0.99, B)
+    P = np.zeros((B, 2, 4), np.float32)
+    V = np.zeros((B, 2, 4), np.float32)
+    for s, e in enumerate(ecc):                 # two half masses, semi-major axis 1, at apocentre (G = 1): period 2 pi
+        ra, va = 1.0 + e, np.sqrt((1.0 - e) / (1.0 + e))
+        P[s] = [[0.5 * ra, 0, 0, 0.5], [-0.5 * ra, 0, 0, 0.5]]
+        V[s] = [[0, 0.5 * va, 0, 0], [0, -0.5 * va, 0, 0]]
+    dt_max = float(np.float32(2 * np.pi / 64))
+    with nb.BatchedSystem(B, 2, integrator="hermite") as batch:
+        walls = []
+        for _ in range(1 + args.repeats):           # the first run warms up (allocations, kernel attributes)
+            batch.set_state(P, V)
+            e0 = batch.energy(0.0)[:, 2]
+            batch.sync()
+            t0 = time.perf_counter()
+            res = batch.evolve(64, dt_max, levels=12, eta=0.01, eta_start=0.01, softening=0.0)
+            walls.append(time.perf_counter() - t0)
+            de = np.abs(batch.energy(0.0)[:, 2] / e0 - 1.0)
+        wall = statistics.median(walls[1:])
+        q = [int(x) for x in np.percentile(res.steps, [0, 25, 50, 75, 90, 99, 100])]
+        print(json.dumps({"scattering_pairs": B, "eccentricities": "0 .. 0.99", "wall_ms_median": round(wall * 1e3, 3),
+                          "wall_ms_repeats": [round(w * 1e3, 3) for w in walls[1:]],
+                          "steps_percentiles_0_25_50_75_90_99_100": q, "steps_total": int(res.steps.sum()),
+                          "max_level": int(res.max_level.max()), "clamped": int(res.clamped.sum()),
+                          "worst_rel_energy_error": float(f"{de.max():.3g}"),
+                          "median_rel_energy_error": float(f"{np.median(de):.3g}")}), flush=True)
+        # fixed steps to the same end time: double the step count until the worst error is the adaptive run's
+        target, k, bound = float(de.max()), 1024, 1 << 18
+        while True:
+            batch.set_state(P, V)
+            batch.sync()
+            t0 = time.perf_counter()
+            batch.step_n(k, float(np.float32(64.0 * dt_max / k)), 0.0)
+            batch.sync()
+            wall_f = time.perf_counter() - t0
+            de_f = float(np.nanmax(np.abs(batch.energy(0.0)[:, 2] / e0 - 1.0)))
+            print(json.dumps({"fixed_steps": k, "wall_ms": round(wall_f * 1e3, 3), "worst_rel_energy_error": float(f"{de_f:.3g}"),
+                              "reaches_adaptive_worst": bool(de_f <= target)}), flush=True)
+            if de_f <= target or k >= bound:
+                break
+            k *= 2
+
+
+if args.adaptive:
+    adaptive_lines()
+    sys.exit(0)
 
 for case in args.cases:
     n, B = (int(x) for x in case.lower().split("x"))
