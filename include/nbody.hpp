@@ -318,6 +318,29 @@ public:
               "nbody_batch_evolve_stats");
         return s;
     }
+    // Stopping conditions of evolve (nbody_batch_stop.h): a system's run ends after the step in which two bodies come
+    // within collisionRadius or a body is farther than escapeRadius from the origin (0: off).  stops(): per system the
+    // reason (bit 1 collision, bit 2 escape; 0: not stopped), the tick, the colliding pair i < j, its separation, the escaper.
+    struct Stops {
+        std::vector<int> reason, pairI, pairJ, escaper;
+        std::vector<std::int64_t> ticks;
+        std::vector<float> separation;
+    };
+    void setStopConditions(float collisionRadius, float escapeRadius)
+    {
+        const nbody_batch_stop_config cfg = {collisionRadius, escapeRadius};
+        check(nbody_batch_stop_set(b_, &cfg), "nbody_batch_stop_set");
+    }
+    Stops stops()
+    {
+        Stops s;
+        const size_t n = (size_t)systems_;
+        s.reason.resize(n), s.pairI.resize(n), s.pairJ.resize(n), s.escaper.resize(n), s.ticks.resize(n), s.separation.resize(n);
+        check(nbody_batch_stop_read(b_, s.reason.data(), s.ticks.data(), s.pairI.data(), s.pairJ.data(), s.separation.data(),
+                                    s.escaper.data()),
+              "nbody_batch_stop_read");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

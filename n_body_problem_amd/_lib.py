@@ -154,6 +154,22 @@ BATCH_EVOLVE_MAX_LEVELS = 20
 BATCH_EVOLVE_DEFAULT_MAX_STEPS = 1048576
 
 
+class BatchStopConfig(ctypes.Structure):
+    """``nbody_batch_stop_config`` of include/nbody_batch_stop.h."""
+    _fields_ = [("collision_radius", c_float), ("escape_radius", c_float)]
+
+
+#: the entry points of include/nbody_batch_stop.h (stopping conditions for Hermite batches), which nbody.h includes
+_STOP_PROTOTYPES = {
+    "nbody_batch_stop_set": (c_int, [c_void_p, POINTER(BatchStopConfig)]),
+    "nbody_batch_stop_read": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int), POINTER(c_int), POINTER(c_float),
+                                      POINTER(c_int)]),
+    "nbody_batch_stop_count": (c_int, [c_void_p, POINTER(c_int64)]),
+}
+BATCH_STOP_COLLISION = 1
+BATCH_STOP_ESCAPE = 2
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -178,7 +194,7 @@ def load() -> ctypes.CDLL:
         except ImportError:  # a torch-free host (ctypes only) uses the system runtime
             pass
         lib = ctypes.CDLL(path)
-        for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()):
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -194,6 +210,11 @@ def exported_names():
 def evolve_names():
     """The entry points of nbody_batch_evolve.h."""
     return list(_EVOLVE_PROTOTYPES)
+
+
+def stop_names():
+    """The entry points of nbody_batch_stop.h."""
+    return list(_STOP_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

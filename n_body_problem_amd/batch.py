@@ -177,6 +177,30 @@ class BatchedSystem:
         """Steps one launch of :meth:`evolve` takes per system at most (default 128); results do not depend on it."""
         _check(self._lib, self._lib.nbody_batch_evolve_launch_steps(self._h, int(steps_per_launch)), self._h)
 
+    def set_stop_conditions(self, collision_radius: float = 0.0, escape_radius: float = 0.0) -> None:
+        """Stopping conditions of :meth:`evolve` (``include/nbody_batch_stop.h`` states them): a system's run ends after the
+        step in which two of its bodies come within ``collision_radius`` of each other, or a body is farther than
+        ``escape_radius`` from the coordinate origin (centre the systems); ``0`` switches a condition off, both ``0`` (the
+        default) all of it.  A stop is a result, not an error: :meth:`stops` tells which systems stopped, when and which
+        bodies; a stopped system stays frozen in later :meth:`evolve` calls.  Forgets earlier stops and the cached
+        accelerations and jerks (as :meth:`set_state`, :meth:`invalidate_forces` and :meth:`step_n` forget the stops)."""
+        cfg = _lib.BatchStopConfig(float(collision_radius), float(escape_radius))
+        _check(self._lib, self._lib.nbody_batch_stop_set(self._h, ctypes.byref(cfg)), self._h)
+
+    def stops(self) -> "StopResult":
+        """What the stopping conditions found, per system (waits for the queued work)."""
+        B = self.num_systems
+        reason, pi, pj, esc = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        ticks, sep = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.float32)
+        i32 = ctypes.POINTER(ctypes.c_int)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_stop_read(self._h, reason.ctypes.data_as(i32),
+                                                          ticks.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                          pi.ctypes.data_as(i32), pj.ctypes.data_as(i32),
+                                                          sep.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                          esc.ctypes.data_as(i32)), self._h)
+        return StopResult(reason, ticks, np.stack([pi, pj], axis=1), sep, esc)
+
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
         _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
@@ -212,10 +236,26 @@ class EvolveResult:
                 f"max_level={self.max_level.tolist()}, clamped={self.clamped.tolist()}, ticks={self.ticks.tolist()})")
 
 
+class StopResult:
+    """What the stopping conditions of :meth:`BatchedSystem.set_stop_conditions` found, per system (``(B,)`` arrays, all zero
+    for a system that has not stopped): ``reason`` (bit 1: collision, bit 2: escape), ``ticks`` (the tick of the stop, in
+    the units of the :meth:`BatchedSystem.evolve` call that found it), ``pair`` (``(B, 2)``: the colliding bodies
+    ``i < j``), their ``separation``, the ``escaper`` (the escaping body of smallest index) and ``stopped`` (boolean).  A
+    stop for one reason only has ``-1`` for the other's indices."""
+
+    def __init__(self, reason, ticks, pair, separation, escaper):
+        self.reason, self.ticks, self.pair, self.separation, self.escaper = reason, ticks, pair, separation, escaper
+        self.stopped = reason != 0
+
+    def __repr__(self):
+        return (f"StopResult(reason={self.reason.tolist()}, ticks={self.ticks.tolist()}, pair={self.pair.tolist()}, "
+                f"separation={self.separation.tolist()}, escaper={self.escaper.tolist()})")
+
+
 def interactions_per_step(counts) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention)."""
     c = np.asarray(counts, dtype=np.int64)
     return int((c * c).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

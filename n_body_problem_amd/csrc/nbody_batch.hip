@@ -179,13 +179,24 @@ __global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *v
 // inv = v_rsq_f32, inv2 = inv inv, s = (m_j inv) inv2 (batch_forces' s), rv = fma(dz, ez, fma(dy, ey, dx ex)),
 // c = (3 rv) inv2; a = fma(d, s, a), j = fma(fma(-c, d, e), s, j).  27 VALU + 1 v_rsq_f32 per interaction.  GUARD: a
 // zero-distance pair has inv = 0, so s = c = 0 and it adds exactly 0 to a and j.
-template <int G, bool GUARD>
+// STOP (include/nbody_batch_stop.h): near2[k] receives, one bit per lane, whether row k met r^2 + eps^2 <= thr (the value
+// before the guard) in at least TWO columns.  The self pair always meets it (its r^2 + eps^2 is eps^2 exactly and
+// thr >= eps^2), so two columns mean a column j != i within the collision radius -- without an index or a compare against
+// the row in the loop.  Per interaction one v_cmp into a scalar pair and three scalar mask operations (seen twice |=
+// seen once & now; seen once |= now): no vector register, and a, j are summed by the same instructions.
+template <int G, bool GUARD, bool STOP = false>
 __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, const float3 (&xp)[G], const float3 (&vp)[G],
-                                                   float eps2, float3 (&a)[G], float3 (&jk)[G])
+                                                   float eps2, float3 (&a)[G], float3 (&jk)[G], float thr = 0.f,
+                                                   unsigned long long *near2 = nullptr)
 {
+    unsigned long long near1[G];
 #pragma unroll
-    for (int k = 0; k < G; ++k)
+    for (int k = 0; k < G; ++k) {
         a[k] = jk[k] = make_float3(0.f, 0.f, 0.f);
+        near1[k] = 0;
+        if (STOP)
+            near2[k] = 0;
+    }
 #pragma unroll 1  // two rows of 27 VALU per column; unrolling would spill at RPL = 4
     for (int j = 0; j < n; ++j) {
         const float4 pj = sh[2 * j];  // wave-uniform addresses: two broadcast ds_read_b128 per column
@@ -197,6 +208,11 @@ __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, cons
             float r2 = __builtin_fmaf(dx, dx, eps2);
             r2 = __builtin_fmaf(dy, dy, r2);
             r2 = __builtin_fmaf(dz, dz, r2);
+            if (STOP) {
+                const unsigned long long now = __ballot(r2 <= thr);
+                near2[k] |= near1[k] & now;
+                near1[k] |= now;
+            }
             if (GUARD)
                 r2 = guard_r2(r2);
             const float inv = __builtin_amdgcn_rsqf(r2);
@@ -246,15 +262,34 @@ __device__ __forceinline__ void hermite_correct(float &x, float &v, float a0, fl
     v = v1;
 }
 
+// Stopping conditions (include/nbody_batch_stop.h) as the kernels take them, formed once on the host in fp32.
+struct BatchStopArgs {
+    float thr;  // a pair collides when its r^2 + eps^2 <= thr = fma(R_c, R_c, eps^2); -1: never
+    float re2;  // a body has escaped when |x|^2 > re2 = R_e R_e; +inf: never
+};
+constexpr int kStopCollision = 1, kStopEscape = 2;
+
+// What the wave found in one row per lane, wave-uniform: kStopCollision when a row r < n (valid) saw a second column within
+// the threshold (batch_forces_jerks), kStopEscape when a row r < n lies outside the escape radius at x.
+__device__ __forceinline__ int stop_examine(unsigned long long near2, const float3 &x, bool valid, const BatchStopArgs &sa)
+{
+    const float d2 = __builtin_fmaf(x.z, x.z, __builtin_fmaf(x.y, x.y, x.x * x.x));
+    return ((near2 & __ballot(valid)) != 0 ? kStopCollision : 0) | (__any(valid && d2 > sa.re2) ? kStopEscape : 0);
+}
+
 // Evaluate (a1, j1) for the lane's rows from the predicted state in LDS and, when CORRECT, apply the corrector; then
 // (a, j) = (a1, j1).  The rows go in groups of at most two, each group one pass over the columns with its own predicted
 // state reread from LDS: four rows at once (x0, v0, a0, j0 live beside the predicted state and the sums) would not fit
 // 128 VGPRs without scratch.  A group's corrector writes only registers, so the next group still reads the predicted state.
-template <int RPL, bool GUARD, bool CORRECT>
+// STOP (the evaluation at the current state, without the corrector): *found receives the stopping conditions the wave's
+// rows meet there, the escape test on the positions the columns hold.
+template <int RPL, bool GUARD, bool CORRECT, bool STOP = false>
 __device__ __forceinline__ void hermite_evaluate(const float4 *sh, int n, int tid, int T, float eps2, float4 (&x)[RPL],
-                                                 float3 (&v)[RPL], float3 (&a)[RPL], float3 (&jk)[RPL], const HermiteSteps &t)
+                                                 float3 (&v)[RPL], float3 (&a)[RPL], float3 (&jk)[RPL], const HermiteSteps &t,
+                                                 const BatchStopArgs *sa = nullptr, int *found = nullptr)
 {
     constexpr int G = RPL < 2 ? RPL : 2;
+    static_assert(!(STOP && CORRECT), "with the corrector the conditions are examined by hermite_evaluate_request");
 #pragma unroll
     for (int g = 0; g < RPL; g += G) {
         float3 xp[G], vp[G], a1[G], j1[G];
@@ -267,7 +302,15 @@ __device__ __forceinline__ void hermite_evaluate(const float4 *sh, int n, int ti
                 vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
             }
         }
-        batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+        if (STOP) {
+            unsigned long long near2[G];
+            batch_forces_jerks<G, GUARD, true>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                *found |= stop_examine(near2[i], xp[i], (g + i) * T + tid < n, *sa);
+        } else {
+            batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+        }
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int q = g + i;
@@ -497,11 +540,13 @@ __device__ __forceinline__ void evolve_raise(EvolveWant &w, bool valid, double n
 // a group's rows are read from the state arrays before the group's column loop (which hides the latency) and the corrected
 // ones written back after it: held in registers for all four rows through both loops, as batch_hermite_kernel holds them,
 // they leave no room for the criterion.  Each row votes as soon as its criterion is formed: nothing of it is carried
-// across the next group's column loop.
-template <int RPL, bool GUARD>
+// across the next group's column loop.  STOP: *found receives the stopping conditions the wave's rows meet, the collision
+// test in the column loop (at the predicted positions), the escape test on the corrected positions.
+template <int RPL, bool GUARD, bool STOP = false>
 __device__ __forceinline__ EvolveWant hermite_evaluate_request(const float4 *sh, int n, int tid, int T, float eps2, float4 *pos,
                                                                float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL],
-                                                               const EvolveSteps &e, const BatchEvolveArgs &p)
+                                                               const EvolveSteps &e, const BatchEvolveArgs &p,
+                                                               const BatchStopArgs *sa = nullptr, int *found = nullptr)
 {
     constexpr int G = RPL < 2 ? RPL : 2;
     EvolveWant want;
@@ -519,13 +564,19 @@ __device__ __forceinline__ EvolveWant hermite_evaluate_request(const float4 *sh,
                 v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
             }
         }
-        batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+        unsigned long long near2[G];
+        if (STOP)
+            batch_forces_jerks<G, GUARD, true>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
+        else
+            batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int q = g + i, r = q * T + tid;
             hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
             hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
             hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            if (STOP)
+                *found |= stop_examine(near2[i], x[i], r < n, *sa);
             if (r < n) {  // x, y, z only: the masses and the velocities' w stay as they are
                 *reinterpret_cast<float3 *>(&pos[r]) = x[i];
                 *reinterpret_cast<float3 *>(&vel[r]) = v[i];
@@ -701,11 +752,252 @@ __global__ __launch_bounds__(1024) void batch_hermite_adaptive_kernel(float4 *po
     }
 }
 
+// Per system, beside BatchEvolveState: what a stopping condition found (include/nbody_batch_stop.h).  All zero: the system
+// has not stopped.  A system whose reason is set is frozen: later launches leave it alone.
+struct BatchStopReport {
+    long long tick;  // of the stop, in the units of the call that found it
+    int reason;      // kStopCollision | kStopEscape
+    int pair_i, pair_j, escaper;  // -1: not that reason
+    float separation;
+    int pad;
+};
+
+// The waves' findings (kStopCollision | kStopEscape) through LDS, as their levels: written where evolve_publish writes, read
+// where evolve_collect reads.
+__device__ __forceinline__ void stop_publish(int *red, int found, int tid)
+{
+    if ((tid & 63) == 0)
+        red[uniform_i32(tid >> 6)] = found;
+}
+__device__ __forceinline__ int stop_collect(const int *red, int T)
+{
+    int m = red[0];
+    for (int w = 1; w < (T >> 6); ++w)
+        m |= red[w];
+    return uniform_i32(m);
+}
+
+// The cold path of a system that stops (workgroup-uniform `found`): the colliding pair of smallest r^2 + eps^2 -- ties to
+// the smallest i, then the smallest j, i < j -- among the columns LDS still holds, and the escaper of smallest index among
+// the positions in the state array.  Every row rescans the columns after its own (a pair's two rows form the same r^2:
+// the differences only change sign) and the workgroup takes a 64-bit minimum in LDS of the key {r^2 bits, i, j}; r^2 >= 0,
+// so its bits order as the values, and an integer minimum does not depend on the order it is taken in.
+__device__ __forceinline__ void stop_report(const float4 *sh, const float4 *pos, int n, int tid, int T, int rpl, float eps2,
+                                            const BatchStopArgs &sa, int found, long long tick, BatchStopReport *out)
+{
+    __shared__ unsigned long long best;
+    __shared__ int escaper;
+    if (tid == 0) {
+        best = ~0ull;
+        escaper = 0x7fffffff;
+    }
+    __syncthreads();
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r >= n)
+            continue;
+        if (found & kStopCollision) {
+            const float4 pi = sh[2 * r];
+            unsigned long long mine = ~0ull;
+            for (int j = r + 1; j < n; ++j) {
+                const float4 pj = sh[2 * j];
+                const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+                float r2 = __builtin_fmaf(dx, dx, eps2);
+                r2 = __builtin_fmaf(dy, dy, r2);
+                r2 = __builtin_fmaf(dz, dz, r2);
+                if (r2 <= sa.thr) {
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(r2) << 24) | ((unsigned)r << 12) | (unsigned)j;
+                    mine = key < mine ? key : mine;
+                }
+            }
+            if (mine != ~0ull)
+                atomicMin(&best, mine);
+        }
+        if (found & kStopEscape) {
+            const float4 xi = pos[r];  // this lane's own writes: the corrected positions
+            if (__builtin_fmaf(xi.z, xi.z, __builtin_fmaf(xi.y, xi.y, xi.x * xi.x)) > sa.re2)
+                atomicMin(&escaper, r);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        BatchStopReport rep{tick, found, -1, -1, -1, 0.f, 0};
+        if ((found & kStopCollision) && best != ~0ull) {
+            rep.pair_i = (int)((best >> 12) & 0xfff);
+            rep.pair_j = (int)(best & 0xfff);
+            const float4 pi = sh[2 * rep.pair_i], pj = sh[2 * rep.pair_j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            rep.separation = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        }
+        if ((found & kStopEscape) && escaper != 0x7fffffff)
+            rep.escaper = escaper;
+        *out = rep;
+    }
+}
+
+// batch_hermite_adaptive_kernel with the stopping conditions of include/nbody_batch_stop.h: a sibling, so that the kernel
+// above stays the code it was.  The same loop; the system also leaves it after the step in which a condition is met,
+// writes report[blockIdx.x] and is neither stepped nor counted as unfinished from then on (frozen).
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_stop_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                  const int *counts, BatchEvolveState *state, int *counters,
+                                                                  int max_bodies, BatchEvolveArgs p, BatchStopArgs sa,
+                                                                  BatchStopReport *report)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    __shared__ int red[16];         // the waves' levels
+    __shared__ int red_stop[16];    // the waves' stopping conditions
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    const bool frozen = uniform_i32(report[blockIdx.x].reason) != 0;
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (frozen || tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target && !frozen) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    // Registers hold the rows' accelerations and jerks only.  Positions and velocities stay in the state arrays between
+    // the steps: the predictor reads them, the corrector reads them again and writes them back (each lane its own rows, so
+    // program order is all the ordering needed); the masses stay in LDS (sh[2 r].w, written once: the predictor rewrites
+    // x, y, z only).  The same fp32 bits as in registers; per row and step two 16-byte reads and two 12-byte writes that
+    // the caches serve, beside 2 x n_b column reads.
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!p.have_acc) {  // (a0, j0) at the current state, which the columns hold
+        __syncthreads();
+        const HermiteSteps unused{0.0, 0.0, 0.0, 0.0};
+        float4 x4[RPL];  // not used without the corrector
+        float3 v3[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            x4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            v3[q] = make_float3(0.f, 0.f, 0.f);
+        }
+        int found = 0;
+        hermite_evaluate<RPL, GUARD, false, true>(sh, n, tid, T, p.eps2, x4, v3, a, jk, unused, &sa, &found);
+        stop_publish(red_stop, found, tid);
+    }
+    if (!p.have_level) {  // the first step: dt = eta_start |a| / |j|, compared as squares
+        EvolveWant want;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+            const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+            evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);  // dt^2 = eta_start^2 |a|^2 / |j|^2
+        }
+        evolve_publish(red, want, tid);
+    }
+    __syncthreads();  // every lane is done reading before the first prediction rewrites the columns; red[] is complete
+    if (!p.have_level) {
+        const EvolveWant want = evolve_collect(red, T);
+        level = want.level > p.levels ? p.levels : want.level;
+        clamped += want.level > p.levels ? 1 : 0;
+    }
+    int stop = 0;  // workgroup-uniform: the conditions met, which end the loop
+    if (!p.have_acc)
+        stop = stop_collect(red_stop, T);
+    for (int run = 0; tick < p.target && run < p.budget && steps < p.max_steps && !stop; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        int found = 0;
+        const EvolveWant mine = hermite_evaluate_request<RPL, GUARD, true>(sh, n, tid, T, p.eps2, pos, vel, a, jk, e, p, &sa, &found);
+        stop_publish(red_stop, found, tid);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        stop = stop_collect(red_stop, T);
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick += 1ll << (p.levels - level);
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target && !stop) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+    if (stop)  // the columns still hold the positions the conditions were examined at
+        stop_report(sh, pos, n, tid, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x]);
+}
+
+// report == nullptr: no stopping conditions, batch_hermite_adaptive_kernel
 template <int RPL, bool GUARD>
 hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
                                float4 *jerk, const int *counts, BatchEvolveState *state, int *counters, int max_bodies,
-                               const BatchEvolveArgs &p)
+                               const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report)
 {
+    if (report) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_stop_kernel<RPL, GUARD>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL((batch_hermite_stop_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
+                           counters, max_bodies, p, sa, report);
+        return hipGetLastError();
+    }
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_adaptive_kernel<RPL, GUARD>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess)
@@ -716,19 +1008,20 @@ hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t st
 }
 
 hipError_t launch_batch_adaptive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, BatchEvolveState *state,
-                                 int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, hipStream_t stream)
+                                 int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
+                                 BatchStopReport *report, hipStream_t stream)
 {
     const BatchShape sh = batch_shape(max_bodies);
     const dim3 grid(n_systems), block(sh.threads);
     const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
     const bool guard = !(p.eps2 > 0.f);
     switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_adaptive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
-    case 3: return launch_adaptive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
-    case 4: return launch_adaptive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
-    case 5: return launch_adaptive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
-    case 8: return launch_adaptive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
-    default: return launch_adaptive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p);
+    case 2: return launch_adaptive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
+    case 3: return launch_adaptive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
+    case 4: return launch_adaptive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
+    case 5: return launch_adaptive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
+    case 8: return launch_adaptive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
+    default: return launch_adaptive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
     }
 }
 
@@ -864,6 +1157,10 @@ struct nbody_batch {
     int level_levels = 0;
     bool evolve_pending = false;               // the last call ran out of steps: systems sit at different ticks
     int evolve_launch_steps = kBatchStepsPerLaunch;
+    // nbody_batch_stop_set: the conditions, and the per-system reports beside evolve_state
+    float stop_collision_radius = 0.f, stop_escape_radius = 0.f;  // both 0: off
+    BatchStopReport *stop_report = nullptr;    // [n_systems], allocated by the first evolve with conditions
+    bool stop_forgotten = true;                // the reports count as all zero: cleared before the next launch reads them
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -872,6 +1169,13 @@ struct nbody_batch {
 };
 
 static thread_local std::string g_batch_create_error;
+
+// The caches are forgotten, and with them the levels (nbody_batch_evolve_on sees to those) and the stops.
+static void forget_caches(nbody_batch *b)
+{
+    b->acc_valid = false;
+    b->stop_forgotten = true;
+}
 
 static int bfail(nbody_batch *b, int status, const std::string &msg)
 {
@@ -961,6 +1265,7 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->jerk) (void)hipFree(b->jerk);
     if (b->evolve_state) (void)hipFree(b->evolve_state);
     if (b->evolve_counters) (void)hipFree(b->evolve_counters);
+    if (b->stop_report) (void)hipFree(b->stop_report);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -983,7 +1288,7 @@ int nbody_batch_set_counts(nbody_batch *b, const int64_t *host_counts)
     BATCH_TRY(b, hipSetDevice(b->device));
     BATCH_TRY(b, hipMemcpyAsync(b->counts_dev, b->counts.data(), sizeof(int) * b->counts.size(), hipMemcpyHostToDevice, b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
-    b->acc_valid = false;
+    forget_caches(b);
     return NBODY_OK;
 }
 
@@ -994,7 +1299,7 @@ int nbody_batch_set_integrator(nbody_batch *b, int integrator)
     if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK && integrator != NBODY_INTEGRATOR_HERMITE)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator (KICK_DRIFT = 0, KDK = 1, HERMITE = 2)");
     if (integrator != b->integrator)
-        b->acc_valid = false;
+        forget_caches(b);
     b->integrator = integrator;
     return NBODY_OK;
 }
@@ -1003,7 +1308,7 @@ int nbody_batch_invalidate_forces(nbody_batch *b)
 {
     if (!b)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_invalidate_forces: batch is NULL");
-    b->acc_valid = false;
+    forget_caches(b);
     return NBODY_OK;
 }
 
@@ -1033,7 +1338,8 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
     if (b->evolve_pending && b->acc_valid && b->integrator == NBODY_INTEGRATOR_HERMITE)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_step_n: the last nbody_batch_evolve_on ran out of steps and its systems sit at "
                                          "different times: complete it, or nbody_batch_invalidate_forces to drop it");
-    b->level_valid = false;  // fixed steps leave the levels behind
+    b->level_valid = false;  // fixed steps leave the levels behind, and the stops
+    b->stop_forgotten = true;
     BATCH_TRY(b, hipSetDevice(b->device));
     const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK, hermite = b->integrator == NBODY_INTEGRATOR_HERMITE;
     const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
@@ -1117,8 +1423,10 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     const int64_t target = n_intervals << cfg->levels;
     if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != cfg->softening || b->acc_integrator != b->integrator)
         b->acc_valid = false;
-    if (!b->acc_valid)
+    if (!b->acc_valid) {
         b->level_valid = b->evolve_pending = false;
+        b->stop_forgotten = true;
+    }
     const bool same_axis = b->level_valid && b->level_dt_max == cfg->dt_max && b->level_levels == cfg->levels;
     const bool resume = b->evolve_pending;
     if (resume) {
@@ -1151,6 +1459,22 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     }
     if (!b->evolve_counters)
         BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
+    // stopping conditions (nbody_batch_stop.h): the thresholds in fp32, and reports that start from zero
+    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f;
+    BatchStopArgs sa{-1.f, __builtin_inff()};
+    if (stopping) {
+        if (b->stop_collision_radius > 0.f)
+            sa.thr = std::fmaf(b->stop_collision_radius, b->stop_collision_radius, cfg->softening * cfg->softening);
+        if (b->stop_escape_radius > 0.f)
+            sa.re2 = b->stop_escape_radius * b->stop_escape_radius;
+        if (!b->stop_report) {
+            BATCH_TRY(b, hipMalloc((void **)&b->stop_report, sizeof(BatchStopReport) * B));
+            b->stop_forgotten = true;
+        }
+        if (b->stop_forgotten)
+            BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
+        b->stop_forgotten = false;
+    }
     BatchEvolveArgs p;
     p.dt = (double)cfg->dt_max;
     p.dt_half = 0.5 * p.dt;
@@ -1176,7 +1500,7 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
         BATCH_TRY(b, launch_batch_adaptive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
                                            b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
-                                           p, b->stream));
+                                           p, sa, stopping ? b->stop_report : nullptr, b->stream));
         b->acc_integrator = b->integrator;
         b->acc_valid = b->level_valid = true;
         b->acc_pos = d_pos;
@@ -1199,8 +1523,13 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         b->evolve_pending = false;
         return NBODY_OK;
     }
+    std::vector<BatchStopReport> stopped(stopping ? B : 0);  // a stopped system sits before the target too, finished
+    if (stopping) {
+        BATCH_TRY(b, hipMemcpyAsync(stopped.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    }
     size_t first_unfinished = 0;
-    while (first_unfinished < B && b->evolve_host[first_unfinished].tick >= target)
+    while (first_unfinished < B && (b->evolve_host[first_unfinished].tick >= target || (stopping && stopped[first_unfinished].reason)))
         ++first_unfinished;
     return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: system " + std::to_string(first_unfinished) + " is unfinished after max_steps = " +
                                          std::to_string(max_steps) + " steps (tick " +
@@ -1223,6 +1552,59 @@ int nbody_batch_evolve_stats(nbody_batch *b, int64_t *steps, int *min_level, int
         if (clamped) clamped[s] = st.clamped;
         if (ticks) ticks[s] = st.tick;
     }
+    return NBODY_OK;
+}
+
+int nbody_batch_stop_set(nbody_batch *b, const nbody_batch_stop_config *cfg)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_set: batch is NULL");
+    const float rc = cfg ? cfg->collision_radius : 0.f, re = cfg ? cfg->escape_radius : 0.f;
+    if (!std::isfinite(rc) || rc < 0.f || !std::isfinite(re) || re < 0.f)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_stop_set: collision_radius and escape_radius must be finite and >= 0 (0: off)");
+    b->stop_collision_radius = rc;
+    b->stop_escape_radius = re;
+    forget_caches(b);  // the next nbody_batch_evolve_on starts with an evaluation, which examines the conditions
+    return NBODY_OK;
+}
+
+int nbody_batch_stop_read(nbody_batch *b, int *reason, int64_t *tick, int *pair_i, int *pair_j, float *separation, int *escaper)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_read: batch is NULL");
+    const size_t B = (size_t)b->n_systems;
+    std::vector<BatchStopReport> rep(B, BatchStopReport{0, 0, 0, 0, 0, 0.f, 0});
+    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f;
+    if (stopping && b->stop_report && !b->stop_forgotten) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        BATCH_TRY(b, hipMemcpyAsync(rep.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    for (size_t s = 0; s < B; ++s) {
+        const BatchStopReport r = b->counts[s] > 0 ? rep[s] : BatchStopReport{0, 0, 0, 0, 0, 0.f, 0};
+        if (reason) reason[s] = r.reason;
+        if (tick) tick[s] = r.tick;
+        if (pair_i) pair_i[s] = r.pair_i;
+        if (pair_j) pair_j[s] = r.pair_j;
+        if (separation) separation[s] = r.separation;
+        if (escaper) escaper[s] = r.escaper;
+    }
+    return NBODY_OK;
+}
+
+int nbody_batch_stop_count(nbody_batch *b, int64_t *stopped)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_count: batch is NULL");
+    if (!stopped)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_stop_count: NULL argument");
+    std::vector<int> reason((size_t)b->n_systems);
+    const int rc = nbody_batch_stop_read(b, reason.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != NBODY_OK)
+        return rc;
+    *stopped = 0;
+    for (int r : reason)
+        *stopped += r != 0;
     return NBODY_OK;
 }
 

@@ -12,7 +12,12 @@ exists for batches only, so its lines have no status-quo figures.
 the same arithmetic through the adaptive kernel, so the difference is the cost of the step criterion, the workgroup minimum
 and the per-launch counter read -- alternated, medians; then one scattering-style line: 1024 Kepler pairs with
 eccentricities spread over 0 .. 0.99 in one batch, evolved one period (dt_max = period / 64, levels = 12, eta = 0.01,
-no softening): wall time, the distribution of the systems' step counts and the worst relative energy error."""
+no softening): wall time, the distribution of the systems' step counts and the worst relative energy error.
+
+--stops: instead, per case, one line with evolve(k, dt, levels=0) without stopping conditions against the same call with
+conditions that cannot trigger (set_stop_conditions(1e-6, 1e6)): the same k steps, so the ratio is the cost of watching
+the conditions -- alternated, medians; then the scattering case above run to completion against the same batch stopped
+at collision radius 0.05 a: how many pairs stop, at what step counts, and the two wall times."""
 import argparse
 import json
 import os
@@ -37,6 +42,8 @@ ap.add_argument("--subset", type=int, default=8, help="systems the status quo is
 ap.add_argument("--dt", type=float, default=1e-3)
 ap.add_argument("--eps", type=float, default=1e-2)
 ap.add_argument("--adaptive", action="store_true", help="Hermite step_n against evolve(levels=0), and a scattering case")
+ap.add_argument("--stops", action="store_true", help="evolve(levels=0) with conditions that cannot trigger against without, "
+                "and the scattering case stopped at a collision radius")
 args = ap.parse_args()
 
 
@@ -135,8 +142,79 @@ def adaptive_lines():
             k *= 2
 
 
+def scattering_pairs(B=1024):
+    ecc = np.linspace(0.0, 0.99, B)
+    P = np.zeros((B, 2, 4), np.float32)
+    V = np.zeros((B, 2, 4), np.float32)
+    for s, e in enumerate(ecc):                 # two half masses, semi-major axis 1, at apocentre (G = 1): period 2 pi
+        ra, va = 1.0 + e, np.sqrt((1.0 - e) / (1.0 + e))
+        P[s] = [[0.5 * ra, 0, 0, 0.5], [-0.5 * ra, 0, 0, 0.5]]
+        V[s] = [[0, 0.5 * va, 0, 0], [0, -0.5 * va, 0, 0]]
+    return P, V, float(np.float32(2 * np.pi / 64))
+
+
+def stops_lines():
+    import time
+    for case in args.cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        inter = B * n * n
+        k = int(min(400, max(10, 2e11 // inter)))
+        dt = float(np.float32(args.dt))
+        with nb.BatchedSystem(B, n, integrator="hermite") as plain, nb.BatchedSystem(B, n, integrator="hermite") as watched:
+            plain.set_state(P, V)
+            watched.set_state(P, V)
+            watched.set_stop_conditions(collision_radius=1e-6, escape_radius=1e6)
+
+            def without():
+                plain.evolve(k, dt, levels=0, softening=args.eps)
+
+            def with_conditions():
+                watched.evolve(k, dt, levels=0, softening=args.eps)
+
+            without()
+            with_conditions()
+            torch.cuda.synchronize()
+            tp, tw = [], []
+            for _ in range(args.repeats):      # alternated
+                tp.append(timed(without) / k)
+                tw.append(timed(with_conditions) / k)
+            mp, mw = statistics.median(tp), statistics.median(tw)
+            stopped = int(watched.stops().stopped.sum())
+        print(json.dumps({"n": n, "B": B, "k": k, "evolve_ms_per_step": round(mp, 5), "evolve_with_conditions_ms_per_step": round(mw, 5),
+                          "ratio": round(mw / mp, 4), "stopped": stopped, "evolve_repeats": [round(x, 5) for x in tp],
+                          "with_conditions_repeats": [round(x, 5) for x in tw]}), flush=True)
+    P, V, dt_max = scattering_pairs()
+    with nb.BatchedSystem(P.shape[0], 2, integrator="hermite") as batch:
+        out = {}
+        for name, rc in (("to_completion", 0.0), ("collision_radius_0.05", 0.05)):
+            walls = []
+            for _ in range(1 + args.repeats):       # the first run warms up
+                batch.set_state(P, V)
+                batch.set_stop_conditions(collision_radius=rc)
+                batch.sync()
+                t0 = time.perf_counter()
+                res = batch.evolve(64, dt_max, levels=12, eta=0.01, eta_start=0.01, softening=0.0)
+                walls.append(time.perf_counter() - t0)
+            st = batch.stops()
+            steps = res.steps[st.stopped] if st.stopped.any() else res.steps
+            out[name] = {"wall_ms_median": round(statistics.median(walls[1:]) * 1e3, 3),
+                         "wall_ms_repeats": [round(w * 1e3, 3) for w in walls[1:]], "stopped": int(st.stopped.sum()),
+                         "steps_total": int(res.steps.sum()),
+                         ("steps_of_stopped_percentiles_0_25_50_75_100" if st.stopped.any() else "steps_percentiles_0_25_50_75_100"):
+                             [int(x) for x in np.percentile(steps, [0, 25, 50, 75, 100])]}
+            if st.stopped.any():
+                idx = np.nonzero(st.stopped)[0]
+                out[name]["first_stopped_pair_eccentricity"] = round(float(np.linspace(0.0, 0.99, P.shape[0])[idx[0]]), 4)
+                out[name]["separation_min_max"] = [float(f"{st.separation[idx].min():.4g}"), float(f"{st.separation[idx].max():.4g}")]
+        print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", **out}), flush=True)
+
+
 if args.adaptive:
     adaptive_lines()
+    sys.exit(0)
+if args.stops:
+    stops_lines()
     sys.exit(0)
 
 for case in args.cases:
