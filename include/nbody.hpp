@@ -341,6 +341,35 @@ public:
               "nbody_batch_stop_read");
         return s;
     }
+    // Collision action of evolve (nbody_batch_merge.h): with merge the colliding pair becomes one body in the survivor's
+    // slot, the count drops and the run goes on.  mergers(): per system the number of mergers and its first logCapacity
+    // events (events[s * logCapacity + e]); counts(): the body counts as evolve left them.
+    struct Mergers {
+        std::vector<std::int64_t> count;
+        std::vector<nbody_batch_merge_event> events;
+        int logCapacity = 0;
+    };
+    void setCollisionAction(bool merge, int logCapacity = 8)
+    {
+        const nbody_batch_merge_config cfg = {merge ? NBODY_BATCH_ON_COLLISION_MERGE : NBODY_BATCH_ON_COLLISION_STOP, logCapacity};
+        check(nbody_batch_merge_set(b_, &cfg), "nbody_batch_merge_set");
+        logCapacity_ = logCapacity;
+    }
+    Mergers mergers()
+    {
+        Mergers m;
+        m.logCapacity = logCapacity_;
+        m.count.resize((size_t)systems_);
+        m.events.resize((size_t)systems_ * (size_t)logCapacity_);
+        check(nbody_batch_merge_read(b_, m.count.data(), m.events.empty() ? nullptr : m.events.data()), "nbody_batch_merge_read");
+        return m;
+    }
+    std::vector<std::int64_t> counts()
+    {
+        std::vector<std::int64_t> c((size_t)systems_);
+        check(nbody_batch_get_counts(b_, c.data()), "nbody_batch_get_counts");
+        return c;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {
@@ -369,6 +398,7 @@ private:
     }
     nbody_batch *b_ = nullptr;
     std::int64_t systems_ = 0, maxBodies_ = 0;
+    int logCapacity_ = 0;
 };
 
 }  // namespace nbody

@@ -170,6 +170,27 @@ BATCH_STOP_COLLISION = 1
 BATCH_STOP_ESCAPE = 2
 
 
+class BatchMergeConfig(ctypes.Structure):
+    """``nbody_batch_merge_config`` of include/nbody_batch_merge.h."""
+    _fields_ = [("on_collision", c_int), ("log_capacity", c_int)]
+
+
+class BatchMergeEvent(ctypes.Structure):
+    """``nbody_batch_merge_event`` of include/nbody_batch_merge.h."""
+    _fields_ = [("tick", c_int64), ("survivor", c_int), ("absorbed", c_int), ("count_before", c_int), ("separation", c_float),
+                ("relative_speed", c_float), ("mass_survivor", c_float), ("mass_absorbed", c_float), ("reserved", c_int)]
+
+
+#: the entry points of include/nbody_batch_merge.h (mergers for Hermite batches), which nbody.h includes
+_MERGE_PROTOTYPES = {
+    "nbody_batch_merge_set": (c_int, [c_void_p, POINTER(BatchMergeConfig)]),
+    "nbody_batch_merge_read": (c_int, [c_void_p, POINTER(c_int64), POINTER(BatchMergeEvent)]),
+    "nbody_batch_get_counts": (c_int, [c_void_p, POINTER(c_int64)]),
+}
+BATCH_ON_COLLISION_STOP = 0
+BATCH_ON_COLLISION_MERGE = 1
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -194,7 +215,8 @@ def load() -> ctypes.CDLL:
         except ImportError:  # a torch-free host (ctypes only) uses the system runtime
             pass
         lib = ctypes.CDLL(path)
-        for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()):
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
+                list(_MERGE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -215,6 +237,11 @@ def evolve_names():
 def stop_names():
     """The entry points of nbody_batch_stop.h."""
     return list(_STOP_PROTOTYPES)
+
+
+def merge_exported_names():
+    """The entry points of nbody_batch_merge.h."""
+    return list(_MERGE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -20,6 +20,12 @@ from .system import SOFTENING_VERSION3, TIME_TICK, _ptr, _torch
 #: NBODY_BATCH_MAX_BODIES: the largest system a batch holds (64 KiB of positions in LDS); larger ones belong to NBodySystem
 BATCH_MAX_BODIES = 4096
 INTEGRATORS = {"kick_drift": 0, "kdk": 1, "hermite": 2}
+COLLISION_ACTIONS = {"stop": _lib.BATCH_ON_COLLISION_STOP, "merge": _lib.BATCH_ON_COLLISION_MERGE}
+#: one merger of the log: numpy's view of ``nbody_batch_merge_event``
+MERGE_EVENT_DTYPE = np.dtype([("tick", np.int64), ("survivor", np.int32), ("absorbed", np.int32), ("count_before", np.int32),
+                              ("separation", np.float32), ("relative_speed", np.float32), ("mass_survivor", np.float32),
+                              ("mass_absorbed", np.float32), ("reserved", np.int32)])
+assert MERGE_EVENT_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMergeEvent)
 
 
 def _check(lib, status: int, handle) -> None:
@@ -59,6 +65,7 @@ class BatchedSystem:
         self.velocities = torch.zeros_like(self.positions)
         self._counts = np.full(self.num_systems, self.max_bodies, dtype=np.int64)
         self.integrator = "kick_drift"
+        self._log_capacity = 0
         self.set_integrator(integrator)
         if counts is not None:
             self.set_counts(counts)
@@ -88,8 +95,13 @@ class BatchedSystem:
     # -- configuration -----------------------------------------------------------------------
     @property
     def counts(self) -> np.ndarray:
-        """Bodies per system (a copy)."""
+        """Bodies per system (a copy); :meth:`evolve` refreshes them, since mergers lower them."""
         return self._counts.copy()
+
+    def _refresh_counts(self) -> None:
+        c = np.zeros(self.num_systems, dtype=np.int64)
+        _check(self._lib, self._lib.nbody_batch_get_counts(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._h)
+        self._counts = c
 
     def set_counts(self, counts) -> None:
         """``B`` body counts in ``[0, max_bodies]``; forgets the cached accelerations (and Hermite jerks)."""
@@ -158,8 +170,10 @@ class BatchedSystem:
         continues.  Returns with the work complete."""
         self._use_current_stream()
         cfg = _lib.BatchEvolveConfig(float(dt_max), int(levels), float(eta), float(eta_start), float(softening), int(max_steps))
-        _check(self._lib, self._lib.nbody_batch_evolve_on(self._h, _ptr(self.positions), _ptr(self.velocities), int(n_intervals),
-                                                          ctypes.byref(cfg)), self._h)
+        status = self._lib.nbody_batch_evolve_on(self._h, _ptr(self.positions), _ptr(self.velocities), int(n_intervals),
+                                                 ctypes.byref(cfg))
+        self._refresh_counts()  # also after a call that ran out of steps: its mergers have happened
+        _check(self._lib, status, self._h)
         return self.evolve_stats()
 
     def evolve_stats(self) -> "EvolveResult":
@@ -200,6 +214,30 @@ class BatchedSystem:
                                                           sep.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                           esc.ctypes.data_as(i32)), self._h)
         return StopResult(reason, ticks, np.stack([pi, pj], axis=1), sep, esc)
+
+    def set_collision_action(self, action: str = "stop", log_capacity: int = 8) -> None:
+        """What :meth:`evolve` does with a collision (``include/nbody_batch_merge.h`` states the rules): ``"stop"`` (the
+        default) ends the system's run as :meth:`set_stop_conditions` describes; ``"merge"`` merges the colliding pair --
+        the mass is the sum, position and velocity the mass-weighted means, the survivor keeps the lower slot, the absorbed
+        body's last state moves to the first slot beyond the count -- lowers :attr:`counts` by one, evaluates the system
+        afresh and carries the run on.  :meth:`mergers` tells how many mergers each system had and logs the first
+        ``log_capacity`` of them.  Acts while a collision radius is set.  Forgets stops, the log and the cached
+        accelerations and jerks, as :meth:`set_stop_conditions` does."""
+        if action not in COLLISION_ACTIONS:
+            raise ValueError(f"action must be one of {tuple(COLLISION_ACTIONS)}")
+        cfg = _lib.BatchMergeConfig(COLLISION_ACTIONS[action], int(log_capacity))
+        _check(self._lib, self._lib.nbody_batch_merge_set(self._h, ctypes.byref(cfg)), self._h)
+        self._log_capacity = int(log_capacity)
+
+    def mergers(self) -> "MergeResult":
+        """The mergers so far, per system (waits for the queued work)."""
+        B, cap = self.num_systems, self._log_capacity
+        count = np.zeros(B, dtype=np.int64)
+        events = np.zeros((B, cap), dtype=MERGE_EVENT_DTYPE)
+        self._use_current_stream()
+        ev = events.ctypes.data_as(ctypes.POINTER(_lib.BatchMergeEvent)) if cap > 0 else None
+        _check(self._lib, self._lib.nbody_batch_merge_read(self._h, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ev), self._h)
+        return MergeResult(count, events)
 
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
@@ -252,10 +290,23 @@ class StopResult:
                 f"separation={self.separation.tolist()}, escaper={self.escaper.tolist()})")
 
 
+class MergeResult:
+    """What the collision action ``"merge"`` did, per system: ``count`` (``(B,)``, the number of mergers) and ``events``
+    (``(B, log_capacity)``, structured: ``tick``, in the units of the :meth:`BatchedSystem.evolve` call that found the
+    collision, ``survivor`` and ``absorbed`` (the pair ``i < j`` before the swap), ``count_before``, ``separation``,
+    ``relative_speed``, ``mass_survivor`` and ``mass_absorbed``; entries from a system's count on are zero)."""
+
+    def __init__(self, count, events):
+        self.count, self.events = count, events
+
+    def __repr__(self):
+        return f"MergeResult(count={self.count.tolist()}, events={self.events.tolist()})"
+
+
 def interactions_per_step(counts) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention)."""
     c = np.asarray(counts, dtype=np.int64)
     return int((c * c).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

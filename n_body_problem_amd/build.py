@@ -17,7 +17,8 @@ SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
            os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(PKG_DIR, "..", "include", "nbody.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_evolve.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_merge.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -184,7 +184,10 @@ __global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *v
 // thr >= eps^2), so two columns mean a column j != i within the collision radius -- without an index or a compare against
 // the row in the loop.  Per interaction one v_cmp into a scalar pair and three scalar mask operations (seen twice |=
 // seen once & now; seen once |= now): no vector register, and a, j are summed by the same instructions.
-template <int G, bool GUARD, bool STOP = false>
+// OWN (here, in hermite_evaluate and in hermite_evaluate_request): a tag without meaning that gives a kernel instantiations
+// of its own.  A template instantiation is optimised once before it is inlined, and one more caller changes what the existing
+// callers inline: batch_hermite_merge_kernel passes 1, so that the kernels before it stay the code they were.
+template <int G, bool GUARD, bool STOP = false, int OWN = 0>
 __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, const float3 (&xp)[G], const float3 (&vp)[G],
                                                    float eps2, float3 (&a)[G], float3 (&jk)[G], float thr = 0.f,
                                                    unsigned long long *near2 = nullptr)
@@ -283,7 +286,7 @@ __device__ __forceinline__ int stop_examine(unsigned long long near2, const floa
 // 128 VGPRs without scratch.  A group's corrector writes only registers, so the next group still reads the predicted state.
 // STOP (the evaluation at the current state, without the corrector): *found receives the stopping conditions the wave's
 // rows meet there, the escape test on the positions the columns hold.
-template <int RPL, bool GUARD, bool CORRECT, bool STOP = false>
+template <int RPL, bool GUARD, bool CORRECT, bool STOP = false, int OWN = 0>
 __device__ __forceinline__ void hermite_evaluate(const float4 *sh, int n, int tid, int T, float eps2, float4 (&x)[RPL],
                                                  float3 (&v)[RPL], float3 (&a)[RPL], float3 (&jk)[RPL], const HermiteSteps &t,
                                                  const BatchStopArgs *sa = nullptr, int *found = nullptr)
@@ -304,12 +307,12 @@ __device__ __forceinline__ void hermite_evaluate(const float4 *sh, int n, int ti
         }
         if (STOP) {
             unsigned long long near2[G];
-            batch_forces_jerks<G, GUARD, true>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
+            batch_forces_jerks<G, GUARD, true, OWN>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
 #pragma unroll
             for (int i = 0; i < G; ++i)
                 *found |= stop_examine(near2[i], xp[i], (g + i) * T + tid < n, *sa);
         } else {
-            batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+            batch_forces_jerks<G, GUARD, false, OWN>(sh, n, xp, vp, eps2, a1, j1);
         }
 #pragma unroll
         for (int i = 0; i < G; ++i) {
@@ -542,7 +545,7 @@ __device__ __forceinline__ void evolve_raise(EvolveWant &w, bool valid, double n
 // they leave no room for the criterion.  Each row votes as soon as its criterion is formed: nothing of it is carried
 // across the next group's column loop.  STOP: *found receives the stopping conditions the wave's rows meet, the collision
 // test in the column loop (at the predicted positions), the escape test on the corrected positions.
-template <int RPL, bool GUARD, bool STOP = false>
+template <int RPL, bool GUARD, bool STOP = false, int OWN = 0>
 __device__ __forceinline__ EvolveWant hermite_evaluate_request(const float4 *sh, int n, int tid, int T, float eps2, float4 *pos,
                                                                float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL],
                                                                const EvolveSteps &e, const BatchEvolveArgs &p,
@@ -566,9 +569,9 @@ __device__ __forceinline__ EvolveWant hermite_evaluate_request(const float4 *sh,
         }
         unsigned long long near2[G];
         if (STOP)
-            batch_forces_jerks<G, GUARD, true>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
+            batch_forces_jerks<G, GUARD, true, OWN>(sh, n, xp, vp, eps2, a1, j1, sa->thr, near2);
         else
-            batch_forces_jerks<G, GUARD>(sh, n, xp, vp, eps2, a1, j1);
+            batch_forces_jerks<G, GUARD, false, OWN>(sh, n, xp, vp, eps2, a1, j1);
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int q = g + i, r = q * T + tid;
@@ -983,6 +986,341 @@ __global__ __launch_bounds__(1024) void batch_hermite_stop_kernel(float4 *pos, f
         stop_report(sh, pos, n, tid, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x]);
 }
 
+// ---- mergers (include/nbody_batch_merge.h): a system whose bodies collide merges the pair and carries its run on.
+
+// Per launch: the systems' merger counts and logs (events: [n_systems][capacity], nullptr for capacity 0).
+struct BatchMergeArgs {
+    int *merges;
+    nbody_batch_merge_event *events;
+    int capacity;
+};
+
+// One component of the merged body: fp64 from the fp32 operands, rounded once; M = (double)m_i + (double)m_j.
+__device__ __forceinline__ float merge_mean(float mi, float ui, float mj, float uj, double M)
+{
+    if (M == 0.0)
+        return (float)(0.5 * ((double)ui + (double)uj));
+    return (float)(__builtin_fma((double)mj, (double)uj, (double)mi * (double)ui) / M);
+}
+
+// The cold path of a system that merges (workgroup-uniform): the pair as stop_report finds it -- the same rescan of the
+// columns LDS still holds, the same key and 64-bit LDS minimum -- then lane 0 merges the pair in the state arrays (the
+// corrected state: every lane's writes lie before the caller's last barrier), swaps the absorbed body with the last one and
+// logs the event; after a barrier the columns are refilled from the current state of the n - 1 bodies left, and a last
+// barrier completes them.  Returns whether a pair was found (always, when a row saw the threshold met: the rescan forms the
+// evaluation's own r^2), workgroup-uniform.
+__device__ __forceinline__ bool merge_absorb(float4 *sh, float4 *pos, float4 *vel, int n, int tid, int T, int rpl, float eps2,
+                                             const BatchStopArgs &sa, long long tick, const BatchMergeArgs &ma,
+                                             unsigned long long &best)
+{
+    asm volatile("" : "+v"(tid));  // the rows' addresses are formed here, not carried through the steps from the kernel's top
+    if (tid == 0)
+        best = ~0ull;
+    __syncthreads();
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r >= n)
+            continue;
+        const float4 pi = sh[2 * r];
+        unsigned long long mine = ~0ull;
+        for (int j = r + 1; j < n; ++j) {
+            const float4 pj = sh[2 * j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            float r2 = __builtin_fmaf(dx, dx, eps2);
+            r2 = __builtin_fmaf(dy, dy, r2);
+            r2 = __builtin_fmaf(dz, dz, r2);
+            if (r2 <= sa.thr) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(r2) << 24) | ((unsigned)r << 12) | (unsigned)j;
+                mine = key < mine ? key : mine;
+            }
+        }
+        if (mine != ~0ull)
+            atomicMin(&best, mine);
+    }
+    __syncthreads();
+    const unsigned long long key = best;
+    if (key == ~0ull)
+        return false;
+    if (tid == 0) {
+        const int i = (int)((key >> 12) & 0xfff), j = (int)(key & 0xfff), last = n - 1;
+        const float4 ci = sh[2 * i], cj = sh[2 * j];  // the positions of the evaluation that found the pair
+        const float dx = cj.x - ci.x, dy = cj.y - ci.y, dz = cj.z - ci.z;
+        const float4 xi = pos[i], xj = pos[j], xl = pos[last], vi = vel[i], vj = vel[j], vl = vel[last];
+        const float ex = vj.x - vi.x, ey = vj.y - vi.y, ez = vj.z - vi.z;
+        const double M = (double)xi.w + (double)xj.w;
+        pos[i] = make_float4(merge_mean(xi.w, xi.x, xj.w, xj.x, M), merge_mean(xi.w, xi.y, xj.w, xj.y, M),
+                             merge_mean(xi.w, xi.z, xj.w, xj.z, M), xi.w + xj.w);
+        vel[i] = make_float4(merge_mean(xi.w, vi.x, xj.w, vj.x, M), merge_mean(xi.w, vi.y, xj.w, vj.y, M),
+                             merge_mean(xi.w, vi.z, xj.w, vj.z, M), vi.w);
+        if (j != last) {
+            pos[j] = xl;
+            vel[j] = vl;
+        }
+        pos[last] = xj;
+        vel[last] = vj;
+        int sys = blockIdx.x;  // formed here: an address formed at the kernel's top would be carried through the steps
+        asm volatile("" : "+s"(sys));
+        const int merges = ma.merges[sys];  // the system's mergers so far: this one's place in the log
+        ma.merges[sys] = merges + 1;
+        if (merges < ma.capacity) {
+            nbody_batch_merge_event ev;
+            ev.tick = tick;
+            ev.survivor = i;
+            ev.absorbed = j;
+            ev.count_before = n;
+            ev.separation = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+            ev.relative_speed = __builtin_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
+            ev.mass_survivor = xi.w;
+            ev.mass_absorbed = xj.w;
+            ev.reserved = 0;
+            ma.events[(size_t)sys * (size_t)ma.capacity + (size_t)merges] = ev;
+        }
+    }
+    __syncthreads();  // the merged state is in the arrays, and every lane is done with the columns
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r < n - 1) {
+            const float4 w = vel[r];
+            sh[2 * r] = pos[r];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// The report of a system that stops under MERGE: an escaper only, found as stop_report finds it -- the smallest index among
+// the positions in the state array that satisfy the test, a 32-bit LDS minimum.  The reason never has the collision bit.
+__device__ __forceinline__ void merge_report_escaper(const float4 *pos, int n, int tid, int T, int rpl, const BatchStopArgs &sa,
+                                                     long long tick, BatchStopReport *out, int &escaper)
+{
+    if (tid == 0)
+        escaper = 0x7fffffff;
+    __syncthreads();
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r >= n)
+            continue;
+        const float4 xi = pos[r];
+        if (__builtin_fmaf(xi.z, xi.z, __builtin_fmaf(xi.y, xi.y, xi.x * xi.x)) > sa.re2)
+            atomicMin(&escaper, r);
+    }
+    __syncthreads();
+    if (tid == 0)
+        *out = BatchStopReport{tick, kStopEscape, -1, -1, escaper != 0x7fffffff ? escaper : -1, 0.f, 0};
+}
+
+// The smallest level whose step 2^(levels - L) divides the tick (0 for tick 0).
+__device__ __forceinline__ int merge_tick_level(long long tick, int levels)
+{
+    if (tick == 0)
+        return 0;
+    const int tz = __builtin_ctzll((unsigned long long)tick);
+    return tz >= levels ? 0 : levels - tz;
+}
+
+// batch_hermite_stop_kernel with the collision action MERGE of include/nbody_batch_merge.h: a sibling again, so that the
+// kernels above stay the code they are.  The same step; the body count is a workgroup-uniform scalar that a merger
+// decrements (written back to counts at exit).  The evaluation at the current state and the first-step rule, which the
+// kernels above run once at their top, are one block here that the loop enters again after every merger.  Launched only
+// with a collision radius; reason never receives the collision bit.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_merge_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                   int *counts, BatchEvolveState *state, int *counters,
+                                                                   int max_bodies, BatchEvolveArgs p, BatchStopArgs sa,
+                                                                   BatchStopReport *report, BatchMergeArgs ma)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    __shared__ int red[16];         // the waves' levels
+    __shared__ int red_stop[16];    // the waves' stopping conditions
+    __shared__ unsigned long long cold_best;  // the cold paths' words: merge_absorb's minimum, merge_report_escaper's
+    __shared__ int cold_escaper;
+    int n = uniform_i32(counts[blockIdx.x]);
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    const bool frozen = uniform_i32(report[blockIdx.x].reason) != 0;
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (frozen || tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target && !frozen) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    // Registers hold the rows' accelerations and jerks only; positions and velocities stay in the state arrays and the
+    // masses in LDS, as in batch_hermite_stop_kernel.
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    int stop = 0;                 // workgroup-uniform: the conditions met at the last evaluation
+    int run = 0;
+    bool evaluate = !p.have_acc;  // (a0, j0) are to be evaluated at the current state, which the columns hold
+    bool choose = !p.have_level;  // the level is to come from the first-step rule
+    // The evaluation at the current state and the first-step rule, then the steps until the target, the budget, max_steps or
+    // a condition; after a collision the merger, and the same again.
+    for (;;) {
+        if (evaluate) {
+            __syncthreads();
+            const HermiteSteps unused{0.0, 0.0, 0.0, 0.0};
+            float4 x4[RPL];  // not used without the corrector
+            float3 v3[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                x4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                v3[q] = make_float3(0.f, 0.f, 0.f);
+            }
+            int found = 0;
+            hermite_evaluate<RPL, GUARD, false, true, 1>(sh, n, tid, T, p.eps2, x4, v3, a, jk, unused, &sa, &found);
+            stop_publish(red_stop, found, tid);
+        }
+        if (choose) {  // dt = eta_start |a| / |j|, compared as squares
+            EvolveWant want;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+                const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+                evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);
+            }
+            evolve_publish(red, want, tid);
+        }
+        __syncthreads();  // every lane is done reading before a prediction rewrites the columns; red[], red_stop[] are complete
+        if (choose) {     // never coarser than the tick allows (tick 0 allows every level)
+            const EvolveWant want = evolve_collect(red, T);
+            const int floor_level = merge_tick_level(tick, p.levels);
+            level = want.level > p.levels ? p.levels : want.level;
+            level = level < floor_level ? floor_level : level;
+            clamped += want.level > p.levels ? 1 : 0;
+        }
+        if (evaluate)
+            stop = stop_collect(red_stop, T);
+        for (; tick < p.target && run < p.budget && steps < p.max_steps && !stop; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        int found = 0;
+        const EvolveWant mine = hermite_evaluate_request<RPL, GUARD, true, 1>(sh, n, tid, T, p.eps2, pos, vel, a, jk, e, p, &sa, &found);
+        stop_publish(red_stop, found, tid);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        stop = stop_collect(red_stop, T);
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick += 1ll << (p.levels - level);
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+        }
+        if (!(stop & kStopCollision))
+            break;
+        // the columns still hold the positions the collision was found at
+        if (!merge_absorb(sh, pos, vel, n, tid, T, RPL, p.eps2, sa, tick, ma, cold_best)) {
+            stop &= ~kStopCollision;
+            break;
+        }
+        --n;
+        evaluate = choose = true;
+    }
+    int lane = tid;  // the rows' indices formed anew: the offsets of the kernel's top are not carried through the steps for this
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + lane;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        counts[blockIdx.x] = n;
+        if (tick < p.target && !stop) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+    if (stop)  // an escaper: among the corrected positions, or the current ones after a merger
+        merge_report_escaper(pos, n, lane, T, RPL, sa, tick, &report[blockIdx.x], cold_escaper);
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_merge_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                            float4 *jerk, int *counts, BatchEvolveState *state, int *counters, int max_bodies,
+                            const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report, const BatchMergeArgs &ma)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_merge_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_merge_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
+                       counters, max_bodies, p, sa, report, ma);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_merge(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, int *counts, BatchEvolveState *state,
+                              int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
+                              BatchStopReport *report, const BatchMergeArgs &ma, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(p.eps2 > 0.f);
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_merge_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    case 3: return launch_merge_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    case 4: return launch_merge_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    case 5: return launch_merge_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    case 8: return launch_merge_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    default: return launch_merge_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
+    }
+}
+
 // report == nullptr: no stopping conditions, batch_hermite_adaptive_kernel
 template <int RPL, bool GUARD>
 hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
@@ -1161,6 +1499,12 @@ struct nbody_batch {
     float stop_collision_radius = 0.f, stop_escape_radius = 0.f;  // both 0: off
     BatchStopReport *stop_report = nullptr;    // [n_systems], allocated by the first evolve with conditions
     bool stop_forgotten = true;                // the reports count as all zero: cleared before the next launch reads them
+    // nbody_batch_merge_set: the collision action, and the per-system merger counts and logs beside the reports (forgotten
+    // with them)
+    int merge_action = NBODY_BATCH_ON_COLLISION_STOP;
+    int merge_capacity = 0;
+    int *merge_count = nullptr;                     // [n_systems], allocated by the first evolve that merges
+    nbody_batch_merge_event *merge_log = nullptr;   // [n_systems][merge_capacity]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -1266,6 +1610,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->evolve_state) (void)hipFree(b->evolve_state);
     if (b->evolve_counters) (void)hipFree(b->evolve_counters);
     if (b->stop_report) (void)hipFree(b->stop_report);
+    if (b->merge_count) (void)hipFree(b->merge_count);
+    if (b->merge_log) (void)hipFree(b->merge_log);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1461,7 +1807,21 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
     // stopping conditions (nbody_batch_stop.h): the thresholds in fp32, and reports that start from zero
     const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f;
+    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && b->stop_collision_radius > 0.f;
     BatchStopArgs sa{-1.f, __builtin_inff()};
+    if (merging) {  // nbody_batch_merge.h: counts and logs that start from zero where the reports do
+        if (!b->merge_count) {
+            BATCH_TRY(b, hipMalloc((void **)&b->merge_count, sizeof(int) * B));
+            b->stop_forgotten = true;
+        }
+        if (b->merge_capacity > 0 && !b->merge_log) {
+            BATCH_TRY(b, hipMalloc((void **)&b->merge_log, sizeof(nbody_batch_merge_event) * B * (size_t)b->merge_capacity));
+            b->stop_forgotten = true;
+        }
+        if (b->stop_forgotten)
+            BATCH_TRY(b, hipMemsetAsync(b->merge_count, 0, sizeof(int) * B, b->stream));
+    }
+    const BatchMergeArgs ma{b->merge_count, b->merge_log, b->merge_capacity};
     if (stopping) {
         if (b->stop_collision_radius > 0.f)
             sa.thr = std::fmaf(b->stop_collision_radius, b->stop_collision_radius, cfg->softening * cfg->softening);
@@ -1498,9 +1858,14 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         p.new_call = first ? 1 : 0;
         p.reset_tick = first && !resume ? 1 : 0;
         BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
-        BATCH_TRY(b, launch_batch_adaptive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
-                                           b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
-                                           p, sa, stopping ? b->stop_report : nullptr, b->stream));
+        if (merging)
+            BATCH_TRY(b, launch_batch_merge(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
+                                            b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
+                                            p, sa, b->stop_report, ma, b->stream));
+        else
+            BATCH_TRY(b, launch_batch_adaptive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
+                                               b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
+                                               p, sa, stopping ? b->stop_report : nullptr, b->stream));
         b->acc_integrator = b->integrator;
         b->acc_valid = b->level_valid = true;
         b->acc_pos = d_pos;
@@ -1514,6 +1879,8 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         if (counters[0] == 0 || counters[0] == counters[1])
             break;
     }
+    if (merging)  // the kernel's own changes of the counts; the caches stay: the restarts have refilled them
+        BATCH_TRY(b, hipMemcpyAsync(b->counts.data(), b->counts_dev, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
     BATCH_TRY(b, hipMemcpyAsync(b->evolve_host.data(), b->evolve_state, sizeof(BatchEvolveState) * B, hipMemcpyDeviceToHost, b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     for (size_t s = 0; s < B; ++s)
@@ -1605,6 +1972,67 @@ int nbody_batch_stop_count(nbody_batch *b, int64_t *stopped)
     *stopped = 0;
     for (int r : reason)
         *stopped += r != 0;
+    return NBODY_OK;
+}
+
+int nbody_batch_merge_set(nbody_batch *b, const nbody_batch_merge_config *cfg)
+{
+    const int action = cfg ? cfg->on_collision : NBODY_BATCH_ON_COLLISION_STOP, capacity = cfg ? cfg->log_capacity : 0;
+    if (action != NBODY_BATCH_ON_COLLISION_STOP && action != NBODY_BATCH_ON_COLLISION_MERGE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_merge_set: unknown collision action (STOP = 0, MERGE = 1)");
+    if (capacity < 0 || capacity > NBODY_BATCH_MAX_BODIES - 1)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_merge_set: log_capacity outside [0, NBODY_BATCH_MAX_BODIES - 1 = 4095]");
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_set: batch is NULL");
+    if (capacity != b->merge_capacity && b->merge_log) {  // allocated anew by the next evolve that merges
+        BATCH_TRY(b, hipSetDevice(b->device));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+        BATCH_TRY(b, hipFree(b->merge_log));
+        b->merge_log = nullptr;
+    }
+    b->merge_action = action;
+    b->merge_capacity = capacity;
+    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
+    return NBODY_OK;
+}
+
+int nbody_batch_merge_read(nbody_batch *b, int64_t *n_merges, nbody_batch_merge_event *events)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_read: batch is NULL");
+    const size_t B = (size_t)b->n_systems, cap = (size_t)b->merge_capacity;
+    std::vector<int> count(B, 0);
+    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && b->stop_collision_radius > 0.f;
+    const bool kept = merging && b->merge_count && !b->stop_forgotten;
+    if (events)
+        std::memset(events, 0, sizeof(nbody_batch_merge_event) * B * cap);
+    if (kept) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        BATCH_TRY(b, hipMemcpyAsync(count.data(), b->merge_count, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+        if (events && cap > 0 && b->merge_log) {
+            std::vector<nbody_batch_merge_event> log(B * cap);
+            BATCH_TRY(b, hipMemcpyAsync(log.data(), b->merge_log, sizeof(nbody_batch_merge_event) * B * cap, hipMemcpyDeviceToHost, b->stream));
+            BATCH_TRY(b, hipStreamSynchronize(b->stream));
+            for (size_t s = 0; s < B; ++s)  // entries beyond a system's count were never written
+                for (size_t e = 0; e < cap && e < (size_t)count[s]; ++e)
+                    events[s * cap + e] = log[s * cap + e];
+        }
+    }
+    if (n_merges)
+        for (size_t s = 0; s < B; ++s)
+            n_merges[s] = count[s];
+    return NBODY_OK;
+}
+
+int nbody_batch_get_counts(nbody_batch *b, int64_t *counts)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_get_counts: batch is NULL");
+    if (!counts)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_get_counts: NULL argument");
+    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
+        counts[s] = b->counts[s];
     return NBODY_OK;
 }
 

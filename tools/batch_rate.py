@@ -17,7 +17,12 @@ no softening): wall time, the distribution of the systems' step counts and the w
 --stops: instead, per case, one line with evolve(k, dt, levels=0) without stopping conditions against the same call with
 conditions that cannot trigger (set_stop_conditions(1e-6, 1e6)): the same k steps, so the ratio is the cost of watching
 the conditions -- alternated, medians; then the scattering case above run to completion against the same batch stopped
-at collision radius 0.05 a: how many pairs stop, at what step counts, and the two wall times."""
+at collision radius 0.05 a: how many pairs stop, at what step counts, and the two wall times.
+
+--merges: instead, per case, one line with evolve(k, dt, levels=0) under the collision action "stop" against the same call
+under "merge", both with conditions that cannot trigger (the stop kernel against the merge kernel on the same k steps) --
+alternated, medians; then the scattering case with collision radius 0.05 a stopped against merged and run to completion: how
+many pairs merge, at what step counts, and the two wall times."""
 import argparse
 import json
 import os
@@ -44,6 +49,8 @@ ap.add_argument("--eps", type=float, default=1e-2)
 ap.add_argument("--adaptive", action="store_true", help="Hermite step_n against evolve(levels=0), and a scattering case")
 ap.add_argument("--stops", action="store_true", help="evolve(levels=0) with conditions that cannot trigger against without, "
                 "and the scattering case stopped at a collision radius")
+ap.add_argument("--merges", action="store_true", help="evolve(levels=0) under the collision action merge against stop, with "
+                "conditions that cannot trigger, and the scattering case merged at a collision radius")
 args = ap.parse_args()
 
 
@@ -210,8 +217,71 @@ def stops_lines():
         print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", **out}), flush=True)
 
 
+def merges_lines():
+    import time
+    for case in args.cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        inter = B * n * n
+        k = int(min(400, max(10, 2e11 // inter)))
+        dt = float(np.float32(args.dt))
+        with nb.BatchedSystem(B, n, integrator="hermite") as stopping, nb.BatchedSystem(B, n, integrator="hermite") as merging:
+            for batch, action in ((stopping, "stop"), (merging, "merge")):
+                batch.set_state(P, V)
+                batch.set_stop_conditions(collision_radius=1e-6, escape_radius=1e6)
+                batch.set_collision_action(action)
+
+            def stop_kernel():
+                stopping.evolve(k, dt, levels=0, softening=args.eps)
+
+            def merge_kernel():
+                merging.evolve(k, dt, levels=0, softening=args.eps)
+
+            stop_kernel()
+            merge_kernel()
+            torch.cuda.synchronize()
+            ts, tm = [], []
+            for _ in range(args.repeats):      # alternated
+                ts.append(timed(stop_kernel) / k)
+                tm.append(timed(merge_kernel) / k)
+            ms, mm = statistics.median(ts), statistics.median(tm)
+            merged = int(merging.mergers().count.sum())
+        print(json.dumps({"n": n, "B": B, "k": k, "evolve_stop_ms_per_step": round(ms, 5), "evolve_merge_ms_per_step": round(mm, 5),
+                          "ratio": round(mm / ms, 4), "mergers": merged, "stop_repeats": [round(x, 5) for x in ts],
+                          "merge_repeats": [round(x, 5) for x in tm]}), flush=True)
+    P, V, dt_max = scattering_pairs()
+    with nb.BatchedSystem(P.shape[0], 2, integrator="hermite") as batch:
+        out = {}
+        for action in ("stop", "merge"):
+            walls = []
+            for _ in range(1 + args.repeats):       # the first run warms up
+                batch.set_counts([2] * P.shape[0])
+                batch.set_state(P, V)
+                batch.set_stop_conditions(collision_radius=0.05)
+                batch.set_collision_action(action)
+                batch.sync()
+                t0 = time.perf_counter()
+                res = batch.evolve(64, dt_max, levels=12, eta=0.01, eta_start=0.01, softening=0.0)
+                walls.append(time.perf_counter() - t0)
+            st, mg = batch.stops(), batch.mergers()
+            hit = st.stopped if action == "stop" else mg.count > 0
+            out[action] = {"wall_ms_median": round(statistics.median(walls[1:]) * 1e3, 3),
+                           "wall_ms_repeats": [round(w * 1e3, 3) for w in walls[1:]], "stopped": int(st.stopped.sum()),
+                           "merged": int((mg.count > 0).sum()), "at_the_end_time": int((res.ticks == 64 << 12).sum()),
+                           "steps_total": int(res.steps.sum()),
+                           "steps_of_colliding_pairs_percentiles_0_25_50_75_100":
+                               [int(x) for x in np.percentile(res.steps[hit], [0, 25, 50, 75, 100])] if hit.any() else []}
+            if action == "merge" and hit.any():
+                ticks = mg.events["tick"][hit, 0]
+                out[action]["merger_ticks_min_max"] = [int(ticks.min()), int(ticks.max())]
+        print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", "collision_radius": 0.05, **out}), flush=True)
+
+
 if args.adaptive:
     adaptive_lines()
+    sys.exit(0)
+if args.merges:
+    merges_lines()
     sys.exit(0)
 if args.stops:
     stops_lines()
