@@ -489,9 +489,10 @@ float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
  *   its own adaptive step h = dt_max 2^-L from Aarseth's criterion and evolves all of them to a common time;
  *   nbody_batch_stop_set (nbody_batch_stop.h, included below) makes it end a system's run when two bodies come within a
  *   collision radius or a body leaves an escape radius, and nbody_batch_stop_read tells when and which;
- *   nbody_batch_merge_set (nbody_batch_merge.h, included below) makes it merge the colliding pair and carry the run on.
- *   No individual per-body time steps, no P(EC)^n iteration, no fp64 state; no per-body radii, no centre-of-mass escape
- *   test, no outcome of a collision other than a stop or a perfect merger.
+ *   nbody_batch_merge_set (nbody_batch_merge.h, included below) makes it merge the colliding pair and carry the run on;
+ *   nbody_batch_radii_set (nbody_batch_radii.h, included below) gives every body a collision radius of its own.
+ *   No individual per-body time steps, no P(EC)^n iteration, no fp64 state; no centre-of-mass escape test, no outcome of
+ *   a collision other than a stop or a perfect merger.
  * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
  * [1, NBODY_BATCH_MAX_BODIES], counts outside [0, max_bodies], k < 0, a non-finite dt, the softening rule, NULL pointers.
  * nbody_batch_step_n_on returns with the work complete, _async only enqueues (nbody_batch_sync waits).  Diagnostics are
@@ -520,6 +521,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_stop.h"
 /* mergers: the colliding pair becomes one body and the system's run goes on */
 #include "nbody_batch_merge.h"
+/* per-body collision radii: a pair collides within the sum of its own radii, and a merged body grows */
+#include "nbody_batch_radii.h"
 
 #ifdef __cplusplus
 }

@@ -370,6 +370,21 @@ public:
         check(nbody_batch_get_counts(b_, c.data()), "nbody_batch_get_counts");
         return c;
     }
+    // Per-body collision radii of evolve (nbody_batch_radii.h): numSystems x maxBodies values laid out like the positions;
+    // two bodies collide within the sum of their radii, and a merged body's radius is cbrt(R_i^3 + R_j^3).  An empty
+    // vector switches radii off.  radii(): the radii as the library left them (throws when none are set).
+    void setRadii(const std::vector<float> &radii)
+    {
+        if (!radii.empty() && (std::int64_t)radii.size() != systems_ * maxBodies_)
+            throw std::runtime_error("Batch::setRadii: numSystems x maxBodies radii, or none");
+        check(nbody_batch_radii_set(b_, radii.empty() ? nullptr : radii.data()), "nbody_batch_radii_set");
+    }
+    std::vector<float> radii()
+    {
+        std::vector<float> r((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_radii_read(b_, r.data()), "nbody_batch_radii_read");
+        return r;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

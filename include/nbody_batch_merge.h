@@ -47,7 +47,8 @@
  *   bit, the same kernels.  With MERGE and a radius that never triggers no bit of any state differs from the plain call.
  *   States, counts and logs are functions of the system alone: not of its slot, B, max_bodies, the other systems or
  *   nbody_batch_evolve_launch_steps; evolve(a) followed by evolve(b) is evolve(a + b) bit for bit, mergers included.
- * Out of scope: per-body radii, fragmentation or any outcome other than perfect merging, mergers in nbody_batch_step_n_*. */
+ * Per-body radii, and the merged body's, are nbody_batch_radii.h.  Out of scope: fragmentation or any outcome other than
+ *   perfect merging, mergers in nbody_batch_step_n_*. */
 #ifndef NBODY_AMD_BATCH_MERGE_H
 #define NBODY_AMD_BATCH_MERGE_H
 

@@ -25,7 +25,8 @@
  *   softening, other buffers, another integrator, nbody_batch_invalidate_forces), by nbody_batch_step_n_* and by a new
  *   nbody_batch_stop_set; nbody_batch_stop_set also forgets the caches, so that the next nbody_batch_evolve_on starts with
  *   an evaluation, which examines the conditions.  Merging the colliding bodies and carrying the run on is the collision
- *   action MERGE of nbody_batch_merge.h.  Per-body radii and a centre-of-mass escape test are out of scope.
+ *   action MERGE of nbody_batch_merge.h, per-body radii in place of R_c are nbody_batch_radii.h.  A centre-of-mass escape
+ *   test is out of scope.
  * No conditions set (the default, NULL, or both radii 0): nbody_batch_evolve_on is what it is without this header, bit
  *   for bit, the same kernels.  Conditions that never trigger change no bit of any state.  Reports and stopped states are
  *   functions of the system alone: not of its slot, B, max_bodies, the other systems or nbody_batch_evolve_launch_steps.

@@ -191,6 +191,13 @@ BATCH_ON_COLLISION_STOP = 0
 BATCH_ON_COLLISION_MERGE = 1
 
 
+#: the entry points of include/nbody_batch_radii.h (per-body collision radii for Hermite batches), which nbody.h includes
+_RADII_PROTOTYPES = {
+    "nbody_batch_radii_set": (c_int, [c_void_p, POINTER(c_float)]),
+    "nbody_batch_radii_read": (c_int, [c_void_p, POINTER(c_float)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -216,7 +223,7 @@ def load() -> ctypes.CDLL:
             pass
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
-                list(_MERGE_PROTOTYPES.items()):
+                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -242,6 +249,11 @@ def stop_names():
 def merge_exported_names():
     """The entry points of nbody_batch_merge.h."""
     return list(_MERGE_PROTOTYPES)
+
+
+def radii_names():
+    """The entry points of nbody_batch_radii.h."""
+    return list(_RADII_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

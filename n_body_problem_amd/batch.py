@@ -195,9 +195,11 @@ class BatchedSystem:
         """Stopping conditions of :meth:`evolve` (``include/nbody_batch_stop.h`` states them): a system's run ends after the
         step in which two of its bodies come within ``collision_radius`` of each other, or a body is farther than
         ``escape_radius`` from the coordinate origin (centre the systems); ``0`` switches a condition off, both ``0`` (the
-        default) all of it.  A stop is a result, not an error: :meth:`stops` tells which systems stopped, when and which
-        bodies; a stopped system stays frozen in later :meth:`evolve` calls.  Forgets earlier stops and the cached
-        accelerations and jerks (as :meth:`set_state`, :meth:`invalidate_forces` and :meth:`step_n` forget the stops)."""
+        default) all of it.  With per-body radii (:meth:`set_radii`) collisions are judged by those instead and
+        ``collision_radius`` must stay ``0``: :meth:`evolve` refuses both together.  A stop is a result, not an error:
+        :meth:`stops` tells which systems stopped, when and which bodies; a stopped system stays frozen in later
+        :meth:`evolve` calls.  Forgets earlier stops and the cached accelerations and jerks (as :meth:`set_state`,
+        :meth:`invalidate_forces` and :meth:`step_n` forget the stops)."""
         cfg = _lib.BatchStopConfig(float(collision_radius), float(escape_radius))
         _check(self._lib, self._lib.nbody_batch_stop_set(self._h, ctypes.byref(cfg)), self._h)
 
@@ -221,13 +223,45 @@ class BatchedSystem:
         the mass is the sum, position and velocity the mass-weighted means, the survivor keeps the lower slot, the absorbed
         body's last state moves to the first slot beyond the count -- lowers :attr:`counts` by one, evaluates the system
         afresh and carries the run on.  :meth:`mergers` tells how many mergers each system had and logs the first
-        ``log_capacity`` of them.  Acts while a collision radius is set.  Forgets stops, the log and the cached
-        accelerations and jerks, as :meth:`set_stop_conditions` does."""
+        ``log_capacity`` of them.  Acts while a collision radius or per-body radii (:meth:`set_radii`) are set; with radii
+        the merged body's radius is ``cbrt(R_i**3 + R_j**3)`` and the radii move with their bodies.  Forgets stops, the log
+        and the cached accelerations and jerks, as :meth:`set_stop_conditions` does."""
         if action not in COLLISION_ACTIONS:
             raise ValueError(f"action must be one of {tuple(COLLISION_ACTIONS)}")
         cfg = _lib.BatchMergeConfig(COLLISION_ACTIONS[action], int(log_capacity))
         _check(self._lib, self._lib.nbody_batch_merge_set(self._h, ctypes.byref(cfg)), self._h)
         self._log_capacity = int(log_capacity)
+
+    def set_radii(self, radii) -> None:
+        """Per-body collision radii of :meth:`evolve` (``include/nbody_batch_radii.h`` states the rules): ``(B, n)``, numpy or
+        torch, ``n <= max_bodies``, one radius ``>= 0`` per slot (slots from ``n`` on get ``0``); ``None`` switches them off.
+        With radii set two bodies collide when they come within the sum of their radii, whether or not a collision radius is
+        set (both together are refused by :meth:`evolve`); the collision action is :meth:`set_collision_action`'s, and a
+        merged body's radius is ``cbrt(R_i**3 + R_j**3)``.  Radii belong to the slots: :meth:`set_state` and
+        :meth:`set_counts` leave them alone.  The shape is checked here, the values by the library (negative or non-finite
+        below a system's count: :class:`NBodyError`).  Forgets stops, the merger log and the cached accelerations and
+        jerks, as :meth:`set_stop_conditions` does."""
+        if radii is None:
+            _check(self._lib, self._lib.nbody_batch_radii_set(self._h, None), self._h)
+            return
+        if hasattr(radii, "detach"):  # a torch tensor
+            radii = radii.detach().cpu().numpy()
+        r = np.asarray(radii, dtype=np.float32)
+        if r.ndim != 2 or r.shape[0] != self.num_systems or r.shape[1] > self.max_bodies:
+            raise ValueError(f"radii must have shape ({self.num_systems}, n <= {self.max_bodies}), got {tuple(r.shape)}")
+        full = np.zeros((self.num_systems, self.max_bodies), dtype=np.float32)
+        full[:, :r.shape[1]] = r
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_radii_set(self._h, full.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._h)
+
+    def radii(self) -> np.ndarray:
+        """The radii as the library left them, ``(B, max_bodies)`` float32 (waits for the queued work): after mergers the
+        survivors have grown and the absorbed bodies' radii lie with their last states beyond the counts.  Raises
+        :class:`NBodyError` (``NBODY_ERR_STATE``) when no radii are set."""
+        out = np.zeros((self.num_systems, self.max_bodies), dtype=np.float32)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_radii_read(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._h)
+        return out
 
     def mergers(self) -> "MergeResult":
         """The mergers so far, per system (waits for the queued work)."""

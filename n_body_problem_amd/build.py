@@ -15,10 +15,12 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
 SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
-           os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(PKG_DIR, "..", "include", "nbody.h"),
+           os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_evolve.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_merge.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_merge.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_radii.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -13,6 +13,7 @@
 // Hermite (NBODY_INTEGRATOR_HERMITE) runs a sibling kernel, batch_hermite_kernel: the same order, with the jerk summed
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
+#include "nbody_batch_radii_check.h"
 #include "nbody_kernels.h"
 
 #include <algorithm>
@@ -174,6 +175,13 @@ __global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *v
 // The column side lives in LDS, 32 B per body: body j's predicted {x, y, z, m} at sh[2j] and {vx, vy, vz, 0} at sh[2j + 1]
 // (128 KiB at 4096 bodies: one workgroup per CU, as the registers of a 1024-thread workgroup allow anyway).
 
+// The collision threshold of a pair with per-body radii (include/nbody_batch_radii.h): fmaf(S, S, eps^2), S = R_i + R_j.
+__device__ __forceinline__ float radii_threshold(float ri, float rj, float eps2)
+{
+    const float S = ri + rj;
+    return __builtin_fmaf(S, S, eps2);
+}
+
 // Accelerations and jerks of G rows at their predicted state (xp, vp) from the n columns in LDS, ascending j, one fp32
 // chain per row and component.  Pair term: d = x_j - x_i, e = v_j - v_i, r^2 + eps^2 by batch_forces' FMA chain,
 // inv = v_rsq_f32, inv2 = inv inv, s = (m_j inv) inv2 (batch_forces' s), rv = fma(dz, ez, fma(dy, ey, dx ex)),
@@ -187,10 +195,13 @@ __global__ __launch_bounds__(1024) void batch_step_kernel(float4 *pos, float4 *v
 // OWN (here, in hermite_evaluate and in hermite_evaluate_request): a tag without meaning that gives a kernel instantiations
 // of its own.  A template instantiation is optimised once before it is inlined, and one more caller changes what the existing
 // callers inline: batch_hermite_merge_kernel passes 1, so that the kernels before it stay the code they were.
-template <int G, bool GUARD, bool STOP = false, int OWN = 0>
+// RADII (include/nbody_batch_radii.h, with STOP): the threshold is the pair's own, fmaf(S, S, eps^2) with S = R_row + R_j, one
+// fp32 add; R_j rides in the fourth word of the column's velocity, which the broadcast read brings anyway, and rr[k] is the
+// row's radius.  Two more VALU per interaction; the self pair still meets its threshold (eps^2 <= fmaf(2 R, 2 R, eps^2)).
+template <int G, bool GUARD, bool STOP = false, int OWN = 0, bool RADII = false>
 __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, const float3 (&xp)[G], const float3 (&vp)[G],
                                                    float eps2, float3 (&a)[G], float3 (&jk)[G], float thr = 0.f,
-                                                   unsigned long long *near2 = nullptr)
+                                                   unsigned long long *near2 = nullptr, const float *rr = nullptr)
 {
     unsigned long long near1[G];
 #pragma unroll
@@ -212,7 +223,7 @@ __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, cons
             r2 = __builtin_fmaf(dy, dy, r2);
             r2 = __builtin_fmaf(dz, dz, r2);
             if (STOP) {
-                const unsigned long long now = __ballot(r2 <= thr);
+                const unsigned long long now = __ballot(r2 <= (RADII ? radii_threshold(rr[k], wj.w, eps2) : thr));
                 near2[k] |= near1[k] & now;
                 near1[k] |= now;
             }
@@ -1321,6 +1332,450 @@ hipError_t launch_batch_merge(float4 *pos, float4 *vel, float4 *acc, float4 *jer
     }
 }
 
+// ---- per-body radii (include/nbody_batch_radii.h): a pair collides when it is within the sum of its own two radii.
+
+// Per launch: the radii ([n_systems][max_bodies], laid out like the positions) and the collision action, workgroup-uniform.
+struct BatchRadiiArgs {
+    float *radii;
+    int merge;  // NBODY_BATCH_ON_COLLISION_MERGE: merge the pair and carry on; otherwise stop and report
+};
+
+// hermite_evaluate<.., CORRECT = false, STOP = true> and hermite_evaluate_request<.., STOP = true> with radii: siblings, so
+// that those stay the code they are for the kernels above.  The same row groups; a row's radius is read with its predicted
+// velocity, one ds_read_b128 where those read 12 bytes, reread for every group, and handed to batch_forces_jerks, which
+// forms the pair's threshold.  Nothing of it outlives the group's column loop.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void radii_evaluate(const float4 *sh, int n, int tid, int T, float eps2, float3 (&a)[RPL],
+                                               float3 (&jk)[RPL], const BatchStopArgs &sa, int *found)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G];
+        float rr[G];
+        unsigned long long near2[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = make_float3(0.f, 0.f, 0.f);
+            rr[i] = 0.f;
+            if (r < n) {
+                const float4 w = sh[2 * r + 1];
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = make_float3(w.x, w.y, w.z);
+                rr[i] = w.w;
+            }
+        }
+        batch_forces_jerks<G, GUARD, true, 2, true>(sh, n, xp, vp, eps2, a1, j1, 0.f, near2, rr);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            *found |= stop_examine(near2[i], xp[i], (g + i) * T + tid < n, sa);
+            a[g + i] = a1[i];
+            jk[g + i] = j1[i];
+        }
+    }
+}
+
+template <int RPL, bool GUARD>
+__device__ __forceinline__ EvolveWant radii_evaluate_request(const float4 *sh, int n, int tid, int T, float eps2, float4 *pos,
+                                                             float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL], const EvolveSteps &e,
+                                                             const BatchEvolveArgs &p, const BatchStopArgs &sa, int *found)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+    EvolveWant want;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G], x[G], v[G];
+        float rr[G];
+        unsigned long long near2[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = x[i] = v[i] = make_float3(0.f, 0.f, 0.f);
+            rr[i] = 0.f;
+            if (r < n) {
+                const float4 w = sh[2 * r + 1];
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = make_float3(w.x, w.y, w.z);
+                rr[i] = w.w;
+                x[i] = *reinterpret_cast<const float3 *>(&pos[r]);
+                v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, true, 2, true>(sh, n, xp, vp, eps2, a1, j1, 0.f, near2, rr);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
+            hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
+            hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            *found |= stop_examine(near2[i], x[i], r < n, sa);
+            if (r < n) {  // x, y, z only: the masses and the velocities' w stay as they are
+                *reinterpret_cast<float3 *>(&pos[r]) = x[i];
+                *reinterpret_cast<float3 *>(&vel[r]) = v[i];
+            }
+            float3 a0 = a[q], j0 = jk[q];
+            renew_f32(a0);  // widened again below, one component at a time: the corrector's fp64 copies end here
+            renew_f32(j0);
+            renew_f32(a1[i]);
+            renew_f32(j1[i]);
+            a[q] = a1[i];
+            jk[q] = j1[i];
+            EvolveNorms s;
+            evolve_norms(s, a0.x, a1[i].x, j0.x, j1[i].x, e);
+            evolve_norms(s, a0.y, a1[i].y, j0.y, j1[i].y, e);
+            evolve_norms(s, a0.z, a1[i].z, j0.z, j1[i].z, e);
+            const double num = p.eta * (__builtin_sqrt(s.a1 * s.a2) + s.j1), den = __builtin_sqrt(s.j1 * s.a3) + s.a2;
+            evolve_raise(want, r < n, num, den, p);
+        }
+    }
+    return want;
+}
+
+// The pair stop_report and merge_absorb would name, with the threshold of each pair its own: the same rescan of the columns
+// LDS still holds (positions at sh[2 j], radii at sh[2 j + 1].w), the same key and 64-bit LDS minimum.  S = R_i + R_j is
+// the sum both of the pair's rows formed in the column loop (an fp32 add commutes).  Returns the key, workgroup-uniform;
+// ~0: no pair.  The barrier that follows in every caller lies before the next use of `best`.
+__device__ __forceinline__ unsigned long long radii_find_pair(const float4 *sh, int n, int tid, int T, int rpl, float eps2,
+                                                              unsigned long long &best)
+{
+    if (tid == 0)
+        best = ~0ull;
+    __syncthreads();
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r >= n)
+            continue;
+        const float4 pi = sh[2 * r];
+        const float ri = sh[2 * r + 1].w;
+        unsigned long long mine = ~0ull;
+        for (int j = r + 1; j < n; ++j) {
+            const float4 pj = sh[2 * j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            float r2 = __builtin_fmaf(dx, dx, eps2);
+            r2 = __builtin_fmaf(dy, dy, r2);
+            r2 = __builtin_fmaf(dz, dz, r2);
+            if (r2 <= radii_threshold(ri, sh[2 * j + 1].w, eps2)) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(r2) << 24) | ((unsigned)r << 12) | (unsigned)j;
+                mine = key < mine ? key : mine;
+            }
+        }
+        if (mine != ~0ull)
+            atomicMin(&best, mine);
+    }
+    __syncthreads();
+    return best;
+}
+
+// stop_report with per-pair thresholds: the pair of radii_find_pair when the collision bit is set, the escaper of smallest
+// index when the escape bit is.  Under MERGE the collision bit never arrives here.
+__device__ __forceinline__ void radii_stop_report(const float4 *sh, const float4 *pos, int n, int tid, int T, int rpl, float eps2,
+                                                  const BatchStopArgs &sa, int found, long long tick, BatchStopReport *out,
+                                                  unsigned long long &best, int &escaper)
+{
+    unsigned long long key = ~0ull;
+    if (found & kStopCollision)
+        key = radii_find_pair(sh, n, tid, T, rpl, eps2, best);
+    if (tid == 0)
+        escaper = 0x7fffffff;
+    __syncthreads();
+    if (found & kStopEscape)
+        for (int q = 0; q < rpl; ++q) {
+            const int r = q * T + tid;
+            if (r >= n)
+                continue;
+            const float4 xi = pos[r];  // this lane's own writes: the corrected positions
+            if (__builtin_fmaf(xi.z, xi.z, __builtin_fmaf(xi.y, xi.y, xi.x * xi.x)) > sa.re2)
+                atomicMin(&escaper, r);
+        }
+    __syncthreads();
+    if (tid == 0) {
+        BatchStopReport rep{tick, found, -1, -1, -1, 0.f, 0};
+        if (key != ~0ull) {
+            rep.pair_i = (int)((key >> 12) & 0xfff);
+            rep.pair_j = (int)(key & 0xfff);
+            const float4 pi = sh[2 * rep.pair_i], pj = sh[2 * rep.pair_j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            rep.separation = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        }
+        if ((found & kStopEscape) && escaper != 0x7fffffff)
+            rep.escaper = escaper;
+        *out = rep;
+    }
+}
+
+// The survivor's radius: volumes add.  fp64 from the fp32 operands, the cubes by two products each, rounded once to fp32.
+__device__ __forceinline__ float merge_radius(float ri, float rj)
+{
+    const double a = (double)ri, b = (double)rj;
+    return (float)cbrt(a * a * a + b * b * b);
+}
+
+// merge_absorb with radii: the pair of radii_find_pair; lane 0 merges it in the state arrays, swaps the absorbed body with
+// the last one and logs the event, as there.  The radii: every lane reads those of the pair and of the last body from the
+// columns before the barrier, and the refill gives each row its own -- the survivor's the merged radius, slot j the last
+// body's, slot n - 1 the absorbed body's (beyond the new count: to the array only) -- the lanes that own those three rows
+// writing them to the radii array too.  Returns whether a pair was found, workgroup-uniform.
+__device__ __forceinline__ bool radii_merge_absorb(float4 *sh, float4 *pos, float4 *vel, float *rad, int n, int tid, int T, int rpl,
+                                                   float eps2, long long tick, const BatchMergeArgs &ma, unsigned long long &best)
+{
+    asm volatile("" : "+v"(tid));  // the rows' addresses are formed here, not carried through the steps from the kernel's top
+    const unsigned long long key = radii_find_pair(sh, n, tid, T, rpl, eps2, best);
+    if (key == ~0ull)
+        return false;
+    const int i = (int)((key >> 12) & 0xfff), j = (int)(key & 0xfff), last = n - 1;
+    const float ri = sh[2 * i + 1].w, rj = sh[2 * j + 1].w, rl = sh[2 * last + 1].w;
+    if (tid == 0) {
+        const float4 ci = sh[2 * i], cj = sh[2 * j];  // the positions of the evaluation that found the pair
+        const float dx = cj.x - ci.x, dy = cj.y - ci.y, dz = cj.z - ci.z;
+        const float4 xi = pos[i], xj = pos[j], xl = pos[last], vi = vel[i], vj = vel[j], vl = vel[last];
+        const float ex = vj.x - vi.x, ey = vj.y - vi.y, ez = vj.z - vi.z;
+        const double M = (double)xi.w + (double)xj.w;
+        pos[i] = make_float4(merge_mean(xi.w, xi.x, xj.w, xj.x, M), merge_mean(xi.w, xi.y, xj.w, xj.y, M),
+                             merge_mean(xi.w, xi.z, xj.w, xj.z, M), xi.w + xj.w);
+        vel[i] = make_float4(merge_mean(xi.w, vi.x, xj.w, vj.x, M), merge_mean(xi.w, vi.y, xj.w, vj.y, M),
+                             merge_mean(xi.w, vi.z, xj.w, vj.z, M), vi.w);
+        if (j != last) {
+            pos[j] = xl;
+            vel[j] = vl;
+        }
+        pos[last] = xj;
+        vel[last] = vj;
+        int sys = blockIdx.x;
+        asm volatile("" : "+s"(sys));
+        const int merges = ma.merges[sys];  // the system's mergers so far: this one's place in the log
+        ma.merges[sys] = merges + 1;
+        if (merges < ma.capacity) {
+            nbody_batch_merge_event ev;
+            ev.tick = tick;
+            ev.survivor = i;
+            ev.absorbed = j;
+            ev.count_before = n;
+            ev.separation = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+            ev.relative_speed = __builtin_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
+            ev.mass_survivor = xi.w;
+            ev.mass_absorbed = xj.w;
+            ev.reserved = 0;
+            ma.events[(size_t)sys * (size_t)ma.capacity + (size_t)merges] = ev;
+        }
+    }
+    __syncthreads();  // the merged state is in the arrays, and every lane is done with the columns
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r >= n)
+            continue;
+        float R = sh[2 * r + 1].w;  // the row's own word: no other lane writes it
+        if (r == i)
+            R = merge_radius(ri, rj);
+        else if (r == last)
+            R = rj;
+        else if (r == j)
+            R = rl;
+        if (r == i || r == j || r == last)
+            rad[r] = R;
+        if (r < last) {
+            const float4 w = vel[r];
+            sh[2 * r] = pos[r];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, R);
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// batch_hermite_merge_kernel with per-body radii, for both collision actions: a sibling once more (OWN = 2), so that the
+// kernels above stay the code they are.  The same loop.  A body's radius rides in sh[2 r + 1].w: the fills write it there and
+// the predictor, which rewrites x, y, z only, leaves it.  With ra.merge a collision is merged as there, radii included;
+// without, the system leaves the loop after the step that found it and reports the pair, as batch_hermite_stop_kernel does.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_radii_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                   int *counts, BatchEvolveState *state, int *counters,
+                                                                   int max_bodies, BatchEvolveArgs p, BatchStopArgs sa,
+                                                                   BatchStopReport *report, BatchMergeArgs ma, BatchRadiiArgs ra)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies, and their radii
+    __shared__ int red[16];         // the waves' levels
+    __shared__ int red_stop[16];    // the waves' stopping conditions
+    __shared__ unsigned long long cold_best;  // the cold paths' words
+    __shared__ int cold_escaper;
+    int n = uniform_i32(counts[blockIdx.x]);
+    if (n <= 0)
+        return;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    const bool frozen = uniform_i32(report[blockIdx.x].reason) != 0;
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (frozen || tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target && !frozen) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    // Registers hold the rows' accelerations and jerks only; positions and velocities stay in the state arrays and the
+    // masses and radii in LDS, as in batch_hermite_stop_kernel.
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float *rad = ra.radii + (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, rad[r]);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    int stop = 0;                 // workgroup-uniform: the conditions met at the last evaluation
+    int run = 0;
+    bool evaluate = !p.have_acc;  // (a0, j0) are to be evaluated at the current state, which the columns hold
+    bool choose = !p.have_level;  // the level is to come from the first-step rule
+    for (;;) {
+        if (evaluate) {
+            __syncthreads();
+            int found = 0;
+            radii_evaluate<RPL, GUARD>(sh, n, tid, T, p.eps2, a, jk, sa, &found);
+            stop_publish(red_stop, found, tid);
+        }
+        if (choose) {  // dt = eta_start |a| / |j|, compared as squares
+            EvolveWant want;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+                const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+                evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);
+            }
+            evolve_publish(red, want, tid);
+        }
+        __syncthreads();  // every lane is done reading before a prediction rewrites the columns; red[], red_stop[] are complete
+        if (choose) {     // never coarser than the tick allows (tick 0 allows every level)
+            const EvolveWant want = evolve_collect(red, T);
+            const int floor_level = merge_tick_level(tick, p.levels);
+            level = want.level > p.levels ? p.levels : want.level;
+            level = level < floor_level ? floor_level : level;
+            clamped += want.level > p.levels ? 1 : 0;
+        }
+        if (evaluate)
+            stop = stop_collect(red_stop, T);
+        for (; tick < p.target && run < p.budget && steps < p.max_steps && !stop; ++run) {
+            const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < n) {  // x, y, z only: the masses and the radii stay
+                    const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                    *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                        make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                    hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                    *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                        make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                    hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+                }
+                renew_f32(a[q]);
+                renew_f32(jk[q]);
+            }
+            __syncthreads();
+            int found = 0;
+            const EvolveWant mine = radii_evaluate_request<RPL, GUARD>(sh, n, tid, T, p.eps2, pos, vel, a, jk, e, p, sa, &found);
+            stop_publish(red_stop, found, tid);
+            evolve_publish(red, mine, tid);
+            __syncthreads();
+            stop = stop_collect(red_stop, T);
+            EvolveWant want = evolve_collect(red, T);
+            clamped += want.level > p.levels ? 1 : 0;
+            want.level = want.level > p.levels ? p.levels : want.level;
+            tick += 1ll << (p.levels - level);
+            ++steps;
+            min_level = level < min_level ? level : min_level;
+            max_level = level > max_level ? level : max_level;
+            if (want.level > level)
+                level = want.level;
+            else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+                --level;  // one level, on a tick the coarser step divides
+        }
+        if (!(stop & kStopCollision) || !ra.merge)
+            break;
+        // the columns still hold the positions the collision was found at
+        if (!radii_merge_absorb(sh, pos, vel, rad, n, tid, T, RPL, p.eps2, tick, ma, cold_best)) {
+            stop &= ~kStopCollision;
+            break;
+        }
+        --n;
+        evaluate = choose = true;
+    }
+    int lane = tid;  // the rows' indices formed anew: the offsets of the kernel's top are not carried through the steps for this
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + lane;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        counts[blockIdx.x] = n;
+        if (tick < p.target && !stop) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+    if (stop)  // the columns still hold the positions the conditions were examined at
+        radii_stop_report(sh, pos, n, lane, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x], cold_best, cold_escaper);
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_radii_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                            float4 *jerk, int *counts, BatchEvolveState *state, int *counters, int max_bodies,
+                            const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report, const BatchMergeArgs &ma,
+                            const BatchRadiiArgs &ra)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_radii_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_radii_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
+                       counters, max_bodies, p, sa, report, ma, ra);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_radii(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, int *counts, BatchEvolveState *state,
+                              int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
+                              BatchStopReport *report, const BatchMergeArgs &ma, const BatchRadiiArgs &ra, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(p.eps2 > 0.f);
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_radii_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    case 3: return launch_radii_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    case 4: return launch_radii_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    case 5: return launch_radii_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    case 8: return launch_radii_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    default: return launch_radii_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
+    }
+}
+
 // report == nullptr: no stopping conditions, batch_hermite_adaptive_kernel
 template <int RPL, bool GUARD>
 hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
@@ -1505,6 +1960,10 @@ struct nbody_batch {
     int merge_capacity = 0;
     int *merge_count = nullptr;                     // [n_systems], allocated by the first evolve that merges
     nbody_batch_merge_event *merge_log = nullptr;   // [n_systems][merge_capacity]
+    // nbody_batch_radii_set: one radius per slot, laid out like the positions; a property of the slots, which only
+    // nbody_batch_radii_set and the mergers change
+    float *radii = nullptr;       // [n_systems][max_bodies], allocated by the first nbody_batch_radii_set
+    bool radii_set = false;
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -1612,6 +2071,7 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->stop_report) (void)hipFree(b->stop_report);
     if (b->merge_count) (void)hipFree(b->merge_count);
     if (b->merge_log) (void)hipFree(b->merge_log);
+    if (b->radii) (void)hipFree(b->radii);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1754,6 +2214,9 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     if (b->integrator != NBODY_INTEGRATOR_HERMITE)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: adaptive steps need NBODY_INTEGRATOR_HERMITE "
                                            "(nbody_batch_set_integrator): the criterion uses its accelerations and jerks");
+    if (b->radii_set && b->stop_collision_radius > 0.f)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: radii and collision_radius are both set (nbody_batch_radii.h: radii "
+                                           "replace the collision radius)");
     if (cfg->levels < 0 || cfg->levels > NBODY_BATCH_EVOLVE_MAX_LEVELS)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: levels outside [0, NBODY_BATCH_EVOLVE_MAX_LEVELS = 20]");
     if (n_intervals < 0 || n_intervals >= ((int64_t)1 << (62 - cfg->levels)))
@@ -1806,8 +2269,10 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     if (!b->evolve_counters)
         BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
     // stopping conditions (nbody_batch_stop.h): the thresholds in fp32, and reports that start from zero
-    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f;
-    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && b->stop_collision_radius > 0.f;
+    // radii (nbody_batch_radii.h) watch collisions without a collision radius, through a kernel of their own
+    const bool radii = b->radii_set;
+    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || radii;
+    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || radii);
     BatchStopArgs sa{-1.f, __builtin_inff()};
     if (merging) {  // nbody_batch_merge.h: counts and logs that start from zero where the reports do
         if (!b->merge_count) {
@@ -1822,6 +2287,7 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
             BATCH_TRY(b, hipMemsetAsync(b->merge_count, 0, sizeof(int) * B, b->stream));
     }
     const BatchMergeArgs ma{b->merge_count, b->merge_log, b->merge_capacity};
+    const BatchRadiiArgs ra{b->radii, merging ? 1 : 0};
     if (stopping) {
         if (b->stop_collision_radius > 0.f)
             sa.thr = std::fmaf(b->stop_collision_radius, b->stop_collision_radius, cfg->softening * cfg->softening);
@@ -1858,7 +2324,11 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         p.new_call = first ? 1 : 0;
         p.reset_tick = first && !resume ? 1 : 0;
         BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
-        if (merging)
+        if (radii)
+            BATCH_TRY(b, launch_batch_radii(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
+                                            b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
+                                            p, sa, b->stop_report, ma, ra, b->stream));
+        else if (merging)
             BATCH_TRY(b, launch_batch_merge(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
                                             b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
                                             p, sa, b->stop_report, ma, b->stream));
@@ -1941,7 +2411,7 @@ int nbody_batch_stop_read(nbody_batch *b, int *reason, int64_t *tick, int *pair_
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_read: batch is NULL");
     const size_t B = (size_t)b->n_systems;
     std::vector<BatchStopReport> rep(B, BatchStopReport{0, 0, 0, 0, 0, 0.f, 0});
-    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f;
+    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set;
     if (stopping && b->stop_report && !b->stop_forgotten) {
         BATCH_TRY(b, hipSetDevice(b->device));
         BATCH_TRY(b, hipMemcpyAsync(rep.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
@@ -2002,7 +2472,7 @@ int nbody_batch_merge_read(nbody_batch *b, int64_t *n_merges, nbody_batch_merge_
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_read: batch is NULL");
     const size_t B = (size_t)b->n_systems, cap = (size_t)b->merge_capacity;
     std::vector<int> count(B, 0);
-    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && b->stop_collision_radius > 0.f;
+    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || b->radii_set);
     const bool kept = merging && b->merge_count && !b->stop_forgotten;
     if (events)
         std::memset(events, 0, sizeof(nbody_batch_merge_event) * B * cap);
@@ -2022,6 +2492,41 @@ int nbody_batch_merge_read(nbody_batch *b, int64_t *n_merges, nbody_batch_merge_
     if (n_merges)
         for (size_t s = 0; s < B; ++s)
             n_merges[s] = count[s];
+    return NBODY_OK;
+}
+
+int nbody_batch_radii_set(nbody_batch *b, const float *host_radii)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radii_set: batch is NULL");
+    if (host_radii) {
+        std::string msg;
+        if (!batch_radii_ok(host_radii, b->counts.data(), b->n_systems, b->max_bodies, &msg))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radii_set: " + msg);
+        const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
+        BATCH_TRY(b, hipSetDevice(b->device));
+        if (!b->radii)
+            BATCH_TRY(b, hipMalloc((void **)&b->radii, sizeof(float) * slots));
+        BATCH_TRY(b, hipMemcpyAsync(b->radii, host_radii, sizeof(float) * slots, hipMemcpyHostToDevice, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the caller's array may change with the next call
+    }
+    b->radii_set = host_radii != nullptr;
+    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
+    return NBODY_OK;
+}
+
+int nbody_batch_radii_read(nbody_batch *b, float *host_radii)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radii_read: batch is NULL");
+    if (!host_radii)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radii_read: NULL argument");
+    if (!b->radii_set)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_radii_read: no radii are set (nbody_batch_radii_set)");
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, hipMemcpyAsync(host_radii, b->radii, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies,
+                                hipMemcpyDeviceToHost, b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }
 

@@ -22,7 +22,12 @@ at collision radius 0.05 a: how many pairs stop, at what step counts, and the tw
 --merges: instead, per case, one line with evolve(k, dt, levels=0) under the collision action "stop" against the same call
 under "merge", both with conditions that cannot trigger (the stop kernel against the merge kernel on the same k steps) --
 alternated, medians; then the scattering case with collision radius 0.05 a stopped against merged and run to completion: how
-many pairs merge, at what step counts, and the two wall times."""
+many pairs merge, at what step counts, and the two wall times.
+
+--radii: instead, per case, one line with evolve(k, dt, levels=0) under set_stop_conditions(1e-6, 1e6) (the stop kernel) against
+the same call with per-body radii of 5e-7 everywhere and no collision radius (the radii kernel); neither can trigger --
+alternated, medians; then the scattering case with unequal radii (0.03 a and 0.02 a, the reach of collision radius 0.05 a)
+stopped against merged: how many pairs collide, at what step counts, the merged radii and the two wall times."""
 import argparse
 import json
 import os
@@ -51,6 +56,8 @@ ap.add_argument("--stops", action="store_true", help="evolve(levels=0) with cond
                 "and the scattering case stopped at a collision radius")
 ap.add_argument("--merges", action="store_true", help="evolve(levels=0) under the collision action merge against stop, with "
                 "conditions that cannot trigger, and the scattering case merged at a collision radius")
+ap.add_argument("--radii", action="store_true", help="evolve(levels=0) with per-body radii against a collision radius, neither "
+                "of which can trigger, and the scattering case with unequal radii stopped and merged")
 args = ap.parse_args()
 
 
@@ -277,6 +284,70 @@ def merges_lines():
         print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", "collision_radius": 0.05, **out}), flush=True)
 
 
+def radii_lines():
+    import time
+    for case in args.cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        inter = B * n * n
+        k = int(min(400, max(10, 2e11 // inter)))
+        dt = float(np.float32(args.dt))
+        with nb.BatchedSystem(B, n, integrator="hermite") as uniform, nb.BatchedSystem(B, n, integrator="hermite") as radii:
+            uniform.set_state(P, V)
+            uniform.set_stop_conditions(collision_radius=1e-6, escape_radius=1e6)
+            radii.set_state(P, V)
+            radii.set_stop_conditions(escape_radius=1e6)
+            radii.set_radii(np.full((B, n), 5e-7, np.float32))
+
+            def stop_kernel():
+                uniform.evolve(k, dt, levels=0, softening=args.eps)
+
+            def radii_kernel():
+                radii.evolve(k, dt, levels=0, softening=args.eps)
+
+            stop_kernel()
+            radii_kernel()
+            torch.cuda.synchronize()
+            ts, tr = [], []
+            for _ in range(args.repeats):      # alternated
+                ts.append(timed(stop_kernel) / k)
+                tr.append(timed(radii_kernel) / k)
+            ms, mr = statistics.median(ts), statistics.median(tr)
+            stopped = int(uniform.stops().stopped.sum()) + int(radii.stops().stopped.sum())
+        print(json.dumps({"n": n, "B": B, "k": k, "evolve_stop_ms_per_step": round(ms, 5), "evolve_radii_ms_per_step": round(mr, 5),
+                          "ratio": round(mr / ms, 4), "stopped": stopped, "stop_repeats": [round(x, 5) for x in ts],
+                          "radii_repeats": [round(x, 5) for x in tr]}), flush=True)
+    P, V, dt_max = scattering_pairs()
+    R = np.tile(np.float32([0.03, 0.02]), (P.shape[0], 1))
+    with nb.BatchedSystem(P.shape[0], 2, integrator="hermite") as batch:
+        out = {}
+        for action in ("stop", "merge"):
+            walls = []
+            for _ in range(1 + args.repeats):       # the first run warms up
+                batch.set_counts([2] * P.shape[0])
+                batch.set_state(P, V)
+                batch.set_collision_action(action)
+                batch.set_radii(R)
+                batch.sync()
+                t0 = time.perf_counter()
+                res = batch.evolve(64, dt_max, levels=12, eta=0.01, eta_start=0.01, softening=0.0)
+                walls.append(time.perf_counter() - t0)
+            st, mg, rr = batch.stops(), batch.mergers(), batch.radii()
+            hit = st.stopped if action == "stop" else mg.count > 0
+            out[action] = {"wall_ms_median": round(statistics.median(walls[1:]) * 1e3, 3),
+                           "wall_ms_repeats": [round(w * 1e3, 3) for w in walls[1:]], "stopped": int(st.stopped.sum()),
+                           "merged": int((mg.count > 0).sum()), "at_the_end_time": int((res.ticks == 64 << 12).sum()),
+                           "steps_total": int(res.steps.sum()),
+                           "steps_of_colliding_pairs_percentiles_0_25_50_75_100":
+                               [int(x) for x in np.percentile(res.steps[hit], [0, 25, 50, 75, 100])] if hit.any() else []}
+            if action == "merge" and hit.any():
+                out[action]["merged_radius_min_max"] = [float(f"{rr[hit, 0].min():.6g}"), float(f"{rr[hit, 0].max():.6g}")]
+        print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", "radii": [0.03, 0.02], **out}), flush=True)
+
+
+if args.radii:
+    radii_lines()
+    sys.exit(0)
 if args.adaptive:
     adaptive_lines()
     sys.exit(0)
