@@ -491,6 +491,8 @@ float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
  *   collision radius or a body leaves an escape radius, and nbody_batch_stop_read tells when and which;
  *   nbody_batch_merge_set (nbody_batch_merge.h, included below) makes it merge the colliding pair and carry the run on;
  *   nbody_batch_radii_set (nbody_batch_radii.h, included below) gives every body a collision radius of its own.
+ *   nbody_batch_massive_set (nbody_batch_massive.h, included below) makes the bodies after a system's first m test
+ *   particles: rows like any other that are never columns, for every integrator and for nbody_batch_evolve_on.
  *   No individual per-body time steps, no P(EC)^n iteration, no fp64 state; no centre-of-mass escape test, no outcome of
  *   a collision other than a stop or a perfect merger.
  * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
@@ -523,6 +525,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_merge.h"
 /* per-body collision radii: a pair collides within the sum of its own radii, and a merged body grows */
 #include "nbody_batch_radii.h"
+/* test particles: the bodies after a system's first massive[s] feel forces and exert none */
+#include "nbody_batch_massive.h"
 
 #ifdef __cplusplus
 }

@@ -385,6 +385,21 @@ public:
         check(nbody_batch_radii_read(b_, r.data()), "nbody_batch_radii_read");
         return r;
     }
+    // Test particles (nbody_batch_massive.h): numSystems values; the first min(massive[s], counts[s]) bodies of system s
+    // are massive, the bodies after them feel those and exert no force (every integrator, and evolve without stopping
+    // conditions or radii).  An empty vector switches the feature off.  massiveCounts(): the values as set (throws when off).
+    void setMassiveCounts(const std::vector<std::int64_t> &massive)
+    {
+        if (!massive.empty() && (std::int64_t)massive.size() != systems_)
+            throw std::runtime_error("Batch::setMassiveCounts: numSystems massive counts, or none");
+        check(nbody_batch_massive_set(b_, massive.empty() ? nullptr : massive.data()), "nbody_batch_massive_set");
+    }
+    std::vector<std::int64_t> massiveCounts()
+    {
+        std::vector<std::int64_t> m((size_t)systems_);
+        check(nbody_batch_massive_read(b_, m.data()), "nbody_batch_massive_read");
+        return m;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

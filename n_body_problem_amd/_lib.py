@@ -198,6 +198,13 @@ _RADII_PROTOTYPES = {
 }
 
 
+#: the entry points of include/nbody_batch_massive.h (test particles for batched ensembles), which nbody.h includes
+_MASSIVE_PROTOTYPES = {
+    "nbody_batch_massive_set": (c_int, [c_void_p, POINTER(c_int64)]),
+    "nbody_batch_massive_read": (c_int, [c_void_p, POINTER(c_int64)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -223,7 +230,7 @@ def load() -> ctypes.CDLL:
             pass
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
-                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()):
+                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -254,6 +261,11 @@ def merge_exported_names():
 def radii_names():
     """The entry points of nbody_batch_radii.h."""
     return list(_RADII_PROTOTYPES)
+
+
+def massive_names():
+    """The entry points of nbody_batch_massive.h."""
+    return list(_MASSIVE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

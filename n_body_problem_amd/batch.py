@@ -263,6 +263,36 @@ class BatchedSystem:
         _check(self._lib, self._lib.nbody_batch_radii_read(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._h)
         return out
 
+    def set_massive_counts(self, massive) -> None:
+        """Test particles (``include/nbody_batch_massive.h`` states the rules): ``B`` integers in ``[0, max_bodies]``, or
+        ``None`` to switch the feature off (the default).  The first ``min(massive[s], counts[s])`` bodies of system ``s``
+        are massive; the bodies after them feel the massive ones and exert no force.  They are stepped like any other body
+        by :meth:`step_n` (every integrator) and :meth:`evolve`, and count in its time-step criterion, but no body receives
+        a force from them, at ``n * m`` interactions per step instead of ``n * n``.  Their mass words
+        ``positions[s, i, 3]`` are read by no force kernel and are preserved; :meth:`energy` and :meth:`momentum` keep
+        reading them, so zero mass words give the massive bodies' energy.  The values belong to the handle:
+        :meth:`set_state` and :meth:`set_counts` leave them alone.  :meth:`evolve` refuses massive counts together with
+        stopping conditions or radii.  The length is checked here, the values by the library.  Forgets what
+        :meth:`set_counts` forgets: the cached accelerations and jerks, the levels and the stops."""
+        self._use_current_stream()
+        if massive is None:
+            _check(self._lib, self._lib.nbody_batch_massive_set(self._h, None), self._h)
+            return
+        m = np.ascontiguousarray(np.asarray(massive).reshape(-1), dtype=np.int64)
+        if m.shape[0] != self.num_systems:
+            raise ValueError(f"expected {self.num_systems} massive counts, got {m.shape[0]}")
+        _check(self._lib, self._lib.nbody_batch_massive_set(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._h)
+
+    @property
+    def massive_counts(self):
+        """The massive counts as they were set (a copy), or ``None`` while the feature is off."""
+        m = np.zeros(self.num_systems, dtype=np.int64)
+        status = self._lib.nbody_batch_massive_read(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        if status == _lib.NBODY_ERR_STATE:
+            return None
+        _check(self._lib, status, self._h)
+        return m
+
     def mergers(self) -> "MergeResult":
         """The mergers so far, per system (waits for the queued work)."""
         B, cap = self.num_systems, self._log_capacity
@@ -337,10 +367,14 @@ class MergeResult:
         return f"MergeResult(count={self.count.tolist()}, events={self.events.tolist()})"
 
 
-def interactions_per_step(counts) -> int:
-    """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention)."""
+def interactions_per_step(counts, massive=None) -> int:
+    """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
+    ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
     c = np.asarray(counts, dtype=np.int64)
-    return int((c * c).sum())
+    if massive is None:
+        return int((c * c).sum())
+    m = np.minimum(np.asarray(massive, dtype=np.int64), c)
+    return int((c * m).sum())
 
 
 __all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

@@ -47,7 +47,8 @@ inline BatchShape batch_shape(int max_bodies)
 }
 
 // Accelerations of the lane's RPL rows from the n columns in LDS, ascending j, one chain per row and component.
-template <int RPL, bool GUARD>
+// OWN: batch_forces_jerks' tag (see there); batch_step_massive_kernel passes 1.
+template <int RPL, bool GUARD, int OWN = 0>
 __device__ __forceinline__ void batch_forces(const float4 *sp, int n, const float4 (&x)[RPL], float eps2, float (&ax)[RPL],
                                              float (&ay)[RPL], float (&az)[RPL])
 {
@@ -1849,6 +1850,498 @@ hipError_t launch_batch_step(float4 *pos, float4 *vel, float4 *acc, const int *c
     return hipGetLastError();
 }
 
+// ---- test particles (include/nbody_batch_massive.h): the first m = min(massive[s], n) bodies of system s are massive, the
+// bodies after them are rows like any other and never columns.  Siblings of batch_step_kernel, batch_hermite_kernel and
+// batch_hermite_adaptive_kernel, which stay the code they are (OWN = 1 for batch_forces, OWN = 3 for batch_forces_jerks):
+// the same kernels with the column loop ending at m, a workgroup-uniform scalar read once.  The row guards stay r < n; the
+// workgroup shape and the LDS layout are batch_shape's.  m = 0: no column, every acceleration and jerk is exactly +0.
+
+// batch_step_kernel with the column bound m.  Only the rows r < m are published to LDS: no row reads the others.
+template <int RPL, bool GUARD, bool KDK>
+__global__ __launch_bounds__(1024) void batch_step_massive_kernel(float4 *pos, float4 *vel, float4 *acc, const int *counts,
+                                                                  const int *massive, int max_bodies, int k, float dt,
+                                                                  float eps2, int have_acc)
+{
+    extern __shared__ float4 sp[];  // the massive bodies' positions, at most max_bodies float4
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int mc = massive[blockIdx.x];
+    const int m = mc < n ? mc : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL], v[RPL];
+    float ax[RPL], ay[RPL], az[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        ax[q] = ay[q] = az[q] = 0.f;
+        if (r < n) {
+            x[q] = pos[base + r];
+            v[q] = vel[base + r];
+            if (r < m)
+                sp[r] = x[q];
+            if (KDK && have_acc) {
+                const float4 a = acc[base + r];
+                ax[q] = a.x;
+                ay[q] = a.y;
+                az[q] = a.z;
+            }
+        }
+    }
+    __syncthreads();
+    const double h = (double)dt, hh = 0.5 * (double)dt;
+    if (KDK && !have_acc) {
+        batch_forces<RPL, GUARD, 1>(sp, m, x, eps2, ax, ay, az);
+        __syncthreads();  // every lane is done reading before the first drift rewrites the positions
+    }
+    for (int s = 0; s < k; ++s) {
+        if (KDK) {
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                batch_kick(v[q], ax[q], ay[q], az[q], hh);
+                batch_drift(x[q], v[q], h);
+                const int r = q * T + tid;
+                if (r < m)
+                    sp[r] = x[q];
+            }
+            __syncthreads();
+            batch_forces<RPL, GUARD, 1>(sp, m, x, eps2, ax, ay, az);
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                batch_kick(v[q], ax[q], ay[q], az[q], hh);
+        } else {
+            batch_forces<RPL, GUARD, 1>(sp, m, x, eps2, ax, ay, az);
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                batch_kick(v[q], ax[q], ay[q], az[q], h);
+                batch_drift(x[q], v[q], h);
+                const int r = q * T + tid;
+                if (r < m)
+                    sp[r] = x[q];
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            pos[base + r] = x[q];  // .w (the mass word) unchanged
+            vel[base + r] = v[q];  // .w unchanged
+            if (KDK)
+                acc[base + r] = make_float4(ax[q], ay[q], az[q], 0.f);
+        }
+    }
+}
+
+// hermite_evaluate<RPL, GUARD, CORRECT> (without STOP) with the column bound m beside the row bound n: a sibling, so that
+// hermite_evaluate stays the code it is for the kernels above.  The same row groups; every row r < n rereads its own
+// predicted state from LDS, whether or not it is a column.
+template <int RPL, bool GUARD, bool CORRECT>
+__device__ __forceinline__ void massive_evaluate(const float4 *sh, int n, int m, int tid, int T, float eps2, float4 (&x)[RPL],
+                                                 float3 (&v)[RPL], float3 (&a)[RPL], float3 (&jk)[RPL], const HermiteSteps &t)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {  // xyz only: ds_read_b96
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, false, 3>(sh, m, xp, vp, eps2, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i;
+            if (CORRECT) {
+                hermite_correct(x[q].x, v[q].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, t);
+                hermite_correct(x[q].y, v[q].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, t);
+                hermite_correct(x[q].z, v[q].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, t);
+            }
+            a[q] = a1[i];
+            jk[q] = j1[i];
+        }
+    }
+}
+
+// hermite_evaluate_request<RPL, GUARD> (without STOP) with the column bound m: a sibling as massive_evaluate is.  Every row
+// r < n forms its criterion and votes: test particles count in the time step.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ EvolveWant massive_evaluate_request(const float4 *sh, int n, int m, int tid, int T, float eps2,
+                                                               float4 *pos, float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL],
+                                                               const EvolveSteps &e, const BatchEvolveArgs &p)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+    EvolveWant want;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G], x[G], v[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = x[i] = v[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+                x[i] = *reinterpret_cast<const float3 *>(&pos[r]);
+                v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, false, 3>(sh, m, xp, vp, eps2, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
+            hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
+            hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            if (r < n) {  // x, y, z only: the mass words and the velocities' w stay as they are
+                *reinterpret_cast<float3 *>(&pos[r]) = x[i];
+                *reinterpret_cast<float3 *>(&vel[r]) = v[i];
+            }
+            float3 a0 = a[q], j0 = jk[q];
+            renew_f32(a0);  // widened again below, one component at a time: the corrector's fp64 copies end here
+            renew_f32(j0);
+            renew_f32(a1[i]);
+            renew_f32(j1[i]);
+            a[q] = a1[i];
+            jk[q] = j1[i];
+            EvolveNorms s;
+            evolve_norms(s, a0.x, a1[i].x, j0.x, j1[i].x, e);
+            evolve_norms(s, a0.y, a1[i].y, j0.y, j1[i].y, e);
+            evolve_norms(s, a0.z, a1[i].z, j0.z, j1[i].z, e);
+            const double num = p.eta * (__builtin_sqrt(s.a1 * s.a2) + s.j1), den = __builtin_sqrt(s.j1 * s.a3) + s.a2;
+            evolve_raise(want, r < n, num, den, p);
+        }
+    }
+    return want;
+}
+
+// batch_hermite_kernel with the column bound m.  Every row r < n writes its predicted state to LDS: a row reads its own
+// back from there.  A test particle's mass word travels through x[q].w and LDS like any other and is read by no column loop.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_massive_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                     const int *counts, const int *massive, int max_bodies,
+                                                                     int k, float dt, float eps2, int have_acc)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int mc = massive[blockIdx.x];
+    const int m = mc < n ? mc : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const double h = (double)dt;
+    const HermiteSteps t{h, 0.5 * h, h / 3.0, h / 6.0};
+    float4 x[RPL];  // {x, y, z, m}
+    float3 v[RPL], a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            if (have_acc) {
+                const float4 a0 = acc[base + r], j0 = jerk[base + r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!have_acc) {  // (a0, j0) at the current state
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                sh[2 * r] = x[q];
+                sh[2 * r + 1] = make_float4(v[q].x, v[q].y, v[q].z, 0.f);
+            }
+        }
+        __syncthreads();
+        massive_evaluate<RPL, GUARD, false>(sh, n, m, tid, T, eps2, x, v, a, jk, t);
+        __syncthreads();  // every lane is done reading before the first prediction rewrites the columns
+    }
+    for (int s = 0; s < k; ++s) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                sh[2 * r] = make_float4(hermite_predict_x(x[q].x, v[q].x, a[q].x, jk[q].x, t),
+                                        hermite_predict_x(x[q].y, v[q].y, a[q].y, jk[q].y, t),
+                                        hermite_predict_x(x[q].z, v[q].z, a[q].z, jk[q].z, t), x[q].w);
+                sh[2 * r + 1] = make_float4(hermite_predict_v(v[q].x, a[q].x, jk[q].x, t),
+                                            hermite_predict_v(v[q].y, a[q].y, jk[q].y, t),
+                                            hermite_predict_v(v[q].z, a[q].z, jk[q].z, t), 0.f);
+            }
+            float3 xq = make_float3(x[q].x, x[q].y, x[q].z);
+            renew_f32(xq);
+            x[q] = make_float4(xq.x, xq.y, xq.z, x[q].w);
+            renew_f32(v[q]);
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        massive_evaluate<RPL, GUARD, true>(sh, n, m, tid, T, eps2, x, v, a, jk, t);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            pos[base + r] = x[q];  // .w (the mass word) unchanged
+            float *w = reinterpret_cast<float *>(vel + base + r);
+            w[0] = v[q].x;  // .w left alone
+            w[1] = v[q].y;
+            w[2] = v[q].z;
+            acc[base + r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[base + r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+}
+
+// batch_hermite_adaptive_kernel with the column bound m: the same loop, the same level rule, every row r < n in the
+// criterion.  With m = 0 both the first-step rule and the criterion have a zero denominator (the header's +inf): level 0.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_adaptive_massive_kernel(float4 *pos, float4 *vel, float4 *acc,
+                                                                              float4 *jerk, const int *counts,
+                                                                              const int *massive, BatchEvolveState *state,
+                                                                              int *counters, int max_bodies, BatchEvolveArgs p)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    __shared__ int red[16];         // the waves' levels
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int mc = massive[blockIdx.x];
+    const int m = uniform_i32(mc < n ? mc : n);
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    // Registers hold the rows' accelerations and jerks only; positions and velocities stay in the state arrays and the mass
+    // words in LDS, as in batch_hermite_adaptive_kernel.
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!p.have_acc) {  // (a0, j0) at the current state, which the columns hold
+        __syncthreads();
+        const HermiteSteps unused{0.0, 0.0, 0.0, 0.0};
+        float4 x4[RPL];  // not used without the corrector
+        float3 v3[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            x4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            v3[q] = make_float3(0.f, 0.f, 0.f);
+        }
+        massive_evaluate<RPL, GUARD, false>(sh, n, m, tid, T, p.eps2, x4, v3, a, jk, unused);
+    }
+    if (!p.have_level) {  // the first step: dt = eta_start |a| / |j|, compared as squares
+        EvolveWant want;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+            const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+            evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);  // dt^2 = eta_start^2 |a|^2 / |j|^2
+        }
+        evolve_publish(red, want, tid);
+    }
+    __syncthreads();  // every lane is done reading before the first prediction rewrites the columns; red[] is complete
+    if (!p.have_level) {
+        const EvolveWant want = evolve_collect(red, T);
+        level = want.level > p.levels ? p.levels : want.level;
+        clamped += want.level > p.levels ? 1 : 0;
+    }
+    for (int run = 0; tick < p.target && run < p.budget && steps < p.max_steps; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        const EvolveWant mine = massive_evaluate_request<RPL, GUARD>(sh, n, m, tid, T, p.eps2, pos, vel, a, jk, e, p);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick += 1ll << (p.levels - level);
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+}
+
+template <int RPL, bool GUARD>
+void launch_step_massive_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel,
+                             float4 *acc, const int *counts, const int *massive, int max_bodies, int k, float dt, float eps2,
+                             int have_acc)
+{
+    if (kdk)
+        hipLaunchKernelGGL((batch_step_massive_kernel<RPL, GUARD, true>), grid, block, lds, stream, pos, vel, acc, counts,
+                           massive, max_bodies, k, dt, eps2, have_acc);
+    else
+        hipLaunchKernelGGL((batch_step_massive_kernel<RPL, GUARD, false>), grid, block, lds, stream, pos, vel, acc, counts,
+                           massive, max_bodies, k, dt, eps2, have_acc);
+}
+
+hipError_t launch_batch_step_massive(float4 *pos, float4 *vel, float4 *acc, const int *counts, const int *massive, int n_systems,
+                                     int max_bodies, int k, float dt, float eps2, bool kdk, bool have_acc, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(eps2 > 0.f);
+    const int ha = have_acc ? 1 : 0;
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: launch_step_massive_rpl<1, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    case 3: launch_step_massive_rpl<1, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    case 4: launch_step_massive_rpl<2, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    case 5: launch_step_massive_rpl<2, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    case 8: launch_step_massive_rpl<4, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    default: launch_step_massive_rpl<4, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
+    }
+    return hipGetLastError();
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_hermite_massive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                                      float4 *jerk, const int *counts, const int *massive, int max_bodies, int k, float dt,
+                                      float eps2, int have_acc)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_massive_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_massive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, massive,
+                       max_bodies, k, dt, eps2, have_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_hermite_massive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
+                                        int n_systems, int max_bodies, int k, float dt, float eps2, bool have_acc,
+                                        hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(eps2 > 0.f);
+    const int ha = have_acc ? 1 : 0;
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_hermite_massive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    case 3: return launch_hermite_massive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    case 4: return launch_hermite_massive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    case 5: return launch_hermite_massive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    case 8: return launch_hermite_massive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    default: return launch_hermite_massive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
+    }
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_adaptive_massive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                                       float4 *jerk, const int *counts, const int *massive, BatchEvolveState *state, int *counters,
+                                       int max_bodies, const BatchEvolveArgs &p)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_adaptive_massive_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_adaptive_massive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts,
+                       massive, state, counters, max_bodies, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_adaptive_massive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
+                                         BatchEvolveState *state, int *counters, int n_systems, int max_bodies,
+                                         const BatchEvolveArgs &p, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(p.eps2 > 0.f);
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_adaptive_massive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    case 3: return launch_adaptive_massive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    case 4: return launch_adaptive_massive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    case 5: return launch_adaptive_massive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    case 8: return launch_adaptive_massive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    default: return launch_adaptive_massive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -1964,6 +2457,11 @@ struct nbody_batch {
     // nbody_batch_radii_set and the mergers change
     float *radii = nullptr;       // [n_systems][max_bodies], allocated by the first nbody_batch_radii_set
     bool radii_set = false;
+    // nbody_batch_massive_set: per system the number of leading bodies that exert forces; a property of the handle, which only
+    // nbody_batch_massive_set changes
+    std::vector<int> massive;     // host copy, [n_systems] while massive_set
+    int *massive_dev = nullptr;   // [n_systems], allocated by the first nbody_batch_massive_set
+    bool massive_set = false;
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -2072,6 +2570,7 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->merge_count) (void)hipFree(b->merge_count);
     if (b->merge_log) (void)hipFree(b->merge_log);
     if (b->radii) (void)hipFree(b->radii);
+    if (b->massive_dev) (void)hipFree(b->massive_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -2162,9 +2661,15 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
     for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
         const int run = std::min(kBatchStepsPerLaunch, k - done);
         float4 *pos = reinterpret_cast<float4 *>(d_pos), *vel = reinterpret_cast<float4 *>(d_vel);
-        if (hermite)
+        if (hermite && b->massive_set)  // test particles (nbody_batch_massive.h): the siblings whose column loop ends early
+            BATCH_TRY(b, launch_batch_hermite_massive(pos, vel, b->acc, b->jerk, b->counts_dev, b->massive_dev, (int)b->n_systems,
+                                                      (int)b->max_bodies, run, dt, eps2, b->acc_valid, b->stream));
+        else if (hermite)
             BATCH_TRY(b, launch_batch_hermite(pos, vel, b->acc, b->jerk, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run,
                                               dt, eps2, b->acc_valid, b->stream));
+        else if (b->massive_set)
+            BATCH_TRY(b, launch_batch_step_massive(pos, vel, b->acc, b->counts_dev, b->massive_dev, (int)b->n_systems,
+                                                   (int)b->max_bodies, run, dt, eps2, kdk, kdk && b->acc_valid, b->stream));
         else
             BATCH_TRY(b, launch_batch_step(pos, vel, b->acc, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run, dt, eps2,
                                            kdk, kdk && b->acc_valid, b->stream));
@@ -2217,6 +2722,10 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     if (b->radii_set && b->stop_collision_radius > 0.f)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: radii and collision_radius are both set (nbody_batch_radii.h: radii "
                                            "replace the collision radius)");
+    if (b->massive_set && (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: massive counts are set together with a stopping condition or radii "
+                                           "(nbody_batch_massive.h: not supported, the collision test counts on a row's own column); "
+                                           "nbody_batch_massive_set(b, NULL) or switch the conditions off");
     if (cfg->levels < 0 || cfg->levels > NBODY_BATCH_EVOLVE_MAX_LEVELS)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: levels outside [0, NBODY_BATCH_EVOLVE_MAX_LEVELS = 20]");
     if (n_intervals < 0 || n_intervals >= ((int64_t)1 << (62 - cfg->levels)))
@@ -2328,6 +2837,10 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
             BATCH_TRY(b, launch_batch_radii(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
                                             b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
                                             p, sa, b->stop_report, ma, ra, b->stream));
+        else if (b->massive_set)  // never with stopping conditions: refused above
+            BATCH_TRY(b, launch_batch_adaptive_massive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc,
+                                                       b->jerk, b->counts_dev, b->massive_dev, b->evolve_state, b->evolve_counters,
+                                                       (int)b->n_systems, (int)b->max_bodies, p, b->stream));
         else if (merging)
             BATCH_TRY(b, launch_batch_merge(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
                                             b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
@@ -2527,6 +3040,43 @@ int nbody_batch_radii_read(nbody_batch *b, float *host_radii)
     BATCH_TRY(b, hipMemcpyAsync(host_radii, b->radii, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies,
                                 hipMemcpyDeviceToHost, b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_massive_set(nbody_batch *b, const int64_t *host_massive)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_massive_set: batch is NULL");
+    if (host_massive) {
+        for (int64_t s = 0; s < b->n_systems; ++s)
+            if (host_massive[s] < 0 || host_massive[s] > b->max_bodies)
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_massive_set: massive count of system " + std::to_string(s) + " (" +
+                                                       std::to_string(host_massive[s]) + ") outside [0, max_bodies = " +
+                                                       std::to_string(b->max_bodies) + "]");
+        b->massive.resize((size_t)b->n_systems);
+        for (int64_t s = 0; s < b->n_systems; ++s)
+            b->massive[(size_t)s] = (int)host_massive[s];
+        BATCH_TRY(b, hipSetDevice(b->device));
+        if (!b->massive_dev)
+            BATCH_TRY(b, hipMalloc((void **)&b->massive_dev, sizeof(int) * b->massive.size()));
+        BATCH_TRY(b, hipMemcpyAsync(b->massive_dev, b->massive.data(), sizeof(int) * b->massive.size(), hipMemcpyHostToDevice, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
+    }
+    b->massive_set = host_massive != nullptr;
+    forget_caches(b);  // as nbody_batch_set_counts: the cached accelerations and jerks belong to the old columns
+    return NBODY_OK;
+}
+
+int nbody_batch_massive_read(nbody_batch *b, int64_t *host_massive)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_massive_read: batch is NULL");
+    if (!host_massive)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_massive_read: NULL argument");
+    if (!b->massive_set)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_massive_read: no massive counts are set (nbody_batch_massive_set)");
+    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
+        host_massive[s] = b->massive[s];
     return NBODY_OK;
 }
 

@@ -27,7 +27,13 @@ many pairs merge, at what step counts, and the two wall times.
 --radii: instead, per case, one line with evolve(k, dt, levels=0) under set_stop_conditions(1e-6, 1e6) (the stop kernel) against
 the same call with per-body radii of 5e-7 everywhere and no collision radius (the radii kernel); neither can trigger --
 alternated, medians; then the scattering case with unequal radii (0.03 a and 0.02 a, the reach of collision radius 0.05 a)
-stopped against merged: how many pairs collide, at what step counts, the merged radii and the two wall times."""
+stopped against merged: how many pairs collide, at what step counts, the merged radii and the two wall times.
+
+--massive: instead, test particles (set_massive_counts).  For n x B = 4096 x 256 and 1024 x 1024 (or --cases) and m in
+1, 8, 64, 512, n, one line per Hermite step_n(k, dt) and one per evolve(k, dt, levels=0): the call with massive counts m
+set against the same call with the feature off, both on the same state with the mass words of the bodies from m on zeroed
+(the two compute the same bits; the second walks all n columns through the kernels that exist without the feature) --
+alternated, medians, both times, their ratio and the spread (max - min over the median) of each side's repeats."""
 import argparse
 import json
 import os
@@ -58,6 +64,8 @@ ap.add_argument("--merges", action="store_true", help="evolve(levels=0) under th
                 "conditions that cannot trigger, and the scattering case merged at a collision radius")
 ap.add_argument("--radii", action="store_true", help="evolve(levels=0) with per-body radii against a collision radius, neither "
                 "of which can trigger, and the scattering case with unequal radii stopped and merged")
+ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolve(levels=0) with massive counts m against the "
+                "feature off on the same state with the other bodies' mass words zero")
 args = ap.parse_args()
 
 
@@ -345,6 +353,49 @@ def radii_lines():
         print(json.dumps({"scattering_pairs": P.shape[0], "eccentricities": "0 .. 0.99", "radii": [0.03, 0.02], **out}), flush=True)
 
 
+def massive_lines():
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["4096x256", "1024x1024"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        k = int(min(400, max(10, 2e11 // (B * n * n))))
+        dt = float(np.float32(args.dt))
+        for m in sorted({min(m, n) for m in (1, 8, 64, 512, n)}):
+            Z = P.copy()
+            Z[:, m:, 3] = 0.0
+            for mode in ("step_n", "evolve_levels0"):
+                with nb.BatchedSystem(B, n, integrator="hermite") as on, nb.BatchedSystem(B, n, integrator="hermite") as off:
+                    on.set_state(Z, V)
+                    on.set_massive_counts([m] * B)
+                    off.set_state(Z, V)
+
+                    def run(batch):
+                        if mode == "step_n":
+                            batch.step_n(k, dt, args.eps)
+                        else:
+                            batch.evolve(k, dt, levels=0, softening=args.eps)
+
+                    run(on)
+                    run(off)
+                    torch.cuda.synchronize()
+                    t_on, t_off = [], []
+                    for _ in range(args.repeats):      # alternated
+                        t_on.append(timed(lambda: run(on)) / k)
+                        t_off.append(timed(lambda: run(off)) / k)
+                    m_on, m_off = statistics.median(t_on), statistics.median(t_off)
+                    same = bool(torch.equal(on.positions, off.positions) and torch.equal(on.velocities, off.velocities))
+                print(json.dumps({"n": n, "B": B, "m": m, "call": mode, "k": k, "massive_ms_per_step": round(m_on, 5),
+                                  "off_zero_mass_ms_per_step": round(m_off, 5), "off_over_massive": round(m_off / m_on, 3),
+                                  "massive_spread": round((max(t_on) - min(t_on)) / m_on, 4),
+                                  "off_spread": round((max(t_off) - min(t_off)) / m_off, 4),
+                                  "interactions_per_step": nb.batch.interactions_per_step([n] * B, [m] * B),
+                                  "states_equal_bit_for_bit": same, "massive_repeats": [round(x, 5) for x in t_on],
+                                  "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
+
+
+if args.massive:
+    massive_lines()
+    sys.exit(0)
 if args.radii:
     radii_lines()
     sys.exit(0)
