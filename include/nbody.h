@@ -527,6 +527,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_radii.h"
 /* test particles: the bodies after a system's first massive[s] feel forces and exert none */
 #include "nbody_batch_massive.h"
+/* tracer fates: with massive counts and conditions, a test particle that hits a massive body or escapes is removed */
+#include "nbody_batch_fate.h"
 
 #ifdef __cplusplus
 }

@@ -400,6 +400,30 @@ public:
         check(nbody_batch_massive_read(b_, m.data()), "nbody_batch_massive_read");
         return m;
     }
+    // Tracer fates (nbody_batch_fate.h): with remove, evolve accepts massive counts together with stopping conditions or
+    // radii; a test particle that hits a massive body or escapes is frozen with a fate and its system carries on.  fates():
+    // per body (fate[s * maxBodies + i], ...) and per system (hit[s], escaped[s]); throws while the action is refuse.
+    struct Fates {
+        std::vector<int> fate, target;
+        std::vector<std::int64_t> ticks, hit, escaped;
+        std::vector<float> separation, relativeSpeed;
+    };
+    void setTracerAction(bool remove)
+    {
+        const nbody_batch_fate_config cfg = {remove ? NBODY_BATCH_TRACERS_REMOVE : NBODY_BATCH_TRACERS_REFUSE};
+        check(nbody_batch_fate_set(b_, &cfg), "nbody_batch_fate_set");
+    }
+    Fates fates()
+    {
+        Fates f;
+        const size_t n = (size_t)systems_ * (size_t)maxBodies_;
+        f.fate.resize(n), f.target.resize(n), f.ticks.resize(n), f.separation.resize(n), f.relativeSpeed.resize(n);
+        f.hit.resize((size_t)systems_), f.escaped.resize((size_t)systems_);
+        check(nbody_batch_fate_read(b_, f.fate.data(), f.ticks.data(), f.target.data(), f.separation.data(), f.relativeSpeed.data()),
+              "nbody_batch_fate_read");
+        check(nbody_batch_fate_count(b_, f.hit.data(), f.escaped.data()), "nbody_batch_fate_count");
+        return f;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

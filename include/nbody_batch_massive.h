@@ -34,13 +34,16 @@
  *   nbody_batch_evolve.h promises holds unchanged: the exact tick axis, independence of
  *   nbody_batch_evolve_launch_steps, evolve(a) followed by evolve(b) is evolve(a + b), resumption after max_steps, and
  *   results that are functions of the system alone -- not of its slot, B, max_bodies or the other systems.
- * Out of scope: stopping conditions, mergers and per-body radii together with massive counts.  nbody_batch_evolve_on is
- *   refused with NBODY_ERR_INVALID and a message while massive counts are set and a collision radius, an escape radius or
- *   radii are (a collision action other than the default acts only with one of those).  The reason: the collision test of
- *   the evaluation (nbody_batch_stop.h) counts on the row's own column being among the columns it walks -- two columns
- *   within the threshold mean a neighbour -- and a test-particle row has no column of its own.  nbody_batch_step_n_*
- *   ignores the conditions, as it does without massive counts.  Also out of scope: test particles that are not the last
- *   bodies of their system, and a force of the test particles on each other. */
+ * Out of scope here: stopping conditions, mergers and per-body radii together with massive counts.  By default
+ *   nbody_batch_evolve_on is refused with NBODY_ERR_INVALID and a message while massive counts are set and a collision
+ *   radius, an escape radius or radii are (a collision action other than the default acts only with one of those).  The
+ *   reason: the collision test of the evaluation (nbody_batch_stop.h) counts on the row's own column being among the columns
+ *   it walks -- two columns within the threshold mean a neighbour -- and a test-particle row has no column of its own.
+ *   nbody_batch_fate.h lifts the refusal for those who opt in (nbody_batch_fate_set, NBODY_BATCH_TRACERS_REMOVE): a
+ *   test-particle row is judged by one column within the threshold, a test particle that hits a massive body or escapes is
+ *   removed with a fate, and the system carries on; mergers together with massive counts stay refused.
+ *   nbody_batch_step_n_* ignores the conditions, as it does without massive counts.  Also out of scope: test particles that
+ *   are not the last bodies of their system, and a force of the test particles on each other. */
 #ifndef NBODY_AMD_BATCH_MASSIVE_H
 #define NBODY_AMD_BATCH_MASSIVE_H
 

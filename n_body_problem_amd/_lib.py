@@ -205,6 +205,24 @@ _MASSIVE_PROTOTYPES = {
 }
 
 
+class BatchFateConfig(ctypes.Structure):
+    """``nbody_batch_fate_config`` of include/nbody_batch_fate.h."""
+    _fields_ = [("action", c_int)]
+
+
+#: the entry points of include/nbody_batch_fate.h (tracer fates for Hermite batches), which nbody.h includes
+_FATE_PROTOTYPES = {
+    "nbody_batch_fate_set": (c_int, [c_void_p, POINTER(BatchFateConfig)]),
+    "nbody_batch_fate_read": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int), POINTER(c_float), POINTER(c_float)]),
+    "nbody_batch_fate_count": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+}
+BATCH_TRACERS_REFUSE = 0
+BATCH_TRACERS_REMOVE = 1
+BATCH_FATE_ALIVE = 0
+BATCH_FATE_HIT = 1
+BATCH_FATE_ESCAPED = 2
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -230,7 +248,7 @@ def load() -> ctypes.CDLL:
             pass
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
-                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()):
+                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -266,6 +284,11 @@ def radii_names():
 def massive_names():
     """The entry points of nbody_batch_massive.h."""
     return list(_MASSIVE_PROTOTYPES)
+
+
+def fate_names():
+    """The entry points of nbody_batch_fate.h."""
+    return list(_FATE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -21,6 +21,7 @@ from .system import SOFTENING_VERSION3, TIME_TICK, _ptr, _torch
 BATCH_MAX_BODIES = 4096
 INTEGRATORS = {"kick_drift": 0, "kdk": 1, "hermite": 2}
 COLLISION_ACTIONS = {"stop": _lib.BATCH_ON_COLLISION_STOP, "merge": _lib.BATCH_ON_COLLISION_MERGE}
+TRACER_ACTIONS = {"refuse": _lib.BATCH_TRACERS_REFUSE, "remove": _lib.BATCH_TRACERS_REMOVE}
 #: one merger of the log: numpy's view of ``nbody_batch_merge_event``
 MERGE_EVENT_DTYPE = np.dtype([("tick", np.int64), ("survivor", np.int32), ("absorbed", np.int32), ("count_before", np.int32),
                               ("separation", np.float32), ("relative_speed", np.float32), ("mass_survivor", np.float32),
@@ -272,7 +273,7 @@ class BatchedSystem:
         ``positions[s, i, 3]`` are read by no force kernel and are preserved; :meth:`energy` and :meth:`momentum` keep
         reading them, so zero mass words give the massive bodies' energy.  The values belong to the handle:
         :meth:`set_state` and :meth:`set_counts` leave them alone.  :meth:`evolve` refuses massive counts together with
-        stopping conditions or radii.  The length is checked here, the values by the library.  Forgets what
+        stopping conditions or radii unless :meth:`set_tracer_action` opts in.  The length is checked here, the values by the library.  Forgets what
         :meth:`set_counts` forgets: the cached accelerations and jerks, the levels and the stops."""
         self._use_current_stream()
         if massive is None:
@@ -292,6 +293,37 @@ class BatchedSystem:
             return None
         _check(self._lib, status, self._h)
         return m
+
+    def set_tracer_action(self, action: str = "refuse") -> None:
+        """What :meth:`evolve` does with massive counts (:meth:`set_massive_counts`) together with stopping conditions or
+        radii (``include/nbody_batch_fate.h`` states the rules): ``"refuse"`` (the default) refuses the call, as
+        :meth:`set_massive_counts` says; ``"remove"`` runs it.  A test particle that comes within the collision radius (or
+        the sum of the two radii) of a massive body, or leaves the escape radius, is then removed from that step on: frozen
+        where it is, with a fate that :meth:`fates` reports, while its system carries on.  A collision between two massive
+        bodies or a massive escaper stops the system as :meth:`set_stop_conditions` describes.  The collision action
+        ``"merge"`` stays refused together with massive counts.  Without massive counts ``"remove"`` changes nothing.
+        Forgets stops, fates and the cached accelerations and jerks, as :meth:`set_stop_conditions` does."""
+        if action not in TRACER_ACTIONS:
+            raise ValueError(f"action must be one of {tuple(TRACER_ACTIONS)}")
+        cfg = _lib.BatchFateConfig(TRACER_ACTIONS[action])
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_fate_set(self._h, ctypes.byref(cfg)), self._h)
+
+    def fates(self) -> "FateResult":
+        """What became of the test particles, per body (waits for the queued work).  Raises :class:`NBodyError`
+        (``NBODY_ERR_STATE``) while the tracer action is ``"refuse"``."""
+        B, n = self.num_systems, self.max_bodies
+        fate, target = np.zeros((B, n), dtype=np.int32), np.zeros((B, n), dtype=np.int32)
+        ticks = np.zeros((B, n), dtype=np.int64)
+        sep, speed = np.zeros((B, n), dtype=np.float32), np.zeros((B, n), dtype=np.float32)
+        hit, escaped = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        i32, i64, f32 = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_fate_read(self._h, fate.ctypes.data_as(i32), ticks.ctypes.data_as(i64),
+                                                          target.ctypes.data_as(i32), sep.ctypes.data_as(f32),
+                                                          speed.ctypes.data_as(f32)), self._h)
+        _check(self._lib, self._lib.nbody_batch_fate_count(self._h, hit.ctypes.data_as(i64), escaped.ctypes.data_as(i64)), self._h)
+        return FateResult(fate, ticks, target, sep, speed, hit, escaped)
 
     def mergers(self) -> "MergeResult":
         """The mergers so far, per system (waits for the queued work)."""
@@ -367,6 +399,21 @@ class MergeResult:
         return f"MergeResult(count={self.count.tolist()}, events={self.events.tolist()})"
 
 
+class FateResult:
+    """What became of the test particles under the tracer action ``"remove"`` (:meth:`BatchedSystem.set_tracer_action`).
+    ``(B, max_bodies)`` arrays: ``fate`` (0 alive, 1 hit a massive body, 2 escaped), ``ticks`` (the tick of the step that
+    found it, in the units of the :meth:`BatchedSystem.evolve` call that found it), ``target`` (the massive body hit, ``-1``
+    otherwise), ``separation`` and ``relative_speed`` at the evaluation that found the hit (0 otherwise); massive bodies, live
+    tracers and empty slots read ``0, 0, -1, 0, 0``.  ``(B,)`` arrays: ``hit`` and ``escaped``, the totals per system."""
+
+    def __init__(self, fate, ticks, target, separation, relative_speed, hit, escaped):
+        self.fate, self.ticks, self.target, self.separation, self.relative_speed = fate, ticks, target, separation, relative_speed
+        self.hit, self.escaped = hit, escaped
+
+    def __repr__(self):
+        return f"FateResult(hit={self.hit.tolist()}, escaped={self.escaped.tolist()})"
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -377,4 +424,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

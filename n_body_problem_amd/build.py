@@ -21,7 +21,8 @@ HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_merge.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_radii.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_massive.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_massive.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_fate.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -199,10 +199,14 @@ __device__ __forceinline__ float radii_threshold(float ri, float rj, float eps2)
 // RADII (include/nbody_batch_radii.h, with STOP): the threshold is the pair's own, fmaf(S, S, eps^2) with S = R_row + R_j, one
 // fp32 add; R_j rides in the fourth word of the column's velocity, which the broadcast read brings anyway, and rr[k] is the
 // row's radius.  Two more VALU per interaction; the self pair still meets its threshold (eps^2 <= fmaf(2 R, 2 R, eps^2)).
+// OWN = kOwnFate (batch_hermite_fate_kernel, with STOP): near1_out[k] receives the rows that met their threshold in at least
+// ONE column.  The tag is a template argument, so the other instantiations do not contain the copy.
+constexpr int kOwnFate = 4;
 template <int G, bool GUARD, bool STOP = false, int OWN = 0, bool RADII = false>
 __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, const float3 (&xp)[G], const float3 (&vp)[G],
                                                    float eps2, float3 (&a)[G], float3 (&jk)[G], float thr = 0.f,
-                                                   unsigned long long *near2 = nullptr, const float *rr = nullptr)
+                                                   unsigned long long *near2 = nullptr, const float *rr = nullptr,
+                                                   unsigned long long *near1_out = nullptr)
 {
     unsigned long long near1[G];
 #pragma unroll
@@ -242,6 +246,11 @@ __device__ __forceinline__ void batch_forces_jerks(const float4 *sh, int n, cons
             jk[k].y = __builtin_fmaf(__builtin_fmaf(-c, dy, ey), s, jk[k].y);
             jk[k].z = __builtin_fmaf(__builtin_fmaf(-c, dz, ez), s, jk[k].z);
         }
+    }
+    if (OWN == kOwnFate) {  // include/nbody_batch_fate.h: a row without a column of its own is judged by one column
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            near1_out[k] = near1[k];
     }
 }
 
@@ -2342,6 +2351,381 @@ hipError_t launch_batch_adaptive_massive(float4 *pos, float4 *vel, float4 *acc, 
     }
 }
 
+// ---- tracer fates (include/nbody_batch_fate.h): massive counts together with a collision radius, radii or an escape radius.
+// A test particle that touches a massive body or leaves the escape radius is removed -- frozen, with a fate -- and its system
+// carries on; a collision among the massive bodies or a massive escaper stops the system as batch_hermite_stop_kernel does.
+
+// Per launch.  One kernel serves both kinds of radius: a shared R_c rides as the radius R_c / 2 of every body, whose fp32 sum
+// is R_c exactly, so the threshold is fmaf(R_c, R_c, eps^2) as nbody_batch_stop.h states it.  The fate arrays are laid out
+// like the positions; all zero: alive.
+struct BatchFate {
+    long long tick;
+    int fate;  // kFateHit, kFateEscaped; 0: alive
+    int target;
+    float separation, speed;
+};
+constexpr int kFateHit = 1, kFateEscaped = 2;
+struct BatchFateArgs {
+    const float *radii;  // [n_systems][max_bodies], or nullptr: every body has the radius half_rc
+    float half_rc;
+    int collide;         // a collision radius or radii are set (otherwise the column loop's masks are dropped)
+    BatchFate *fates;    // one pointer: the kernel's scalar registers are all taken
+};
+
+// The cold path of a tracer that is removed, by its own lane only: the massive body of smallest r^2 + eps^2 among those
+// within the pair's threshold (ties to the smallest index: the scan ascends and replaces on less-than only), with the
+// evaluation's own chain on the columns LDS still holds, the separation and the relative speed at the row's predicted state,
+// which it rereads from LDS with its radius: nothing is kept alive across the corrector for this.
+__device__ __forceinline__ void fate_record(const float4 *sh, int m, int r, float eps2, bool hit, long long tick,
+                                            const BatchFateArgs &fa)
+{
+    int target = -1;
+    float sep = 0.f, speed = 0.f;
+    if (hit) {
+        const float4 xp = sh[2 * r], vp = sh[2 * r + 1];
+        const float rr = vp.w;
+        float best = __builtin_inff();
+#pragma unroll 1
+        for (int j = 0; j < m; ++j) {
+            const float4 pj = sh[2 * j];
+            const float dx = pj.x - xp.x, dy = pj.y - xp.y, dz = pj.z - xp.z;
+            float r2 = __builtin_fmaf(dx, dx, eps2);
+            r2 = __builtin_fmaf(dy, dy, r2);
+            r2 = __builtin_fmaf(dz, dz, r2);
+            if (r2 <= radii_threshold(rr, sh[2 * j + 1].w, eps2) && r2 < best) {
+                best = r2;
+                target = j;
+            }
+        }
+        if (target >= 0) {
+            const float4 pj = sh[2 * target], wj = sh[2 * target + 1];
+            const float dx = pj.x - xp.x, dy = pj.y - xp.y, dz = pj.z - xp.z;
+            const float ex = wj.x - vp.x, ey = wj.y - vp.y, ez = wj.z - vp.z;
+            sep = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+            speed = __builtin_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
+        }
+    }
+    fa.fates[r] = BatchFate{tick, hit ? kFateHit : kFateEscaped, target, sep, speed};
+}
+
+// What one row found, after its group's column loop: the verdict per row group is (near2 & massive rows) | (near1 & tracer
+// rows), both masks of the valid, live rows only -- a massive row walks its own column, a tracer row has none.  A massive
+// row that collides or escapes sets its bit in *found (the system stops); for a tracer row that hits or escapes the result is
+// kFateHit or kFateEscaped (it is dead from here on), otherwise 0.  x: the positions of the escape test.
+__device__ __forceinline__ unsigned fate_examine(int m, int r, bool alive, unsigned long long near1, unsigned long long near2,
+                                                 const float3 &x, const BatchStopArgs &sa, const BatchFateArgs &fa, int *found)
+{
+    const unsigned long long massive = __ballot(alive && r < m), tracer = __ballot(alive && r >= m);
+    const unsigned long long touch = fa.collide ? (near2 & massive) | (near1 & tracer) : 0ull;
+    const float d2 = __builtin_fmaf(x.z, x.z, __builtin_fmaf(x.y, x.y, x.x * x.x));
+    const bool out = alive && d2 > sa.re2;
+    *found |= ((touch & massive) != 0 ? kStopCollision : 0) | (__any(out && r < m) ? kStopEscape : 0);
+    const bool hit = __builtin_amdgcn_inverse_ballot_w64(touch & tracer);  // the scalar mask as the lanes' condition
+    return hit ? kFateHit : out && r >= m ? kFateEscaped : 0u;
+}
+
+// The rows' fates in one register per lane: bit q, row q is dead; bit 8 + q, it hit in the evaluation just made; bit 16 + q,
+// it escaped there.  fate_note sets the bits of a row found; fate_flush, after the evaluation and before the barrier that
+// precedes the next prediction, records the rows found and clears their upper bits: the cold path is kept out of the rows'
+// loop, where the corrector needs every register.
+__device__ __forceinline__ void fate_note(unsigned &dead, int q, unsigned what)
+{
+    dead |= what ? (1u | (what == kFateHit ? 1u << 8 : 1u << 16)) << q : 0u;
+}
+__device__ __forceinline__ void fate_flush(const float4 *sh, int m, int tid, int T, int rpl, float eps2, long long tick,
+                                           const BatchFateArgs &fa, unsigned &dead)
+{
+    if (dead >> 8) {
+        asm volatile("" : "+v"(tid));  // the rows' addresses are formed here, not carried through the steps from the kernel's top
+        for (int q = 0; q < rpl; ++q)
+            if ((dead >> (8 + q)) & 0x101u)
+                fate_record(sh, m, q * T + tid, eps2, (dead >> (8 + q)) & 1u, tick, fa);
+        dead &= 0xffu;
+    }
+}
+
+// radii_evaluate with the column bound m and the rows' fates: a sibling (OWN = kOwnFate).  `dead` holds a bit per row of
+// the lane; a dead row rides through the column loop and its result is dropped.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void fate_evaluate(const float4 *sh, int n, int m, int tid, int T, float eps2, float3 (&a)[RPL],
+                                              float3 (&jk)[RPL], const BatchStopArgs &sa, const BatchFateArgs &fa,
+                                              unsigned &dead, int *found)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G];
+        float rr[G];
+        unsigned long long near1[G], near2[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = make_float3(0.f, 0.f, 0.f);
+            rr[i] = 0.f;
+            if (r < n) {
+                const float4 w = sh[2 * r + 1];
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = make_float3(w.x, w.y, w.z);
+                rr[i] = w.w;
+            }
+        }
+        batch_forces_jerks<G, GUARD, true, kOwnFate, true>(sh, m, xp, vp, eps2, a1, j1, 0.f, near2, rr, near1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            const bool alive = r < n && !((dead >> q) & 1u);
+            fate_note(dead, q, fate_examine(m, r, alive, near1[i], near2[i], xp[i], sa, fa, found));
+            a[q] = a1[i];
+            jk[q] = j1[i];
+        }
+    }
+}
+
+// radii_evaluate_request with the column bound m and the rows' fates.  A row that was dead before the step is neither
+// corrected nor written and does not vote; a row found in this step is corrected and written, and does not vote.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ EvolveWant fate_evaluate_request(const float4 *sh, int n, int m, int tid, int T, float eps2,
+                                                            float4 *pos, float4 *vel, float3 (&a)[RPL], float3 (&jk)[RPL],
+                                                            const EvolveSteps &e, const BatchEvolveArgs &p,
+                                                            const BatchStopArgs &sa, const BatchFateArgs &fa, unsigned &dead,
+                                                            int *found)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+    EvolveWant want;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G], x[G], v[G];
+        float rr[G];
+        unsigned long long near1[G], near2[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = x[i] = v[i] = make_float3(0.f, 0.f, 0.f);
+            rr[i] = 0.f;
+            if (r < n) {
+                const float4 w = sh[2 * r + 1];
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = make_float3(w.x, w.y, w.z);
+                rr[i] = w.w;
+                x[i] = *reinterpret_cast<const float3 *>(&pos[r]);
+                v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, true, kOwnFate, true>(sh, m, xp, vp, eps2, a1, j1, 0.f, near2, rr, near1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            const bool alive = r < n && !((dead >> q) & 1u);
+            hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
+            hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
+            hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            const unsigned gone = fate_examine(m, r, alive, near1[i], near2[i], x[i], sa, fa, found);
+            fate_note(dead, q, gone);
+            if (alive) {  // x, y, z only: the mass words and the velocities' w stay as they are
+                *reinterpret_cast<float3 *>(&pos[r]) = x[i];
+                *reinterpret_cast<float3 *>(&vel[r]) = v[i];
+            }
+            float3 a0 = a[q], j0 = jk[q];
+            renew_f32(a0);  // widened again below, one component at a time: the corrector's fp64 copies end here
+            renew_f32(j0);
+            renew_f32(a1[i]);
+            renew_f32(j1[i]);
+            a[q] = a1[i];
+            jk[q] = j1[i];
+            EvolveNorms s;
+            evolve_norms(s, a0.x, a1[i].x, j0.x, j1[i].x, e);
+            evolve_norms(s, a0.y, a1[i].y, j0.y, j1[i].y, e);
+            evolve_norms(s, a0.z, a1[i].z, j0.z, j1[i].z, e);
+            const double num = p.eta * (__builtin_sqrt(s.a1 * s.a2) + s.j1), den = __builtin_sqrt(s.j1 * s.a3) + s.a2;
+            evolve_raise(want, alive && !gone, num, den, p);
+        }
+    }
+    return want;
+}
+
+// batch_hermite_adaptive_massive_kernel with the conditions of batch_hermite_stop_kernel / batch_hermite_radii_kernel and the
+// tracers' fates: a sibling once more, so that those stay the code they are.  The same loop, LDS layout and workgroup shapes.
+// A body's radius rides in sh[2 r + 1].w as in batch_hermite_radii_kernel.  Dead rows are known from the fate array, read at
+// the launch's start, and kept as a bit per row in one register; they are not predicted, so their columns -- which nobody
+// reads: they lie beyond m -- and their own predicted state stay the frozen state.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_fate_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                  const int *counts, const int *massive, BatchEvolveState *state,
+                                                                  int *counters, int max_bodies, BatchEvolveArgs p,
+                                                                  BatchStopArgs sa, BatchStopReport *report, BatchFateArgs fa)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies, and their radii
+    __shared__ int red[16];         // the waves' levels
+    __shared__ int red_stop[16];    // the waves' stopping conditions (massive rows only)
+    __shared__ unsigned long long cold_best;  // the cold path's words
+    __shared__ int cold_escaper;
+    const int n = uniform_i32(counts[blockIdx.x]);
+    if (n <= 0)
+        return;
+    const int mc = massive[blockIdx.x];
+    const int m = uniform_i32(mc < n ? mc : n);
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    const bool frozen = uniform_i32(report[blockIdx.x].reason) != 0;
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (frozen || tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target && !frozen) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    pos += base;
+    vel += base;
+    acc += base;
+    jerk += base;
+    fa.fates += base;
+    float3 a[RPL], jk[RPL];
+    unsigned dead = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, fa.radii ? fa.radii[base + r] : fa.half_rc);
+            dead |= fa.fates[r].fate != 0 ? 1u << q : 0u;
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!p.have_acc) {  // (a0, j0) at the current state, which the columns hold
+        __syncthreads();
+        int found = 0;
+        fate_evaluate<RPL, GUARD>(sh, n, m, tid, T, p.eps2, a, jk, sa, fa, dead, &found);
+        fate_flush(sh, m, tid, T, RPL, p.eps2, tick, fa, dead);
+        stop_publish(red_stop, found, tid);
+    }
+    if (!p.have_level) {  // the first step: dt = eta_start |a| / |j|, compared as squares; dead rows do not vote
+        EvolveWant want;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+            const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+            evolve_raise(want, q * T + tid < n && !((dead >> q) & 1u), p.eta_start2 * a2, j2, p);
+        }
+        evolve_publish(red, want, tid);
+    }
+    __syncthreads();  // every lane is done reading before the first prediction rewrites the columns; red[], red_stop[] are complete
+    if (!p.have_level) {
+        const EvolveWant want = evolve_collect(red, T);
+        level = want.level > p.levels ? p.levels : want.level;
+        clamped += want.level > p.levels ? 1 : 0;
+    }
+    int stop = 0;  // workgroup-uniform: the conditions the massive bodies met, which end the loop
+    if (!p.have_acc)
+        stop = stop_collect(red_stop, T);
+    for (int run = 0; tick < p.target && run < p.budget && steps < p.max_steps && !stop; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n && !((dead >> q) & 1u)) {  // x, y, z only: the mass words and the radii stay
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        int found = 0;
+        const long long after = tick + (1ll << (p.levels - level));  // the tick of a fate, as of a stop: the step's end
+        const EvolveWant mine = fate_evaluate_request<RPL, GUARD>(sh, n, m, tid, T, p.eps2, pos, vel, a, jk, e, p, sa, fa, dead, &found);
+        fate_flush(sh, m, tid, T, RPL, p.eps2, after, fa, dead);
+        stop_publish(red_stop, found, tid);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        stop = stop_collect(red_stop, T);
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick = after;
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+    }
+    int lane = tid;  // the rows' indices formed anew, as in batch_hermite_radii_kernel
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + lane;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target && !stop) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+    if (stop)  // among the massive bodies: the columns still hold the positions the conditions were examined at
+        radii_stop_report(sh, pos, m, lane, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x], cold_best, cold_escaper);
+}
+
+template <int RPL, bool GUARD>
+hipError_t launch_fate_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
+                           float4 *jerk, const int *counts, const int *massive, BatchEvolveState *state, int *counters,
+                           int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report,
+                           const BatchFateArgs &fa)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_fate_kernel<RPL, GUARD>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((batch_hermite_fate_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, massive,
+                       state, counters, max_bodies, p, sa, report, fa);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_fate(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
+                             BatchEvolveState *state, int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p,
+                             const BatchStopArgs &sa, BatchStopReport *report, const BatchFateArgs &fa, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const dim3 grid(n_systems), block(sh.threads);
+    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
+    const bool guard = !(p.eps2 > 0.f);
+    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return launch_fate_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    case 3: return launch_fate_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    case 4: return launch_fate_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    case 5: return launch_fate_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    case 8: return launch_fate_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    default: return launch_fate_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -2462,6 +2846,10 @@ struct nbody_batch {
     std::vector<int> massive;     // host copy, [n_systems] while massive_set
     int *massive_dev = nullptr;   // [n_systems], allocated by the first nbody_batch_massive_set
     bool massive_set = false;
+    // nbody_batch_fate_set: what becomes of a test particle that meets a condition, and the per-body fates beside the
+    // reports (forgotten with them), laid out like the positions and allocated by the first REMOVE
+    int tracer_action = NBODY_BATCH_TRACERS_REFUSE;
+    BatchFate *fates = nullptr;   // [n_systems][max_bodies]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -2571,6 +2959,7 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->merge_log) (void)hipFree(b->merge_log);
     if (b->radii) (void)hipFree(b->radii);
     if (b->massive_dev) (void)hipFree(b->massive_dev);
+    if (b->fates) (void)hipFree(b->fates);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -2722,7 +3111,14 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     if (b->radii_set && b->stop_collision_radius > 0.f)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: radii and collision_radius are both set (nbody_batch_radii.h: radii "
                                            "replace the collision radius)");
-    if (b->massive_set && (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set))
+    // tracer fates (nbody_batch_fate.h): with REMOVE massive counts go together with the conditions, through a kernel of their own
+    const bool fates = b->massive_set && b->tracer_action == NBODY_BATCH_TRACERS_REMOVE &&
+                       (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set);
+    if (fates && b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || b->radii_set))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: the collision action MERGE together with massive counts "
+                                           "(nbody_batch_fate.h: mergers among massive bodies while massive counts are set are "
+                                           "not supported); nbody_batch_merge_set(b, NULL) or nbody_batch_massive_set(b, NULL)");
+    if (!fates && b->massive_set && (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set))
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: massive counts are set together with a stopping condition or radii "
                                            "(nbody_batch_massive.h: not supported, the collision test counts on a row's own column); "
                                            "nbody_batch_massive_set(b, NULL) or switch the conditions off");
@@ -2808,8 +3204,12 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         }
         if (b->stop_forgotten)
             BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
+        if (b->stop_forgotten && fates)  // nbody_batch_fate.h: the fates are forgotten where the stops are
+            BATCH_TRY(b, hipMemsetAsync(b->fates, 0, sizeof(BatchFate) * slots, b->stream));
         b->stop_forgotten = false;
     }
+    const BatchFateArgs fa{radii ? b->radii : nullptr, 0.5f * b->stop_collision_radius,
+                           radii || b->stop_collision_radius > 0.f ? 1 : 0, b->fates};
     BatchEvolveArgs p;
     p.dt = (double)cfg->dt_max;
     p.dt_half = 0.5 * p.dt;
@@ -2833,11 +3233,15 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         p.new_call = first ? 1 : 0;
         p.reset_tick = first && !resume ? 1 : 0;
         BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
-        if (radii)
+        if (fates)
+            BATCH_TRY(b, launch_batch_fate(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
+                                           b->counts_dev, b->massive_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems,
+                                           (int)b->max_bodies, p, sa, b->stop_report, fa, b->stream));
+        else if (radii)
             BATCH_TRY(b, launch_batch_radii(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
                                             b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
                                             p, sa, b->stop_report, ma, ra, b->stream));
-        else if (b->massive_set)  // never with stopping conditions: refused above
+        else if (b->massive_set)  // never with stopping conditions: refused above, or the fate kernel's
             BATCH_TRY(b, launch_batch_adaptive_massive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc,
                                                        b->jerk, b->counts_dev, b->massive_dev, b->evolve_state, b->evolve_counters,
                                                        (int)b->n_systems, (int)b->max_bodies, p, b->stream));
@@ -3077,6 +3481,77 @@ int nbody_batch_massive_read(nbody_batch *b, int64_t *host_massive)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_massive_read: no massive counts are set (nbody_batch_massive_set)");
     for (size_t s = 0; s < (size_t)b->n_systems; ++s)
         host_massive[s] = b->massive[s];
+    return NBODY_OK;
+}
+
+int nbody_batch_fate_set(nbody_batch *b, const nbody_batch_fate_config *cfg)
+{
+    const int action = cfg ? cfg->action : NBODY_BATCH_TRACERS_REFUSE;
+    if (action != NBODY_BATCH_TRACERS_REFUSE && action != NBODY_BATCH_TRACERS_REMOVE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_fate_set: unknown tracer action (REFUSE = 0, REMOVE = 1)");
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_set: batch is NULL");
+    if (action == NBODY_BATCH_TRACERS_REMOVE && !b->fates) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        BATCH_TRY(b, hipMalloc((void **)&b->fates, sizeof(BatchFate) * (size_t)b->n_systems * (size_t)b->max_bodies));
+    }
+    b->tracer_action = action;
+    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
+    return NBODY_OK;
+}
+
+// Whether the fate arrays hold what the last nbody_batch_evolve_on calls found (otherwise every body reads alive).
+static bool fates_kept(const nbody_batch *b)
+{
+    return b->massive_set && b->fates && !b->stop_forgotten &&
+           (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set);
+}
+
+int nbody_batch_fate_read(nbody_batch *b, int *fate, int64_t *tick, int *target, float *separation, float *relative_speed)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_read: batch is NULL");
+    if (b->tracer_action != NBODY_BATCH_TRACERS_REMOVE)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_read: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
+    const size_t B = (size_t)b->n_systems, cap = (size_t)b->max_bodies, slots = B * cap;
+    std::vector<BatchFate> f(slots, BatchFate{0, 0, 0, 0.f, 0.f});
+    if (fates_kept(b)) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        BATCH_TRY(b, hipMemcpyAsync(f.data(), b->fates, sizeof(BatchFate) * slots, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    for (size_t s = 0; s < B; ++s)
+        for (size_t i = 0; i < cap; ++i) {
+            const size_t k = s * cap + i;
+            const bool gone = (int64_t)i < (int64_t)b->counts[s] && f[k].fate != 0;  // alive, massive or beyond the count: 0, 0, -1, 0, 0
+            if (fate) fate[k] = gone ? f[k].fate : NBODY_BATCH_FATE_ALIVE;
+            if (tick) tick[k] = gone ? f[k].tick : 0;
+            if (target) target[k] = gone ? f[k].target : -1;
+            if (separation) separation[k] = gone ? f[k].separation : 0.f;
+            if (relative_speed) relative_speed[k] = gone ? f[k].speed : 0.f;
+        }
+    return NBODY_OK;
+}
+
+int nbody_batch_fate_count(nbody_batch *b, int64_t *hit, int64_t *escaped)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_count: batch is NULL");
+    if (b->tracer_action != NBODY_BATCH_TRACERS_REMOVE)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_count: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
+    std::vector<int> fate((size_t)b->n_systems * (size_t)b->max_bodies);
+    const int rc = nbody_batch_fate_read(b, fate.data(), nullptr, nullptr, nullptr, nullptr);
+    if (rc != NBODY_OK)
+        return rc;
+    for (size_t s = 0; s < (size_t)b->n_systems; ++s) {
+        int64_t h = 0, e = 0;
+        for (size_t i = 0; i < (size_t)b->max_bodies; ++i) {
+            h += fate[s * (size_t)b->max_bodies + i] == NBODY_BATCH_FATE_HIT;
+            e += fate[s * (size_t)b->max_bodies + i] == NBODY_BATCH_FATE_ESCAPED;
+        }
+        if (hit) hit[s] = h;
+        if (escaped) escaped[s] = e;
+    }
     return NBODY_OK;
 }
 

@@ -29,6 +29,11 @@ the same call with per-body radii of 5e-7 everywhere and no collision radius (th
 alternated, medians; then the scattering case with unequal radii (0.03 a and 0.02 a, the reach of collision radius 0.05 a)
 stopped against merged: how many pairs collide, at what step counts, the merged radii and the two wall times.
 
+--fates: instead, tracer fates (set_tracer_action("remove")).  For n x B = 4096 x 256 and 1024 x 1024 (or --cases) and m in
+1, 8, 64, one line per evolve(k, dt, levels=0): the call with massive counts m, the tracer action "remove" and a collision and
+an escape radius that never trigger, against the same call with massive counts alone, alternated, medians and spreads, and
+whether the two states are equal bit for bit.
+
 --massive: instead, test particles (set_massive_counts).  For n x B = 4096 x 256 and 1024 x 1024 (or --cases) and m in
 1, 8, 64, 512, n, one line per Hermite step_n(k, dt) and one per evolve(k, dt, levels=0): the call with massive counts m
 set against the same call with the feature off, both on the same state with the mass words of the bodies from m on zeroed
@@ -64,6 +69,8 @@ ap.add_argument("--merges", action="store_true", help="evolve(levels=0) under th
                 "conditions that cannot trigger, and the scattering case merged at a collision radius")
 ap.add_argument("--radii", action="store_true", help="evolve(levels=0) with per-body radii against a collision radius, neither "
                 "of which can trigger, and the scattering case with unequal radii stopped and merged")
+ap.add_argument("--fates", action="store_true", help="evolve(levels=0) with massive counts m and the tracer action 'remove' under "
+                "conditions that never trigger against the same state with the feature off")
 ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolve(levels=0) with massive counts m against the "
                 "feature off on the same state with the other bodies' mass words zero")
 args = ap.parse_args()
@@ -393,8 +400,48 @@ def massive_lines():
                                   "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
 
 
+def fates_lines():
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["4096x256", "1024x1024"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        dt = float(np.float32(args.dt))
+        for m in sorted({min(m, n) for m in (1, 8, 64)}):
+            k = int(min(400, max(10, 2e11 // (B * n * m))))
+            with nb.BatchedSystem(B, n, integrator="hermite") as on, nb.BatchedSystem(B, n, integrator="hermite") as off:
+                for batch in (on, off):
+                    batch.set_state(P, V)
+                    batch.set_massive_counts([m] * B)
+                on.set_tracer_action("remove")
+                on.set_stop_conditions(collision_radius=1e-9, escape_radius=1e9)   # conditions that never trigger
+
+                def run(batch):
+                    batch.evolve(k, dt, levels=0, softening=args.eps)
+
+                run(on)
+                run(off)
+                torch.cuda.synchronize()
+                t_on, t_off = [], []
+                for _ in range(args.repeats):      # alternated
+                    t_on.append(timed(lambda: run(on)) / k)
+                    t_off.append(timed(lambda: run(off)) / k)
+                m_on, m_off = statistics.median(t_on), statistics.median(t_off)
+                same = bool(torch.equal(on.positions, off.positions) and torch.equal(on.velocities, off.velocities))
+                f = on.fates()
+            print(json.dumps({"n": n, "B": B, "m": m, "call": "evolve_levels0", "k": k, "fates_ms_per_step": round(m_on, 5),
+                              "off_ms_per_step": round(m_off, 5), "fates_over_off": round(m_on / m_off, 3),
+                              "fates_spread": round((max(t_on) - min(t_on)) / m_on, 4),
+                              "off_spread": round((max(t_off) - min(t_off)) / m_off, 4),
+                              "interactions_per_step": nb.batch.interactions_per_step([n] * B, [m] * B),
+                              "states_equal_bit_for_bit": same, "removed": int(f.hit.sum() + f.escaped.sum()),
+                              "fates_repeats": [round(x, 5) for x in t_on], "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
+
+
 if args.massive:
     massive_lines()
+    sys.exit(0)
+if args.fates:
+    fates_lines()
     sys.exit(0)
 if args.radii:
     radii_lines()
