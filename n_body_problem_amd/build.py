@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
 SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
            os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
+           os.path.join(CSRC, "nbody_batch_choice.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_evolve.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),

@@ -13,6 +13,7 @@
 // Hermite (NBODY_INTEGRATOR_HERMITE) runs a sibling kernel, batch_hermite_kernel: the same order, with the jerk summed
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
+#include "nbody_batch_choice.h"
 #include "nbody_batch_radii_check.h"
 #include "nbody_kernels.h"
 
@@ -20,30 +21,66 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace nbody {
 namespace {
 
-static_assert(NBODY_BATCH_MAX_BODIES == 4096, "64 KiB of LDS per workgroup: two workgroups on a CU's 160 KiB");
+static_assert(NBODY_BATCH_MAX_BODIES == 4096, "LDS per workgroup: 64 KiB of positions for the step kernels (two workgroups on a "
+                                              "CU's 160 KiB), 128 KiB of positions and velocities for the Hermite families");
+static_assert(sizeof(float4) == kBatchBytesPerBody, "nbody_batch_choice.h counts the dynamic LDS in float4");
 
 // Steps per launch at most: a long k is cut into launches of this many steps.  The state goes through HBM between them as
 // the same fp32 bits (the KDK accelerations through the handle's cache), so the cut changes nothing.
 constexpr int kBatchStepsPerLaunch = 128;
 
-// Workgroup shape for a capacity: rows per lane and threads.  Small systems keep a whole wave busy (one or two rows per
-// lane); from 129 bodies on four rows per lane feed on every broadcast LDS read, 64 threads per 256 bodies (4096 bodies:
-// 1024 threads, 16 waves).
-struct BatchShape {
-    int rpl, threads;
-};
-inline BatchShape batch_shape(int max_bodies)
+// The kernels below are instantiated for <RPL, GUARD>: rows per lane and the eps = 0 guard (nbody_batch_choice.h chooses
+// them, and which family runs).  with_shape is the one place that turns the two numbers into template arguments:
+// f(integral_constant<int, RPL>, bool_constant<GUARD>).
+template <class F>
+hipError_t with_shape(int rpl, bool guard, F &&f)
 {
-    if (max_bodies <= 64)
-        return {1, 64};
-    if (max_bodies <= 128)
-        return {2, 64};
-    return {4, (max_bodies + 255) / 256 * 64};
+    switch (rpl * 2 + (guard ? 1 : 0)) {
+    case 2: return f(std::integral_constant<int, 1>{}, std::bool_constant<false>{});
+    case 3: return f(std::integral_constant<int, 1>{}, std::bool_constant<true>{});
+    case 4: return f(std::integral_constant<int, 2>{}, std::bool_constant<false>{});
+    case 5: return f(std::integral_constant<int, 2>{}, std::bool_constant<true>{});
+    case 8: return f(std::integral_constant<int, 4>{}, std::bool_constant<false>{});
+    default: return f(std::integral_constant<int, 4>{}, std::bool_constant<true>{});
+    }
+}
+
+// What the launches of a call share: the choice, the systems, the stream, the caller's state and the handle's arrays (those a
+// family does not read may be null).
+struct BatchEvolveState;
+struct BatchStopReport;
+struct BatchLaunch {
+    BatchChoice choice;
+    int n_systems, max_bodies;
+    hipStream_t stream;
+    float4 *pos, *vel, *acc, *jerk;
+    int *counts;
+    const int *massive;
+    BatchEvolveState *state;
+    int *counters;
+    BatchStopReport *report;
+};
+
+// One launch of a batch kernel, one workgroup per system, with the choice's workgroup and dynamic LDS.  The Hermite families
+// raise their limit first: above the default 64 KiB of dynamic LDS from 2049 bodies on (128 KiB at 4096).
+template <class... P, class... A>
+hipError_t launch_batch_kernel(void (*kernel)(P...), const BatchLaunch &l, const A &...args)
+{
+    const BatchChoice &c = l.choice;
+    if (c.raises_lds_limit()) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)c.lds);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(l.n_systems), dim3(c.threads), c.lds, l.stream, args...);
+    return hipGetLastError();
 }
 
 // Accelerations of the lane's RPL rows from the n columns in LDS, ascending j, one chain per row and component.
@@ -433,36 +470,12 @@ __global__ __launch_bounds__(1024) void batch_hermite_kernel(float4 *pos, float4
     }
 }
 
-template <int RPL, bool GUARD>
-hipError_t launch_hermite_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                              float4 *jerk, const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
+hipError_t launch_batch_hermite(const BatchLaunch &l, int k, float dt, float eps2, int have_acc)
 {
-    // above the default 64 KiB of dynamic LDS from 2049 bodies on (128 KiB at 4096)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies,
-                       k, dt, eps2, have_acc);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_hermite(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, int n_systems,
-                                int max_bodies, int k, float dt, float eps2, bool have_acc, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(eps2 > 0.f);
-    const int ha = have_acc ? 1 : 0;
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_hermite_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    case 3: return launch_hermite_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    case 4: return launch_hermite_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    case 5: return launch_hermite_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    case 8: return launch_hermite_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    default: return launch_hermite_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, max_bodies, k, dt, eps2, ha);
-    }
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts, l.max_bodies,
+                                   k, dt, eps2, have_acc);
+    });
 }
 
 // ---- adaptive shared steps (include/nbody_batch_evolve.h): every system on its own step h = dt_max 2^-L, to a common tick.
@@ -1310,36 +1323,12 @@ __global__ __launch_bounds__(1024) void batch_hermite_merge_kernel(float4 *pos, 
         merge_report_escaper(pos, n, lane, T, RPL, sa, tick, &report[blockIdx.x], cold_escaper);
 }
 
-template <int RPL, bool GUARD>
-hipError_t launch_merge_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                            float4 *jerk, int *counts, BatchEvolveState *state, int *counters, int max_bodies,
-                            const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report, const BatchMergeArgs &ma)
+hipError_t launch_batch_merge(const BatchLaunch &l, const BatchEvolveArgs &p, const BatchStopArgs &sa, const BatchMergeArgs &ma)
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_merge_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_merge_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
-                       counters, max_bodies, p, sa, report, ma);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_merge(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, int *counts, BatchEvolveState *state,
-                              int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
-                              BatchStopReport *report, const BatchMergeArgs &ma, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(p.eps2 > 0.f);
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_merge_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    case 3: return launch_merge_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    case 4: return launch_merge_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    case 5: return launch_merge_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    case 8: return launch_merge_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    default: return launch_merge_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma);
-    }
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_merge_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts, l.state,
+                                   l.counters, l.max_bodies, p, sa, l.report, ma);
+    });
 }
 
 // ---- per-body radii (include/nbody_batch_radii.h): a pair collides when it is within the sum of its own two radii.
@@ -1753,110 +1742,36 @@ __global__ __launch_bounds__(1024) void batch_hermite_radii_kernel(float4 *pos, 
         radii_stop_report(sh, pos, n, lane, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x], cold_best, cold_escaper);
 }
 
-template <int RPL, bool GUARD>
-hipError_t launch_radii_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                            float4 *jerk, int *counts, BatchEvolveState *state, int *counters, int max_bodies,
-                            const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report, const BatchMergeArgs &ma,
-                            const BatchRadiiArgs &ra)
+hipError_t launch_batch_radii(const BatchLaunch &l, const BatchEvolveArgs &p, const BatchStopArgs &sa, const BatchMergeArgs &ma,
+                              const BatchRadiiArgs &ra)
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_radii_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_radii_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
-                       counters, max_bodies, p, sa, report, ma, ra);
-    return hipGetLastError();
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_radii_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts, l.state,
+                                   l.counters, l.max_bodies, p, sa, l.report, ma, ra);
+    });
 }
 
-hipError_t launch_batch_radii(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, int *counts, BatchEvolveState *state,
-                              int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
-                              BatchStopReport *report, const BatchMergeArgs &ma, const BatchRadiiArgs &ra, hipStream_t stream)
+// BatchKernel::stop: batch_hermite_stop_kernel; BatchKernel::adaptive, no stopping conditions: batch_hermite_adaptive_kernel
+hipError_t launch_batch_adaptive(const BatchLaunch &l, const BatchEvolveArgs &p, const BatchStopArgs &sa)
 {
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(p.eps2 > 0.f);
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_radii_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    case 3: return launch_radii_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    case 4: return launch_radii_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    case 5: return launch_radii_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    case 8: return launch_radii_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    default: return launch_radii_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report, ma, ra);
-    }
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        if (l.choice.kernel == BatchKernel::stop)
+            return launch_batch_kernel(batch_hermite_stop_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts,
+                                       l.state, l.counters, l.max_bodies, p, sa, l.report);
+        return launch_batch_kernel(batch_hermite_adaptive_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts,
+                                   l.state, l.counters, l.max_bodies, p);
+    });
 }
 
-// report == nullptr: no stopping conditions, batch_hermite_adaptive_kernel
-template <int RPL, bool GUARD>
-hipError_t launch_adaptive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                               float4 *jerk, const int *counts, BatchEvolveState *state, int *counters, int max_bodies,
-                               const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report)
+hipError_t launch_batch_step(const BatchLaunch &l, bool kdk, int k, float dt, float eps2, int have_acc)
 {
-    if (report) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_stop_kernel<RPL, GUARD>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL((batch_hermite_stop_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
-                           counters, max_bodies, p, sa, report);
-        return hipGetLastError();
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_adaptive_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_adaptive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, state,
-                       counters, max_bodies, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_adaptive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, BatchEvolveState *state,
-                                 int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa,
-                                 BatchStopReport *report, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(p.eps2 > 0.f);
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_adaptive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    case 3: return launch_adaptive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    case 4: return launch_adaptive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    case 5: return launch_adaptive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    case 8: return launch_adaptive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    default: return launch_adaptive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, state, counters, max_bodies, p, sa, report);
-    }
-}
-
-template <int RPL, bool GUARD>
-void launch_step_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                     const int *counts, int max_bodies, int k, float dt, float eps2, int have_acc)
-{
-    if (kdk)
-        hipLaunchKernelGGL((batch_step_kernel<RPL, GUARD, true>), grid, block, lds, stream, pos, vel, acc, counts, max_bodies,
-                           k, dt, eps2, have_acc);
-    else
-        hipLaunchKernelGGL((batch_step_kernel<RPL, GUARD, false>), grid, block, lds, stream, pos, vel, acc, counts, max_bodies,
-                           k, dt, eps2, have_acc);
-}
-
-hipError_t launch_batch_step(float4 *pos, float4 *vel, float4 *acc, const int *counts, int n_systems, int max_bodies, int k,
-                             float dt, float eps2, bool kdk, bool have_acc, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(eps2 > 0.f);
-    const int ha = have_acc ? 1 : 0;
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: launch_step_rpl<1, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    case 3: launch_step_rpl<1, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    case 4: launch_step_rpl<2, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    case 5: launch_step_rpl<2, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    case 8: launch_step_rpl<4, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    default: launch_step_rpl<4, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, max_bodies, k, dt, eps2, ha); break;
-    }
-    return hipGetLastError();
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        if (kdk)
+            return launch_batch_kernel(batch_step_kernel<rpl(), guard(), true>, l, l.pos, l.vel, l.acc, l.counts, l.max_bodies, k,
+                                       dt, eps2, have_acc);
+        return launch_batch_kernel(batch_step_kernel<rpl(), guard(), false>, l, l.pos, l.vel, l.acc, l.counts, l.max_bodies, k,
+                                   dt, eps2, have_acc);
+    });
 }
 
 // ---- test particles (include/nbody_batch_massive.h): the first m = min(massive[s], n) bodies of system s are massive, the
@@ -2254,101 +2169,31 @@ __global__ __launch_bounds__(1024) void batch_hermite_adaptive_massive_kernel(fl
     }
 }
 
-template <int RPL, bool GUARD>
-void launch_step_massive_rpl(bool kdk, dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel,
-                             float4 *acc, const int *counts, const int *massive, int max_bodies, int k, float dt, float eps2,
-                             int have_acc)
+hipError_t launch_batch_step_massive(const BatchLaunch &l, bool kdk, int k, float dt, float eps2, int have_acc)
 {
-    if (kdk)
-        hipLaunchKernelGGL((batch_step_massive_kernel<RPL, GUARD, true>), grid, block, lds, stream, pos, vel, acc, counts,
-                           massive, max_bodies, k, dt, eps2, have_acc);
-    else
-        hipLaunchKernelGGL((batch_step_massive_kernel<RPL, GUARD, false>), grid, block, lds, stream, pos, vel, acc, counts,
-                           massive, max_bodies, k, dt, eps2, have_acc);
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        if (kdk)
+            return launch_batch_kernel(batch_step_massive_kernel<rpl(), guard(), true>, l, l.pos, l.vel, l.acc, l.counts,
+                                       l.massive, l.max_bodies, k, dt, eps2, have_acc);
+        return launch_batch_kernel(batch_step_massive_kernel<rpl(), guard(), false>, l, l.pos, l.vel, l.acc, l.counts, l.massive,
+                                   l.max_bodies, k, dt, eps2, have_acc);
+    });
 }
 
-hipError_t launch_batch_step_massive(float4 *pos, float4 *vel, float4 *acc, const int *counts, const int *massive, int n_systems,
-                                     int max_bodies, int k, float dt, float eps2, bool kdk, bool have_acc, hipStream_t stream)
+hipError_t launch_batch_hermite_massive(const BatchLaunch &l, int k, float dt, float eps2, int have_acc)
 {
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(eps2 > 0.f);
-    const int ha = have_acc ? 1 : 0;
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: launch_step_massive_rpl<1, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    case 3: launch_step_massive_rpl<1, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    case 4: launch_step_massive_rpl<2, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    case 5: launch_step_massive_rpl<2, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    case 8: launch_step_massive_rpl<4, false>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    default: launch_step_massive_rpl<4, true>(kdk, grid, block, lds, stream, pos, vel, acc, counts, massive, max_bodies, k, dt, eps2, ha); break;
-    }
-    return hipGetLastError();
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_massive_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts,
+                                   l.massive, l.max_bodies, k, dt, eps2, have_acc);
+    });
 }
 
-template <int RPL, bool GUARD>
-hipError_t launch_hermite_massive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                                      float4 *jerk, const int *counts, const int *massive, int max_bodies, int k, float dt,
-                                      float eps2, int have_acc)
+hipError_t launch_batch_adaptive_massive(const BatchLaunch &l, const BatchEvolveArgs &p)
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_massive_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_massive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, massive,
-                       max_bodies, k, dt, eps2, have_acc);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_hermite_massive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
-                                        int n_systems, int max_bodies, int k, float dt, float eps2, bool have_acc,
-                                        hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(eps2 > 0.f);
-    const int ha = have_acc ? 1 : 0;
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_hermite_massive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    case 3: return launch_hermite_massive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    case 4: return launch_hermite_massive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    case 5: return launch_hermite_massive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    case 8: return launch_hermite_massive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    default: return launch_hermite_massive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, max_bodies, k, dt, eps2, ha);
-    }
-}
-
-template <int RPL, bool GUARD>
-hipError_t launch_adaptive_massive_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                                       float4 *jerk, const int *counts, const int *massive, BatchEvolveState *state, int *counters,
-                                       int max_bodies, const BatchEvolveArgs &p)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_adaptive_massive_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_adaptive_massive_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts,
-                       massive, state, counters, max_bodies, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_adaptive_massive(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
-                                         BatchEvolveState *state, int *counters, int n_systems, int max_bodies,
-                                         const BatchEvolveArgs &p, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(p.eps2 > 0.f);
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_adaptive_massive_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    case 3: return launch_adaptive_massive_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    case 4: return launch_adaptive_massive_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    case 5: return launch_adaptive_massive_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    case 8: return launch_adaptive_massive_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    default: return launch_adaptive_massive_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p);
-    }
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_adaptive_massive_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk,
+                                   l.counts, l.massive, l.state, l.counters, l.max_bodies, p);
+    });
 }
 
 // ---- tracer fates (include/nbody_batch_fate.h): massive counts together with a collision radius, radii or an escape radius.
@@ -2693,37 +2538,12 @@ __global__ __launch_bounds__(1024) void batch_hermite_fate_kernel(float4 *pos, f
         radii_stop_report(sh, pos, m, lane, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x], cold_best, cold_escaper);
 }
 
-template <int RPL, bool GUARD>
-hipError_t launch_fate_rpl(dim3 grid, dim3 block, size_t lds, hipStream_t stream, float4 *pos, float4 *vel, float4 *acc,
-                           float4 *jerk, const int *counts, const int *massive, BatchEvolveState *state, int *counters,
-                           int max_bodies, const BatchEvolveArgs &p, const BatchStopArgs &sa, BatchStopReport *report,
-                           const BatchFateArgs &fa)
+hipError_t launch_batch_fate(const BatchLaunch &l, const BatchEvolveArgs &p, const BatchStopArgs &sa, const BatchFateArgs &fa)
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_hermite_fate_kernel<RPL, GUARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((batch_hermite_fate_kernel<RPL, GUARD>), grid, block, lds, stream, pos, vel, acc, jerk, counts, massive,
-                       state, counters, max_bodies, p, sa, report, fa);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_fate(float4 *pos, float4 *vel, float4 *acc, float4 *jerk, const int *counts, const int *massive,
-                             BatchEvolveState *state, int *counters, int n_systems, int max_bodies, const BatchEvolveArgs &p,
-                             const BatchStopArgs &sa, BatchStopReport *report, const BatchFateArgs &fa, hipStream_t stream)
-{
-    const BatchShape sh = batch_shape(max_bodies);
-    const dim3 grid(n_systems), block(sh.threads);
-    const size_t lds = 2 * sizeof(float4) * (size_t)max_bodies;
-    const bool guard = !(p.eps2 > 0.f);
-    switch (sh.rpl * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_fate_rpl<1, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    case 3: return launch_fate_rpl<1, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    case 4: return launch_fate_rpl<2, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    case 5: return launch_fate_rpl<2, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    case 8: return launch_fate_rpl<4, false>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    default: return launch_fate_rpl<4, true>(grid, block, lds, stream, pos, vel, acc, jerk, counts, massive, state, counters, max_bodies, p, sa, report, fa);
-    }
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_fate_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts, l.massive,
+                                   l.state, l.counters, l.max_bodies, p, sa, l.report, fa);
+    });
 }
 
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
@@ -2810,7 +2630,9 @@ struct nbody_batch {
     int64_t n_systems = 0, max_bodies = 0;
     std::vector<int> counts;      // host copy of the per-system body counts
     int *counts_dev = nullptr;    // [n_systems]
-    int integrator = NBODY_INTEGRATOR_KICK_DRIFT;
+    // what picks the kernels (nbody_batch_choice.h): the integrator, whether massive counts and radii are set, the stopping
+    // conditions, the collision action and the tracer action, each written by its setter
+    BatchConfig config;
     float4 *acc = nullptr;        // KDK, Hermite: [n_systems][max_bodies] accelerations at the current state (slots < n_b)
     float4 *jerk = nullptr;       // Hermite: [n_systems][max_bodies] jerks at the current state, allocated on first use
     bool acc_valid = false;
@@ -2827,28 +2649,22 @@ struct nbody_batch {
     int level_levels = 0;
     bool evolve_pending = false;               // the last call ran out of steps: systems sit at different ticks
     int evolve_launch_steps = kBatchStepsPerLaunch;
-    // nbody_batch_stop_set: the conditions, and the per-system reports beside evolve_state
-    float stop_collision_radius = 0.f, stop_escape_radius = 0.f;  // both 0: off
+    // nbody_batch_stop_set: the per-system reports beside evolve_state
     BatchStopReport *stop_report = nullptr;    // [n_systems], allocated by the first evolve with conditions
     bool stop_forgotten = true;                // the reports count as all zero: cleared before the next launch reads them
-    // nbody_batch_merge_set: the collision action, and the per-system merger counts and logs beside the reports (forgotten
-    // with them)
-    int merge_action = NBODY_BATCH_ON_COLLISION_STOP;
+    // nbody_batch_merge_set: the per-system merger counts and logs beside the reports (forgotten with them)
     int merge_capacity = 0;
     int *merge_count = nullptr;                     // [n_systems], allocated by the first evolve that merges
     nbody_batch_merge_event *merge_log = nullptr;   // [n_systems][merge_capacity]
     // nbody_batch_radii_set: one radius per slot, laid out like the positions; a property of the slots, which only
     // nbody_batch_radii_set and the mergers change
     float *radii = nullptr;       // [n_systems][max_bodies], allocated by the first nbody_batch_radii_set
-    bool radii_set = false;
     // nbody_batch_massive_set: per system the number of leading bodies that exert forces; a property of the handle, which only
     // nbody_batch_massive_set changes
-    std::vector<int> massive;     // host copy, [n_systems] while massive_set
+    std::vector<int> massive;     // host copy, [n_systems] while config.massive_set
     int *massive_dev = nullptr;   // [n_systems], allocated by the first nbody_batch_massive_set
-    bool massive_set = false;
-    // nbody_batch_fate_set: what becomes of a test particle that meets a condition, and the per-body fates beside the
-    // reports (forgotten with them), laid out like the positions and allocated by the first REMOVE
-    int tracer_action = NBODY_BATCH_TRACERS_REFUSE;
+    // nbody_batch_fate_set: the per-body fates beside the reports (forgotten with them), laid out like the positions and
+    // allocated by the first REMOVE
     BatchFate *fates = nullptr;   // [n_systems][max_bodies]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
@@ -2883,10 +2699,122 @@ static int bfail(nbody_batch *b, int status, const std::string &msg)
                          std::string(#call) + ": " + hipGetErrorString(e_));                               \
     } while (0)
 
-// nbody_step's rule: finite, and 0 or at least NBODY_MIN_SOFTENING
-static bool softening_ok(float softening)
+// nbody_batch_evolve_on's buffers: the caches and the per-system state, and what the mode keeps beside them -- merger counts and
+// logs, stop reports, fates -- allocated on first use and zeroed where the stops count as forgotten.
+static int evolve_prepare_buffers(nbody_batch *b, const BatchMode &mode)
 {
-    return std::isfinite(softening) && softening >= 0.f && !(softening > 0.f && softening < NBODY_MIN_SOFTENING);
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    if (!b->acc)
+        BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
+    if (!b->jerk)
+        BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
+    if (!b->evolve_state) {
+        BATCH_TRY(b, hipMalloc((void **)&b->evolve_state, sizeof(BatchEvolveState) * B));
+        BATCH_TRY(b, hipMemsetAsync(b->evolve_state, 0, sizeof(BatchEvolveState) * B, b->stream));
+    }
+    if (!b->evolve_counters)
+        BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
+    if (mode.merging) {  // nbody_batch_merge.h: counts and logs that start from zero where the reports do
+        if (!b->merge_count) {
+            BATCH_TRY(b, hipMalloc((void **)&b->merge_count, sizeof(int) * B));
+            b->stop_forgotten = true;
+        }
+        if (b->merge_capacity > 0 && !b->merge_log) {
+            BATCH_TRY(b, hipMalloc((void **)&b->merge_log, sizeof(nbody_batch_merge_event) * B * (size_t)b->merge_capacity));
+            b->stop_forgotten = true;
+        }
+        if (b->stop_forgotten)
+            BATCH_TRY(b, hipMemsetAsync(b->merge_count, 0, sizeof(int) * B, b->stream));
+    }
+    if (mode.stopping) {  // nbody_batch_stop.h: reports that start from zero
+        if (!b->stop_report) {
+            BATCH_TRY(b, hipMalloc((void **)&b->stop_report, sizeof(BatchStopReport) * B));
+            b->stop_forgotten = true;
+        }
+        if (b->stop_forgotten)
+            BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
+        if (b->stop_forgotten && mode.fates)  // nbody_batch_fate.h: the fates are forgotten where the stops are
+            BATCH_TRY(b, hipMemsetAsync(b->fates, 0, sizeof(BatchFate) * slots, b->stream));
+        b->stop_forgotten = false;
+    }
+    return NBODY_OK;
+}
+
+// What one nbody_batch_evolve_on call hands its kernel; p's have_acc, have_level, new_call and reset_tick change per launch.
+struct BatchEvolveLaunch {
+    BatchEvolveArgs p;
+    BatchStopArgs sa;
+    BatchMergeArgs ma;
+    BatchRadiiArgs ra;
+    BatchFateArgs fa;
+};
+
+// The arguments from the handle's settings and the call's (after evolve_prepare_buffers: they carry its pointers).
+static BatchEvolveLaunch evolve_launch_args(const nbody_batch *b, const BatchMode &mode, const nbody_batch_evolve_config *cfg,
+                                            int64_t target, int64_t max_steps)
+{
+    const BatchConfig &c = b->config;
+    BatchEvolveLaunch a;
+    BatchEvolveArgs &p = a.p;
+    p.dt = (double)cfg->dt_max;
+    p.dt_half = 0.5 * p.dt;
+    p.dt_six = 6.0 * p.dt;
+    p.dt_third = p.dt / 3.0;
+    p.dt_sixth = p.dt / 6.0;
+    p.dt2 = p.dt * p.dt;
+    p.inv_dt2 = 1.0 / (p.dt * p.dt);
+    p.inv_dt3 = 1.0 / (p.dt * p.dt * p.dt);
+    p.eta = (double)cfg->eta;
+    p.eta_start2 = (double)cfg->eta_start * (double)cfg->eta_start;
+    p.target = target;
+    p.max_steps = max_steps;
+    p.eps2 = cfg->softening * cfg->softening;
+    p.levels = cfg->levels;
+    p.budget = b->evolve_launch_steps;
+    // stopping conditions (nbody_batch_stop.h): the thresholds in fp32; radii (nbody_batch_radii.h) watch collisions without one
+    a.sa = BatchStopArgs{-1.f, __builtin_inff()};
+    if (c.collision_radius > 0.f)
+        a.sa.thr = std::fmaf(c.collision_radius, c.collision_radius, cfg->softening * cfg->softening);
+    if (c.escape_radius > 0.f)
+        a.sa.re2 = c.escape_radius * c.escape_radius;
+    a.ma = BatchMergeArgs{b->merge_count, b->merge_log, b->merge_capacity};
+    a.ra = BatchRadiiArgs{b->radii, mode.merging ? 1 : 0};
+    a.fa = BatchFateArgs{c.radii_set ? b->radii : nullptr, 0.5f * c.collision_radius, mode.collisions ? 1 : 0, b->fates};
+    return a;
+}
+
+// What every launch of a call on these buffers shares.
+static BatchLaunch batch_launch(const nbody_batch *b, const BatchChoice &choice, float *d_pos, float *d_vel)
+{
+    return BatchLaunch{choice, (int)b->n_systems, (int)b->max_bodies, b->stream, reinterpret_cast<float4 *>(d_pos),
+                       reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk, b->counts_dev, b->massive_dev, b->evolve_state,
+                       b->evolve_counters, b->stop_report};
+}
+
+// One launch of nbody_batch_evolve_on by the chosen family.
+static hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLaunch &a)
+{
+    switch (l.choice.kernel) {
+    case BatchKernel::fate: return launch_batch_fate(l, a.p, a.sa, a.fa);
+    case BatchKernel::radii: return launch_batch_radii(l, a.p, a.sa, a.ma, a.ra);
+    case BatchKernel::adaptive_massive: return launch_batch_adaptive_massive(l, a.p);
+    case BatchKernel::merge: return launch_batch_merge(l, a.p, a.sa, a.ma);
+    case BatchKernel::stop:
+    case BatchKernel::adaptive: return launch_batch_adaptive(l, a.p, a.sa);
+    default: return hipErrorInvalidValue;  // a fixed-step family: batch_evolve_choice names none
+    }
+}
+
+// One launch of nbody_batch_step_n_async by the chosen family: `run` steps of every system.  Kick-drift keeps no accelerations.
+static hipError_t launch_batch_steps(const BatchLaunch &l, bool kdk, int run, float dt, float eps2, bool acc_valid)
+{
+    switch (l.choice.kernel) {
+    case BatchKernel::hermite_massive: return launch_batch_hermite_massive(l, run, dt, eps2, acc_valid ? 1 : 0);
+    case BatchKernel::hermite: return launch_batch_hermite(l, run, dt, eps2, acc_valid ? 1 : 0);
+    case BatchKernel::step_massive: return launch_batch_step_massive(l, kdk, run, dt, eps2, kdk && acc_valid ? 1 : 0);
+    case BatchKernel::step: return launch_batch_step(l, kdk, run, dt, eps2, kdk && acc_valid ? 1 : 0);
+    default: return hipErrorInvalidValue;  // an evolve family: batch_step_choice names none
+    }
 }
 
 extern "C" {
@@ -2992,9 +2920,9 @@ int nbody_batch_set_integrator(nbody_batch *b, int integrator)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_integrator: batch is NULL");
     if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK && integrator != NBODY_INTEGRATOR_HERMITE)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator (KICK_DRIFT = 0, KDK = 1, HERMITE = 2)");
-    if (integrator != b->integrator)
+    if (integrator != b->config.integrator)
         forget_caches(b);
-    b->integrator = integrator;
+    b->config.integrator = integrator;
     return NBODY_OK;
 }
 
@@ -3024,18 +2952,18 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: k < 0");
     if (!std::isfinite(dt))
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: dt must be finite");
-    if (!softening_ok(softening))
+    if (!batch_softening_ok(softening))
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
                                            "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
     if (k == 0)
         return NBODY_OK;
-    if (b->evolve_pending && b->acc_valid && b->integrator == NBODY_INTEGRATOR_HERMITE)
+    if (b->evolve_pending && b->acc_valid && b->config.integrator == NBODY_INTEGRATOR_HERMITE)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_step_n: the last nbody_batch_evolve_on ran out of steps and its systems sit at "
                                          "different times: complete it, or nbody_batch_invalidate_forces to drop it");
     b->level_valid = false;  // fixed steps leave the levels behind, and the stops
     b->stop_forgotten = true;
     BATCH_TRY(b, hipSetDevice(b->device));
-    const bool kdk = b->integrator == NBODY_INTEGRATOR_KDK, hermite = b->integrator == NBODY_INTEGRATOR_HERMITE;
+    const bool kdk = b->config.integrator == NBODY_INTEGRATOR_KDK, hermite = b->config.integrator == NBODY_INTEGRATOR_HERMITE;
     const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
     if (kdk || hermite) {
         if (!b->acc)
@@ -3043,27 +2971,16 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
         if (hermite && !b->jerk)
             BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
         // KDK's accelerations come without jerks: a cache is used only by the integrator that filled it
-        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening || b->acc_integrator != b->integrator)
+        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening || b->acc_integrator != b->config.integrator)
             b->acc_valid = false;
     }
+    const BatchLaunch launch = batch_launch(b, batch_step_choice(b->config, (int)b->max_bodies, softening), d_pos, d_vel);
     const float eps2 = softening * softening;
     for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
         const int run = std::min(kBatchStepsPerLaunch, k - done);
-        float4 *pos = reinterpret_cast<float4 *>(d_pos), *vel = reinterpret_cast<float4 *>(d_vel);
-        if (hermite && b->massive_set)  // test particles (nbody_batch_massive.h): the siblings whose column loop ends early
-            BATCH_TRY(b, launch_batch_hermite_massive(pos, vel, b->acc, b->jerk, b->counts_dev, b->massive_dev, (int)b->n_systems,
-                                                      (int)b->max_bodies, run, dt, eps2, b->acc_valid, b->stream));
-        else if (hermite)
-            BATCH_TRY(b, launch_batch_hermite(pos, vel, b->acc, b->jerk, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run,
-                                              dt, eps2, b->acc_valid, b->stream));
-        else if (b->massive_set)
-            BATCH_TRY(b, launch_batch_step_massive(pos, vel, b->acc, b->counts_dev, b->massive_dev, (int)b->n_systems,
-                                                   (int)b->max_bodies, run, dt, eps2, kdk, kdk && b->acc_valid, b->stream));
-        else
-            BATCH_TRY(b, launch_batch_step(pos, vel, b->acc, b->counts_dev, (int)b->n_systems, (int)b->max_bodies, run, dt, eps2,
-                                           kdk, kdk && b->acc_valid, b->stream));
+        BATCH_TRY(b, launch_batch_steps(launch, kdk, run, dt, eps2, b->acc_valid));
         if (kdk || hermite) {
-            b->acc_integrator = b->integrator;
+            b->acc_integrator = b->config.integrator;
             b->acc_valid = true;
             b->acc_pos = d_pos;
             b->acc_vel = d_vel;
@@ -3105,37 +3022,15 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve: batch is NULL");
     if (!d_pos || !d_vel || !cfg)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: NULL argument");
-    if (b->integrator != NBODY_INTEGRATOR_HERMITE)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: adaptive steps need NBODY_INTEGRATOR_HERMITE "
-                                           "(nbody_batch_set_integrator): the criterion uses its accelerations and jerks");
-    if (b->radii_set && b->stop_collision_radius > 0.f)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: radii and collision_radius are both set (nbody_batch_radii.h: radii "
-                                           "replace the collision radius)");
-    // tracer fates (nbody_batch_fate.h): with REMOVE massive counts go together with the conditions, through a kernel of their own
-    const bool fates = b->massive_set && b->tracer_action == NBODY_BATCH_TRACERS_REMOVE &&
-                       (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set);
-    if (fates && b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || b->radii_set))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: the collision action MERGE together with massive counts "
-                                           "(nbody_batch_fate.h: mergers among massive bodies while massive counts are set are "
-                                           "not supported); nbody_batch_merge_set(b, NULL) or nbody_batch_massive_set(b, NULL)");
-    if (!fates && b->massive_set && (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: massive counts are set together with a stopping condition or radii "
-                                           "(nbody_batch_massive.h: not supported, the collision test counts on a row's own column); "
-                                           "nbody_batch_massive_set(b, NULL) or switch the conditions off");
-    if (cfg->levels < 0 || cfg->levels > NBODY_BATCH_EVOLVE_MAX_LEVELS)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: levels outside [0, NBODY_BATCH_EVOLVE_MAX_LEVELS = 20]");
-    if (n_intervals < 0 || n_intervals >= ((int64_t)1 << (62 - cfg->levels)))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: n_intervals < 0 or n_intervals x 2^levels >= 2^62");
-    if (!std::isfinite(cfg->dt_max) || !(cfg->dt_max > 0.f))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: dt_max must be finite and positive");
-    if (!std::isfinite(cfg->eta) || !(cfg->eta > 0.f) || !std::isfinite(cfg->eta_start) || !(cfg->eta_start > 0.f))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: eta and eta_start must be finite and positive");
-    if (!softening_ok(cfg->softening))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
-                                           "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
+    const BatchMode mode = batch_mode(b->config);
+    const BatchChoice choice = batch_evolve_choice(b->config, (int)b->max_bodies, cfg->softening);
+    if (choice.refusal != BatchRefusal::none)
+        return bfail(b, batch_refusal_status(choice.refusal), batch_refusal_message(choice.refusal));
+    if (const char *msg = batch_evolve_args_error(cfg->levels, n_intervals, cfg->dt_max, cfg->eta, cfg->eta_start, cfg->softening))
+        return bfail(b, NBODY_ERR_INVALID, msg);
     const int64_t max_steps = cfg->max_steps > 0 ? cfg->max_steps : NBODY_BATCH_EVOLVE_DEFAULT_MAX_STEPS;
     const int64_t target = n_intervals << cfg->levels;
-    if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != cfg->softening || b->acc_integrator != b->integrator)
+    if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != cfg->softening || b->acc_integrator != b->config.integrator)
         b->acc_valid = false;
     if (!b->acc_valid) {
         b->level_valid = b->evolve_pending = false;
@@ -3162,70 +3057,11 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
     if (target == 0)
         return NBODY_OK;
     BATCH_TRY(b, hipSetDevice(b->device));
-    const size_t slots = B * (size_t)b->max_bodies;
-    if (!b->acc)
-        BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
-    if (!b->jerk)
-        BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
-    if (!b->evolve_state) {
-        BATCH_TRY(b, hipMalloc((void **)&b->evolve_state, sizeof(BatchEvolveState) * B));
-        BATCH_TRY(b, hipMemsetAsync(b->evolve_state, 0, sizeof(BatchEvolveState) * B, b->stream));
-    }
-    if (!b->evolve_counters)
-        BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
-    // stopping conditions (nbody_batch_stop.h): the thresholds in fp32, and reports that start from zero
-    // radii (nbody_batch_radii.h) watch collisions without a collision radius, through a kernel of their own
-    const bool radii = b->radii_set;
-    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || radii;
-    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || radii);
-    BatchStopArgs sa{-1.f, __builtin_inff()};
-    if (merging) {  // nbody_batch_merge.h: counts and logs that start from zero where the reports do
-        if (!b->merge_count) {
-            BATCH_TRY(b, hipMalloc((void **)&b->merge_count, sizeof(int) * B));
-            b->stop_forgotten = true;
-        }
-        if (b->merge_capacity > 0 && !b->merge_log) {
-            BATCH_TRY(b, hipMalloc((void **)&b->merge_log, sizeof(nbody_batch_merge_event) * B * (size_t)b->merge_capacity));
-            b->stop_forgotten = true;
-        }
-        if (b->stop_forgotten)
-            BATCH_TRY(b, hipMemsetAsync(b->merge_count, 0, sizeof(int) * B, b->stream));
-    }
-    const BatchMergeArgs ma{b->merge_count, b->merge_log, b->merge_capacity};
-    const BatchRadiiArgs ra{b->radii, merging ? 1 : 0};
-    if (stopping) {
-        if (b->stop_collision_radius > 0.f)
-            sa.thr = std::fmaf(b->stop_collision_radius, b->stop_collision_radius, cfg->softening * cfg->softening);
-        if (b->stop_escape_radius > 0.f)
-            sa.re2 = b->stop_escape_radius * b->stop_escape_radius;
-        if (!b->stop_report) {
-            BATCH_TRY(b, hipMalloc((void **)&b->stop_report, sizeof(BatchStopReport) * B));
-            b->stop_forgotten = true;
-        }
-        if (b->stop_forgotten)
-            BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
-        if (b->stop_forgotten && fates)  // nbody_batch_fate.h: the fates are forgotten where the stops are
-            BATCH_TRY(b, hipMemsetAsync(b->fates, 0, sizeof(BatchFate) * slots, b->stream));
-        b->stop_forgotten = false;
-    }
-    const BatchFateArgs fa{radii ? b->radii : nullptr, 0.5f * b->stop_collision_radius,
-                           radii || b->stop_collision_radius > 0.f ? 1 : 0, b->fates};
-    BatchEvolveArgs p;
-    p.dt = (double)cfg->dt_max;
-    p.dt_half = 0.5 * p.dt;
-    p.dt_six = 6.0 * p.dt;
-    p.dt_third = p.dt / 3.0;
-    p.dt_sixth = p.dt / 6.0;
-    p.dt2 = p.dt * p.dt;
-    p.inv_dt2 = 1.0 / (p.dt * p.dt);
-    p.inv_dt3 = 1.0 / (p.dt * p.dt * p.dt);
-    p.eta = (double)cfg->eta;
-    p.eta_start2 = (double)cfg->eta_start * (double)cfg->eta_start;
-    p.target = target;
-    p.max_steps = max_steps;
-    p.eps2 = cfg->softening * cfg->softening;
-    p.levels = cfg->levels;
-    p.budget = b->evolve_launch_steps;
+    if (const int rc = evolve_prepare_buffers(b, mode); rc != NBODY_OK)
+        return rc;
+    const BatchLaunch launch = batch_launch(b, choice, d_pos, d_vel);
+    BatchEvolveLaunch args = evolve_launch_args(b, mode, cfg, target, max_steps);
+    BatchEvolveArgs &p = args.p;
     int counters[2] = {0, 0};
     for (bool first = true;; first = false) {
         p.have_acc = b->acc_valid ? 1 : 0;
@@ -3233,27 +3069,8 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         p.new_call = first ? 1 : 0;
         p.reset_tick = first && !resume ? 1 : 0;
         BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
-        if (fates)
-            BATCH_TRY(b, launch_batch_fate(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
-                                           b->counts_dev, b->massive_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems,
-                                           (int)b->max_bodies, p, sa, b->stop_report, fa, b->stream));
-        else if (radii)
-            BATCH_TRY(b, launch_batch_radii(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
-                                            b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
-                                            p, sa, b->stop_report, ma, ra, b->stream));
-        else if (b->massive_set)  // never with stopping conditions: refused above, or the fate kernel's
-            BATCH_TRY(b, launch_batch_adaptive_massive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc,
-                                                       b->jerk, b->counts_dev, b->massive_dev, b->evolve_state, b->evolve_counters,
-                                                       (int)b->n_systems, (int)b->max_bodies, p, b->stream));
-        else if (merging)
-            BATCH_TRY(b, launch_batch_merge(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
-                                            b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
-                                            p, sa, b->stop_report, ma, b->stream));
-        else
-            BATCH_TRY(b, launch_batch_adaptive(reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk,
-                                               b->counts_dev, b->evolve_state, b->evolve_counters, (int)b->n_systems, (int)b->max_bodies,
-                                               p, sa, stopping ? b->stop_report : nullptr, b->stream));
-        b->acc_integrator = b->integrator;
+        BATCH_TRY(b, launch_batch_evolve(launch, args));
+        b->acc_integrator = b->config.integrator;
         b->acc_valid = b->level_valid = true;
         b->acc_pos = d_pos;
         b->acc_vel = d_vel;
@@ -3266,7 +3083,7 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         if (counters[0] == 0 || counters[0] == counters[1])
             break;
     }
-    if (merging)  // the kernel's own changes of the counts; the caches stay: the restarts have refilled them
+    if (mode.merging)  // the kernel's own changes of the counts; the caches stay: the restarts have refilled them
         BATCH_TRY(b, hipMemcpyAsync(b->counts.data(), b->counts_dev, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
     BATCH_TRY(b, hipMemcpyAsync(b->evolve_host.data(), b->evolve_state, sizeof(BatchEvolveState) * B, hipMemcpyDeviceToHost, b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
@@ -3277,13 +3094,13 @@ int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_
         b->evolve_pending = false;
         return NBODY_OK;
     }
-    std::vector<BatchStopReport> stopped(stopping ? B : 0);  // a stopped system sits before the target too, finished
-    if (stopping) {
+    std::vector<BatchStopReport> stopped(mode.stopping ? B : 0);  // a stopped system sits before the target too, finished
+    if (mode.stopping) {
         BATCH_TRY(b, hipMemcpyAsync(stopped.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
         BATCH_TRY(b, hipStreamSynchronize(b->stream));
     }
     size_t first_unfinished = 0;
-    while (first_unfinished < B && (b->evolve_host[first_unfinished].tick >= target || (stopping && stopped[first_unfinished].reason)))
+    while (first_unfinished < B && (b->evolve_host[first_unfinished].tick >= target || (mode.stopping && stopped[first_unfinished].reason)))
         ++first_unfinished;
     return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: system " + std::to_string(first_unfinished) + " is unfinished after max_steps = " +
                                          std::to_string(max_steps) + " steps (tick " +
@@ -3316,8 +3133,8 @@ int nbody_batch_stop_set(nbody_batch *b, const nbody_batch_stop_config *cfg)
     const float rc = cfg ? cfg->collision_radius : 0.f, re = cfg ? cfg->escape_radius : 0.f;
     if (!std::isfinite(rc) || rc < 0.f || !std::isfinite(re) || re < 0.f)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_stop_set: collision_radius and escape_radius must be finite and >= 0 (0: off)");
-    b->stop_collision_radius = rc;
-    b->stop_escape_radius = re;
+    b->config.collision_radius = rc;
+    b->config.escape_radius = re;
     forget_caches(b);  // the next nbody_batch_evolve_on starts with an evaluation, which examines the conditions
     return NBODY_OK;
 }
@@ -3328,8 +3145,7 @@ int nbody_batch_stop_read(nbody_batch *b, int *reason, int64_t *tick, int *pair_
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_read: batch is NULL");
     const size_t B = (size_t)b->n_systems;
     std::vector<BatchStopReport> rep(B, BatchStopReport{0, 0, 0, 0, 0, 0.f, 0});
-    const bool stopping = b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set;
-    if (stopping && b->stop_report && !b->stop_forgotten) {
+    if (batch_mode(b->config).stopping && b->stop_report && !b->stop_forgotten) {
         BATCH_TRY(b, hipSetDevice(b->device));
         BATCH_TRY(b, hipMemcpyAsync(rep.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
         BATCH_TRY(b, hipStreamSynchronize(b->stream));
@@ -3377,7 +3193,7 @@ int nbody_batch_merge_set(nbody_batch *b, const nbody_batch_merge_config *cfg)
         BATCH_TRY(b, hipFree(b->merge_log));
         b->merge_log = nullptr;
     }
-    b->merge_action = action;
+    b->config.collision_action = action;
     b->merge_capacity = capacity;
     forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
     return NBODY_OK;
@@ -3389,8 +3205,7 @@ int nbody_batch_merge_read(nbody_batch *b, int64_t *n_merges, nbody_batch_merge_
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_read: batch is NULL");
     const size_t B = (size_t)b->n_systems, cap = (size_t)b->merge_capacity;
     std::vector<int> count(B, 0);
-    const bool merging = b->merge_action == NBODY_BATCH_ON_COLLISION_MERGE && (b->stop_collision_radius > 0.f || b->radii_set);
-    const bool kept = merging && b->merge_count && !b->stop_forgotten;
+    const bool kept = batch_mode(b->config).merging && b->merge_count && !b->stop_forgotten;
     if (events)
         std::memset(events, 0, sizeof(nbody_batch_merge_event) * B * cap);
     if (kept) {
@@ -3427,7 +3242,7 @@ int nbody_batch_radii_set(nbody_batch *b, const float *host_radii)
         BATCH_TRY(b, hipMemcpyAsync(b->radii, host_radii, sizeof(float) * slots, hipMemcpyHostToDevice, b->stream));
         BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the caller's array may change with the next call
     }
-    b->radii_set = host_radii != nullptr;
+    b->config.radii_set = host_radii != nullptr;
     forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
     return NBODY_OK;
 }
@@ -3438,7 +3253,7 @@ int nbody_batch_radii_read(nbody_batch *b, float *host_radii)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radii_read: batch is NULL");
     if (!host_radii)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radii_read: NULL argument");
-    if (!b->radii_set)
+    if (!b->config.radii_set)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_radii_read: no radii are set (nbody_batch_radii_set)");
     BATCH_TRY(b, hipSetDevice(b->device));
     BATCH_TRY(b, hipMemcpyAsync(host_radii, b->radii, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies,
@@ -3466,7 +3281,7 @@ int nbody_batch_massive_set(nbody_batch *b, const int64_t *host_massive)
         BATCH_TRY(b, hipMemcpyAsync(b->massive_dev, b->massive.data(), sizeof(int) * b->massive.size(), hipMemcpyHostToDevice, b->stream));
         BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
     }
-    b->massive_set = host_massive != nullptr;
+    b->config.massive_set = host_massive != nullptr;
     forget_caches(b);  // as nbody_batch_set_counts: the cached accelerations and jerks belong to the old columns
     return NBODY_OK;
 }
@@ -3477,7 +3292,7 @@ int nbody_batch_massive_read(nbody_batch *b, int64_t *host_massive)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_massive_read: batch is NULL");
     if (!host_massive)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_massive_read: NULL argument");
-    if (!b->massive_set)
+    if (!b->config.massive_set)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_massive_read: no massive counts are set (nbody_batch_massive_set)");
     for (size_t s = 0; s < (size_t)b->n_systems; ++s)
         host_massive[s] = b->massive[s];
@@ -3495,23 +3310,23 @@ int nbody_batch_fate_set(nbody_batch *b, const nbody_batch_fate_config *cfg)
         BATCH_TRY(b, hipSetDevice(b->device));
         BATCH_TRY(b, hipMalloc((void **)&b->fates, sizeof(BatchFate) * (size_t)b->n_systems * (size_t)b->max_bodies));
     }
-    b->tracer_action = action;
+    b->config.tracer_action = action;
     forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
     return NBODY_OK;
 }
 
-// Whether the fate arrays hold what the last nbody_batch_evolve_on calls found (otherwise every body reads alive).
+// Whether the fate arrays hold what the last nbody_batch_evolve_on calls found (otherwise every body reads alive).  Asked under
+// the tracer action REMOVE only: nbody_batch_fate_read refuses REFUSE first.
 static bool fates_kept(const nbody_batch *b)
 {
-    return b->massive_set && b->fates && !b->stop_forgotten &&
-           (b->stop_collision_radius > 0.f || b->stop_escape_radius > 0.f || b->radii_set);
+    return batch_mode(b->config).fates && b->fates && !b->stop_forgotten;
 }
 
 int nbody_batch_fate_read(nbody_batch *b, int *fate, int64_t *tick, int *target, float *separation, float *relative_speed)
 {
     if (!b)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_read: batch is NULL");
-    if (b->tracer_action != NBODY_BATCH_TRACERS_REMOVE)
+    if (b->config.tracer_action != NBODY_BATCH_TRACERS_REMOVE)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_read: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
     const size_t B = (size_t)b->n_systems, cap = (size_t)b->max_bodies, slots = B * cap;
     std::vector<BatchFate> f(slots, BatchFate{0, 0, 0, 0.f, 0.f});
@@ -3537,7 +3352,7 @@ int nbody_batch_fate_count(nbody_batch *b, int64_t *hit, int64_t *escaped)
 {
     if (!b)
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_count: batch is NULL");
-    if (b->tracer_action != NBODY_BATCH_TRACERS_REMOVE)
+    if (b->config.tracer_action != NBODY_BATCH_TRACERS_REMOVE)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_count: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
     std::vector<int> fate((size_t)b->n_systems * (size_t)b->max_bodies);
     const int rc = nbody_batch_fate_read(b, fate.data(), nullptr, nullptr, nullptr, nullptr);
@@ -3583,7 +3398,7 @@ int nbody_batch_energy(nbody_batch *b, const float *d_pos, const float *d_vel, f
         return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_energy: batch is NULL");
     if (!d_pos || !d_vel || !out3B)
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: NULL argument");
-    if (!softening_ok(softening))
+    if (!batch_softening_ok(softening))
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
     const int rc = batch_diag(b, d_pos, d_vel, softening, true);
     if (rc != NBODY_OK)
