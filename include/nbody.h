@@ -529,6 +529,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_massive.h"
 /* tracer fates: with massive counts and conditions, a test particle that hits a massive body or escapes is removed */
 #include "nbody_batch_fate.h"
+/* accreting tracers: a test particle that hits a massive body gives it its mass word, and the body grows */
+#include "nbody_batch_accrete.h"
 
 #ifdef __cplusplus
 }

@@ -424,6 +424,26 @@ public:
         check(nbody_batch_fate_count(b_, f.hit.data(), f.escaped.data()), "nbody_batch_fate_count");
         return f;
     }
+    // Accreting tracers (nbody_batch_accrete.h): with accrete, a test particle that hits a massive body gives it its mass
+    // word -- the body grows, the tracer's mass word becomes 0 -- and the system is evaluated afresh and carries on.
+    // accretions(): given[s * maxBodies + i], the mass tracer i gave, and count[s]; throws while the action is remove.
+    struct Accretions {
+        std::vector<float> given;
+        std::vector<std::int64_t> count;
+    };
+    void setHitAction(bool accrete)
+    {
+        const nbody_batch_accrete_config cfg = {accrete ? NBODY_BATCH_ON_HIT_ACCRETE : NBODY_BATCH_ON_HIT_REMOVE};
+        check(nbody_batch_accrete_set(b_, &cfg), "nbody_batch_accrete_set");
+    }
+    Accretions accretions()
+    {
+        Accretions a;
+        a.given.resize((size_t)systems_ * (size_t)maxBodies_);
+        a.count.resize((size_t)systems_);
+        check(nbody_batch_accrete_read(b_, a.given.data(), a.count.data()), "nbody_batch_accrete_read");
+        return a;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

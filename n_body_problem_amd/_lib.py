@@ -223,6 +223,20 @@ BATCH_FATE_HIT = 1
 BATCH_FATE_ESCAPED = 2
 
 
+class BatchAccreteConfig(ctypes.Structure):
+    """``nbody_batch_accrete_config`` of include/nbody_batch_accrete.h."""
+    _fields_ = [("on_hit", c_int)]
+
+
+#: the entry points of include/nbody_batch_accrete.h (accreting tracers for Hermite batches), which nbody.h includes
+_ACCRETE_PROTOTYPES = {
+    "nbody_batch_accrete_set": (c_int, [c_void_p, POINTER(BatchAccreteConfig)]),
+    "nbody_batch_accrete_read": (c_int, [c_void_p, POINTER(c_float), POINTER(c_int64)]),
+}
+BATCH_ON_HIT_REMOVE = 0
+BATCH_ON_HIT_ACCRETE = 1
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -248,7 +262,8 @@ def load() -> ctypes.CDLL:
             pass
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
-                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()):
+                list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
+                list(_ACCRETE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -289,6 +304,11 @@ def massive_names():
 def fate_names():
     """The entry points of nbody_batch_fate.h."""
     return list(_FATE_PROTOTYPES)
+
+
+def accrete_names():
+    """The entry points of nbody_batch_accrete.h."""
+    return list(_ACCRETE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

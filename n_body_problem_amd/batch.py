@@ -22,6 +22,7 @@ BATCH_MAX_BODIES = 4096
 INTEGRATORS = {"kick_drift": 0, "kdk": 1, "hermite": 2}
 COLLISION_ACTIONS = {"stop": _lib.BATCH_ON_COLLISION_STOP, "merge": _lib.BATCH_ON_COLLISION_MERGE}
 TRACER_ACTIONS = {"refuse": _lib.BATCH_TRACERS_REFUSE, "remove": _lib.BATCH_TRACERS_REMOVE}
+HIT_ACTIONS = {"remove": _lib.BATCH_ON_HIT_REMOVE, "accrete": _lib.BATCH_ON_HIT_ACCRETE}
 #: one merger of the log: numpy's view of ``nbody_batch_merge_event``
 MERGE_EVENT_DTYPE = np.dtype([("tick", np.int64), ("survivor", np.int32), ("absorbed", np.int32), ("count_before", np.int32),
                               ("separation", np.float32), ("relative_speed", np.float32), ("mass_survivor", np.float32),
@@ -272,9 +273,10 @@ class BatchedSystem:
         a force from them, at ``n * m`` interactions per step instead of ``n * n``.  Their mass words
         ``positions[s, i, 3]`` are read by no force kernel and are preserved; :meth:`energy` and :meth:`momentum` keep
         reading them, so zero mass words give the massive bodies' energy.  The values belong to the handle:
-        :meth:`set_state` and :meth:`set_counts` leave them alone.  :meth:`evolve` refuses massive counts together with
-        stopping conditions or radii unless :meth:`set_tracer_action` opts in.  The length is checked here, the values by the library.  Forgets what
-        :meth:`set_counts` forgets: the cached accelerations and jerks, the levels and the stops."""
+        :meth:`set_state` and :meth:`set_counts` leave them alone.  With the default tracer action :meth:`evolve` refuses
+        massive counts together with stopping conditions or radii; :meth:`set_tracer_action` ``"remove"`` runs them, and
+        :meth:`set_hit_action` says what a hit does to the body hit.  The length is checked here, the values by the
+        library.  Forgets what :meth:`set_counts` forgets: the cached accelerations and jerks, the levels and the stops."""
         self._use_current_stream()
         if massive is None:
             _check(self._lib, self._lib.nbody_batch_massive_set(self._h, None), self._h)
@@ -324,6 +326,31 @@ class BatchedSystem:
                                                           speed.ctypes.data_as(f32)), self._h)
         _check(self._lib, self._lib.nbody_batch_fate_count(self._h, hit.ctypes.data_as(i64), escaped.ctypes.data_as(i64)), self._h)
         return FateResult(fate, ticks, target, sep, speed, hit, escaped)
+
+    def set_hit_action(self, action: str = "remove") -> None:
+        """What a test particle's hit does to the massive body it hits, where :meth:`set_tracer_action` ``"remove"`` acts and
+        collisions are watched (``include/nbody_batch_accrete.h`` states the rules): ``"remove"`` (the default) leaves the
+        body as it is; ``"accrete"`` merges the tracer's mass word ``positions[s, i, 3]`` into it -- the mass is the sum,
+        position and velocity the mass-weighted means, with radii the body's radius becomes ``cbrt(R_t**3 + R_i**3)`` --
+        zeroes the tracer's mass word, evaluates the system afresh and carries the run on; a tracer with a zero mass word
+        is removed as before.  Slots and counts do not change.  :meth:`accretions` tells what every tracer gave.  With an
+        escape radius alone or without massive counts ``"accrete"`` changes nothing.  Forgets stops, fates, accretions and
+        the cached accelerations and jerks, as :meth:`set_stop_conditions` does."""
+        if action not in HIT_ACTIONS:
+            raise ValueError(f"action must be one of {tuple(HIT_ACTIONS)}")
+        cfg = _lib.BatchAccreteConfig(HIT_ACTIONS[action])
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_accrete_set(self._h, ctypes.byref(cfg)), self._h)
+
+    def accretions(self) -> "AccretionResult":
+        """What the test particles gave the bodies they hit (waits for the queued work).  Raises :class:`NBodyError`
+        (``NBODY_ERR_STATE``) while the hit action is ``"remove"``."""
+        given = np.zeros((self.num_systems, self.max_bodies), dtype=np.float32)
+        count = np.zeros(self.num_systems, dtype=np.int64)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_accrete_read(self._h, given.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                             count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._h)
+        return AccretionResult(given, count)
 
     def mergers(self) -> "MergeResult":
         """The mergers so far, per system (waits for the queued work)."""
@@ -414,6 +441,18 @@ class FateResult:
         return f"FateResult(hit={self.hit.tolist()}, escaped={self.escaped.tolist()})"
 
 
+class AccretionResult:
+    """What the hit action ``"accrete"`` did (:meth:`BatchedSystem.set_hit_action`): ``given`` (``(B, max_bodies)`` float32,
+    the mass word each test particle gave the body it hit, 0 elsewhere; the body is the fate's ``target``) and ``count``
+    (``(B,)`` int64, the accretions per system)."""
+
+    def __init__(self, given, count):
+        self.given, self.count = given, count
+
+    def __repr__(self):
+        return f"AccretionResult(count={self.count.tolist()})"
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -424,4 +463,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]

@@ -2211,7 +2211,7 @@ struct BatchFate {
 };
 constexpr int kFateHit = 1, kFateEscaped = 2;
 struct BatchFateArgs {
-    const float *radii;  // [n_systems][max_bodies], or nullptr: every body has the radius half_rc
+    float *radii;        // [n_systems][max_bodies], or nullptr: every body has the radius half_rc (written by accretion only)
     float half_rc;
     int collide;         // a collision radius or radii are set (otherwise the column loop's masks are dropped)
     BatchFate *fates;    // one pointer: the kernel's scalar registers are all taken
@@ -2546,6 +2546,272 @@ hipError_t launch_batch_fate(const BatchLaunch &l, const BatchEvolveArgs &p, con
     });
 }
 
+// ---- accreting tracers (include/nbody_batch_accrete.h): a tracer that hits a massive body gives it its mass word.
+
+// Per launch: the mass each tracer gave ([n_systems][max_bodies], laid out like the positions) and the systems' accretions.
+struct BatchAccreteArgs {
+    float *given;
+    int *accretions;
+};
+constexpr int kFoundHit = 4;        // beside kStopCollision | kStopEscape in the waves' findings: a tracer hit at this evaluation
+constexpr int kAccreteWords = NBODY_BATCH_MAX_BODIES / 32;  // a bit per row
+
+// The rows of this lane that hit at the evaluation just made (bits 8 + q of `dead`, before fate_flush clears them) into the
+// workgroup's bit map.  Cold: entered by a lane that found one.
+__device__ __forceinline__ void accrete_mark(unsigned *hitmap, unsigned dead, int tid, int T, int rpl)
+{
+    asm volatile("" : "+v"(tid));
+    for (int q = 0; q < rpl; ++q)
+        if ((dead >> (8 + q)) & 1u) {
+            const int r = q * T + tid;
+            atomicOr(&hitmap[r >> 5], 1u << (r & 31));
+        }
+}
+
+// The cold path of a system whose tracers hit and which did not stop (workgroup-uniform), after fate_flush and a barrier:
+// lane 0 walks the bit map in ascending row index and merges each tracer that carries mass onto the target its fate names,
+// in the state arrays and the radii array -- nbody_batch_merge.h's arithmetic, the target the survivor -- and writes given
+// and the counter; it clears the map as it goes.  After a barrier, when a mass moved, the columns are refilled from the
+// current state and radii as merge_absorb refills them, and a last barrier completes them.  Returns whether a mass moved,
+// workgroup-uniform: if none did nothing was written and the columns are untouched.
+__device__ __forceinline__ bool accrete_absorb(float4 *sh, float4 *pos, float4 *vel, float *rad, int n, int tid, int T, int rpl,
+                                               const BatchFateArgs &fa, const BatchAccreteArgs &aa, size_t base,
+                                               unsigned *hitmap, int &moved)
+{
+    asm volatile("" : "+v"(tid));  // the rows' addresses are formed here, not carried through the steps from the kernel's top
+    if (tid == 0) {
+        int count = 0;
+        for (int w = 0; w < (n + 31) >> 5; ++w) {
+            unsigned bits = hitmap[w];
+            hitmap[w] = 0u;
+            while (bits) {
+                const int i = (w << 5) + __builtin_ctz(bits);
+                bits &= bits - 1u;
+                const int t = fa.fates[i].target;
+                const float4 xi = pos[i];
+                if (xi.w == 0.f || t < 0 || i >= n)  // nothing to give: the tracer is REMOVE's
+                    continue;
+                const float4 xt = pos[t], vt = vel[t], vi = vel[i];
+                const double M = (double)xt.w + (double)xi.w;
+                pos[t] = make_float4(merge_mean(xt.w, xt.x, xi.w, xi.x, M), merge_mean(xt.w, xt.y, xi.w, xi.y, M),
+                                     merge_mean(xt.w, xt.z, xi.w, xi.z, M), xt.w + xi.w);
+                vel[t] = make_float4(merge_mean(xt.w, vt.x, xi.w, vi.x, M), merge_mean(xt.w, vt.y, xi.w, vi.y, M),
+                                     merge_mean(xt.w, vt.z, xi.w, vi.z, M), vt.w);
+                pos[i].w = 0.f;
+                if (rad)
+                    rad[t] = merge_radius(rad[t], rad[i]);
+                aa.given[base + i] = xi.w;
+                ++count;
+            }
+        }
+        if (count) {
+            int sys = blockIdx.x;  // formed here, as in merge_absorb
+            asm volatile("" : "+s"(sys));
+            aa.accretions[sys] += count;
+        }
+        moved = count;
+    }
+    __syncthreads();  // the merged state is in the arrays, and every lane is done with the columns
+    if (!uniform_i32(moved))
+        return false;
+    for (int q = 0; q < rpl; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            const float4 w = vel[r];
+            sh[2 * r] = pos[r];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, rad ? rad[r] : fa.half_rc);
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// batch_hermite_fate_kernel with the hit action ACCRETE of include/nbody_batch_accrete.h: a sibling again, so that the fate
+// kernel stays the code it is.  The step is the fate kernel's -- the same column loop, LDS layout and workgroup shapes -- and
+// the loop is batch_hermite_merge_kernel's: the evaluation at the current state and the first-step rule are one block that
+// the outer loop enters again after an accretion.  A tracer hit at an evaluation sets kFoundHit beside the stopping
+// conditions; when the massive bodies met none, accrete_absorb follows.  Launched only while collisions are watched.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) void batch_hermite_accrete_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                     const int *counts, const int *massive, BatchEvolveState *state,
+                                                                     int *counters, int max_bodies, BatchEvolveArgs p,
+                                                                     BatchStopArgs sa, BatchStopReport *report, BatchFateArgs fa,
+                                                                     BatchAccreteArgs aa)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies, and their radii
+    __shared__ int red[16];         // the waves' levels
+    __shared__ int red_stop[16];    // the waves' stopping conditions (massive rows only) and kFoundHit
+    __shared__ unsigned long long cold_best;  // the cold paths' words
+    __shared__ int cold_escaper;
+    __shared__ int cold_moved;
+    __shared__ unsigned hitmap[kAccreteWords];  // the rows hit at the evaluation just made
+    const int n = uniform_i32(counts[blockIdx.x]);
+    if (n <= 0)
+        return;
+    const int mc = massive[blockIdx.x];
+    const int m = uniform_i32(mc < n ? mc : n);
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    const bool frozen = uniform_i32(report[blockIdx.x].reason) != 0;
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (frozen || tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target && !frozen) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    pos += base;
+    vel += base;
+    acc += base;
+    jerk += base;
+    fa.fates += base;
+    for (int w = tid; w < kAccreteWords; w += T)  // a barrier lies before the first evaluation's marks
+        hitmap[w] = 0u;
+    float3 a[RPL], jk[RPL];
+    unsigned dead = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, fa.radii ? fa.radii[base + r] : fa.half_rc);
+            dead |= fa.fates[r].fate != 0 ? 1u << q : 0u;
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    int stop = 0;                 // workgroup-uniform: what the last evaluation found, kFoundHit included
+    int run = 0;
+    bool evaluate = !p.have_acc;  // (a0, j0) are to be evaluated at the current state, which the columns hold
+    bool choose = !p.have_level;  // the level is to come from the first-step rule
+    // The evaluation at the current state and the first-step rule, then the steps until the target, the budget, max_steps, a
+    // condition or a hit; after a hit the accretion, and -- if a mass moved -- the same again.
+    for (;;) {
+        if (evaluate) {
+            __syncthreads();
+            int found = 0;
+            fate_evaluate<RPL, GUARD>(sh, n, m, tid, T, p.eps2, a, jk, sa, fa, dead, &found);
+            if ((dead >> 8) & 0xffu)
+                accrete_mark(hitmap, dead, tid, T, RPL);
+            found |= __any((dead >> 8) & 0xffu) ? kFoundHit : 0;  // wave-uniform, as the stop bits: lane 0 publishes
+            fate_flush(sh, m, tid, T, RPL, p.eps2, tick, fa, dead);
+            stop_publish(red_stop, found, tid);
+        }
+        if (choose) {  // dt = eta_start |a| / |j|, compared as squares; dead rows do not vote
+            EvolveWant want;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+                const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+                evolve_raise(want, q * T + tid < n && !((dead >> q) & 1u), p.eta_start2 * a2, j2, p);
+            }
+            evolve_publish(red, want, tid);
+        }
+        __syncthreads();  // every lane is done reading before a prediction rewrites the columns; red[], red_stop[] are complete
+        if (choose) {     // never coarser than the tick allows (tick 0 allows every level)
+            const EvolveWant want = evolve_collect(red, T);
+            const int floor_level = merge_tick_level(tick, p.levels);
+            level = want.level > p.levels ? p.levels : want.level;
+            level = level < floor_level ? floor_level : level;
+            clamped += want.level > p.levels ? 1 : 0;
+        }
+        if (evaluate)
+            stop = stop_collect(red_stop, T);
+        for (; tick < p.target && run < p.budget && steps < p.max_steps && !stop; ++run) {
+            const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < n && !((dead >> q) & 1u)) {  // x, y, z only: the mass words and the radii stay
+                    const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                    *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                        make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                    hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                    *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                        make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                    hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+                }
+                renew_f32(a[q]);
+                renew_f32(jk[q]);
+            }
+            __syncthreads();
+            int found = 0;
+            const long long after = tick + (1ll << (p.levels - level));  // the tick of a fate, as of a stop: the step's end
+            const EvolveWant mine = fate_evaluate_request<RPL, GUARD>(sh, n, m, tid, T, p.eps2, pos, vel, a, jk, e, p, sa, fa, dead, &found);
+            if ((dead >> 8) & 0xffu)
+                accrete_mark(hitmap, dead, tid, T, RPL);
+            found |= __any((dead >> 8) & 0xffu) ? kFoundHit : 0;  // wave-uniform, as the stop bits: lane 0 publishes
+            fate_flush(sh, m, tid, T, RPL, p.eps2, after, fa, dead);
+            stop_publish(red_stop, found, tid);
+            evolve_publish(red, mine, tid);
+            __syncthreads();
+            stop = stop_collect(red_stop, T);
+            EvolveWant want = evolve_collect(red, T);
+            clamped += want.level > p.levels ? 1 : 0;
+            want.level = want.level > p.levels ? p.levels : want.level;
+            tick = after;
+            ++steps;
+            min_level = level < min_level ? level : min_level;
+            max_level = level > max_level ? level : max_level;
+            if (want.level > level)
+                level = want.level;
+            else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+                --level;  // one level, on a tick the coarser step divides
+        }
+        if (stop != kFoundHit)  // nothing found, or the massive bodies met a condition: a step that stops accretes nothing
+            break;
+        stop = 0;
+        // every lane's corrected state and the fates of this evaluation lie before the last barrier
+        evaluate = choose = accrete_absorb(sh, pos, vel, fa.radii ? fa.radii + base : nullptr, n, tid, T, RPL, fa, aa, base, hitmap,
+                                           cold_moved);
+    }
+    stop &= kStopCollision | kStopEscape;
+    int lane = tid;  // the rows' indices formed anew, as in batch_hermite_radii_kernel
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + lane;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target && !stop) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+    if (stop)  // among the massive bodies: the columns still hold the positions the conditions were examined at
+        radii_stop_report(sh, pos, m, lane, T, RPL, p.eps2, sa, stop, tick, &report[blockIdx.x], cold_best, cold_escaper);
+}
+
+hipError_t launch_batch_accrete(const BatchLaunch &l, const BatchEvolveArgs &p, const BatchStopArgs &sa, const BatchFateArgs &fa,
+                                const BatchAccreteArgs &aa)
+{
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_accrete_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts,
+                                   l.massive, l.state, l.counters, l.max_bodies, p, sa, l.report, fa, aa);
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -2666,6 +2932,9 @@ struct nbody_batch {
     // nbody_batch_fate_set: the per-body fates beside the reports (forgotten with them), laid out like the positions and
     // allocated by the first REMOVE
     BatchFate *fates = nullptr;   // [n_systems][max_bodies]
+    // nbody_batch_accrete_set: what the tracers gave, beside the fates (forgotten with them) and allocated by the first ACCRETE
+    float *given = nullptr;       // [n_systems][max_bodies]
+    int *accretions = nullptr;    // [n_systems]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -2700,7 +2969,7 @@ static int bfail(nbody_batch *b, int status, const std::string &msg)
     } while (0)
 
 // nbody_batch_evolve_on's buffers: the caches and the per-system state, and what the mode keeps beside them -- merger counts and
-// logs, stop reports, fates -- allocated on first use and zeroed where the stops count as forgotten.
+// logs, stop reports, fates, accretions -- allocated on first use and zeroed where the stops count as forgotten.
 static int evolve_prepare_buffers(nbody_batch *b, const BatchMode &mode)
 {
     const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
@@ -2735,6 +3004,10 @@ static int evolve_prepare_buffers(nbody_batch *b, const BatchMode &mode)
             BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
         if (b->stop_forgotten && mode.fates)  // nbody_batch_fate.h: the fates are forgotten where the stops are
             BATCH_TRY(b, hipMemsetAsync(b->fates, 0, sizeof(BatchFate) * slots, b->stream));
+        if (b->stop_forgotten && mode.accreting) {  // nbody_batch_accrete.h: zeroed exactly where the fates are
+            BATCH_TRY(b, hipMemsetAsync(b->given, 0, sizeof(float) * slots, b->stream));
+            BATCH_TRY(b, hipMemsetAsync(b->accretions, 0, sizeof(int) * B, b->stream));
+        }
         b->stop_forgotten = false;
     }
     return NBODY_OK;
@@ -2747,6 +3020,7 @@ struct BatchEvolveLaunch {
     BatchMergeArgs ma;
     BatchRadiiArgs ra;
     BatchFateArgs fa;
+    BatchAccreteArgs aa;
 };
 
 // The arguments from the handle's settings and the call's (after evolve_prepare_buffers: they carry its pointers).
@@ -2780,6 +3054,7 @@ static BatchEvolveLaunch evolve_launch_args(const nbody_batch *b, const BatchMod
     a.ma = BatchMergeArgs{b->merge_count, b->merge_log, b->merge_capacity};
     a.ra = BatchRadiiArgs{b->radii, mode.merging ? 1 : 0};
     a.fa = BatchFateArgs{c.radii_set ? b->radii : nullptr, 0.5f * c.collision_radius, mode.collisions ? 1 : 0, b->fates};
+    a.aa = BatchAccreteArgs{b->given, b->accretions};
     return a;
 }
 
@@ -2795,7 +3070,8 @@ static BatchLaunch batch_launch(const nbody_batch *b, const BatchChoice &choice,
 static hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLaunch &a)
 {
     switch (l.choice.kernel) {
-    case BatchKernel::fate: return launch_batch_fate(l, a.p, a.sa, a.fa);
+    case BatchKernel::fate:  // nbody_batch_accrete.h: the accreting sibling where the choice says so
+        return l.choice.accrete ? launch_batch_accrete(l, a.p, a.sa, a.fa, a.aa) : launch_batch_fate(l, a.p, a.sa, a.fa);
     case BatchKernel::radii: return launch_batch_radii(l, a.p, a.sa, a.ma, a.ra);
     case BatchKernel::adaptive_massive: return launch_batch_adaptive_massive(l, a.p);
     case BatchKernel::merge: return launch_batch_merge(l, a.p, a.sa, a.ma);
@@ -2888,6 +3164,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->radii) (void)hipFree(b->radii);
     if (b->massive_dev) (void)hipFree(b->massive_dev);
     if (b->fates) (void)hipFree(b->fates);
+    if (b->given) (void)hipFree(b->given);
+    if (b->accretions) (void)hipFree(b->accretions);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -3367,6 +3645,50 @@ int nbody_batch_fate_count(nbody_batch *b, int64_t *hit, int64_t *escaped)
         if (hit) hit[s] = h;
         if (escaped) escaped[s] = e;
     }
+    return NBODY_OK;
+}
+
+int nbody_batch_accrete_set(nbody_batch *b, const nbody_batch_accrete_config *cfg)
+{
+    const int on_hit = cfg ? cfg->on_hit : NBODY_BATCH_ON_HIT_REMOVE;
+    if (on_hit != NBODY_BATCH_ON_HIT_REMOVE && on_hit != NBODY_BATCH_ON_HIT_ACCRETE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_accrete_set: unknown hit action (REMOVE = 0, ACCRETE = 1)");
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_accrete_set: batch is NULL (refused as an unknown hit action is)");
+    if (on_hit == NBODY_BATCH_ON_HIT_ACCRETE && (!b->given || !b->accretions)) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        if (!b->given)
+            BATCH_TRY(b, hipMalloc((void **)&b->given, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies));
+        if (!b->accretions)
+            BATCH_TRY(b, hipMalloc((void **)&b->accretions, sizeof(int) * (size_t)b->n_systems));
+    }
+    b->config.hit_action = on_hit;
+    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
+    return NBODY_OK;
+}
+
+int nbody_batch_accrete_read(nbody_batch *b, float *given, int64_t *accretions)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_accrete_read: batch is NULL");
+    if (b->config.hit_action != NBODY_BATCH_ON_HIT_ACCRETE)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_accrete_read: the hit action is REMOVE (nbody_batch_accrete_set): no accretions are kept");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    // kept: the arrays hold what the last nbody_batch_evolve_on calls found; otherwise nobody gave anything
+    const bool kept = batch_mode(b->config).accreting && b->given && b->accretions && !b->stop_forgotten;
+    std::vector<int> count(B, 0);
+    if (given)
+        std::fill(given, given + slots, 0.f);
+    if (kept) {
+        BATCH_TRY(b, hipSetDevice(b->device));
+        if (given)
+            BATCH_TRY(b, hipMemcpyAsync(given, b->given, sizeof(float) * slots, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipMemcpyAsync(count.data(), b->accretions, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    if (accretions)
+        for (size_t s = 0; s < B; ++s)
+            accretions[s] = count[s];
     return NBODY_OK;
 }
 

@@ -27,13 +27,14 @@ inline BatchShape batch_shape(int max_bodies)
 }
 
 // What the choice depends on: the handle's settings, each written by its setter (nbody_batch_set_integrator, _massive_set,
-// _radii_set, _stop_set, _merge_set, _fate_set).
+// _radii_set, _stop_set, _merge_set, _fate_set, _accrete_set).
 struct BatchConfig {
     int integrator = NBODY_INTEGRATOR_KICK_DRIFT;
     bool massive_set = false, radii_set = false;
     float collision_radius = 0.f, escape_radius = 0.f;  // nbody_batch_stop_set; both 0: off
     int collision_action = NBODY_BATCH_ON_COLLISION_STOP;
     int tracer_action = NBODY_BATCH_TRACERS_REFUSE;
+    int hit_action = NBODY_BATCH_ON_HIT_REMOVE;
 };
 
 // What the settings amount to for nbody_batch_evolve_on and for the calls that read what it kept.
@@ -42,6 +43,7 @@ struct BatchMode {
     bool stopping;    // stop reports are kept: collisions or an escape radius
     bool merging;     // a collision merges the pair: merger counts and logs are kept
     bool fates;       // tracer fates are kept: massive counts with REMOVE and a condition
+    bool accreting;   // a tracer that hits gives its mass word to its target: fates, collisions watched and ACCRETE
 };
 inline BatchMode batch_mode(const BatchConfig &c)
 {
@@ -50,6 +52,7 @@ inline BatchMode batch_mode(const BatchConfig &c)
     m.stopping = m.collisions || c.escape_radius > 0.f;
     m.merging = c.collision_action == NBODY_BATCH_ON_COLLISION_MERGE && m.collisions;
     m.fates = c.massive_set && c.tracer_action == NBODY_BATCH_TRACERS_REMOVE && m.stopping;
+    m.accreting = m.fates && m.collisions && c.hit_action == NBODY_BATCH_ON_HIT_ACCRETE;
     return m;
 }
 
@@ -92,6 +95,8 @@ struct BatchChoice {
     // The Hermite families pass the default 64 KiB of dynamic LDS from 2049 bodies on and raise their limit before every
     // launch; the two step families stay below it.
     bool raises_lds_limit() const { return kernel != BatchKernel::step && kernel != BatchKernel::step_massive; }
+    // nbody_batch_accrete.h: the fate family's accreting sibling (the same shape and LDS); no family of its own
+    bool accrete = false;
 };
 
 constexpr size_t kBatchBytesPerBody = 16;  // one float4
@@ -100,7 +105,7 @@ inline BatchChoice batch_choice(BatchKernel kernel, int max_bodies, float soften
 {
     const BatchShape sh = batch_shape(max_bodies);
     const float eps2 = softening * softening;
-    BatchChoice c{kernel, sh.rpl, sh.threads, !(eps2 > 0.f), kBatchBytesPerBody * (size_t)max_bodies, BatchRefusal::none};
+    BatchChoice c{kernel, sh.rpl, sh.threads, !(eps2 > 0.f), kBatchBytesPerBody * (size_t)max_bodies, BatchRefusal::none, false};
     if (c.raises_lds_limit())  // the predicted positions and velocities of the system's bodies
         c.lds *= 2;
     return c;
@@ -117,7 +122,8 @@ inline BatchChoice batch_step_choice(const BatchConfig &cfg, int max_bodies, flo
 }
 
 // nbody_batch_evolve_on.  Massive counts never meet the plain condition kernels: with conditions they are the fate kernel's
-// (REMOVE) or refused (REFUSE), and MERGE is refused with them either way.
+// (REMOVE) or refused (REFUSE), and MERGE is refused with them either way.  The hit action ACCRETE picks the fate family's
+// accreting sibling where collisions are watched, and changes nothing else.
 inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, float softening)
 {
     const BatchMode m = batch_mode(cfg);
@@ -143,6 +149,7 @@ inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, f
         k = m.stopping ? BatchKernel::stop : BatchKernel::adaptive;
     BatchChoice c = batch_choice(k, max_bodies, softening);
     c.refusal = r;
+    c.accrete = k == BatchKernel::fate && m.accreting;
     return c;
 }
 

@@ -34,6 +34,14 @@ stopped against merged: how many pairs collide, at what step counts, the merged 
 an escape radius that never trigger, against the same call with massive counts alone, alternated, medians and spreads, and
 whether the two states are equal bit for bit.
 
+--accrete: instead, accreting tracers (set_hit_action("accrete")).  For the same cases and m, one line per evolve(k, dt,
+levels=0): massive counts m, the tracer action "remove", a collision and an escape radius that never trigger and the hit
+action "accrete", against the same call on the same state with the hit action "remove" (the fate kernel) -- nothing hits, so
+the difference is the sibling kernel's own -- alternated, medians and spreads, and whether the two states are equal bit for bit.
+Then one line for a state where about 1 % of the tracers accrete over the run (n = 1024, B = 256, m = 8, a collision radius
+found by bisection on the run that removes): both actions from the same fresh state in every repeat, the accretions and the
+two times.
+
 --massive: instead, test particles (set_massive_counts).  For n x B = 4096 x 256 and 1024 x 1024 (or --cases) and m in
 1, 8, 64, 512, n, one line per Hermite step_n(k, dt) and one per evolve(k, dt, levels=0): the call with massive counts m
 set against the same call with the feature off, both on the same state with the mass words of the bodies from m on zeroed
@@ -71,6 +79,8 @@ ap.add_argument("--radii", action="store_true", help="evolve(levels=0) with per-
                 "of which can trigger, and the scattering case with unequal radii stopped and merged")
 ap.add_argument("--fates", action="store_true", help="evolve(levels=0) with massive counts m and the tracer action 'remove' under "
                 "conditions that never trigger against the same state with the feature off")
+ap.add_argument("--accrete", action="store_true", help="evolve(levels=0) under the hit action 'accrete' against 'remove' on a state "
+                "where nothing hits, and a state where about 1 %% of the tracers accrete")
 ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolve(levels=0) with massive counts m against the "
                 "feature off on the same state with the other bodies' mass words zero")
 args = ap.parse_args()
@@ -437,6 +447,89 @@ def fates_lines():
                               "fates_repeats": [round(x, 5) for x in t_on], "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
 
 
+def accrete_lines():
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    dt = float(np.float32(args.dt))
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        for m in sorted({min(m, n) for m in (1, 8, 64)}):
+            k = int(min(400, max(10, 2e11 // (B * n * m))))
+            with nb.BatchedSystem(B, n, integrator="hermite") as acc, nb.BatchedSystem(B, n, integrator="hermite") as rem:
+                for batch, action in ((acc, "accrete"), (rem, "remove")):
+                    batch.set_state(P, V)
+                    batch.set_massive_counts([m] * B)
+                    batch.set_tracer_action("remove")
+                    batch.set_hit_action(action)
+                    batch.set_stop_conditions(collision_radius=1e-9, escape_radius=1e9)   # conditions that never trigger
+
+                def run(batch):
+                    batch.evolve(k, dt, levels=0, softening=args.eps)
+
+                run(acc)
+                run(rem)
+                torch.cuda.synchronize()
+                t_acc, t_rem = [], []
+                for _ in range(args.repeats):      # alternated
+                    t_acc.append(timed(lambda: run(acc)) / k)
+                    t_rem.append(timed(lambda: run(rem)) / k)
+                m_acc, m_rem = statistics.median(t_acc), statistics.median(t_rem)
+                same = bool(torch.equal(acc.positions, rem.positions) and torch.equal(acc.velocities, rem.velocities))
+                f, a = acc.fates(), acc.accretions()
+            print(json.dumps({"n": n, "B": B, "m": m, "call": "evolve_levels0", "k": k, "accrete_ms_per_step": round(m_acc, 5),
+                              "remove_ms_per_step": round(m_rem, 5), "accrete_over_remove": round(m_acc / m_rem, 4),
+                              "accrete_spread": round((max(t_acc) - min(t_acc)) / m_acc, 4),
+                              "remove_spread": round((max(t_rem) - min(t_rem)) / m_rem, 4),
+                              "interactions_per_step": nb.batch.interactions_per_step([n] * B, [m] * B),
+                              "states_equal_bit_for_bit": same, "removed": int(f.hit.sum() + f.escaped.sum()),
+                              "accretions": int(a.count.sum()), "accrete_repeats": [round(x, 5) for x in t_acc],
+                              "remove_repeats": [round(x, 5) for x in t_rem]}), flush=True)
+    # about 1 % of the tracers accrete: the tracers' mass words are 1e-3 of the massive bodies'
+    n, B, m, k = 1024, 256, 8, 200
+    P, V = ensemble(n, B)
+    P[:, m:, 3] = P[:, :m, 3].mean() * 1e-3
+    with nb.BatchedSystem(B, n, integrator="hermite") as batch:
+        batch.set_massive_counts([m] * B)
+        batch.set_tracer_action("remove")
+
+        def fresh(action, rc):
+            batch.set_state(P, V)
+            batch.set_hit_action(action)
+            batch.set_stop_conditions(collision_radius=rc, escape_radius=1e9)
+            batch.sync()
+
+        def evolve():
+            batch.evolve(k, dt, levels=0, softening=args.eps)
+
+        lo, hi = 1e-4, 1.0                         # bisection on the run that removes, geometric: hits grow with the radius
+        for _ in range(12):
+            rc = float(np.sqrt(lo * hi))
+            fresh("remove", rc)
+            evolve()
+            frac = float(batch.fates().hit.sum()) / (B * (n - m))
+            lo, hi = (rc, hi) if frac < 0.01 else (lo, rc)
+        rc = float(np.sqrt(lo * hi))
+        t_acc, t_rem = [], []
+        for _ in range(1 + args.repeats):          # the first pair warms up; alternated
+            fresh("accrete", rc)
+            t_acc.append(timed(evolve) / k)
+            f, a, st = batch.fates(), batch.accretions(), batch.stops()
+            fresh("remove", rc)
+            t_rem.append(timed(evolve) / k)
+        t_acc, t_rem = t_acc[1:], t_rem[1:]
+        m_acc, m_rem = statistics.median(t_acc), statistics.median(t_rem)
+    print(json.dumps({"n": n, "B": B, "m": m, "call": "evolve_levels0", "k": k, "collision_radius": float(f"{rc:.4g}"),
+                      "tracers_hit_fraction": round(float(f.hit.sum()) / (B * (n - m)), 5), "accretions": int(a.count.sum()),
+                      "systems_stopped": int(st.stopped.sum()), "accrete_ms_per_step": round(m_acc, 5),
+                      "remove_ms_per_step": round(m_rem, 5), "accrete_over_remove": round(m_acc / m_rem, 4),
+                      "accrete_spread": round((max(t_acc) - min(t_acc)) / m_acc, 4),
+                      "remove_spread": round((max(t_rem) - min(t_rem)) / m_rem, 4),
+                      "accrete_repeats": [round(x, 5) for x in t_acc], "remove_repeats": [round(x, 5) for x in t_rem]}), flush=True)
+
+
+if args.accrete:
+    accrete_lines()
+    sys.exit(0)
 if args.massive:
     massive_lines()
     sys.exit(0)
