@@ -493,6 +493,8 @@ float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
  *   nbody_batch_radii_set (nbody_batch_radii.h, included below) gives every body a collision radius of its own.
  *   nbody_batch_massive_set (nbody_batch_massive.h, included below) makes the bodies after a system's first m test
  *   particles: rows like any other that are never columns, for every integrator and for nbody_batch_evolve_on.
+ *   nbody_batch_field_set (nbody_batch_field.h, included below) adds a static analytic background field to every row of
+ *   nbody_batch_evolve_on.
  *   No individual per-body time steps, no P(EC)^n iteration, no fp64 state; no centre-of-mass escape test, no outcome of
  *   a collision other than a stop or a perfect merger.
  * Arguments are checked before any device work (NBODY_ERR_INVALID with a message): B <= 0, max_bodies outside
@@ -531,6 +533,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_fate.h"
 /* accreting tracers: a test particle that hits a massive body gives it its mass word, and the body grows */
 #include "nbody_batch_accrete.h"
+/* external fields: a static Plummer, logarithmic-halo or Miyamoto-Nagai background next to the pair sum */
+#include "nbody_batch_field.h"
 
 #ifdef __cplusplus
 }

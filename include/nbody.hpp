@@ -444,6 +444,30 @@ public:
         check(nbody_batch_accrete_read(b_, a.given.data(), a.count.data()), "nbody_batch_accrete_read");
         return a;
     }
+    // External field of evolve (nbody_batch_field.h): numSystems x nComponents components (nComponents in [1, 4]),
+    // components[s * nComponents + c], a static Plummer, logarithmic-halo or Miyamoto-Nagai background centred on the origin
+    // that every body feels next to the pair forces.  An empty vector switches the field off.  field(): the components as
+    // set (throws when off); fieldPotential(): numSystems x maxBodies values of the field's potential at the positions, fp64.
+    void setField(const std::vector<nbody_batch_field_component> &components, int nComponents)
+    {
+        if (!components.empty() && (nComponents < 1 || (std::int64_t)components.size() != systems_ * nComponents))
+            throw std::runtime_error("Batch::setField: numSystems x nComponents components, or none");
+        check(nbody_batch_field_set(b_, components.empty() ? nullptr : components.data(), nComponents), "nbody_batch_field_set");
+    }
+    std::vector<nbody_batch_field_component> field()
+    {
+        std::vector<nbody_batch_field_component> c((size_t)systems_ * NBODY_BATCH_FIELD_MAX_COMPONENTS);
+        int n = 0;
+        check(nbody_batch_field_read(b_, c.data(), &n), "nbody_batch_field_read");
+        c.resize((size_t)systems_ * (size_t)n);
+        return c;
+    }
+    std::vector<double> fieldPotential(const float *dPositions)
+    {
+        std::vector<double> phi((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_field_potential(b_, dPositions, phi.data()), "nbody_batch_field_potential");
+        return phi;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

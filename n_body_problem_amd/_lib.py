@@ -237,6 +237,24 @@ BATCH_ON_HIT_REMOVE = 0
 BATCH_ON_HIT_ACCRETE = 1
 
 
+class BatchFieldComponent(ctypes.Structure):
+    """``nbody_batch_field_component`` of include/nbody_batch_field.h."""
+    _fields_ = [("kind", c_int), ("p", c_float * 3)]
+
+
+#: the entry points of include/nbody_batch_field.h (external fields for Hermite batches), which nbody.h includes
+_FIELD_PROTOTYPES = {
+    "nbody_batch_field_set": (c_int, [c_void_p, POINTER(BatchFieldComponent), c_int]),
+    "nbody_batch_field_read": (c_int, [c_void_p, POINTER(BatchFieldComponent), POINTER(c_int)]),
+    "nbody_batch_field_potential": (c_int, [c_void_p, c_void_p, POINTER(c_double)]),
+}
+BATCH_FIELD_MAX_COMPONENTS = 4
+BATCH_FIELD_NONE = 0
+BATCH_FIELD_PLUMMER = 1
+BATCH_FIELD_LOG_HALO = 2
+BATCH_FIELD_MIYAMOTO_NAGAI = 3
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -263,7 +281,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
-                list(_ACCRETE_PROTOTYPES.items()):
+                list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -309,6 +327,11 @@ def fate_names():
 def accrete_names():
     """The entry points of nbody_batch_accrete.h."""
     return list(_ACCRETE_PROTOTYPES)
+
+
+def field_names():
+    """The entry points of nbody_batch_field.h."""
+    return list(_FIELD_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -23,6 +23,8 @@ INTEGRATORS = {"kick_drift": 0, "kdk": 1, "hermite": 2}
 COLLISION_ACTIONS = {"stop": _lib.BATCH_ON_COLLISION_STOP, "merge": _lib.BATCH_ON_COLLISION_MERGE}
 TRACER_ACTIONS = {"refuse": _lib.BATCH_TRACERS_REFUSE, "remove": _lib.BATCH_TRACERS_REMOVE}
 HIT_ACTIONS = {"remove": _lib.BATCH_ON_HIT_REMOVE, "accrete": _lib.BATCH_ON_HIT_ACCRETE}
+FIELD_KINDS = {"none": _lib.BATCH_FIELD_NONE, "plummer": _lib.BATCH_FIELD_PLUMMER, "log_halo": _lib.BATCH_FIELD_LOG_HALO,
+               "miyamoto_nagai": _lib.BATCH_FIELD_MIYAMOTO_NAGAI}
 #: one merger of the log: numpy's view of ``nbody_batch_merge_event``
 MERGE_EVENT_DTYPE = np.dtype([("tick", np.int64), ("survivor", np.int32), ("absorbed", np.int32), ("count_before", np.int32),
                               ("separation", np.float32), ("relative_speed", np.float32), ("mass_survivor", np.float32),
@@ -352,6 +354,83 @@ class BatchedSystem:
                                                              count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._h)
         return AccretionResult(given, count)
 
+    def set_external_field(self, components) -> None:
+        """A static background potential centred on the origin, felt by every body of :meth:`evolve` next to the pair forces
+        (``include/nbody_batch_field.h`` states the formulas and the fp32 operation order): the sum of up to four
+        components, ``G = 1``.  ``components`` is a list of ``(kind, p0, p1, p2)`` applied to every system, ``kind`` one of
+        ``"plummer"`` ``(M, b, -)``, ``"log_halo"`` ``(v0, rc, q)``, ``"miyamoto_nagai"`` ``(M, a, b)`` or ``"none"``
+        (skipped); or an array ``(B, C, 4)`` with a numeric kind (``FIELD_KINDS``) in ``[..., 0]``, one set per system; or
+        ``None`` to switch the field off (the default).  The field counts in the time-step criterion; it reads no mass
+        word, so test particles (:meth:`set_massive_counts`) feel it like any other body.  A Plummer term is bit for bit a
+        body of mass ``M`` fixed at the origin with softening ``b``.  :meth:`evolve` takes the field with or without
+        massive counts (``levels=0`` gives fixed steps) and refuses it together with stopping conditions, radii, mergers
+        or tracer fates; :meth:`step_n` refuses it.  The shape is checked here, the values by the library
+        (:class:`NBodyError`).  Forgets what :meth:`set_massive_counts` forgets."""
+        self._use_current_stream()
+        if components is None:
+            _check(self._lib, self._lib.nbody_batch_field_set(self._h, None, 0), self._h)
+            return
+        if isinstance(components, (list, tuple)) and all(isinstance(c, (list, tuple)) and len(c) > 0 and isinstance(c[0], str)
+                                                         for c in components):
+            rows = []
+            for c in components:
+                if c[0] not in FIELD_KINDS:
+                    raise ValueError(f"field kind must be one of {tuple(FIELD_KINDS)}, got {c[0]!r}")
+                p = [float(u) for u in c[1:]]
+                if len(p) > 3:
+                    raise ValueError(f"a field component has at most three parameters, got {c!r}")
+                rows.append([float(FIELD_KINDS[c[0]])] + p + [0.0] * (3 - len(p)))
+            arr = np.broadcast_to(np.asarray(rows, dtype=np.float64).reshape(1, len(rows), 4), (self.num_systems, len(rows), 4))
+        else:
+            arr = np.asarray(components, dtype=np.float64)
+        if arr.ndim != 3 or arr.shape[0] != self.num_systems or arr.shape[2] != 4:
+            raise ValueError(f"field components must have shape ({self.num_systems}, C, 4), got {tuple(arr.shape)}")
+        kinds = arr[..., 0]
+        if not np.all(np.isfinite(kinds)) or not np.all(kinds == np.round(kinds)):
+            raise ValueError("field kinds (components[..., 0]) must be integers")
+        C = arr.shape[1]
+        buf = (_lib.BatchFieldComponent * (self.num_systems * C))()
+        for s in range(self.num_systems):
+            for c in range(C):
+                u = buf[s * C + c]
+                u.kind = int(kinds[s, c])
+                u.p[0], u.p[1], u.p[2] = (float(np.float32(v)) for v in arr[s, c, 1:])
+        _check(self._lib, self._lib.nbody_batch_field_set(self._h, buf, int(C)), self._h)
+
+    def external_field(self):
+        """The field's components as they were set, ``(B, C, 4)`` float32 with the kind in ``[..., 0]``, or ``None`` while no
+        field is set."""
+        buf = (_lib.BatchFieldComponent * (self.num_systems * _lib.BATCH_FIELD_MAX_COMPONENTS))()
+        n = ctypes.c_int(0)
+        status = self._lib.nbody_batch_field_read(self._h, buf, ctypes.byref(n))
+        if status == _lib.NBODY_ERR_STATE:
+            return None
+        _check(self._lib, status, self._h)
+        C = n.value
+        out = np.zeros((self.num_systems, C, 4), dtype=np.float32)
+        for s in range(self.num_systems):
+            for c in range(C):
+                u = buf[s * C + c]
+                out[s, c] = (u.kind, u.p[0], u.p[1], u.p[2])
+        return out
+
+    def field_potential(self) -> np.ndarray:
+        """``(B, max_bodies)`` float64: the field's potential at every body's position (fp64 from the fp32 positions and
+        parameters; 0 beyond the counts and while no field is set; waits for the queued work)."""
+        out = np.zeros((self.num_systems, self.max_bodies), dtype=np.float64)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_field_potential(self._h, _ptr(self.positions),
+                                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), self._h)
+        return out
+
+    def field_energy(self) -> np.ndarray:
+        """``(B,)`` float64: per system the sum of mass word times field potential over its bodies -- the field's part of the
+        energy, which :meth:`energy` (the pair energy) does not contain."""
+        phi = self.field_potential()
+        m = self.positions[:, :, 3].cpu().numpy().astype(np.float64)
+        live = np.arange(self.max_bodies)[None, :] < self._counts[:, None]
+        return np.where(live, m * phi, 0.0).sum(axis=1)
+
     def mergers(self) -> "MergeResult":
         """The mergers so far, per system (waits for the queued work)."""
         B, cap = self.num_systems, self._log_capacity
@@ -463,4 +542,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

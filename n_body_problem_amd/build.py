@@ -24,7 +24,8 @@ HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_radii.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_massive.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_fate.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_accrete.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_accrete.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_field.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -55,6 +55,7 @@ hipError_t with_shape(int rpl, bool guard, F &&f)
 // family does not read may be null).
 struct BatchEvolveState;
 struct BatchStopReport;
+struct BatchFieldTerm;
 struct BatchLaunch {
     BatchChoice choice;
     int n_systems, max_bodies;
@@ -65,6 +66,7 @@ struct BatchLaunch {
     BatchEvolveState *state;
     int *counters;
     BatchStopReport *report;
+    const BatchFieldTerm *field;  // nbody_batch_field.h: [n_systems][4], null while no field is set
 };
 
 // One launch of a batch kernel, one workgroup per system, with the choice's workgroup and dynamic LDS.  The Hermite families
@@ -2196,6 +2198,376 @@ hipError_t launch_batch_adaptive_massive(const BatchLaunch &l, const BatchEvolve
     });
 }
 
+// ---- external fields (include/nbody_batch_field.h): a static analytic background next to the pair sum, up to four components
+// per system.  The components are workgroup-uniform: one launch reads them once, through uniform_i32, into scalar registers,
+// and every kind is chosen by a scalar branch.
+
+// One component as the kernels take it, formed by nbody_batch_field_set on the host in fp32 (the header's "once per
+// nbody_batch_field_set"): PLUMMER {M, b b, -}, LOG_HALO {v0 v0, rc rc, 1 / (q q)}, MIYAMOTO_NAGAI {M, a, b b}.
+struct BatchFieldTerm {
+    int kind;
+    float c0, c1, c2;
+};
+static_assert(sizeof(BatchFieldTerm) == 16 && sizeof(nbody_batch_field_component) == 16, "one dwordx4 per component");
+
+struct BatchField {
+    BatchFieldTerm term[NBODY_BATCH_FIELD_MAX_COMPONENTS];
+};
+
+__device__ __forceinline__ float uniform_f32(float x) { return __int_as_float(uniform_i32(__float_as_int(x))); }
+
+// The system's components in scalar registers.  `terms` is [n_systems][NBODY_BATCH_FIELD_MAX_COMPONENTS]; components the
+// caller did not give are NONE.
+__device__ __forceinline__ BatchField field_load(const BatchFieldTerm *terms)
+{
+    BatchField f;
+    terms += (size_t)blockIdx.x * NBODY_BATCH_FIELD_MAX_COMPONENTS;
+#pragma unroll
+    for (int c = 0; c < NBODY_BATCH_FIELD_MAX_COMPONENTS; ++c) {
+        const BatchFieldTerm u = terms[c];
+        f.term[c] = BatchFieldTerm{uniform_i32(u.kind), uniform_f32(u.c0), uniform_f32(u.c1), uniform_f32(u.c2)};
+    }
+    return f;
+}
+
+// The three kinds for one row at its predicted state (x, v), added to the row's sums (a, j): the header's operation
+// order, to the letter.  Per row, by reading the ISA: PLUMMER 26 VALU + 1 v_rsq_f32, the column interaction's, and 4 more for
+// the guard (b is known at run time only); LOG_HALO 20 VALU + 1 v_rcp_f32; MIYAMOTO_NAGAI 32 VALU + 2 v_rsq_f32.
+__device__ __forceinline__ void field_plummer(float M, float b2, const float3 &x, const float3 &v, float3 &a, float3 &j)
+{
+    const float dx = 0.f - x.x, dy = 0.f - x.y, dz = 0.f - x.z;
+    const float ex = 0.f - v.x, ey = 0.f - v.y, ez = 0.f - v.z;
+    float r2 = __builtin_fmaf(dx, dx, b2);
+    r2 = __builtin_fmaf(dy, dy, r2);
+    r2 = __builtin_fmaf(dz, dz, r2);
+    if (!(b2 > 0.f))  // uniform: b = 0 takes the guard, as a zero-distance pair does
+        r2 = guard_r2(r2);
+    const float inv = __builtin_amdgcn_rsqf(r2);
+    const float inv2 = inv * inv;
+    const float s = (M * inv) * inv2;
+    const float rv = __builtin_fmaf(dz, ez, __builtin_fmaf(dy, ey, dx * ex));
+    const float c = (3.f * rv) * inv2;
+    a.x = __builtin_fmaf(dx, s, a.x);
+    a.y = __builtin_fmaf(dy, s, a.y);
+    a.z = __builtin_fmaf(dz, s, a.z);
+    j.x = __builtin_fmaf(__builtin_fmaf(-c, dx, ex), s, j.x);
+    j.y = __builtin_fmaf(__builtin_fmaf(-c, dy, ey), s, j.y);
+    j.z = __builtin_fmaf(__builtin_fmaf(-c, dz, ez), s, j.z);
+}
+__device__ __forceinline__ void field_log_halo(float k, float rc2, float wz, const float3 &x, const float3 &v, float3 &a, float3 &j)
+{
+    const float zw = wz * x.z, vw = wz * v.z;
+    const float D = __builtin_fmaf(zw, x.z, __builtin_fmaf(x.y, x.y, __builtin_fmaf(x.x, x.x, rc2)));
+    const float hd = __builtin_fmaf(zw, v.z, __builtin_fmaf(x.y, v.y, x.x * v.x));
+    const float iD = __builtin_amdgcn_rcpf(D);
+    const float g = k * iD;
+    const float t = (2.f * hd) * iD;
+    a.x = __builtin_fmaf(-g, x.x, a.x);
+    a.y = __builtin_fmaf(-g, x.y, a.y);
+    a.z = __builtin_fmaf(-g, zw, a.z);
+    j.x = __builtin_fmaf(-g, __builtin_fmaf(-t, x.x, v.x), j.x);
+    j.y = __builtin_fmaf(-g, __builtin_fmaf(-t, x.y, v.y), j.y);
+    j.z = __builtin_fmaf(-g, __builtin_fmaf(-t, zw, vw), j.z);
+}
+__device__ __forceinline__ void field_miyamoto_nagai(float M, float la, float b2, const float3 &x, const float3 &v, float3 &a,
+                                                     float3 &j)
+{
+    const float s2 = __builtin_fmaf(x.z, x.z, b2);
+    const float is = __builtin_amdgcn_rsqf(s2);
+    const float s = s2 * is;
+    const float A = la + s;
+    const float f = A * is;
+    const float sd = (x.z * v.z) * is;
+    const float fd = -((la * sd) * (is * is));
+    const float D = __builtin_fmaf(A, A, __builtin_fmaf(x.y, x.y, x.x * x.x));
+    const float hd = __builtin_fmaf(A, sd, __builtin_fmaf(x.y, v.y, x.x * v.x));
+    const float iD = __builtin_amdgcn_rsqf(D);
+    const float iD2 = iD * iD;
+    const float mu = (M * iD) * iD2;
+    const float c = (3.f * hd) * iD2;
+    const float zf = x.z * f;
+    const float zd = __builtin_fmaf(v.z, f, x.z * fd);
+    a.x = __builtin_fmaf(-x.x, mu, a.x);
+    a.y = __builtin_fmaf(-x.y, mu, a.y);
+    a.z = __builtin_fmaf(-zf, mu, a.z);
+    j.x = __builtin_fmaf(__builtin_fmaf(c, x.x, -v.x), mu, j.x);
+    j.y = __builtin_fmaf(__builtin_fmaf(c, x.y, -v.y), mu, j.y);
+    j.z = __builtin_fmaf(__builtin_fmaf(c, zf, -zd), mu, j.z);
+}
+
+// The system's components added to the sums of a group's rows, ascending component order; NONE is skipped.
+template <int G>
+__device__ __forceinline__ void field_add(const BatchField &f, const float3 (&xp)[G], const float3 (&vp)[G], float3 (&a1)[G],
+                                          float3 (&j1)[G])
+{
+#pragma unroll
+    for (int c = 0; c < NBODY_BATCH_FIELD_MAX_COMPONENTS; ++c) {
+        const BatchFieldTerm &u = f.term[c];
+        if (u.kind == NBODY_BATCH_FIELD_PLUMMER) {
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                field_plummer(u.c0, u.c1, xp[i], vp[i], a1[i], j1[i]);
+        } else if (u.kind == NBODY_BATCH_FIELD_LOG_HALO) {
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                field_log_halo(u.c0, u.c1, u.c2, xp[i], vp[i], a1[i], j1[i]);
+        } else if (u.kind == NBODY_BATCH_FIELD_MIYAMOTO_NAGAI) {
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                field_miyamoto_nagai(u.c0, u.c1, u.c2, xp[i], vp[i], a1[i], j1[i]);
+        }
+    }
+}
+
+// massive_evaluate<RPL, GUARD, false> followed by the field: (a, j) at the state the columns hold, without the corrector.
+constexpr int kOwnField = 5;
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void field_evaluate(const float4 *sh, int n, int m, int tid, int T, float eps2, const BatchField &f,
+                                               float3 (&a)[RPL], float3 (&jk)[RPL])
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {  // xyz only: ds_read_b96
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, false, kOwnField>(sh, m, xp, vp, eps2, a1, j1);
+        field_add<G>(f, xp, vp, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            a[g + i] = a1[i];
+            jk[g + i] = j1[i];
+        }
+    }
+}
+
+// massive_evaluate_request<RPL, GUARD> with the field added between the column loop and the corrector: the criterion sees
+// the field's accelerations and jerks at both ends of the step.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ EvolveWant field_evaluate_request(const float4 *sh, int n, int m, int tid, int T, float eps2,
+                                                             const BatchField &f, float4 *pos, float4 *vel, float3 (&a)[RPL],
+                                                             float3 (&jk)[RPL], const EvolveSteps &e, const BatchEvolveArgs &p)
+{
+    constexpr int G = RPL < 2 ? RPL : 2;
+    EvolveWant want;
+#pragma unroll
+    for (int g = 0; g < RPL; g += G) {
+        float3 xp[G], vp[G], a1[G], j1[G], x[G], v[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int r = (g + i) * T + tid;
+            xp[i] = vp[i] = x[i] = v[i] = make_float3(0.f, 0.f, 0.f);
+            if (r < n) {
+                xp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r]);
+                vp[i] = *reinterpret_cast<const float3 *>(&sh[2 * r + 1]);
+                x[i] = *reinterpret_cast<const float3 *>(&pos[r]);
+                v[i] = *reinterpret_cast<const float3 *>(&vel[r]);
+            }
+        }
+        batch_forces_jerks<G, GUARD, false, kOwnField>(sh, m, xp, vp, eps2, a1, j1);
+        field_add<G>(f, xp, vp, a1, j1);
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int q = g + i, r = q * T + tid;
+            hermite_correct(x[i].x, v[i].x, a[q].x, a1[i].x, jk[q].x, j1[i].x, e.t);
+            hermite_correct(x[i].y, v[i].y, a[q].y, a1[i].y, jk[q].y, j1[i].y, e.t);
+            hermite_correct(x[i].z, v[i].z, a[q].z, a1[i].z, jk[q].z, j1[i].z, e.t);
+            if (r < n) {  // x, y, z only: the mass words and the velocities' w stay as they are
+                *reinterpret_cast<float3 *>(&pos[r]) = x[i];
+                *reinterpret_cast<float3 *>(&vel[r]) = v[i];
+            }
+            float3 a0 = a[q], j0 = jk[q];
+            renew_f32(a0);  // widened again below, one component at a time: the corrector's fp64 copies end here
+            renew_f32(j0);
+            renew_f32(a1[i]);
+            renew_f32(j1[i]);
+            a[q] = a1[i];
+            jk[q] = j1[i];
+            EvolveNorms s;
+            evolve_norms(s, a0.x, a1[i].x, j0.x, j1[i].x, e);
+            evolve_norms(s, a0.y, a1[i].y, j0.y, j1[i].y, e);
+            evolve_norms(s, a0.z, a1[i].z, j0.z, j1[i].z, e);
+            const double num = p.eta * (__builtin_sqrt(s.a1 * s.a2) + s.j1), den = __builtin_sqrt(s.j1 * s.a3) + s.a2;
+            evolve_raise(want, r < n, num, den, p);
+        }
+    }
+    return want;
+}
+
+// batch_hermite_adaptive_massive_kernel with the field: the same loop, level rule, tick arithmetic, state and counters, the
+// same row groups and LDS layout.  massive == nullptr: no massive counts, every body is a column (m = n).  With m = 0 a row's
+// accelerations and jerks are the field's alone.
+// One row per lane is asked to stay at eight waves per SIMD (64 VGPRs), where the sibling is: the components' scalar registers
+// press some of the loop's scalars into lanes of one more vector register otherwise.
+template <int RPL, bool GUARD>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4, RPL == 1 ? 8 : 4))) void batch_hermite_field_kernel(float4 *pos, float4 *vel, float4 *acc, float4 *jerk,
+                                                                   const int *counts, const int *massive,
+                                                                   const BatchFieldTerm *terms, BatchEvolveState *state,
+                                                                   int *counters, int max_bodies, BatchEvolveArgs p)
+{
+    extern __shared__ float4 sh[];  // 2 x max_bodies float4: the predicted state of the system's bodies
+    __shared__ int red[16];         // the waves' levels
+    const int n = counts[blockIdx.x];
+    if (n <= 0)
+        return;
+    const int mc = massive ? massive[blockIdx.x] : n;
+    const int m = uniform_i32(mc < n ? mc : n);
+    const int tid = threadIdx.x, T = blockDim.x;
+    const BatchEvolveState st0 = state[blockIdx.x];
+    long long tick = p.reset_tick ? 0 : uniform_i64(st0.tick);
+    long long steps = p.new_call ? 0 : uniform_i64(st0.steps), clamped = p.new_call ? 0 : uniform_i64(st0.clamped);
+    int level = uniform_i32(st0.level);
+    int min_level = p.new_call ? kEvolveNoLevel : uniform_i32(st0.min_level);
+    int max_level = p.new_call ? -1 : uniform_i32(st0.max_level);
+    if (tick >= p.target || steps >= p.max_steps) {  // nothing to do in this launch
+        if (tid == 0) {
+            if (p.new_call)
+                state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+            if (tick < p.target) {
+                atomicAdd(&counters[0], 1);
+                atomicAdd(&counters[1], 1);
+            }
+        }
+        return;
+    }
+    const BatchField f = field_load(terms);
+    pos += (size_t)blockIdx.x * (size_t)max_bodies;
+    vel += (size_t)blockIdx.x * (size_t)max_bodies;
+    acc += (size_t)blockIdx.x * (size_t)max_bodies;
+    jerk += (size_t)blockIdx.x * (size_t)max_bodies;
+    float3 a[RPL], jk[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        a[q] = jk[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            const float4 xm = pos[r], w = vel[r];
+            sh[2 * r] = xm;
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (p.have_acc) {
+                const float4 a0 = acc[r], j0 = jerk[r];
+                a[q] = make_float3(a0.x, a0.y, a0.z);
+                jk[q] = make_float3(j0.x, j0.y, j0.z);
+            }
+        }
+    }
+    if (!p.have_acc) {  // (a0, j0) at the current state, which the columns hold
+        __syncthreads();
+        field_evaluate<RPL, GUARD>(sh, n, m, tid, T, p.eps2, f, a, jk);
+    }
+    if (!p.have_level) {  // the first step: dt = eta_start |a| / |j|, compared as squares
+        EvolveWant want;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const double a2 = (double)a[q].x * (double)a[q].x + (double)a[q].y * (double)a[q].y + (double)a[q].z * (double)a[q].z;
+            const double j2 = (double)jk[q].x * (double)jk[q].x + (double)jk[q].y * (double)jk[q].y + (double)jk[q].z * (double)jk[q].z;
+            evolve_raise(want, q * T + tid < n, p.eta_start2 * a2, j2, p);  // dt^2 = eta_start^2 |a|^2 / |j|^2
+        }
+        evolve_publish(red, want, tid);
+    }
+    __syncthreads();  // every lane is done reading before the first prediction rewrites the columns; red[] is complete
+    if (!p.have_level) {
+        const EvolveWant want = evolve_collect(red, T);
+        level = want.level > p.levels ? p.levels : want.level;
+        clamped += want.level > p.levels ? 1 : 0;
+    }
+    for (int run = 0; tick < p.target && run < p.budget && steps < p.max_steps; ++run) {
+        const EvolveSteps e = evolve_steps(p, level);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float3 x = *reinterpret_cast<const float3 *>(&pos[r]), v = *reinterpret_cast<const float3 *>(&vel[r]);
+                *reinterpret_cast<float3 *>(&sh[2 * r]) =
+                    make_float3(hermite_predict_x(x.x, v.x, a[q].x, jk[q].x, e.t), hermite_predict_x(x.y, v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_x(x.z, v.z, a[q].z, jk[q].z, e.t));
+                *reinterpret_cast<float3 *>(&sh[2 * r + 1]) =
+                    make_float3(hermite_predict_v(v.x, a[q].x, jk[q].x, e.t), hermite_predict_v(v.y, a[q].y, jk[q].y, e.t),
+                                hermite_predict_v(v.z, a[q].z, jk[q].z, e.t));
+            }
+            renew_f32(a[q]);
+            renew_f32(jk[q]);
+        }
+        __syncthreads();
+        const EvolveWant mine = field_evaluate_request<RPL, GUARD>(sh, n, m, tid, T, p.eps2, f, pos, vel, a, jk, e, p);
+        evolve_publish(red, mine, tid);
+        __syncthreads();
+        EvolveWant want = evolve_collect(red, T);
+        clamped += want.level > p.levels ? 1 : 0;
+        want.level = want.level > p.levels ? p.levels : want.level;
+        tick += 1ll << (p.levels - level);
+        ++steps;
+        min_level = level < min_level ? level : min_level;
+        max_level = level > max_level ? level : max_level;
+        if (want.level > level)
+            level = want.level;
+        else if (want.level < level && (tick & ((2ll << (p.levels - level)) - 1)) == 0)
+            --level;  // one level, on a tick the coarser step divides
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            acc[r] = make_float4(a[q].x, a[q].y, a[q].z, 0.f);
+            jerk[r] = make_float4(jk[q].x, jk[q].y, jk[q].z, 0.f);
+        }
+    }
+    if (tid == 0) {
+        state[blockIdx.x] = BatchEvolveState{tick, steps, clamped, level, min_level, max_level, 0};
+        if (tick < p.target) {
+            atomicAdd(&counters[0], 1);
+            if (steps >= p.max_steps)
+                atomicAdd(&counters[1], 1);
+        }
+    }
+}
+
+hipError_t launch_batch_field(const BatchLaunch &l, const BatchEvolveArgs &p)
+{
+    const int *massive = l.choice.kernel == BatchKernel::adaptive_massive ? l.massive : nullptr;
+    return with_shape(l.choice.rpl, l.choice.guard, [&](auto rpl, auto guard) {
+        return launch_batch_kernel(batch_hermite_field_kernel<rpl(), guard()>, l, l.pos, l.vel, l.acc, l.jerk, l.counts, massive,
+                                   l.field, l.state, l.counters, l.max_bodies, p);
+    });
+}
+
+// Phi(x_i) per body in fp64 (the header's "Potential"): one thread per slot, 0 beyond the counts.  Not the hot path.
+__global__ __launch_bounds__(256) void batch_field_potential_kernel(const float4 *pos, const int *counts,
+                                                                    const nbody_batch_field_component *comps, int n_components,
+                                                                    int max_bodies, double *phi)
+{
+    const int s = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= max_bodies)
+        return;
+    const size_t slot = (size_t)s * (size_t)max_bodies + (size_t)i;
+    double sum = 0.0;
+    if (i < counts[s]) {
+        const float4 xm = pos[slot];
+        const double x = (double)xm.x, y = (double)xm.y, z = (double)xm.z;
+        for (int c = 0; c < n_components; ++c) {
+            const nbody_batch_field_component u = comps[(size_t)s * (size_t)n_components + c];
+            const double p0 = (double)u.p[0], p1 = (double)u.p[1], p2 = (double)u.p[2];
+            if (u.kind == NBODY_BATCH_FIELD_PLUMMER) {
+                const double r2 = x * x + y * y + z * z + p1 * p1;
+                sum += r2 > 0.0 ? -p0 / __builtin_sqrt(r2) : 0.0;
+            } else if (u.kind == NBODY_BATCH_FIELD_LOG_HALO) {
+                sum += 0.5 * (p0 * p0) * log(x * x + y * y + z * z / (p2 * p2) + p1 * p1);
+            } else if (u.kind == NBODY_BATCH_FIELD_MIYAMOTO_NAGAI) {
+                const double A = p1 + __builtin_sqrt(z * z + p2 * p2);
+                sum += -p0 / __builtin_sqrt(x * x + y * y + A * A);
+            }
+        }
+    }
+    phi[slot] = sum;
+}
+
 // ---- tracer fates (include/nbody_batch_fate.h): massive counts together with a collision radius, radii or an escape radius.
 // A test particle that touches a massive body or leaves the escape radius is removed -- frozen, with a fate -- and its system
 // carries on; a collision among the massive bodies or a massive escaper stops the system as batch_hermite_stop_kernel does.
@@ -2935,6 +3307,11 @@ struct nbody_batch {
     // nbody_batch_accrete_set: what the tracers gave, beside the fates (forgotten with them) and allocated by the first ACCRETE
     float *given = nullptr;       // [n_systems][max_bodies]
     int *accretions = nullptr;    // [n_systems]
+    // nbody_batch_field_set: the external field's components; a property of the handle, which only nbody_batch_field_set changes
+    std::vector<nbody_batch_field_component> field;  // host copy as set, [n_systems][field_components] while config.field_set
+    int field_components = 0;
+    BatchFieldTerm *field_dev = nullptr;              // [n_systems][4] as the kernels take them, allocated by the first set
+    nbody_batch_field_component *field_raw_dev = nullptr;  // [n_systems][4] as set, for nbody_batch_field_potential
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -3063,12 +3440,16 @@ static BatchLaunch batch_launch(const nbody_batch *b, const BatchChoice &choice,
 {
     return BatchLaunch{choice, (int)b->n_systems, (int)b->max_bodies, b->stream, reinterpret_cast<float4 *>(d_pos),
                        reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk, b->counts_dev, b->massive_dev, b->evolve_state,
-                       b->evolve_counters, b->stop_report};
+                       b->evolve_counters, b->stop_report, b->field_dev};
 }
 
 // One launch of nbody_batch_evolve_on by the chosen family.
 static hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLaunch &a)
 {
+    if (l.choice.field)  // nbody_batch_field.h: the two families without conditions, through their sibling with the field
+        return l.choice.kernel == BatchKernel::adaptive_massive || l.choice.kernel == BatchKernel::adaptive
+                   ? launch_batch_field(l, a.p)
+                   : hipErrorInvalidValue;
     switch (l.choice.kernel) {
     case BatchKernel::fate:  // nbody_batch_accrete.h: the accreting sibling where the choice says so
         return l.choice.accrete ? launch_batch_accrete(l, a.p, a.sa, a.fa, a.aa) : launch_batch_fate(l, a.p, a.sa, a.fa);
@@ -3166,6 +3547,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->fates) (void)hipFree(b->fates);
     if (b->given) (void)hipFree(b->given);
     if (b->accretions) (void)hipFree(b->accretions);
+    if (b->field_dev) (void)hipFree(b->field_dev);
+    if (b->field_raw_dev) (void)hipFree(b->field_raw_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -3233,6 +3616,9 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
     if (!batch_softening_ok(softening))
         return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
                                            "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
+    const BatchChoice choice = batch_step_choice(b->config, (int)b->max_bodies, softening);
+    if (choice.refusal != BatchRefusal::none)  // nbody_batch_field.h: no fixed-step kernel takes a field
+        return bfail(b, batch_refusal_status(choice.refusal), batch_refusal_message(choice.refusal));
     if (k == 0)
         return NBODY_OK;
     if (b->evolve_pending && b->acc_valid && b->config.integrator == NBODY_INTEGRATOR_HERMITE)
@@ -3252,7 +3638,7 @@ int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, 
         if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening || b->acc_integrator != b->config.integrator)
             b->acc_valid = false;
     }
-    const BatchLaunch launch = batch_launch(b, batch_step_choice(b->config, (int)b->max_bodies, softening), d_pos, d_vel);
+    const BatchLaunch launch = batch_launch(b, choice, d_pos, d_vel);
     const float eps2 = softening * softening;
     for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
         const int run = std::min(kBatchStepsPerLaunch, k - done);
@@ -3689,6 +4075,102 @@ int nbody_batch_accrete_read(nbody_batch *b, float *given, int64_t *accretions)
     if (accretions)
         for (size_t s = 0; s < B; ++s)
             accretions[s] = count[s];
+    return NBODY_OK;
+}
+
+// What the kernels take of one component (BatchFieldTerm): the squares and 1 / (q q) in fp32, formed here once.
+static BatchFieldTerm field_term(const nbody_batch_field_component &u)
+{
+    switch (u.kind) {
+    case NBODY_BATCH_FIELD_PLUMMER: return BatchFieldTerm{u.kind, u.p[0], u.p[1] * u.p[1], 0.f};
+    case NBODY_BATCH_FIELD_LOG_HALO: return BatchFieldTerm{u.kind, u.p[0] * u.p[0], u.p[1] * u.p[1], 1.f / (u.p[2] * u.p[2])};
+    case NBODY_BATCH_FIELD_MIYAMOTO_NAGAI: return BatchFieldTerm{u.kind, u.p[0], u.p[1], u.p[2] * u.p[2]};
+    default: return BatchFieldTerm{NBODY_BATCH_FIELD_NONE, 0.f, 0.f, 0.f};
+    }
+}
+
+int nbody_batch_field_set(nbody_batch *b, const nbody_batch_field_component *host, int n_components)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_set: batch is NULL");
+    if (host) {
+        if (n_components < 1 || n_components > NBODY_BATCH_FIELD_MAX_COMPONENTS)
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_set: n_components (" + std::to_string(n_components) +
+                                                   ") outside [1, NBODY_BATCH_FIELD_MAX_COMPONENTS = 4]");
+        const size_t B = (size_t)b->n_systems, C = (size_t)n_components;
+        for (size_t s = 0; s < B; ++s)
+            for (size_t c = 0; c < C; ++c) {
+                const nbody_batch_field_component &u = host[s * C + c];
+                if (const char *msg = batch_field_component_error(u.kind, u.p))
+                    return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_set: system " + std::to_string(s) + ", component " +
+                                                           std::to_string(c) + " (kind " + std::to_string(u.kind) + ", p = " +
+                                                           std::to_string(u.p[0]) + ", " + std::to_string(u.p[1]) + ", " +
+                                                           std::to_string(u.p[2]) + "): " + msg);
+            }
+        // padded to four components per system with NONE, for the kernels and for the potential
+        std::vector<BatchFieldTerm> terms(B * NBODY_BATCH_FIELD_MAX_COMPONENTS, BatchFieldTerm{NBODY_BATCH_FIELD_NONE, 0.f, 0.f, 0.f});
+        std::vector<nbody_batch_field_component> raw(B * NBODY_BATCH_FIELD_MAX_COMPONENTS,
+                                                     nbody_batch_field_component{NBODY_BATCH_FIELD_NONE, {0.f, 0.f, 0.f}});
+        for (size_t s = 0; s < B; ++s)
+            for (size_t c = 0; c < C; ++c) {
+                terms[s * NBODY_BATCH_FIELD_MAX_COMPONENTS + c] = field_term(host[s * C + c]);
+                raw[s * NBODY_BATCH_FIELD_MAX_COMPONENTS + c] = host[s * C + c];
+            }
+        BATCH_TRY(b, hipSetDevice(b->device));
+        if (!b->field_dev)
+            BATCH_TRY(b, hipMalloc((void **)&b->field_dev, sizeof(BatchFieldTerm) * terms.size()));
+        if (!b->field_raw_dev)
+            BATCH_TRY(b, hipMalloc((void **)&b->field_raw_dev, sizeof(nbody_batch_field_component) * raw.size()));
+        BATCH_TRY(b, hipMemcpyAsync(b->field_dev, terms.data(), sizeof(BatchFieldTerm) * terms.size(), hipMemcpyHostToDevice, b->stream));
+        BATCH_TRY(b, hipMemcpyAsync(b->field_raw_dev, raw.data(), sizeof(nbody_batch_field_component) * raw.size(),
+                                    hipMemcpyHostToDevice, b->stream));
+        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copies end with this call
+        b->field.assign(host, host + B * C);
+        b->field_components = n_components;
+    }
+    b->config.field_set = host != nullptr;
+    forget_caches(b);  // as nbody_batch_massive_set: the cached accelerations and jerks belong to the old field
+    return NBODY_OK;
+}
+
+int nbody_batch_field_read(nbody_batch *b, nbody_batch_field_component *host, int *n_components)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_read: batch is NULL");
+    if (!host || !n_components)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_read: NULL argument");
+    if (!b->config.field_set)
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_field_read: no field is set (nbody_batch_field_set)");
+    std::copy(b->field.begin(), b->field.end(), host);
+    *n_components = b->field_components;
+    return NBODY_OK;
+}
+
+int nbody_batch_field_potential(nbody_batch *b, const float *d_pos, double *host_phi)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_potential: batch is NULL");
+    if (!d_pos || !host_phi)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_potential: NULL argument");
+    const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
+    std::fill(host_phi, host_phi + slots, 0.0);
+    if (!b->config.field_set)
+        return NBODY_OK;
+    if (b->n_systems > 65535)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_potential: more than 65535 systems");
+    BATCH_TRY(b, hipSetDevice(b->device));
+    double *phi = nullptr;
+    BATCH_TRY(b, hipMalloc((void **)&phi, sizeof(double) * slots));
+    hipLaunchKernelGGL(batch_field_potential_kernel, dim3((unsigned)((b->max_bodies + 255) / 256), (unsigned)b->n_systems), dim3(256), 0,
+                       b->stream, reinterpret_cast<const float4 *>(d_pos), b->counts_dev, b->field_raw_dev,
+                       NBODY_BATCH_FIELD_MAX_COMPONENTS, (int)b->max_bodies, phi);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(host_phi, phi, sizeof(double) * slots, hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(b->stream);
+    (void)hipFree(phi);
+    BATCH_TRY(b, e);
     return NBODY_OK;
 }
 

@@ -27,7 +27,7 @@ inline BatchShape batch_shape(int max_bodies)
 }
 
 // What the choice depends on: the handle's settings, each written by its setter (nbody_batch_set_integrator, _massive_set,
-// _radii_set, _stop_set, _merge_set, _fate_set, _accrete_set).
+// _radii_set, _stop_set, _merge_set, _fate_set, _accrete_set, _field_set).
 struct BatchConfig {
     int integrator = NBODY_INTEGRATOR_KICK_DRIFT;
     bool massive_set = false, radii_set = false;
@@ -35,6 +35,7 @@ struct BatchConfig {
     int collision_action = NBODY_BATCH_ON_COLLISION_STOP;
     int tracer_action = NBODY_BATCH_TRACERS_REFUSE;
     int hit_action = NBODY_BATCH_ON_HIT_REMOVE;
+    bool field_set = false;  // nbody_batch_field_set: an external field (nbody_batch_field.h)
 };
 
 // What the settings amount to for nbody_batch_evolve_on and for the calls that read what it kept.
@@ -60,7 +61,15 @@ inline BatchMode batch_mode(const BatchConfig &c)
 enum class BatchKernel { step, step_massive, hermite, hermite_massive, adaptive, stop, merge, radii, adaptive_massive, fate };
 
 // What nbody_batch_evolve_on refuses, in the order it looks.
-enum class BatchRefusal { none, not_hermite, radii_and_collision_radius, merge_with_massive, massive_with_conditions };
+enum class BatchRefusal {
+    none,
+    not_hermite,
+    radii_and_collision_radius,
+    merge_with_massive,
+    massive_with_conditions,
+    field_with_conditions,  // nbody_batch_field.h: nbody_batch_evolve_on, after the four above
+    field_with_step_n       // nbody_batch_field.h: nbody_batch_step_n_*
+};
 
 inline int batch_refusal_status(BatchRefusal r) { return r == BatchRefusal::none ? NBODY_OK : NBODY_ERR_INVALID; }
 
@@ -81,6 +90,14 @@ inline const char *batch_refusal_message(BatchRefusal r)
         return "nbody_batch_evolve: massive counts are set together with a stopping condition or radii "
                "(nbody_batch_massive.h: not supported, the collision test counts on a row's own column); "
                "nbody_batch_massive_set(b, NULL) or switch the conditions off";
+    case BatchRefusal::field_with_conditions:
+        return "nbody_batch_evolve: an external field is set together with a collision radius, an escape radius, "
+               "radii, the collision action MERGE or the tracer action REMOVE (nbody_batch_field.h: the condition, "
+               "fate and accrete kernels take no field); nbody_batch_field_set(b, NULL, 0) or switch the conditions off";
+    case BatchRefusal::field_with_step_n:
+        return "nbody_batch_step_n: an external field is set (nbody_batch_field.h: fixed steps with a field are "
+               "nbody_batch_evolve_on with levels = 0, NBODY_INTEGRATOR_HERMITE); nbody_batch_field_set(b, NULL, 0) "
+               "switches the field off";
     default: return "";
     }
 }
@@ -97,6 +114,9 @@ struct BatchChoice {
     bool raises_lds_limit() const { return kernel != BatchKernel::step && kernel != BatchKernel::step_massive; }
     // nbody_batch_accrete.h: the fate family's accreting sibling (the same shape and LDS); no family of its own
     bool accrete = false;
+    // nbody_batch_field.h: the adaptive families' sibling that adds the external field (the same shape and LDS); no family
+    // of its own
+    bool field = false;
 };
 
 constexpr size_t kBatchBytesPerBody = 16;  // one float4
@@ -111,19 +131,25 @@ inline BatchChoice batch_choice(BatchKernel kernel, int max_bodies, float soften
     return c;
 }
 
-// nbody_batch_step_n_async: fixed steps know no conditions and refuse nothing.
+// nbody_batch_step_n_async: fixed steps know no conditions; they refuse an external field (nbody_batch_field.h) and nothing
+// else.
 inline BatchChoice batch_step_choice(const BatchConfig &cfg, int max_bodies, float softening)
 {
     const bool hermite = cfg.integrator == NBODY_INTEGRATOR_HERMITE;
     // test particles (nbody_batch_massive.h): the siblings whose column loop ends early
     const BatchKernel k = hermite ? (cfg.massive_set ? BatchKernel::hermite_massive : BatchKernel::hermite)
                                   : (cfg.massive_set ? BatchKernel::step_massive : BatchKernel::step);
-    return batch_choice(k, max_bodies, softening);
+    BatchChoice c = batch_choice(k, max_bodies, softening);
+    if (cfg.field_set)
+        c.refusal = BatchRefusal::field_with_step_n;
+    return c;
 }
 
 // nbody_batch_evolve_on.  Massive counts never meet the plain condition kernels: with conditions they are the fate kernel's
 // (REMOVE) or refused (REFUSE), and MERGE is refused with them either way.  The hit action ACCRETE picks the fate family's
-// accreting sibling where collisions are watched, and changes nothing else.
+// accreting sibling where collisions are watched, and changes nothing else.  An external field (nbody_batch_field.h) runs with
+// the two families without conditions, through their sibling with the field, and is refused with everything that watches a
+// condition -- looked at after the older refusals, so that every answer without a field stays what it was.
 inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, float softening)
 {
     const BatchMode m = batch_mode(cfg);
@@ -136,6 +162,8 @@ inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, f
         r = BatchRefusal::merge_with_massive;
     else if (!m.fates && cfg.massive_set && m.stopping)
         r = BatchRefusal::massive_with_conditions;
+    else if (cfg.field_set && m.stopping)  // MERGE and REMOVE act only where a condition is watched
+        r = BatchRefusal::field_with_conditions;
     BatchKernel k;
     if (m.fates)  // nbody_batch_fate.h: massive counts together with the conditions, through a kernel of their own
         k = BatchKernel::fate;
@@ -150,6 +178,7 @@ inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, f
     BatchChoice c = batch_choice(k, max_bodies, softening);
     c.refusal = r;
     c.accrete = k == BatchKernel::fate && m.accreting;
+    c.field = cfg.field_set;
     return c;
 }
 
@@ -157,6 +186,39 @@ inline BatchChoice batch_evolve_choice(const BatchConfig &cfg, int max_bodies, f
 inline bool batch_softening_ok(float softening)
 {
     return std::isfinite(softening) && softening >= 0.f && !(softening > 0.f && softening < NBODY_MIN_SOFTENING);
+}
+
+// One component of nbody_batch_field_set (nbody_batch_field.h) against its domain: what is wrong with it, for the message that
+// names the function, the system, the component and the value (NBODY_ERR_INVALID), or nullptr.
+inline const char *batch_field_component_error(int kind, const float *p)
+{
+    const auto bad = [](float u) { return !std::isfinite(u) || u < 0.f; };  // not a finite number >= 0
+    switch (kind) {
+    case NBODY_BATCH_FIELD_NONE: return nullptr;  // skipped: its parameters are not read
+    case NBODY_BATCH_FIELD_PLUMMER:
+        if (bad(p[0]))
+            return "PLUMMER: the mass p[0] must be finite and >= 0";
+        if (bad(p[1]) || (p[1] > 0.f && p[1] < NBODY_MIN_SOFTENING))
+            return "PLUMMER: the scale b = p[1] must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)";
+        return nullptr;
+    case NBODY_BATCH_FIELD_LOG_HALO:
+        if (bad(p[0]))
+            return "LOG_HALO: the velocity v0 = p[0] must be finite and >= 0";
+        if (bad(p[1]) || !(p[1] > 0.f))
+            return "LOG_HALO: the core radius rc = p[1] must be finite and > 0";
+        if (bad(p[2]) || !(p[2] > 0.f))
+            return "LOG_HALO: the flattening q = p[2] must be finite and > 0";
+        return nullptr;
+    case NBODY_BATCH_FIELD_MIYAMOTO_NAGAI:
+        if (bad(p[0]))
+            return "MIYAMOTO_NAGAI: the mass p[0] must be finite and >= 0";
+        if (bad(p[1]))
+            return "MIYAMOTO_NAGAI: the scale length a = p[1] must be finite and >= 0";
+        if (bad(p[2]) || !(p[2] > 0.f))
+            return "MIYAMOTO_NAGAI: the scale height b = p[2] must be finite and > 0";
+        return nullptr;
+    default: return "unknown kind (NONE = 0, PLUMMER = 1, LOG_HALO = 2, MIYAMOTO_NAGAI = 3)";
+    }
 }
 
 // The numeric arguments of nbody_batch_evolve_on: the message to report (NBODY_ERR_INVALID), or nullptr.

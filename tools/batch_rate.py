@@ -46,7 +46,13 @@ two times.
 1, 8, 64, 512, n, one line per Hermite step_n(k, dt) and one per evolve(k, dt, levels=0): the call with massive counts m
 set against the same call with the feature off, both on the same state with the mass words of the bodies from m on zeroed
 (the two compute the same bits; the second walks all n columns through the kernels that exist without the feature) --
-alternated, medians, both times, their ratio and the spread (max - min over the median) of each side's repeats."""
+alternated, medians, both times, their ratio and the spread (max - min over the median) of each side's repeats.
+
+--field: instead, external fields (set_external_field).  For n x B = 4096 x 256 and 1024 x 1024 (or --cases) and m in
+1, 8, 64, n, one line per evolve(k, dt, levels=0): the call with a three-component field (bulge + disc + halo) against the
+same call with the field off, both with massive counts m and from the same state -- alternated, medians, both times, their
+ratio and the spread of each side's repeats.  The two runs differ (the field moves the bodies); the work per step does not
+depend on the state."""
 import argparse
 import json
 import os
@@ -83,6 +89,8 @@ ap.add_argument("--accrete", action="store_true", help="evolve(levels=0) under t
                 "where nothing hits, and a state where about 1 %% of the tracers accrete")
 ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolve(levels=0) with massive counts m against the "
                 "feature off on the same state with the other bodies' mass words zero")
+ap.add_argument("--field", action="store_true", help="evolve(levels=0) with a three-component external field against the "
+                "field off, with massive counts m, on the same state")
 args = ap.parse_args()
 
 
@@ -410,6 +418,42 @@ def massive_lines():
                                   "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
 
 
+def field_lines():
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["4096x256", "1024x1024"]
+    galaxy = [("plummer", 0.3, 0.05, 0.0), ("miyamoto_nagai", 1.0, 0.5, 0.1), ("log_halo", 0.7, 1.0, 0.9)]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        dt = float(np.float32(args.dt))
+        for m in sorted({min(m, n) for m in (1, 8, 64, n)}):
+            k = int(min(400, max(10, 2e11 // (B * n * m))))
+            with nb.BatchedSystem(B, n, integrator="hermite") as on, nb.BatchedSystem(B, n, integrator="hermite") as off:
+                for batch in (on, off):
+                    batch.set_state(P, V)
+                    batch.set_massive_counts([m] * B)
+                on.set_external_field(galaxy)
+
+                def run(batch):
+                    batch.evolve(k, dt, levels=0, softening=args.eps)
+
+                run(on)
+                run(off)
+                torch.cuda.synchronize()
+                t_on, t_off = [], []
+                for _ in range(args.repeats):      # alternated
+                    t_on.append(timed(lambda: run(on)) / k)
+                    t_off.append(timed(lambda: run(off)) / k)
+                m_on, m_off = statistics.median(t_on), statistics.median(t_off)
+            print(json.dumps({"n": n, "B": B, "m": m, "call": "evolve_levels0", "k": k, "components": [c[0] for c in galaxy],
+                              "field_ms_per_step": round(m_on, 5), "off_ms_per_step": round(m_off, 5),
+                              "field_over_off": round(m_on / m_off, 3),
+                              "field_ns_per_body_step": round((m_on - m_off) * 1e6 / (B * n), 4),
+                              "field_spread": round((max(t_on) - min(t_on)) / m_on, 4),
+                              "off_spread": round((max(t_off) - min(t_off)) / m_off, 4),
+                              "interactions_per_step": nb.batch.interactions_per_step([n] * B, [m] * B),
+                              "field_repeats": [round(x, 5) for x in t_on], "off_repeats": [round(x, 5) for x in t_off]}), flush=True)
+
+
 def fates_lines():
     cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["4096x256", "1024x1024"]
     for case in cases:
@@ -527,6 +571,9 @@ def accrete_lines():
                       "accrete_repeats": [round(x, 5) for x in t_acc], "remove_repeats": [round(x, 5) for x in t_rem]}), flush=True)
 
 
+if args.field:
+    field_lines()
+    sys.exit(0)
 if args.accrete:
     accrete_lines()
     sys.exit(0)
