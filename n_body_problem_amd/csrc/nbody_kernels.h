@@ -34,7 +34,8 @@ struct ForceArgs {
     float eps2;          // softening length squared
     const float *eps_pp; // optional per-particle softening lengths (n_total floats): eps_ij^2 = eps2 + eps_i^2 + eps_j^2
     const float *split_mass;  // [n_splits]: the one mass of a split's bodies, or NaN (launch_split_mass)
-    int own_split_mass;       // force_kernel_r4pk_w1, one-tile splits: the kernel forms that flag itself (nothing was launched)
+    int own_split_mass;       // force_kernel_r4pk_w1, splits of up to 512 columns: the kernel forms that flag itself, over the
+                              // split's split_len columns (nothing was launched)
 };
 
 struct SymArgs {

@@ -567,7 +567,9 @@ __global__ __launch_bounds__(kTile) void force_kernel_r4pk(ForceArgs a)
 // waves, six to a SIMD, dealt as slots free up; the wave stages its own 256-column tiles (four float4 a lane, no barrier
 // partner) and runs the identical hand-allocated loop, so each row's sum is the same FMA chain: not a bit changes.
 // Splits of up to 512 columns (every system below 32 768 bodies) need no split_mass_kernel launch in front: the wave holds
-// the split's masses in registers and forms the same flag itself (one launch less per step).
+// the split's masses in registers and forms the same flag itself (one launch less per step): over the split's split_len columns,
+// a column at or beyond n_total counting as mass 0, exactly split_mass_kernel's rule -- not over the staged registers beyond a
+// split of 64, 128 or 192 columns (the staged tile is 256 columns whatever the split), or the blockings would disagree there.
 template <bool GUARD, int QT, bool PPS = false>
 __global__ __launch_bounds__(64) void force_kernel_r4pk_w1(ForceArgs a)
 {
@@ -631,9 +633,15 @@ __global__ __launch_bounds__(64) void force_kernel_r4pk_w1(ForceArgs a)
         if (a.own_split_mass) {
             const unsigned m0 = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, stage[0].w));
             bool differs = false;
+            // the split's own split_len columns and no more: a split shorter than the staged 256-column tile (64, 128, 192) leaves
+            // staged registers beyond it, zero-mass padding that is no body of the split.  NOT bounded by j1: inside split_len a
+            // column at or beyond n_total still counts as mass 0, so a ragged last split stays non-uniform (its last four-column
+            // iteration runs over padding, which the equal-mass loop, leaving the mass out, would count as bodies)
 #pragma unroll
             for (int k = 0; k < NS; ++k)
-                differs |= __builtin_bit_cast(unsigned, stage[k].w) != m0;
+                differs |= k * 64 + lane < a.split_len && __builtin_bit_cast(unsigned, stage[k].w) != m0;
+            // (not reached today: force_choice sets own_split_mass for splits of up to 512 columns only, and those are staged
+            // whole; kept, since it is compiled into the QT = 0 kernels and taking it out would change their code)
             if (!WHOLE)  // the columns beyond the first tile: their masses straight from memory
                 for (int c = kTile + lane; c < a.split_len; c += 64) {
                     const float m = j0 + c < a.n_total ? a.pos[j0 + c].w : 0.f;  // a ragged split's missing bodies: mass 0

@@ -210,8 +210,9 @@ inline ForceChoice force_choice(int setting, int split_len, int64_t row_count, i
     // the loop (N = 20 225: 0.165 ms per step with the compiler-allocated one-row kernel it used to take).
     const int64_t blocks4 = (row_count + (int64_t)kTile * 4 - 1) / ((int64_t)kTile * 4) * split_count;
     k.rows_per_lane = setting ? setting : blocks4 >= (split_len <= 512 ? 10LL : 4LL) * cu_count ? 4 : 41;
-    // the one-wave kernel forms the equal-mass flag of a split of one or two tiles itself (from the tile it holds and, for the
-    // second, the masses in memory): no launch in front
+    // the one-wave kernel forms the equal-mass flag of a split of up to 512 columns itself, from the columns it has staged: no launch
+    // in front.  The flag covers the split's split_len columns, one at or beyond n_total counting as mass 0 (split_mass_kernel's
+    // rule: the flag must not depend on who forms it) -- so not the rest of the 256-column tile staged for a split of 64, 128 or 192
     k.own_split_mass = k.rows_per_lane == 41 && split_len <= 2 * kTile && equal_mass_path;
     switch (k.rows_per_lane) {
     case 4: return kernel(F::force_kernel_r4pk, !eps, eps_pp, 0, kTile * 4, kTile);  // packed fp32; per-particle softening: its own loop
