@@ -535,6 +535,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_accrete.h"
 /* external fields: a static Plummer, logarithmic-halo or Miyamoto-Nagai background next to the pair sum */
 #include "nbody_batch_field.h"
+/* bound pairs: every body's partner by two-body energy, the pair's orbital elements and the binaries of every system */
+#include "nbody_batch_pairs.h"
 
 #ifdef __cplusplus
 }

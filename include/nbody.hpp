@@ -468,6 +468,22 @@ public:
         check(nbody_batch_field_potential(b_, dPositions, phi.data()), "nbody_batch_field_potential");
         return phi;
     }
+    // Bound pairs (nbody_batch_pairs.h): numSystems x maxBodies records laid out like the positions -- every body's partner by
+    // the smallest two-body energy, whether the choice is mutual, and the pair's energy, semi-major axis, eccentricity,
+    // inclination and separation in fp64 -- found on the device from the state in the caller's buffers.  Changes nothing the
+    // handle keeps.  binaries(): per system the mutual pairs with negative energy of the last pairs() call (throws before one).
+    std::vector<nbody_batch_pair_record> pairs(const float *dPositions, const float *dVelocities)
+    {
+        std::vector<nbody_batch_pair_record> r((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_pairs(b_, dPositions, dVelocities, r.data()), "nbody_batch_pairs");
+        return r;
+    }
+    std::vector<std::int64_t> binaries()
+    {
+        std::vector<std::int64_t> n((size_t)systems_);
+        check(nbody_batch_pairs_binaries(b_, n.data()), "nbody_batch_pairs_binaries");
+        return n;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -255,6 +255,19 @@ BATCH_FIELD_LOG_HALO = 2
 BATCH_FIELD_MIYAMOTO_NAGAI = 3
 
 
+class BatchPairRecord(ctypes.Structure):
+    """``nbody_batch_pair_record`` of include/nbody_batch_pairs.h."""
+    _fields_ = [("partner", c_int), ("mutual", c_int), ("energy", c_double), ("semi_major_axis", c_double),
+                ("eccentricity", c_double), ("inclination", c_double), ("separation", c_double)]
+
+
+#: the entry points of include/nbody_batch_pairs.h (bound pairs of batched ensembles), which nbody.h includes
+_PAIRS_PROTOTYPES = {
+    "nbody_batch_pairs": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(BatchPairRecord)]),
+    "nbody_batch_pairs_binaries": (c_int, [c_void_p, POINTER(c_int64)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -281,7 +294,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
-                list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()):
+                list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -332,6 +345,11 @@ def accrete_names():
 def field_names():
     """The entry points of nbody_batch_field.h."""
     return list(_FIELD_PROTOTYPES)
+
+
+def pairs_names():
+    """The entry points of nbody_batch_pairs.h."""
+    return list(_PAIRS_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

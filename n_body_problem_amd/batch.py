@@ -30,6 +30,10 @@ MERGE_EVENT_DTYPE = np.dtype([("tick", np.int64), ("survivor", np.int32), ("abso
                               ("separation", np.float32), ("relative_speed", np.float32), ("mass_survivor", np.float32),
                               ("mass_absorbed", np.float32), ("reserved", np.int32)])
 assert MERGE_EVENT_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMergeEvent)
+#: one record of :meth:`BatchedSystem.pairs`: numpy's view of ``nbody_batch_pair_record``
+PAIR_RECORD_DTYPE = np.dtype([("partner", np.int32), ("mutual", np.int32), ("energy", np.float64), ("semi_major_axis", np.float64),
+                              ("eccentricity", np.float64), ("inclination", np.float64), ("separation", np.float64)])
+assert PAIR_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairRecord) == 48
 
 
 def _check(lib, status: int, handle) -> None:
@@ -441,6 +445,22 @@ class BatchedSystem:
         _check(self._lib, self._lib.nbody_batch_merge_read(self._h, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ev), self._h)
         return MergeResult(count, events)
 
+    def pairs(self) -> "PairResult":
+        """Every body's partner and the orbital elements of the pair (``include/nbody_batch_pairs.h`` states the rules), found
+        on the device from the current state (waits for the queued work).  The partner of body ``i`` is the body ``j`` of
+        its system with the smallest two-body energy ``v_ij**2 / 2 - (m_i + m_j) / r_ij`` (``G = 1``, no softening); with
+        massive counts (:meth:`set_massive_counts`) only massive bodies are partners and a test particle's own mass word
+        does not count.  The search runs in fp32, the elements of the chosen pair in fp64.  Changes nothing: an
+        :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        rec = np.zeros((self.num_systems, self.max_bodies), dtype=PAIR_RECORD_DTYPE)
+        binaries = np.zeros(self.num_systems, dtype=np.int64)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_pairs(self._h, _ptr(self.positions), _ptr(self.velocities),
+                                                      rec.ctypes.data_as(ctypes.POINTER(_lib.BatchPairRecord))), self._h)
+        _check(self._lib, self._lib.nbody_batch_pairs_binaries(self._h, binaries.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               self._h)
+        return PairResult(rec, binaries)
+
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
         _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
@@ -532,6 +552,32 @@ class AccretionResult:
         return f"AccretionResult(count={self.count.tolist()})"
 
 
+class PairResult:
+    """What :meth:`BatchedSystem.pairs` found.  ``(B, max_bodies)`` arrays: ``partner`` (int32, ``-1`` for a body without a
+    candidate), ``mutual`` (bool: the partner's partner is the body itself) and, float64, the pair's ``energy``
+    (``v**2 / 2 - mu / r``), ``semi_major_axis`` (negative for a hyperbolic pair, ``inf`` at zero energy), ``eccentricity``,
+    ``inclination`` (radians, against the z axis) and ``separation``; bodies without a partner and slots from the count on
+    read ``-1, False, 0, 0, 0, 0, 0``.  ``binaries`` (``(B,)`` int64): the mutual pairs with negative energy per system, each
+    counted once."""
+
+    def __init__(self, records, binaries):
+        self.partner = np.ascontiguousarray(records["partner"])
+        self.mutual = records["mutual"] != 0
+        self.energy, self.semi_major_axis, self.eccentricity, self.inclination, self.separation = (
+            np.ascontiguousarray(records[k]) for k in ("energy", "semi_major_axis", "eccentricity", "inclination", "separation"))
+        self.binaries = binaries
+
+    def bound_pairs(self, s: int) -> np.ndarray:
+        """The binaries of system ``s``: one row ``(i, j, a, e, energy)`` per mutual pair ``i < j`` with negative energy
+        (float64, ``(binaries[s], 5)``)."""
+        i = np.nonzero(self.mutual[s] & (self.energy[s] < 0.0) & (np.arange(self.partner.shape[1]) < self.partner[s]))[0]
+        return np.stack([i.astype(np.float64), self.partner[s, i].astype(np.float64), self.semi_major_axis[s, i],
+                         self.eccentricity[s, i], self.energy[s, i]], axis=1)
+
+    def __repr__(self):
+        return f"PairResult(binaries={self.binaries.tolist()})"
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -542,4 +588,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "MERGE_EVENT_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
 SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
            os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
-           os.path.join(CSRC, "nbody_batch_choice.h"),
+           os.path.join(CSRC, "nbody_batch_choice.h"), os.path.join(CSRC, "nbody_batch_pairs_elements.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_evolve.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),
@@ -25,7 +25,8 @@ HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_massive.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_fate.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_accrete.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_field.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_field.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_pairs.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -14,6 +14,7 @@
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
+#include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radii_check.h"
 #include "nbody_kernels.h"
 
@@ -3184,6 +3185,143 @@ hipError_t launch_batch_accrete(const BatchLaunch &l, const BatchEvolveArgs &p, 
     });
 }
 
+// ---- bound pairs (include/nbody_batch_pairs.h): every row's partner by the smallest two-body energy, the fp64 record of the
+// pair, and the binaries of every system.  A sibling of the force kernels: one workgroup per system with batch_shape's
+// workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  It reads the state and writes only the
+// handle's records and counts.
+
+static_assert(sizeof(BatchPairRecord) == sizeof(nbody_batch_pair_record) && sizeof(nbody_batch_pair_record) == 48 &&
+                  offsetof(BatchPairRecord, mutual) == offsetof(nbody_batch_pair_record, mutual) &&
+                  offsetof(BatchPairRecord, energy) == offsetof(nbody_batch_pair_record, energy) &&
+                  offsetof(BatchPairRecord, separation) == offsetof(nbody_batch_pair_record, separation),
+              "nbody_batch_pairs_elements.h mirrors the record of nbody_batch_pairs.h");
+
+// LDS: sh[2 j] = {x, y, z, m} and sh[2 j + 1] = {vx, vy, vz, partner} of body j (the Hermite families' layout, 128 KiB at
+// 4096 bodies); the partner's bits replace the unused fourth word of the velocity after the search.
+// m: the candidates are the columns j < m (the massive ones, or all n); a row r >= m is a test particle and adds no mass.
+// The search needs few registers at every RPL; the rolled fp64 record sets the kernel's count.  One row per lane is held to
+// the 64 registers of eight waves per SIMD, batch_hermite_kernel<1>'s; the other two shapes are below theirs unasked.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_pairs_kernel(const float4 *pos, const float4 *vel, const int *counts,
+                                                           const int *massive, int max_bodies, BatchPairRecord *records,
+                                                           int *binaries)
+{
+    extern __shared__ float4 sh[];
+    __shared__ int wave_binaries[16];
+    const int n = counts[blockIdx.x];
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the mass this row adds to mu}
+    float3 v[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            sh[2 * r] = x[q];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (r >= m)
+                x[q].w = 0.f;
+        }
+    }
+    __syncthreads();
+    float best[RPL];
+    int bj[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        best[q] = __builtin_inff();
+        bj[q] = -1;
+    }
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[2 * j], vj = sh[2 * j + 1];  // wave-uniform addresses: broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float wx = vj.x - v[q].x, wy = vj.y - v[q].y, wz = vj.z - v[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const float v2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+            const float inv = __builtin_amdgcn_rsqf(r2);
+            const float mu = pj.w + x[q].w;
+            const float eps = __builtin_fmaf(-mu, inv, 0.5f * v2);
+            const bool take = r2 > 0.f && eps < best[q];  // r2 == 0: the self pair and coincident bodies are no candidates
+            best[q] = take ? eps : best[q];
+            bj[q] = take ? j : bj[q];
+        }
+    }
+    __syncthreads();  // every lane is done with the columns before the partners replace the velocities' fourth words
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            sh[2 * r + 1].w = __int_as_float(bj[q]);
+    }
+    __syncthreads();
+    // The records, one row at a time from LDS (the loop is kept rolled: the fp64 arithmetic is instantiated once).
+    int mine = 0;
+#pragma unroll 1
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r >= max_bodies)
+            break;
+        BatchPairRecord rec = batch_pair_empty();
+        if (r < n) {
+            const float4 xi = sh[2 * r], vi = sh[2 * r + 1];
+            const int j = __float_as_int(vi.w);
+            if (j >= 0) {
+                const float4 xj = sh[2 * j], vj = sh[2 * j + 1];
+                const int mutual = __float_as_int(vj.w) == r ? 1 : 0;
+                const float pi[3] = {xi.x, xi.y, xi.z}, wi[3] = {vi.x, vi.y, vi.z};
+                const float pj[3] = {xj.x, xj.y, xj.z}, wj[3] = {vj.x, vj.y, vj.z};
+                const double mu = r < m ? (double)xj.w + (double)xi.w : (double)xj.w;
+                rec = batch_pair_record(j, mutual, pi, wi, pj, wj, mu);
+                mine += (mutual && rec.energy < 0.0 && r < j) ? 1 : 0;
+            }
+        }
+        records[base + r] = rec;
+    }
+    // binaries of the system: lanes -> wave -> workgroup
+    for (int off = 32; off > 0; off >>= 1)
+        mine += __shfl_down(mine, off, 64);
+    if ((tid & 63) == 0)
+        wave_binaries[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < T / 64; ++w)
+            total += wave_binaries[w];
+        binaries[blockIdx.x] = total;
+    }
+}
+
+// One launch over all systems.  Positions and velocities of a system's bodies in dynamic LDS: above the default 64 KiB from
+// 2049 bodies on, so the limit is raised first, as for the Hermite families (launch_batch_kernel).
+hipError_t launch_batch_pairs(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                              int max_bodies, BatchPairRecord *records, int *binaries, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = 2 * kBatchBytesPerBody * (size_t)max_bodies;
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, vel, counts, massive, max_bodies, records,
+                           binaries);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_pairs_kernel<1>);
+    case 2: return launch(batch_pairs_kernel<2>);
+    default: return launch(batch_pairs_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -3312,6 +3450,10 @@ struct nbody_batch {
     int field_components = 0;
     BatchFieldTerm *field_dev = nullptr;              // [n_systems][4] as the kernels take them, allocated by the first set
     nbody_batch_field_component *field_raw_dev = nullptr;  // [n_systems][4] as set, for nbody_batch_field_potential
+    // nbody_batch_pairs: the records and the binaries of the last call; they belong to no cache and nothing forgets them
+    BatchPairRecord *pairs_dev = nullptr;  // [n_systems][max_bodies], allocated by the first nbody_batch_pairs
+    int *pairs_binaries_dev = nullptr;     // [n_systems]
+    std::vector<int> pairs_binaries;       // host copy of the last call's, empty before any call
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -3549,6 +3691,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->accretions) (void)hipFree(b->accretions);
     if (b->field_dev) (void)hipFree(b->field_dev);
     if (b->field_raw_dev) (void)hipFree(b->field_raw_dev);
+    if (b->pairs_dev) (void)hipFree(b->pairs_dev);
+    if (b->pairs_binaries_dev) (void)hipFree(b->pairs_binaries_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -4171,6 +4315,42 @@ int nbody_batch_field_potential(nbody_batch *b, const float *d_pos, double *host
         e = hipStreamSynchronize(b->stream);
     (void)hipFree(phi);
     BATCH_TRY(b, e);
+    return NBODY_OK;
+}
+
+int nbody_batch_pairs(nbody_batch *b, const float *d_pos, const float *d_vel, nbody_batch_pair_record *records_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_pairs: batch is NULL");
+    if (!d_pos || !d_vel || !records_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pairs: NULL argument");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->pairs_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->pairs_dev, sizeof(BatchPairRecord) * slots));
+    if (!b->pairs_binaries_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->pairs_binaries_dev, sizeof(int) * B));
+    std::vector<int> found(B);
+    BATCH_TRY(b, launch_batch_pairs(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                    b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                    b->pairs_dev, b->pairs_binaries_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(records_out, b->pairs_dev, sizeof(BatchPairRecord) * slots, hipMemcpyDeviceToHost, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(found.data(), b->pairs_binaries_dev, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    b->pairs_binaries.swap(found);
+    return NBODY_OK;
+}
+
+int nbody_batch_pairs_binaries(nbody_batch *b, int64_t *count_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_pairs_binaries: batch is NULL");
+    if (!count_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pairs_binaries: NULL argument");
+    if (b->pairs_binaries.empty())
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_pairs_binaries: no nbody_batch_pairs call has been made");
+    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
+        count_out[s] = b->pairs_binaries[s];
     return NBODY_OK;
 }
 

@@ -1,0 +1,329 @@
+"""CPU-only: bound pairs of batched ensembles (nbody_batch_pairs, include/nbody_batch_pairs.h).  The header is self-contained
+C99, included by nbody.h after the field header, and declares its two entry points alone; they are exported, bound and listed
+apart; the fp64 record arithmetic (csrc/nbody_batch_pairs_elements.h), built into a stand-alone driver with g++, gives the
+closed forms of circular, elliptic, parabolic, hyperbolic, radial, retrograde and polar orbits and the mu = 0 case; the numpy
+reference (hermite_pairs_ref) finds the pairs of a known hierarchy and follows the test-particle rule; and on every input of
+the GPU suite the float32 search chooses the fp64 partner, so that those inputs, not a tolerance, carry the GPU test."""
+import ctypes
+import glob
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import hermite_pairs_ref as pref
+from conftest import ROOT
+
+PAIRS_NAMES = ["nbody_batch_pairs", "nbody_batch_pairs_binaries"]
+INCLUDE = os.path.join(ROOT, "include")
+CSRC = os.path.join(ROOT, "n_body_problem_amd", "csrc")
+#: fp64 round-off of a few dozen operations with a wide margin: every case below has |energy| >= 1e-3 of its two terms
+RTOL = 1e-9
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from n_body_problem_amd import _lib, build
+    build.build_library()
+    return _lib.load()
+
+
+def declared(text):
+    return set(re.findall(r"\b(nbody_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
+
+
+# ---- the surface --------------------------------------------------------------------------------------------------------
+def test_the_header_is_included_by_nbody_h_after_the_field_and_declares_its_two_entry_points_alone():
+    assert declared(open(os.path.join(INCLUDE, "nbody_batch_pairs.h")).read()) == set(PAIRS_NAMES)
+    for header in glob.glob(os.path.join(INCLUDE, "*.h")):
+        if os.path.basename(header) != "nbody_batch_pairs.h":
+            assert not declared(open(header).read()) & set(PAIRS_NAMES), header
+    res = subprocess.run(["gcc", "-E", "-P", "-std=c99", os.path.join(INCLUDE, "nbody.h")], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    assert set(PAIRS_NAMES) <= set(re.findall(r"\b(nbody_[a-z0-9_]+)\s*\(", res.stdout))
+    nbody_h = open(os.path.join(INCLUDE, "nbody.h")).read()
+    assert nbody_h.index('#include "nbody_batch_field.h"') < nbody_h.index('#include "nbody_batch_pairs.h"')
+
+
+def test_the_header_is_self_contained_c99_and_the_record_is_48_bytes(tmp_path):
+    src = tmp_path / "pairs.c"
+    src.write_text(r'''
+#include "nbody.h"
+#include <stddef.h>
+typedef char record_is_48_bytes[sizeof(nbody_batch_pair_record) == 48 ? 1 : -1];
+typedef char energy_at_8[offsetof(nbody_batch_pair_record, energy) == 8 ? 1 : -1];
+typedef char separation_at_40[offsetof(nbody_batch_pair_record, separation) == 40 ? 1 : -1];
+int main(void) {
+    nbody_batch_pair_record r = {-1, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int64_t n = 0;
+    return (nbody_batch_pairs(0, 0, 0, &r) != NBODY_ERR_INVALID) + (nbody_batch_pairs_binaries(0, &n) != NBODY_ERR_INVALID) +
+           (NBODY_ABI_VERSION != 5);
+}
+''')
+    res = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I" + INCLUDE, str(src)],
+                         capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+
+
+def test_the_header_states_the_rules_and_what_is_out_of_scope():
+    text = " ".join(open(os.path.join(INCLUDE, "nbody_batch_pairs.h")).read().replace(" *", " ").split())
+    for phrase in ("ABI version 5", "no new status", "smallest specific two-body energy", "G = 1", "no softening",
+                   "j < min(massive[s], counts[s])", "rows, never columns", "j == i is never a candidate",
+                   "fp32 squared distance is 0", "mu_ij = m_j when row i is a test particle", "v_rsq_f32",
+                   "eps = fmaf(-mu, inv, 0.5f v2)", "ties go to the lower j", "partner -1", "in fp64 from the fp32 state",
+                   "+inf at energy == 0", "the eccentricity vector", "acos(h_z / |h|)", "0 where |h| == 0",
+                   "Where mu == 0: semi_major_axis = 0 and eccentricity = +inf", "partner[partner[i]] == i", "counted once (i < j)",
+                   "{-1, 0, 0, 0, 0, 0, 0}", "frozen tracers are ordinary rows", "as nbody_batch_energy does", "NBODY_ERR_STATE",
+                   "names the function", "forgets nothing", "bit for bit", "allocated on first use", "Out of scope",
+                   "softened elements, triples and hierarchies, neighbour lists, and a search among test particles"):
+        assert phrase in text, phrase
+
+
+def test_the_names_are_mirrored_in_a_list_of_their_own_exported_and_bound(lib):
+    from n_body_problem_amd import _lib
+    assert set(_lib.pairs_names()) == set(PAIRS_NAMES)
+    assert not set(PAIRS_NAMES) & (set(_lib.exported_names()) | set(_lib.evolve_names()) | set(_lib.stop_names()) |
+                                   set(_lib.merge_exported_names()) | set(_lib.radii_names()) | set(_lib.massive_names()) |
+                                   set(_lib.fate_names()) | set(_lib.accrete_names()) | set(_lib.field_names()))
+    for name in PAIRS_NAMES:
+        assert hasattr(lib, name) and getattr(lib, name).argtypes is not None, name
+    assert ctypes.sizeof(_lib.BatchPairRecord) == 48
+    assert [f[0] for f in _lib.BatchPairRecord._fields_] == ["partner", "mutual", *pref.FIELDS]
+
+
+def test_the_abi_stays_at_version_5_and_null_handles_are_refused_without_a_device(lib):
+    from n_body_problem_amd import _lib
+    assert lib.nbody_abi_version() == 5
+    rec = (_lib.BatchPairRecord * 1)()
+    n = ctypes.c_int64(0)
+    assert lib.nbody_batch_pairs(None, None, None, rec) == _lib.NBODY_ERR_INVALID
+    assert b"nbody_batch_pairs: batch is NULL" in lib.nbody_batch_last_error(None)
+    assert lib.nbody_batch_pairs_binaries(None, ctypes.byref(n)) == _lib.NBODY_ERR_INVALID
+    assert b"nbody_batch_pairs_binaries: batch is NULL" in lib.nbody_batch_last_error(None)
+
+
+def test_the_python_wrapper_has_the_documented_surface():
+    import n_body_problem_amd as nb
+    from n_body_problem_amd import batch
+    assert list(inspect.signature(nb.BatchedSystem.pairs).parameters) == ["self"]
+    assert list(inspect.signature(nb.PairResult.bound_pairs).parameters) == ["self", "s"]
+    assert "PairResult" in batch.__all__ and nb.PairResult is batch.PairResult
+    assert batch.PAIR_RECORD_DTYPE.itemsize == 48 and list(batch.PAIR_RECORD_DTYPE.names) == ["partner", "mutual", *pref.FIELDS]
+    rec = np.zeros((2, 4), dtype=batch.PAIR_RECORD_DTYPE)
+    rec["partner"] = -1
+    rec[1, 0], rec[1, 2] = (2, 1, -0.5, 1.0, 0.6, 0.4, 0.7), (0, 1, -0.5, 1.0, 0.6, 0.4, 0.7)
+    rec[1, 1] = (0, 0, 0.3, -2.0, 1.5, 0.1, 9.0)
+    res = batch.PairResult(rec, np.array([0, 1], dtype=np.int64))
+    assert res.partner.dtype == np.int32 and res.mutual.dtype == bool and res.energy.dtype == np.float64
+    assert res.bound_pairs(0).shape == (0, 5) and res.bound_pairs(1).tolist() == [[0.0, 2.0, 1.0, 0.6, -0.5]]
+
+
+def test_the_cpp_wrapper_compiles_and_links(tmp_path):
+    from n_body_problem_amd import build
+    build.build_library()
+    src = tmp_path / "batch_pairs.cpp"
+    src.write_text(r'''
+#include "nbody.hpp"
+#include <cstdio>
+static_assert(sizeof(nbody_batch_pair_record) == 48, "the record");
+int main() {
+    try {
+        nbody::Batch b(16, 64);
+        std::vector<nbody_batch_pair_record> r = b.pairs(nullptr, nullptr);
+        std::vector<std::int64_t> n = b.binaries();
+        std::printf("%lld %lld\n", (long long)r.size(), (long long)n.size());
+    } catch (const std::exception &e) {
+        std::printf("error: %s\n", e.what());
+    }
+    return 0;
+}
+''')
+    exe = tmp_path / "batch_pairs"
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-L" + os.path.join(ROOT, "n_body_problem_amd"),
+           "-lnbody_amd", "-L/opt/rocm/lib", "-Wl,-rpath," + os.path.join(ROOT, "n_body_problem_amd"), "-Wl,-rpath,/opt/rocm/lib",
+           "-o", str(exe)]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+
+
+def test_the_elements_header_is_a_build_dependency_and_free_of_hip():
+    from n_body_problem_amd import build
+    assert os.path.join(CSRC, "nbody_batch_pairs_elements.h") in build.HEADERS
+    assert any(os.path.basename(h) == "nbody_batch_pairs.h" for h in build.HEADERS)
+    text = open(os.path.join(CSRC, "nbody_batch_pairs_elements.h")).read()
+    assert "hip/" not in text and "NBODY_HD inline" in text
+    assert '#include "nbody_batch_pairs_elements.h"' in open(os.path.join(CSRC, "nbody_batch.hip")).read()
+
+
+# ---- the elements, through the driver -------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("pairs") / "driver")
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I" + CSRC, os.path.join(ROOT, "tests", "batch_pairs_driver.cpp"), "-o", exe]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+
+    def run(cases):
+        """One record (partner, mutual, energy, a, e, inclination, separation) per case (xi, vi, xj, vj, mu)."""
+        lines = [c if isinstance(c, str) else " ".join(repr(float(u)) for u in (*c[0], *c[1], *c[2], *c[3], c[4])) for c in cases]
+        res = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr
+        out = [[float(w) for w in line.split()] for line in res.stdout.splitlines()]
+        assert len(out) == len(cases)
+        return out
+    return run
+
+
+O = (0.0, 0.0, 0.0)
+#: name -> ((xi, vi, xj, vj, mu), (energy, a, e, inclination, separation) in closed form); every number is exact in fp32
+ORBITS = {
+    "circular": ((O, O, (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), 1.0), (-0.5, 1.0, 0.0, 0.0, 1.0)),
+    # e = 0.5, a = 1, mu = 0.75: r_p = 0.5 with v_p = 1.5, r_a = 1.5 with v_a = 0.5
+    "pericentre of e = 0.5": ((O, O, (0.5, 0.0, 0.0), (0.0, 1.5, 0.0), 0.75), (-0.375, 1.0, 0.5, 0.0, 0.5)),
+    "apocentre of e = 0.5": ((O, O, (-1.5, 0.0, 0.0), (0.0, -0.5, 0.0), 0.75), (-0.375, 1.0, 0.5, 0.0, 1.5)),
+    "parabolic": ((O, O, (2.0, 0.0, 0.0), (0.0, 1.0, 0.0), 1.0), (0.0, np.inf, 1.0, 0.0, 2.0)),
+    "hyperbolic": ((O, O, (1.0, 0.0, 0.0), (0.0, 2.0, 0.0), 1.0), (1.0, -0.5, 3.0, 0.0, 1.0)),
+    "radial": ((O, O, (0.0, 0.0, 2.0), (0.0, 0.0, 0.5), 1.0), (-0.375, 4.0 / 3.0, 1.0, 0.0, 2.0)),
+    "retrograde": ((O, O, (1.0, 0.0, 0.0), (0.0, -1.0, 0.0), 1.0), (-0.5, 1.0, 0.0, np.pi, 1.0)),
+    "polar": ((O, O, (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), 1.0), (-0.5, 1.0, 0.0, np.pi / 2, 1.0)),
+    # the row is not at rest at the origin: only the differences count
+    "shifted and boosted": (((3.0, -2.0, 5.0), (0.25, 0.5, -1.0), (3.5, -2.0, 5.0), (0.25, 2.0, -1.0), 0.75), (-0.375, 1.0, 0.5, 0.0, 0.5)),
+    "mu = 0": ((O, O, (0.0, 2.0, 0.0), (1.0, 0.0, 0.0), 0.0), (0.5, 0.0, np.inf, np.pi, 2.0)),
+}
+
+
+@pytest.mark.parametrize("name", list(ORBITS))
+def test_the_elements_of_known_orbits(driver, name):
+    case, want = ORBITS[name]
+    partner, mutual, *got = driver([case])[0]
+    print(name, got, want)
+    assert (partner, mutual) == (1, 1)
+    for g, w, k in zip(got, want, pref.FIELDS):
+        if k == "eccentricity" and w == 0.0:
+            assert g < 1e-12, (k, g)                           # circular: the eccentricity vector cancels to round-off
+        elif w == 0.0 or np.isinf(w):
+            assert g == w, (k, g, w)
+        else:
+            assert abs(g - w) <= RTOL * abs(w), (k, g, w)
+    ref = pref.elements(*(np.asarray(u, np.float32) for u in case[:4]), np.float64(case[4]))
+    for g, w, k in zip(got, ref, pref.FIELDS):
+        assert g == w or abs(g - w) <= max(RTOL * abs(w), 1e-12 if k == "eccentricity" else 0.0), (k, g, w)
+
+
+def test_the_elements_of_random_pairs_agree_with_the_numpy_reference(driver):
+    rng = np.random.default_rng(31)
+    cases = []
+    while len(cases) < 200:
+        xi, vi, xj, vj = (rng.normal(size=3).astype(np.float32) for _ in range(4))
+        mu = float(rng.uniform(0.2, 3.0))
+        kin, pot = 0.5 * float(((vj - vi).astype(np.float64) ** 2).sum()), mu / float(np.linalg.norm((xj - xi).astype(np.float64)))
+        if abs(kin - pot) >= 1e-3 * (kin + pot):              # RTOL's premise
+            cases.append((xi, vi, xj, vj, mu))
+    worst = 0.0
+    for case, (_, _, *got) in zip(cases, driver(cases)):
+        ref = pref.elements(*case[:4], np.float64(case[4]))
+        for g, w in zip(got, ref):
+            worst = max(worst, abs(g - w) / abs(w))
+    print(f"worst relative difference {worst:.3g}")
+    assert worst <= RTOL
+
+
+def test_the_empty_record_and_the_size(driver):
+    assert driver(["empty", "sizeof"]) == [[-1, 0, 0, 0, 0, 0, 0], [48]]
+
+
+# ---- the reference itself ---------------------------------------------------------------------------------------------------
+def hierarchy():
+    """A tight binary (0, 3), a wide binary (1, 4) far from it, and a single (2) passing fast: the stated pairs."""
+    pos = np.zeros((5, 4), np.float32)
+    vel = np.zeros((5, 4), np.float32)
+    pos[:, 3] = [1.0, 0.5, 0.25, 1.0, 0.5]
+    pos[0, :3], pos[3, :3] = [-0.05, 0, 0], [0.05, 0, 0]
+    vel[0, :3], vel[3, :3] = [0, -2.2, 0], [0, 2.2, 0]        # mu / r = 20, v^2 / 2 = 9.68: bound
+    pos[1, :3], pos[4, :3] = [30, -1, 0], [30, 1, 0]
+    vel[1, :3], vel[4, :3] = [0, 0, -0.3], [0, 0, 0.3]         # mu / r = 0.5, v^2 / 2 = 0.18: bound
+    pos[2, :3], vel[2, :3] = [15, 10, 0], [0, -3, 0]          # v^2 / 2 >= 3 against everybody: unbound
+    return pos, vel
+
+
+def test_the_reference_finds_the_pairs_of_a_known_hierarchy():
+    pos, vel = hierarchy()
+    ref = pref.pairs(pos, vel, 5)
+    assert ref["partner"][[0, 3, 1, 4]].tolist() == [3, 0, 4, 1] and ref["mutual"].tolist() == [True, True, False, True, True]
+    assert ref["binaries"] == 2 and ref["energy"][2] > 0 and ref["semi_major_axis"][2] < 0 and ref["eccentricity"][2] > 1
+    assert np.allclose(ref["energy"][[0, 3]], 9.68 - 20.0, rtol=1e-6) and np.allclose(ref["separation"][[1, 4]], 2.0)
+    assert np.allclose(ref["inclination"][[0, 3]], [0.0, 0.0], atol=1e-12) and np.allclose(ref["inclination"][[1, 4]], np.pi / 2)
+    assert np.array_equal(pref.select_f32(pos, vel, 5), ref["partner"])
+    # fewer bodies than slots: the rest reads the empty record; n = 1 and n = 0 have no candidate
+    short = pref.pairs(pos, vel, 4)
+    assert short["partner"].tolist()[4] == -1 and not short["mutual"][4] and short["binaries"] == 1 and short["partner"][1] != 4
+    for n in (0, 1):
+        none = pref.pairs(pos, vel, n)
+        assert np.all(none["partner"] == -1) and none["binaries"] == 0 and not any(none[k].any() for k in pref.FIELDS)
+    # coincident bodies are no candidates, ties go to the lower j
+    twin, tv = np.zeros((3, 4), np.float32), np.zeros((3, 4), np.float32)
+    twin[:, 3] = 1.0
+    twin[1, :3] = twin[2, :3] = [1.0, 0.0, 0.0]                # bodies 1 and 2 coincide: equal energies against body 0
+    ref2 = pref.pairs(twin, tv, 3)
+    assert ref2["partner"].tolist() == [1, 0, 0] and ref2["mutual"].tolist() == [True, True, False] and ref2["binaries"] == 1
+    assert np.array_equal(pref.select_f32(twin, tv, 3), ref2["partner"])
+
+
+def test_the_test_particle_rule_gives_mu_equal_to_the_column_mass():
+    pos, vel = hierarchy()
+    on = pref.pairs(pos, vel, 5, massive=2)                    # bodies 0 and 1 are massive, 2, 3 and 4 feel them
+    assert np.all(on["partner"] < 2) and on["partner"].tolist() == [1, 0, on["partner"][2], 0, 1]
+    assert not on["mutual"][2:].any() and on["mutual"][:2].all()
+    # body 3 around body 0: mu = m_0 = 1, not m_0 + m_3 = 2
+    want = pref.elements(pos[3, :3], vel[3, :3], pos[0, :3], vel[0, :3], np.float64(1.0))
+    assert [on[k][3] for k in pref.FIELDS] == [float(u) for u in want]
+    assert on["energy"][3] == pytest.approx(0.5 * 4.4 ** 2 - 1.0 / 0.1, rel=1e-4)   # 9.68 - 10 from fp32 words
+    heavier = pos.copy()
+    heavier[2:, 3] *= 5.0                                      # the tracers' mass words bind nothing
+    again = pref.pairs(heavier, vel, 5, massive=2)
+    assert all(np.array_equal(on[k], again[k]) for k in ("partner", "mutual", *pref.FIELDS))
+    assert np.array_equal(pref.select_f32(pos, vel, 5, massive=2), on["partner"])
+    off = pref.pairs(pos, vel, 5, massive=0)
+    assert np.all(off["partner"] == -1) and off["binaries"] == 0
+    assert all(np.array_equal(pref.pairs(pos, vel, 5, massive=5)[k], pref.pairs(pos, vel, 5)[k]) for k in ("partner", *pref.FIELDS))
+
+
+def test_the_known_binary_has_its_closed_form_elements_in_the_reference():
+    """The analytic case of the GPU suite: 1e-6 is the fp32 rounding of the state, which the reference shares."""
+    for phase, E in pref.KNOWN_PHASES.items():
+        P, V, want = pref.known_binary(E)
+        ref = pref.pairs(P[0], V[0], 3)
+        assert ref["partner"].tolist() == [2, 0, 0] and ref["binaries"] == 1
+        got = [ref[k][0] for k in ("semi_major_axis", "eccentricity", "inclination", "energy", "separation")]
+        err = max(abs(g - w) / abs(w) for g, w in zip(got, want))
+        print(f"{phase}: {err:.3g}")
+        assert err <= 1e-6
+
+
+def test_the_inputs_condition():
+    """On every input of the GPU suite the float32 emulation of the search chooses the fp64 reference's partner on at least
+    99 % of the rows of every system, every chosen pair's energy is at least 1e-4 of its two terms (so that 1e-9 relative on
+    the records is round-off's to meet, not cancellation's), and the eccentricities of the binaries are away from 0."""
+    from test_batch_pairs_gpu import all_inputs
+    seen = 0
+    for name, P, V, counts, massive in all_inputs():
+        for s, n in enumerate(counts):
+            ms = None if massive is None else massive[s]
+            ref = pref.pairs(P[s], V[s], n, ms, chunk=512)
+            emu = pref.select_f32(P[s], V[s], n, ms, chunk=512)
+            agree = int((emu[:n] == ref["partner"][:n]).sum())
+            has = ref["partner"][:n] >= 0
+            print(f"{name}, system {s}: n = {n}, {agree} of {n} rows agree, {ref['binaries']} binaries")
+            assert agree >= 0.99 * n, (name, s, agree, n)
+            assert np.all(emu[n:] == -1)
+            if has.any():
+                ratio = np.abs(ref["energy"][:n][has]) / ref["terms"][:n][has]
+                assert ratio.min() >= 1e-4, (name, s, ratio.min())
+            bound = has & ref["mutual"][:n] & (ref["energy"][:n] < 0)
+            if bound.any() and massive is None:
+                assert ref["eccentricity"][:n][bound].min() >= 0.05, (name, s)
+            seen += 1
+    assert seen == 4 * 6 + 2 + 4

@@ -52,7 +52,12 @@ alternated, medians, both times, their ratio and the spread (max - min over the 
 1, 8, 64, n, one line per evolve(k, dt, levels=0): the call with a three-component field (bulge + disc + halo) against the
 same call with the field off, both with massive counts m and from the same state -- alternated, medians, both times, their
 ratio and the spread of each side's repeats.  The two runs differ (the field moves the bodies); the work per step does not
-depend on the state."""
+depend on the state.
+
+--pairs: instead, bound pairs (BatchedSystem.pairs).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one line per case:
+pairs() against energy(0) on the same state -- both synchronous calls, wall clock, alternated, medians and spreads.  pairs()
+evaluates n x n pairs with positions and velocities and returns 48 bytes per body; energy() evaluates the same pairs with
+positions alone and returns three numbers per system."""
 import argparse
 import json
 import os
@@ -91,6 +96,7 @@ ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolv
                 "feature off on the same state with the other bodies' mass words zero")
 ap.add_argument("--field", action="store_true", help="evolve(levels=0) with a three-component external field against the "
                 "field off, with massive counts m, on the same state")
+ap.add_argument("--pairs", action="store_true", help="pairs() against energy() on the same state, wall clock")
 args = ap.parse_args()
 
 
@@ -571,6 +577,39 @@ def accrete_lines():
                       "accrete_repeats": [round(x, 5) for x in t_acc], "remove_repeats": [round(x, 5) for x in t_rem]}), flush=True)
 
 
+def pairs_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            wall(batch.pairs)                           # the first call allocates the records and sets the kernel's LDS limit
+            wall(lambda: batch.energy(0.0))
+            tp, te = [], []
+            for _ in range(args.repeats):               # alternated
+                t, res = wall(batch.pairs)
+                tp.append(t)
+                te.append(wall(lambda: batch.energy(0.0))[0])
+            mp, me = statistics.median(tp), statistics.median(te)
+        print(json.dumps({"n": n, "B": B, "pairs_ms": round(mp, 3), "energy_ms": round(me, 3), "pairs_over_energy": round(mp / me, 3),
+                          "pair_evaluations_per_s": float(f"{B * n * n / (mp * 1e-3):.4g}"), "record_megabytes": round(B * n * 48 / 1e6, 1),
+                          "binaries_found": int(res.binaries.sum()), "pairs_spread": round((max(tp) - min(tp)) / mp, 4),
+                          "energy_spread": round((max(te) - min(te)) / me, 4), "pairs_repeats": [round(x, 3) for x in tp],
+                          "energy_repeats": [round(x, 3) for x in te]}), flush=True)
+
+
+if args.pairs:
+    pairs_lines()
+    sys.exit(0)
 if args.field:
     field_lines()
     sys.exit(0)
