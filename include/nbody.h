@@ -537,6 +537,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_field.h"
 /* bound pairs: every body's partner by two-body energy, the pair's orbital elements and the binaries of every system */
 #include "nbody_batch_pairs.h"
+/* cluster structure: neighbour densities, the density centre, core radius and density, Lagrangian radii of every system */
+#include "nbody_batch_structure.h"
 
 #ifdef __cplusplus
 }

@@ -484,6 +484,27 @@ public:
         check(nbody_batch_pairs_binaries(b_, n.data()), "nbody_batch_pairs_binaries");
         return n;
     }
+    // Cluster structure (nbody_batch_structure.h): per system the density centre, the core radius and density, the total weight
+    // and the Lagrangian radii about the centre that enclose the given fractions (up to eight), from every body's k-th
+    // neighbour density (1 <= k <= 8; weight NBODY_BATCH_WEIGHT_MASS or _NUMBER), found on the device from the positions in the
+    // caller's buffer.  The second form also fills numSystems x maxBodies per-body records laid out like the positions; the first
+    // copies 120 bytes per system and nothing per body.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_structure_system> structure(const float *dPositions, int k, int weight, const std::vector<double> &fractions)
+    {
+        std::vector<nbody_batch_structure_system> s((size_t)systems_);
+        check(nbody_batch_structure(b_, dPositions, k, weight, fractions.empty() ? nullptr : fractions.data(), (int)fractions.size(),
+                                    s.data(), nullptr), "nbody_batch_structure");
+        return s;
+    }
+    std::vector<nbody_batch_structure_system> structure(const float *dPositions, int k, int weight, const std::vector<double> &fractions,
+                                                        std::vector<nbody_batch_structure_body> &bodies)
+    {
+        std::vector<nbody_batch_structure_system> s((size_t)systems_);
+        bodies.resize((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_structure(b_, dPositions, k, weight, fractions.empty() ? nullptr : fractions.data(), (int)fractions.size(),
+                                    s.data(), bodies.data()), "nbody_batch_structure");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

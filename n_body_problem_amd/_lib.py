@@ -268,6 +268,31 @@ _PAIRS_PROTOTYPES = {
 }
 
 
+BATCH_WEIGHT_MASS = 0
+BATCH_WEIGHT_NUMBER = 1
+BATCH_STRUCTURE_MAX_NEIGHBOUR = 8
+BATCH_STRUCTURE_FRACTIONS = 8
+
+
+class BatchStructureBody(ctypes.Structure):
+    """``nbody_batch_structure_body`` of include/nbody_batch_structure.h."""
+    _fields_ = [("density", c_double), ("radius", c_double), ("enclosed", c_double), ("neighbour_r2", c_float),
+                ("neighbour_weight", c_float), ("inside", c_int), ("reserved", c_int)]
+
+
+class BatchStructureSystem(ctypes.Structure):
+    """``nbody_batch_structure_system`` of include/nbody_batch_structure.h."""
+    _fields_ = [("centre", c_double * 3), ("core_radius", c_double), ("core_density", c_double), ("total_weight", c_double),
+                ("lagrange", c_double * 8), ("estimated", c_int), ("reserved", c_int)]
+
+
+#: the entry point of include/nbody_batch_structure.h (cluster structure of batched ensembles), which nbody.h includes
+_STRUCTURE_PROTOTYPES = {
+    "nbody_batch_structure": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_double), c_int, POINTER(BatchStructureSystem),
+                                      POINTER(BatchStructureBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -294,7 +319,8 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(path)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
-                list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()):
+                list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
+                list(_STRUCTURE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -350,6 +376,11 @@ def field_names():
 def pairs_names():
     """The entry points of nbody_batch_pairs.h."""
     return list(_PAIRS_PROTOTYPES)
+
+
+def structure_names():
+    """The entry point of nbody_batch_structure.h."""
+    return list(_STRUCTURE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -34,6 +34,16 @@ assert MERGE_EVENT_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMergeEvent)
 PAIR_RECORD_DTYPE = np.dtype([("partner", np.int32), ("mutual", np.int32), ("energy", np.float64), ("semi_major_axis", np.float64),
                               ("eccentricity", np.float64), ("inclination", np.float64), ("separation", np.float64)])
 assert PAIR_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairRecord) == 48
+#: the records of :meth:`BatchedSystem.structure`: numpy's views of ``nbody_batch_structure_body`` and ``_system``
+STRUCTURE_BODY_DTYPE = np.dtype([("density", np.float64), ("radius", np.float64), ("enclosed", np.float64), ("neighbour_r2", np.float32),
+                                 ("neighbour_weight", np.float32), ("inside", np.int32), ("reserved", np.int32)])
+STRUCTURE_SYSTEM_DTYPE = np.dtype([("centre", np.float64, 3), ("core_radius", np.float64), ("core_density", np.float64),
+                                   ("total_weight", np.float64), ("lagrange", np.float64, 8), ("estimated", np.int32),
+                                   ("reserved", np.int32)])
+assert STRUCTURE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchStructureBody) == 40
+assert STRUCTURE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchStructureSystem) == 120
+#: the weight of a body in :meth:`BatchedSystem.structure`: its mass word, or 1
+WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
 
 def _check(lib, status: int, handle) -> None:
@@ -461,6 +471,28 @@ class BatchedSystem:
                self._h)
         return PairResult(rec, binaries)
 
+    def structure(self, k: int = 6, weight: str = "mass", fractions=(0.1, 0.5, 0.9), bodies: bool = True) -> "StructureResult":
+        """How every system is built (``include/nbody_batch_structure.h`` states the rules), found on the device from the
+        current positions (waits for the queued work): every body's density from its ``k``-th neighbour (Casertano & Hut's
+        unbiased estimator, ``1 <= k <= 8``), and per system the density centre, the core radius and density, and the
+        Lagrangian radii about the centre that enclose the given ``fractions`` (up to eight, each in ``(0, 1]``) of the
+        total weight.  ``weight``: ``"mass"`` (the mass words) or ``"number"`` (every body weighs 1, so that test particles
+        count).  All ``counts[s]`` bodies of a system take part, whatever the massive counts.  ``bodies=False`` skips the 40
+        bytes per body on their way to the host: the per-body arrays of the result are ``None``, the per-system ones the same
+        bits.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+        f = np.ascontiguousarray(np.asarray(fractions, dtype=np.float64).reshape(-1))
+        systems = np.zeros(self.num_systems, dtype=STRUCTURE_SYSTEM_DTYPE)
+        rec = np.zeros((self.num_systems, self.max_bodies), dtype=STRUCTURE_BODY_DTYPE) if bodies else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_structure(
+            self._h, _ptr(self.positions), int(k), WEIGHTS[weight],
+            f.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if f.size else None, int(f.size),
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchStructureSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchStructureBody)) if bodies else None), self._h)
+        return StructureResult(systems, rec, f, int(k), weight, self.counts)
+
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
         _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
@@ -578,6 +610,53 @@ class PairResult:
         return f"PairResult(binaries={self.binaries.tolist()})"
 
 
+class StructureResult:
+    """What :meth:`BatchedSystem.structure` found.  Per system: ``centre`` ``(B, 3)``, ``core_radius``, ``core_density``,
+    ``total_weight`` (float64, ``(B,)``), ``estimated`` (int32: the bodies that have a ``k``-th neighbour), ``fractions`` as
+    given and ``lagrangian`` ``(B, len(fractions))``, the radii about the centre that enclose them.  Per body, ``(B,
+    max_bodies)`` arrays or ``None`` without ``bodies``: ``density``, ``radius`` (from the centre), ``enclosed`` (the weight
+    within that radius, the body included), ``neighbour_distance`` (float64, to the ``k``-th neighbour; ``inf`` without one),
+    ``neighbour_weight`` (float32) and ``inside`` (int32), the weight and number of the bodies strictly nearer than that;
+    slots from the count on read 0.  ``k`` and ``weight`` as given, ``counts`` the systems' live counts at the call."""
+
+    def __init__(self, systems, bodies, fractions, k, weight, counts):
+        self.k, self.weight = k, weight
+        self.counts = np.array(counts, dtype=np.int64)
+        self.fractions = np.array(fractions, dtype=np.float64)
+        self.centre = np.ascontiguousarray(systems["centre"])
+        self.core_radius, self.core_density, self.total_weight, self.estimated = (
+            np.ascontiguousarray(systems[name]) for name in ("core_radius", "core_density", "total_weight", "estimated"))
+        self.lagrangian = np.ascontiguousarray(systems["lagrange"][:, :len(self.fractions)])
+        self.density = self.radius = self.enclosed = self.neighbour_distance = self.neighbour_weight = self.inside = None
+        if bodies is not None:
+            self.density, self.radius, self.enclosed, self.neighbour_weight, self.inside = (
+                np.ascontiguousarray(bodies[name]) for name in ("density", "radius", "enclosed", "neighbour_weight", "inside"))
+            self.neighbour_distance = np.sqrt(bodies["neighbour_r2"].astype(np.float64))
+
+    def lagrangian_radii(self, fractions) -> np.ndarray:
+        """The header's rule applied on the host to the per-body records, for fractions beyond eight or chosen afterwards:
+        ``(B, len(fractions))``, per fraction ``f`` the smallest ``radius`` whose ``enclosed`` is at least ``f * total_weight``,
+        the largest radius where no body qualifies, 0 for a system of no weight or no bodies.  Needs ``bodies=True``."""
+        if self.radius is None:
+            raise ValueError("lagrangian_radii needs the per-body records: structure(bodies=True)")
+        f = np.asarray(fractions, dtype=np.float64).reshape(-1)
+        if not np.all((f > 0.0) & (f <= 1.0)):
+            raise ValueError("a fraction must be in (0, 1]")
+        out = np.zeros((self.radius.shape[0], f.size))
+        for s in range(self.radius.shape[0]):
+            n = int(self.counts[s])
+            if self.total_weight[s] == 0.0 or n == 0:
+                continue
+            radius, enclosed = self.radius[s, :n], self.enclosed[s, :n]
+            for q, fq in enumerate(f):
+                ok = enclosed >= fq * self.total_weight[s]
+                out[s, q] = radius[ok].min() if ok.any() else radius.max()
+        return out
+
+    def __repr__(self):
+        return f"StructureResult(k={self.k}, weight={self.weight!r}, core_radius={self.core_radius.tolist()})"
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -588,4 +667,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

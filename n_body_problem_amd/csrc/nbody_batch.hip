@@ -16,6 +16,7 @@
 #include "nbody_batch_choice.h"
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radii_check.h"
+#include "nbody_batch_structure_math.h"
 #include "nbody_kernels.h"
 
 #include <algorithm>
@@ -3322,6 +3323,268 @@ hipError_t launch_batch_pairs(const float4 *pos, const float4 *vel, const int *c
     }
 }
 
+// ---- cluster structure (include/nbody_batch_structure.h): every row's k-th neighbour distance, neighbour weight and density,
+// and per system the density centre, core radius and density, and the Lagrangian radii about the centre.  A sibling of
+// batch_pairs_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per
+// lane at r = q * T + lane.  It reads the positions and writes only the handle's records.
+
+static_assert(sizeof(BatchStructureBody) == sizeof(nbody_batch_structure_body) && sizeof(nbody_batch_structure_body) == 40 &&
+                  offsetof(BatchStructureBody, radius) == offsetof(nbody_batch_structure_body, radius) &&
+                  offsetof(BatchStructureBody, enclosed) == offsetof(nbody_batch_structure_body, enclosed) &&
+                  offsetof(BatchStructureBody, neighbour_r2) == offsetof(nbody_batch_structure_body, neighbour_r2) &&
+                  offsetof(BatchStructureBody, neighbour_weight) == offsetof(nbody_batch_structure_body, neighbour_weight) &&
+                  offsetof(BatchStructureBody, inside) == offsetof(nbody_batch_structure_body, inside),
+              "nbody_batch_structure_math.h mirrors the body record of nbody_batch_structure.h");
+static_assert(sizeof(BatchStructureSystem) == sizeof(nbody_batch_structure_system) && sizeof(nbody_batch_structure_system) == 120 &&
+                  offsetof(BatchStructureSystem, core_radius) == offsetof(nbody_batch_structure_system, core_radius) &&
+                  offsetof(BatchStructureSystem, core_density) == offsetof(nbody_batch_structure_system, core_density) &&
+                  offsetof(BatchStructureSystem, total_weight) == offsetof(nbody_batch_structure_system, total_weight) &&
+                  offsetof(BatchStructureSystem, lagrange) == offsetof(nbody_batch_structure_system, lagrange) &&
+                  offsetof(BatchStructureSystem, estimated) == offsetof(nbody_batch_structure_system, estimated),
+              "nbody_batch_structure_math.h mirrors the system record of nbody_batch_structure.h");
+static_assert(kStructureMaxNeighbour == NBODY_BATCH_STRUCTURE_MAX_NEIGHBOUR && kStructureFractions == NBODY_BATCH_STRUCTURE_FRACTIONS,
+              "nbody_batch_structure_math.h mirrors the limits of nbody_batch_structure.h");
+
+struct BatchStructureArgs {
+    double fraction[kStructureFractions];
+    int n_fractions, k, weight;
+};
+
+constexpr int kStructureSums = 10;  // sum rho, rho x, rho y, rho z, rho^2, w, w x, w y, w z, and the bodies with a k-th neighbour
+
+// The workgroup's sums of N values in a fixed order -- the lanes of a wave by shuffles, the waves in ascending order through
+// red[16][N] -- returned to every lane.
+template <int N>
+__device__ inline void structure_block_sum(double (&v)[N], double *red, int tid, int T)
+{
+#pragma unroll
+    for (int c = 0; c < N; ++c)
+        for (int off = 32; off > 0; off >>= 1)
+            v[c] += __shfl_down(v[c], off, 64);
+    __syncthreads();  // every lane has read what red held before
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            red[(tid >> 6) * N + c] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        double s = red[c];
+        for (int w = 1; w < T / 64; ++w)
+            s += red[w * N + c];
+        v[c] = s;
+    }
+}
+
+// The workgroup's minimum, returned to every lane.
+__device__ inline double structure_block_min(double v, double *red, int tid, int T)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v = fmin(v, __shfl_down(v, off, 64));
+    __syncthreads();
+    if ((tid & 63) == 0)
+        red[tid >> 6] = v;
+    __syncthreads();
+    double m = red[0];
+    for (int w = 1; w < T / 64; ++w)
+        m = fmin(m, red[w]);
+    return m;
+}
+
+// LDS: sh[j] = {x, y, z, w_j} of body j (64 KiB at 4096 bodies; with the reduction words above the default limit, which is
+// raised before the launch); after the densities the same bytes hold {s_j, (double)w_j}, 16 bytes per body again.
+// The eight smallest r2 of every row stay in registers (structure_insert); one row per lane is held to the 64 registers of
+// eight waves per SIMD, batch_hermite_kernel<1>'s.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_structure_kernel(
+    const float4 *pos, const int *counts, int max_bodies, BatchStructureArgs p, BatchStructureBody *bodies, BatchStructureSystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ double red[16 * kStructureSums];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float inf = __builtin_inff();
+    float4 x[RPL];  // {x, y, z, w}
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            if (p.weight == NBODY_BATCH_WEIGHT_NUMBER)
+                x[q].w = 1.f;
+            sh[r] = x[q];
+        }
+    }
+    __syncthreads();
+    // Phase 1: the k-th smallest r2 > 0 of every row.
+    float r2k[RPL];
+    {
+        float a[RPL][kStructureMaxNeighbour];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+#pragma unroll
+            for (int t = 0; t < kStructureMaxNeighbour; ++t)
+                a[q][t] = inf;
+        // Measured on an MI355X (profiles/batch_rate_structure.txt): unrolled by 4 the kernel is 4 % faster than by 2, and a
+        // wave-uniform skip of the insertion (no lane's r2 below its list's largest; the same bits) costs 19 - 25 % at 1024
+        // bodies and 2 - 7 % at 4096 -- some lane of 64 nearly always inserts, and the vote and branch are paid per column.
+        // So: 4, no skip.
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const float4 pj = sh[j];  // a wave-uniform address: one broadcast LDS read (ds_read_b96: the weight is not needed)
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+                const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                structure_insert(a[q], r2 > 0.f ? r2 : inf);  // the self pair, coincident bodies and NaN are no neighbour pairs
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            r2k[q] = structure_kth(a[q], p.k);
+    }
+    // Phase 2: the pairs strictly inside the k-th distance, and their weight in ascending j.
+    int inside[RPL];
+    float nw[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        inside[q] = 0;
+        nw[q] = 0.f;
+    }
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = sh[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const bool in = r2 > 0.f && r2 < r2k[q];
+            inside[q] += in ? 1 : 0;
+            nw[q] += in ? pj.w : 0.f;  // + 0 leaves the sum's bits: no branch
+        }
+    }
+    // Phase 3: densities, the system's sums, the centre.
+    double rho[RPL], sum[kStructureSums];
+#pragma unroll
+    for (int c = 0; c < kStructureSums; ++c)
+        sum[c] = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const bool live = q * T + tid < n;
+        rho[q] = live ? structure_density(r2k[q], nw[q]) : 0.0;
+        const double w = live ? (double)x[q].w : 0.0;
+        sum[0] += rho[q];
+        sum[1] += rho[q] * (double)x[q].x;
+        sum[2] += rho[q] * (double)x[q].y;
+        sum[3] += rho[q] * (double)x[q].z;
+        sum[4] += rho[q] * rho[q];
+        sum[5] += w;
+        sum[6] += w * (double)x[q].x;
+        sum[7] += w * (double)x[q].y;
+        sum[8] += w * (double)x[q].z;
+        sum[9] += live && r2k[q] < inf ? 1.0 : 0.0;
+    }
+    structure_block_sum(sum, red, tid, T);  // its barriers: every lane is done with the columns
+    const bool none = sum[0] == 0.0, zero = none && sum[5] == 0.0;
+    double cx = 0.0, cy = 0.0, cz = 0.0;
+    if (!zero) {
+        cx = none ? sum[6] / sum[5] : sum[1] / sum[0];
+        cy = none ? sum[7] / sum[5] : sum[2] / sum[0];
+        cz = none ? sum[8] / sum[5] : sum[3] / sum[0];
+    }
+    // Phase 4: radii about the centre, the core radius, the enclosed weights and the Lagrangian radii.
+    double2 *sd = reinterpret_cast<double2 *>(sh);
+    double s[RPL], core[1] = {0.0};
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const double dx = (double)x[q].x - cx, dy = (double)x[q].y - cy, dz = (double)x[q].z - cz;
+        s[q] = r < n ? dx * dx + dy * dy + dz * dz : 0.0;
+        core[0] += rho[q] * rho[q] * s[q];
+        if (r < n)
+            sd[r] = make_double2(s[q], (double)x[q].w);
+    }
+    structure_block_sum(core, red, tid, T);  // its barriers: the {s_j, w_j} are in place
+    double enc[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        enc[q] = 0.0;
+#pragma unroll 2
+    for (int j = 0; j < n; ++j) {
+        const double2 cj = sd[j];  // broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            enc[q] += cj.x <= s[q] ? cj.y : 0.0;
+    }
+    double radius[RPL], far = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        radius[q] = sqrt(s[q]);
+        far = fmax(far, radius[q]);  // rows from the count on have s = 0
+    }
+    far = 0.0 - structure_block_min(-far, red, tid, T);  // the largest radius; 0 without bodies
+    // The system record, field by field: a record indexed by the fraction would live in scratch memory.
+    BatchStructureSystem *out = systems + blockIdx.x;
+    if (tid == 0) {
+        out->centre[0] = cx;
+        out->centre[1] = cy;
+        out->centre[2] = cz;
+        out->core_radius = none ? 0.0 : sqrt(core[0] / sum[4]);
+        out->core_density = none ? 0.0 : sum[4] / sum[0];
+        out->total_weight = zero ? 0.0 : sum[5];
+        out->estimated = (int)sum[9];
+        out->reserved = 0;
+    }
+#pragma unroll 1
+    for (int f = 0; f < p.n_fractions; ++f) {
+        const double target = p.fraction[f] * sum[5];
+        double m = (double)inf;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            m = (q * T + tid < n && enc[q] >= target) ? fmin(m, radius[q]) : m;
+        m = structure_block_min(m, red, tid, T);
+        if (tid == 0)
+            out->lagrange[f] = zero ? 0.0 : (m < (double)inf ? m : far);
+    }
+    if (tid == 0)
+        for (int f = p.n_fractions; f < kStructureFractions; ++f)
+            out->lagrange[f] = 0.0;  // unused slots
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = r < n ? BatchStructureBody{rho[q], radius[q], enc[q], r2k[q], nw[q], inside[q], 0}
+                                         : structure_empty_body();
+        }
+    }
+}
+
+// One launch over all systems.  64 KiB of dynamic LDS at 4096 bodies beside the reduction words: the limit is raised first, as
+// launch_batch_pairs does.  bodies may be NULL: the per-body records are then not stored.
+hipError_t launch_batch_structure(const float4 *pos, const int *counts, int n_systems, int max_bodies, const BatchStructureArgs &p,
+                                  BatchStructureBody *bodies, BatchStructureSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, counts, max_bodies, p, bodies, systems);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_structure_kernel<1>);
+    case 2: return launch(batch_structure_kernel<2>);
+    default: return launch(batch_structure_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -3454,6 +3717,9 @@ struct nbody_batch {
     BatchPairRecord *pairs_dev = nullptr;  // [n_systems][max_bodies], allocated by the first nbody_batch_pairs
     int *pairs_binaries_dev = nullptr;     // [n_systems]
     std::vector<int> pairs_binaries;       // host copy of the last call's, empty before any call
+    // nbody_batch_structure: the records of the last call, each allocated by the first call that asks for it
+    BatchStructureSystem *structure_systems_dev = nullptr;  // [n_systems]
+    BatchStructureBody *structure_bodies_dev = nullptr;     // [n_systems][max_bodies]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -3693,6 +3959,8 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->field_raw_dev) (void)hipFree(b->field_raw_dev);
     if (b->pairs_dev) (void)hipFree(b->pairs_dev);
     if (b->pairs_binaries_dev) (void)hipFree(b->pairs_binaries_dev);
+    if (b->structure_systems_dev) (void)hipFree(b->structure_systems_dev);
+    if (b->structure_bodies_dev) (void)hipFree(b->structure_bodies_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -4351,6 +4619,46 @@ int nbody_batch_pairs_binaries(nbody_batch *b, int64_t *count_out)
         return bfail(b, NBODY_ERR_STATE, "nbody_batch_pairs_binaries: no nbody_batch_pairs call has been made");
     for (size_t s = 0; s < (size_t)b->n_systems; ++s)
         count_out[s] = b->pairs_binaries[s];
+    return NBODY_OK;
+}
+
+int nbody_batch_structure(nbody_batch *b, const float *d_pos, int k, int weight, const double *fractions, int n_fractions,
+                          nbody_batch_structure_system *systems_out, nbody_batch_structure_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_structure: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: NULL argument");
+    if (k < 1 || k > NBODY_BATCH_STRUCTURE_MAX_NEIGHBOUR)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: k must be 1 ... 8");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (n_fractions < 0 || n_fractions > NBODY_BATCH_STRUCTURE_FRACTIONS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: n_fractions must be 0 ... 8");
+    if (n_fractions > 0 && !fractions)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: fractions is NULL");
+    BatchStructureArgs p{};
+    p.n_fractions = n_fractions;
+    p.k = k;
+    p.weight = weight;
+    for (int q = 0; q < n_fractions; ++q) {
+        if (!(fractions[q] > 0.0 && fractions[q] <= 1.0))  // NaN is refused too
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: a fraction must be in (0, 1]");
+        p.fraction[q] = fractions[q];
+    }
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->structure_systems_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->structure_systems_dev, sizeof(BatchStructureSystem) * B));
+    if (bodies_out && !b->structure_bodies_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->structure_bodies_dev, sizeof(BatchStructureBody) * slots));
+    BATCH_TRY(b, launch_batch_structure(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, (int)b->n_systems, (int)b->max_bodies, p,
+                                        bodies_out ? b->structure_bodies_dev : nullptr, b->structure_systems_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(systems_out, b->structure_systems_dev, sizeof(BatchStructureSystem) * B, hipMemcpyDeviceToHost, b->stream));
+    if (bodies_out)
+        BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->structure_bodies_dev, sizeof(BatchStructureBody) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }
 

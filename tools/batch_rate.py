@@ -57,7 +57,13 @@ depend on the state.
 --pairs: instead, bound pairs (BatchedSystem.pairs).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one line per case:
 pairs() against energy(0) on the same state -- both synchronous calls, wall clock, alternated, medians and spreads.  pairs()
 evaluates n x n pairs with positions and velocities and returns 48 bytes per body; energy() evaluates the same pairs with
-positions alone and returns three numbers per system."""
+positions alone and returns three numbers per system.
+
+--structure: instead, the cluster structure (BatchedSystem.structure).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one
+line per case: structure() with the per-body records and with bodies=False against energy(0) and pairs() on the same state --
+all synchronous calls, wall clock, alternated, medians and spreads.  structure() walks the n x n pairs three times (the
+eight-smallest lists, the neighbours inside the k-th distance, the enclosed weights in fp64) and returns 120 bytes per system
+and, with the records, 40 bytes per body.  The kernel's time alone comes from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -97,6 +103,8 @@ ap.add_argument("--massive", action="store_true", help="Hermite step_n and evolv
 ap.add_argument("--field", action="store_true", help="evolve(levels=0) with a three-component external field against the "
                 "field off, with massive counts m, on the same state")
 ap.add_argument("--pairs", action="store_true", help="pairs() against energy() on the same state, wall clock")
+ap.add_argument("--structure", action="store_true", help="structure() with and without the per-body records against energy() "
+                "and pairs() on the same state, wall clock")
 args = ap.parse_args()
 
 
@@ -607,6 +615,50 @@ def pairs_lines():
                           "energy_repeats": [round(x, 3) for x in te]}), flush=True)
 
 
+def structure_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"structure": batch.structure, "structure_lean": lambda: batch.structure(bodies=False),
+                     "energy": lambda: batch.energy(0.0), "pairs": batch.pairs}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    if name == "structure":
+                        res = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        line.update({"lean_over_energy": round(med["structure_lean"] / med["energy"], 3),
+                     "pair_walks_per_s": float(f"{3 * B * n * n / (med['structure_lean'] * 1e-3):.4g}"),
+                     "record_megabytes": round(B * n * 40 / 1e6, 1), "system_kilobytes": round(B * 120 / 1e3, 1),
+                     "median_core_radius": round(float(np.median(res.core_radius)), 4),
+                     "median_half_weight_radius": round(float(np.median(res.lagrangian[:, 1])), 4)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.structure:
+    structure_lines()
+    sys.exit(0)
 if args.pairs:
     pairs_lines()
     sys.exit(0)
