@@ -539,6 +539,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_pairs.h"
 /* cluster structure: neighbour densities, the density centre, core radius and density, Lagrangian radii of every system */
 #include "nbody_batch_structure.h"
+/* bound members: per-body potentials and energies by iterative unbinding, the bound mass and its frame of every system */
+#include "nbody_batch_members.h"
 
 #ifdef __cplusplus
 }

@@ -505,6 +505,30 @@ public:
                                     s.data(), bodies.data()), "nbody_batch_structure");
         return s;
     }
+    // Bound members (nbody_batch_members.h): iterative unbinding on the device from the state in the caller's buffers -- per
+    // system the bound mass, its centre and velocity, the kinetic and potential energy of the final member sources, the member
+    // counts and the iterations evaluated (1 <= maxIterations <= 64).  initial: numSystems x maxBodies bytes that pick the
+    // starting set, or nullptr for every body.  The second form also fills numSystems x maxBodies per-body records (potential,
+    // energy, member, removed_at) laid out like the positions; the first copies 88 bytes per system and nothing per body.
+    // Changes nothing the handle keeps.
+    std::vector<nbody_batch_member_system> members(const float *dPositions, const float *dVelocities, float softening,
+                                                   int maxIterations = 32, const unsigned char *initial = nullptr)
+    {
+        std::vector<nbody_batch_member_system> s((size_t)systems_);
+        check(nbody_batch_members(b_, dPositions, dVelocities, softening, maxIterations, initial, s.data(), nullptr),
+              "nbody_batch_members");
+        return s;
+    }
+    std::vector<nbody_batch_member_system> members(const float *dPositions, const float *dVelocities, float softening,
+                                                   int maxIterations, const unsigned char *initial,
+                                                   std::vector<nbody_batch_member_body> &bodies)
+    {
+        std::vector<nbody_batch_member_system> s((size_t)systems_);
+        bodies.resize((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_members(b_, dPositions, dVelocities, softening, maxIterations, initial, s.data(), bodies.data()),
+              "nbody_batch_members");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

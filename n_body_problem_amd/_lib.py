@@ -293,6 +293,27 @@ _STRUCTURE_PROTOTYPES = {
 }
 
 
+BATCH_MEMBERS_MAX_ITERATIONS = 64
+
+
+class BatchMemberBody(ctypes.Structure):
+    """``nbody_batch_member_body`` of include/nbody_batch_members.h."""
+    _fields_ = [("potential", c_double), ("energy", c_double), ("member", c_int), ("removed_at", c_int)]
+
+
+class BatchMemberSystem(ctypes.Structure):
+    """``nbody_batch_member_system`` of include/nbody_batch_members.h."""
+    _fields_ = [("bound_mass", c_double), ("centre", c_double * 3), ("velocity", c_double * 3), ("kinetic", c_double),
+                ("potential", c_double), ("members", c_int), ("sources", c_int), ("iterations", c_int), ("converged", c_int)]
+
+
+#: the entry point of include/nbody_batch_members.h (bound members of batched ensembles), which nbody.h includes
+_MEMBERS_PROTOTYPES = {
+    "nbody_batch_members": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, POINTER(BatchMemberSystem),
+                                    POINTER(BatchMemberBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -320,7 +341,7 @@ def load() -> ctypes.CDLL:
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
-                list(_STRUCTURE_PROTOTYPES.items()):
+                list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -381,6 +402,11 @@ def pairs_names():
 def structure_names():
     """The entry point of nbody_batch_structure.h."""
     return list(_STRUCTURE_PROTOTYPES)
+
+
+def members_names():
+    """The entry point of nbody_batch_members.h."""
+    return list(_MEMBERS_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

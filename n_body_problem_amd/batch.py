@@ -42,6 +42,13 @@ STRUCTURE_SYSTEM_DTYPE = np.dtype([("centre", np.float64, 3), ("core_radius", np
                                    ("reserved", np.int32)])
 assert STRUCTURE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchStructureBody) == 40
 assert STRUCTURE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchStructureSystem) == 120
+#: the records of :meth:`BatchedSystem.members`: numpy's views of ``nbody_batch_member_body`` and ``_system``
+MEMBER_BODY_DTYPE = np.dtype([("potential", np.float64), ("energy", np.float64), ("member", np.int32), ("removed_at", np.int32)])
+MEMBER_SYSTEM_DTYPE = np.dtype([("bound_mass", np.float64), ("centre", np.float64, 3), ("velocity", np.float64, 3),
+                                ("kinetic", np.float64), ("potential", np.float64), ("members", np.int32), ("sources", np.int32),
+                                ("iterations", np.int32), ("converged", np.int32)])
+assert MEMBER_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMemberBody) == 24
+assert MEMBER_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMemberSystem) == 88
 #: the weight of a body in :meth:`BatchedSystem.structure`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -493,6 +500,45 @@ class BatchedSystem:
             rec.ctypes.data_as(ctypes.POINTER(_lib.BatchStructureBody)) if bodies else None), self._h)
         return StructureResult(systems, rec, f, int(k), weight, self.counts)
 
+    def members(self, softening: float, max_iterations: int = 32, initial=None, bodies: bool = True) -> "MemberResult":
+        """Which bodies still belong to their system, and how much mass that is (``include/nbody_batch_members.h`` states the
+        rules): iterative unbinding on the device from the current state (waits for the queued work).  Every body's
+        potential from the member sources (fp32 pair terms as :meth:`energy` forms them, fp64 sums) and its energy in their
+        centre-of-mass frame; the bodies with energy ``>= 0`` leave; again with the survivors until nothing changes or
+        ``max_iterations`` (1 ... 64) are done.  With massive counts (:meth:`set_massive_counts`) only massive bodies are
+        sources; test particles can be members and their mass words are not read.  ``initial``: a ``(B, max_bodies)`` bool
+        or uint8 array that picks the starting set, or ``None`` for every body.  The criterion is the self-gravity of the
+        set alone: an external field is not part of it.  ``bodies=False`` skips the 24 bytes per body on their way to the
+        host: the per-body arrays of the result are ``None``, the per-system ones the same bits.  Changes nothing: an
+        :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        init = None
+        if initial is not None:
+            init = np.ascontiguousarray(np.asarray(initial))
+            if init.dtype != np.bool_ and init.dtype != np.uint8:
+                raise ValueError(f"initial must be bool or uint8, not {init.dtype}")
+            if init.shape != (self.num_systems, self.max_bodies):
+                raise ValueError(f"initial must have shape ({self.num_systems}, {self.max_bodies}), got {tuple(init.shape)}")
+            init = init.view(np.uint8)
+        systems = np.zeros(self.num_systems, dtype=MEMBER_SYSTEM_DTYPE)
+        rec = np.zeros((self.num_systems, self.max_bodies), dtype=MEMBER_BODY_DTYPE) if bodies else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_members(
+            self._h, _ptr(self.positions), _ptr(self.velocities), float(softening), int(max_iterations),
+            init.ctypes.data_as(ctypes.c_void_p) if init is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchMemberSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchMemberBody)) if bodies else None), self._h)
+        return MemberResult(systems, rec, self._source_mass())
+
+    def _source_mass(self) -> np.ndarray:
+        """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
+        fp64 sum of the massive bodies' mass words alone."""
+        massive = self.massive_counts
+        if massive is None:
+            return self.momentum()[:, 3]
+        m = self.positions[:, :, 3].cpu().numpy().astype(np.float64)
+        source = np.arange(self.max_bodies)[None, :] < np.minimum(massive, self._counts)[:, None]
+        return np.where(source, m, 0.0).sum(axis=1)
+
     def sync(self) -> None:
         """Wait for the queued work and report a kernel failure."""
         _check(self._lib, self._lib.nbody_batch_sync(self._h), self._h)
@@ -657,6 +703,39 @@ class StructureResult:
         return f"StructureResult(k={self.k}, weight={self.weight!r}, core_radius={self.core_radius.tolist()})"
 
 
+class MemberResult:
+    """What :meth:`BatchedSystem.members` found.  Per system (``(B,)`` arrays): ``bound_mass`` (float64, the mass words of the
+    final member sources), ``centre`` and ``velocity`` (``(B, 3)``, their centre of mass and its velocity; 0 where nothing is
+    bound), ``kinetic_energy`` and ``potential_energy`` (over the final member sources, in the last iteration's frame and
+    potential: exact for the final set when converged), ``count`` (int32: the final members, test particles included),
+    ``sources`` (int32: the final member sources), ``iterations`` (int32: those evaluated) and ``converged`` (bool: the last one
+    removed nobody or left no member).  ``source_mass`` (float64): the mass of all sources, members or not, as
+    :meth:`BatchedSystem.momentum` counts it.  Per body, ``(B, max_bodies)`` arrays or ``None`` without ``bodies``: ``member``
+    (bool), ``removed_at`` (int32: the iteration that removed the body; 0 for a member and for a body outside ``initial``),
+    ``potential`` and ``energy`` (float64, the last iteration's); slots from the count on read 0."""
+
+    def __init__(self, systems, bodies, source_mass):
+        self.source_mass = np.array(source_mass, dtype=np.float64)
+        self.bound_mass = np.ascontiguousarray(systems["bound_mass"])
+        self.centre, self.velocity = np.ascontiguousarray(systems["centre"]), np.ascontiguousarray(systems["velocity"])
+        self.kinetic_energy, self.potential_energy = np.ascontiguousarray(systems["kinetic"]), np.ascontiguousarray(systems["potential"])
+        self.count, self.sources, self.iterations = (np.ascontiguousarray(systems[name]) for name in ("members", "sources", "iterations"))
+        self.converged = systems["converged"] != 0
+        self.member = self.removed_at = self.potential = self.energy = None
+        if bodies is not None:
+            self.member = bodies["member"] != 0
+            self.removed_at, self.potential, self.energy = (np.ascontiguousarray(bodies[name]) for name in ("removed_at", "potential", "energy"))
+
+    def bound_fraction(self) -> np.ndarray:
+        """``(B,)`` float64: ``bound_mass`` over the mass of all sources; 0 for a system without source mass."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.source_mass != 0.0, self.bound_mass / self.source_mass, 0.0)
+
+    def __repr__(self):
+        return (f"MemberResult(bound_mass={self.bound_mass.tolist()}, count={self.count.tolist()}, "
+                f"iterations={self.iterations.tolist()}, converged={self.converged.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -667,4 +746,4 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -14,6 +14,7 @@
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
+#include "nbody_batch_members_math.h"
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radii_check.h"
 #include "nbody_batch_structure_math.h"
@@ -3585,6 +3586,222 @@ hipError_t launch_batch_structure(const float4 *pos, const int *counts, int n_sy
     }
 }
 
+// ---- bound members (include/nbody_batch_members.h): iterative unbinding.  Every row's potential from the member sources and
+// its energy in their rest frame, the rows with e >= 0 dropped, again with the survivors until nothing changes; then the bound
+// mass, centre, velocity and energies of what is left.  A sibling of batch_structure_kernel: one workgroup per system with
+// batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  The iterations run inside
+// the kernel: the member mask and the frame never leave the CU.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchMemberBody) == sizeof(nbody_batch_member_body) && sizeof(nbody_batch_member_body) == 24 &&
+                  offsetof(BatchMemberBody, energy) == offsetof(nbody_batch_member_body, energy) &&
+                  offsetof(BatchMemberBody, member) == offsetof(nbody_batch_member_body, member) &&
+                  offsetof(BatchMemberBody, removed_at) == offsetof(nbody_batch_member_body, removed_at),
+              "nbody_batch_members_math.h mirrors the body record of nbody_batch_members.h");
+static_assert(sizeof(BatchMemberSystem) == sizeof(nbody_batch_member_system) && sizeof(nbody_batch_member_system) == 88 &&
+                  offsetof(BatchMemberSystem, centre) == offsetof(nbody_batch_member_system, centre) &&
+                  offsetof(BatchMemberSystem, velocity) == offsetof(nbody_batch_member_system, velocity) &&
+                  offsetof(BatchMemberSystem, kinetic) == offsetof(nbody_batch_member_system, kinetic) &&
+                  offsetof(BatchMemberSystem, potential) == offsetof(nbody_batch_member_system, potential) &&
+                  offsetof(BatchMemberSystem, members) == offsetof(nbody_batch_member_system, members) &&
+                  offsetof(BatchMemberSystem, sources) == offsetof(nbody_batch_member_system, sources) &&
+                  offsetof(BatchMemberSystem, iterations) == offsetof(nbody_batch_member_system, iterations) &&
+                  offsetof(BatchMemberSystem, converged) == offsetof(nbody_batch_member_system, converged),
+              "nbody_batch_members_math.h mirrors the system record of nbody_batch_members.h");
+static_assert(kMembersMaxIterations == NBODY_BATCH_MEMBERS_MAX_ITERATIONS, "nbody_batch_members_math.h mirrors the limit of nbody_batch_members.h");
+
+// The final set's sums: mass, m x, m y, m z, m vx, m vy, m vz, kinetic, potential, members, member sources.
+constexpr int kMembersSums = 11;
+
+// One pass over the sources j < m for RPL rows: sum[q] += (double)(m_j inv) in ascending j, the fp32 term batch_diag_kernel
+// forms for nbody_batch_energy (GUARD: the eps = 0 guard).  sh[j].w is the source's mass word, or 0 for a non-member: its
+// term is +0, no branch.  Column reads are wave-uniform broadcasts.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void members_columns(const float4 *sh, int m, const float4 (&x)[RPL], int tid, int T, float eps2,
+                                                double (&sum)[RPL])
+{
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, eps2)));
+            float inv = __builtin_amdgcn_rsqf(GUARD ? guard_r2(r2) : r2);
+            inv = j != q * T + tid ? inv : 0.f;
+            sum[q] += (double)(pj.w * inv);
+        }
+    }
+}
+
+// LDS: sh[j] = {x, y, z, masked mass} of body j (64 KiB at 4096 bodies; with the reduction words above the default limit,
+// which is raised before the launch).  The velocities stay in the rows' registers: only the frame needs them.
+// The iteration loop holds barriers, so its trip count is workgroup-uniform: n, max_iterations and t are, and "removed" and
+// "left" come out of one structure_block_sum, which hands every lane the same words of red; no lane leaves on data of its own.
+// One row per lane is held to the 64 registers of eight waves per SIMD, batch_hermite_kernel<1>'s.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_members_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, int max_bodies, float eps2, int max_iterations,
+    const unsigned char *initial, BatchMemberBody *bodies, BatchMemberSystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ double red[16 * kMembersSums];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the row's mass word as a source; 0 for a test particle}
+    float3 v[RPL];
+    bool in[RPL];   // member of the current set; never for a row from the count on
+    int gone[RPL];  // the iteration that removed the row
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = make_float3(0.f, 0.f, 0.f);
+        in[q] = false;
+        gone[q] = 0;
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            in[q] = initial ? initial[base + r] != 0 : true;
+            if (r >= m)
+                x[q].w = 0.f;
+            sh[r] = make_float4(x[q].x, x[q].y, x[q].z, in[q] ? x[q].w : 0.f);
+        }
+    }
+    double phi[RPL], e[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        phi[q] = e[q] = 0.0;
+    double Vx = 0.0, Vy = 0.0, Vz = 0.0;
+    int iterations = 0, converged = 1;  // a system without bodies evaluates nothing
+    if (n > 0) {
+        for (int t = 1;; ++t) {
+            // The frame of the member sources.
+            double f[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const double w = in[q] ? (double)x[q].w : 0.0;
+                f[0] += w;
+                f[1] += w * (double)v[q].x;
+                f[2] += w * (double)v[q].y;
+                f[3] += w * (double)v[q].z;
+            }
+            structure_block_sum(f, red, tid, T);  // its barriers: the masked mass words are in place
+            const bool massless = f[0] == 0.0;
+            Vx = massless ? 0.0 : f[1] / f[0];
+            Vy = massless ? 0.0 : f[2] / f[0];
+            Vz = massless ? 0.0 : f[3] / f[0];
+            // The potentials, the energies, the decision.
+            double sum[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                sum[q] = 0.0;
+            if (eps2 > 0.f)
+                members_columns<RPL, false>(sh, m, x, tid, T, eps2, sum);
+            else
+                members_columns<RPL, true>(sh, m, x, tid, T, eps2, sum);
+            double c[2] = {0.0, 0.0};  // removed by this iteration, members left
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                phi[q] = 0.0 - sum[q];
+                e[q] = members_energy(v[q].x, v[q].y, v[q].z, Vx, Vy, Vz, phi[q]);
+                const bool stays = members_stays(in[q], e[q]);
+                const bool leaves = in[q] && !stays;
+                gone[q] = leaves ? t : gone[q];
+                in[q] = stays;
+                c[0] += leaves ? 1.0 : 0.0;
+                c[1] += stays ? 1.0 : 0.0;
+            }
+            structure_block_sum(c, red, tid, T);  // its barriers: every lane is done with the columns
+            // The same two words of red in every lane of every wave: the exit is the workgroup's.
+            const int removed = __builtin_amdgcn_readfirstlane((int)c[0]), left = __builtin_amdgcn_readfirstlane((int)c[1]);
+            iterations = t;
+            converged = (removed == 0 || left == 0) ? 1 : 0;
+            if (converged || t >= max_iterations)
+                break;
+            // Every lane masks its own rows' mass words for the next iteration; the next sum's barriers publish them.
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < m)
+                    sh[r].w = in[q] ? x[q].w : 0.f;
+            }
+        }
+    }
+    // The final set.
+    double g[kMembersSums];
+#pragma unroll
+    for (int c = 0; c < kMembersSums; ++c)
+        g[c] = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const double w = in[q] ? (double)x[q].w : 0.0;
+        g[0] += w;
+        g[1] += w * (double)x[q].x;
+        g[2] += w * (double)x[q].y;
+        g[3] += w * (double)x[q].z;
+        g[4] += w * (double)v[q].x;
+        g[5] += w * (double)v[q].y;
+        g[6] += w * (double)v[q].z;
+        g[7] += in[q] ? w * members_kinetic(v[q].x, v[q].y, v[q].z, Vx, Vy, Vz) : 0.0;
+        g[8] += in[q] ? 0.5 * w * phi[q] : 0.0;
+        g[9] += in[q] ? 1.0 : 0.0;
+        g[10] += in[q] && q * T + tid < m ? 1.0 : 0.0;
+    }
+    structure_block_sum(g, red, tid, T);
+    if (tid == 0) {
+        const bool massless = g[0] == 0.0;
+        BatchMemberSystem *out = systems + blockIdx.x;
+        out->bound_mass = g[0];
+        out->centre[0] = massless ? 0.0 : g[1] / g[0];
+        out->centre[1] = massless ? 0.0 : g[2] / g[0];
+        out->centre[2] = massless ? 0.0 : g[3] / g[0];
+        out->velocity[0] = massless ? 0.0 : g[4] / g[0];
+        out->velocity[1] = massless ? 0.0 : g[5] / g[0];
+        out->velocity[2] = massless ? 0.0 : g[6] / g[0];
+        out->kinetic = g[7];
+        out->potential = g[8];
+        out->members = (int)g[9];
+        out->sources = (int)g[10];
+        out->iterations = iterations;
+        out->converged = converged;
+    }
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = r < n ? BatchMemberBody{phi[q], e[q], in[q] ? 1 : 0, gone[q]} : members_empty_body();
+        }
+    }
+}
+
+// One launch over all systems.  64 KiB of dynamic LDS at 4096 bodies beside the reduction words: the limit is raised first, as
+// launch_batch_structure does.  massive, initial and bodies may be NULL.
+hipError_t launch_batch_members(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                                int max_bodies, float eps2, int max_iterations, const unsigned char *initial, BatchMemberBody *bodies,
+                                BatchMemberSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, vel, counts, massive, max_bodies, eps2,
+                           max_iterations, initial, bodies, systems);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_members_kernel<1>);
+    case 2: return launch(batch_members_kernel<2>);
+    default: return launch(batch_members_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -3720,6 +3937,11 @@ struct nbody_batch {
     // nbody_batch_structure: the records of the last call, each allocated by the first call that asks for it
     BatchStructureSystem *structure_systems_dev = nullptr;  // [n_systems]
     BatchStructureBody *structure_bodies_dev = nullptr;     // [n_systems][max_bodies]
+    // nbody_batch_members: the records of the last call and the device copy of `initial`, each allocated by the first call that
+    // asks for it
+    BatchMemberSystem *members_systems_dev = nullptr;  // [n_systems]
+    BatchMemberBody *members_bodies_dev = nullptr;     // [n_systems][max_bodies]
+    unsigned char *members_initial_dev = nullptr;      // [n_systems][max_bodies]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -3961,6 +4183,9 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->pairs_binaries_dev) (void)hipFree(b->pairs_binaries_dev);
     if (b->structure_systems_dev) (void)hipFree(b->structure_systems_dev);
     if (b->structure_bodies_dev) (void)hipFree(b->structure_bodies_dev);
+    if (b->members_systems_dev) (void)hipFree(b->members_systems_dev);
+    if (b->members_bodies_dev) (void)hipFree(b->members_bodies_dev);
+    if (b->members_initial_dev) (void)hipFree(b->members_initial_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -4657,6 +4882,40 @@ int nbody_batch_structure(nbody_batch *b, const float *d_pos, int k, int weight,
     BATCH_TRY(b, hipMemcpyAsync(systems_out, b->structure_systems_dev, sizeof(BatchStructureSystem) * B, hipMemcpyDeviceToHost, b->stream));
     if (bodies_out)
         BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->structure_bodies_dev, sizeof(BatchStructureBody) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_members(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, int max_iterations,
+                        const unsigned char *initial, nbody_batch_member_system *systems_out, nbody_batch_member_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_members: batch is NULL");
+    if (!d_pos || !d_vel || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: NULL argument");
+    if (max_iterations < 1 || max_iterations > NBODY_BATCH_MEMBERS_MAX_ITERATIONS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: max_iterations must be 1 ... 64");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->members_systems_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->members_systems_dev, sizeof(BatchMemberSystem) * B));
+    if (bodies_out && !b->members_bodies_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->members_bodies_dev, sizeof(BatchMemberBody) * slots));
+    if (initial) {
+        if (!b->members_initial_dev)
+            BATCH_TRY(b, hipMalloc((void **)&b->members_initial_dev, slots));
+        BATCH_TRY(b, hipMemcpyAsync(b->members_initial_dev, initial, slots, hipMemcpyHostToDevice, b->stream));
+    }
+    BATCH_TRY(b, launch_batch_members(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                      b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                      softening * softening, max_iterations, initial ? b->members_initial_dev : nullptr,
+                                      bodies_out ? b->members_bodies_dev : nullptr, b->members_systems_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(systems_out, b->members_systems_dev, sizeof(BatchMemberSystem) * B, hipMemcpyDeviceToHost, b->stream));
+    if (bodies_out)
+        BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->members_bodies_dev, sizeof(BatchMemberBody) * slots, hipMemcpyDeviceToHost,
                                     b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

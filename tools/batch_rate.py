@@ -63,7 +63,15 @@ positions alone and returns three numbers per system.
 line per case: structure() with the per-body records and with bodies=False against energy(0) and pairs() on the same state --
 all synchronous calls, wall clock, alternated, medians and spreads.  structure() walks the n x n pairs three times (the
 eight-smallest lists, the neighbours inside the k-th distance, the enclosed weights in fp64) and returns 120 bytes per system
-and, with the records, 40 bytes per body.  The kernel's time alone comes from a traced run of this mode."""
+and, with the records, 40 bytes per body.  The kernel's time alone comes from a traced run of this mode.
+
+--members: instead, the bound members (BatchedSystem.members).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one line
+per case on boosted Plummer spheres (a third of the velocities multiplied by 1.5 ... 4, so that unbinding takes several
+iterations): members(0) with the per-body records, with bodies=False, and with bodies=False and one iteration, against energy(0)
+and pairs() on the same state -- all synchronous calls, wall clock, alternated, medians and spreads.  An iteration is one
+n x n walk of fp32 pair terms summed in fp64, energy()'s own terms: the one-iteration call is one iteration of every system,
+and the difference of the two lean calls is given over the further iterations of the slowest system and of the mean.  The
+kernel's time alone comes from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -105,6 +113,8 @@ ap.add_argument("--field", action="store_true", help="evolve(levels=0) with a th
 ap.add_argument("--pairs", action="store_true", help="pairs() against energy() on the same state, wall clock")
 ap.add_argument("--structure", action="store_true", help="structure() with and without the per-body records against energy() "
                 "and pairs() on the same state, wall clock")
+ap.add_argument("--members", action="store_true", help="members() with and without the per-body records and with one iteration "
+                "against energy() and pairs() on the same boosted state, wall clock, and the time per iteration")
 args = ap.parse_args()
 
 
@@ -656,6 +666,78 @@ def structure_lines():
         print(json.dumps(line), flush=True)
 
 
+def boosted_ensemble(n, B):
+    """B boosted Plummer spheres of n bodies, the state of tests/hermite_members_ref.py: plummer(n, seed=100 + s) with the
+    velocities of a random 35 % of the bodies (default_rng(s)) multiplied by a uniform 1.5 ... 4 and a bulk velocity added, one
+    sphere per seed for the first 64 systems, then copies jittered by 1e-4.  Iterative unbinding drops 20 - 30 % of them."""
+    P = np.zeros((B, n, 4), np.float32)
+    V = np.zeros((B, n, 4), np.float32)
+    jitter = np.random.default_rng(n * 7 + B)
+    for s in range(B):
+        if s < 64:
+            P[s], V[s] = nb.plummer(n, seed=100 + s)
+            rng = np.random.default_rng(s)
+            fast = rng.random(n) < 0.35
+            factor = np.where(fast, rng.uniform(1.5, 4.0, size=n), 1.0)
+            V[s, :, :3] = (V[s, :, :3].astype(np.float64) * factor[:, None] + np.asarray((0.3, -0.2, 0.1))).astype(np.float32)
+        else:
+            P[s], V[s] = P[s % 64], V[s % 64]
+            P[s, :, :3] += jitter.normal(0, 1e-4, (n, 3)).astype(np.float32)
+    return P, V
+
+
+def members_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = boosted_ensemble(n, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"members": lambda: batch.members(0.0), "members_lean": lambda: batch.members(0.0, bodies=False),
+                     "members_lean_one_iteration": lambda: batch.members(0.0, max_iterations=1, bodies=False),
+                     "energy": lambda: batch.energy(0.0), "pairs": batch.pairs}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    if name == "members_lean":
+                        res = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        # One iteration of every system is the one-iteration call.  The two lean calls differ in the iterations after the first
+        # alone (the launch, the loads, the final sums and the copies cancel): where all B workgroups are resident at once the
+        # system with the most iterations sets that difference, in a larger batch the mean does, so both quotients are given.
+        more = med["members_lean"] - med["members_lean_one_iteration"]
+        line.update({"iterations_mean": round(float(res.iterations.mean()), 3), "iterations_max": int(res.iterations.max()),
+                     "converged": int(res.converged.sum()),
+                     "one_iteration_over_energy": round(med["members_lean_one_iteration"] / med["energy"], 3),
+                     "pair_evaluations_per_s_one_iteration": float(f"{B * n * n / (med['members_lean_one_iteration'] * 1e-3):.4g}"),
+                     "ms_per_further_iteration_of_the_slowest": round(more / max(int(res.iterations.max()) - 1, 1), 4),
+                     "ms_per_further_iteration_of_the_mean": round(more / max(float(res.iterations.mean()) - 1.0, 1e-9), 4),
+                     "record_megabytes": round(B * n * 24 / 1e6, 1), "system_kilobytes": round(B * 88 / 1e3, 1),
+                     "median_bound_fraction": round(float(np.median(res.bound_fraction())), 4)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.members:
+    members_lines()
+    sys.exit(0)
 if args.structure:
     structure_lines()
     sys.exit(0)
