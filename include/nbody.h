@@ -541,6 +541,7 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_structure.h"
 /* bound members: per-body potentials and energies by iterative unbinding, the bound mass and its frame of every system */
 #include "nbody_batch_members.h"
+#include "nbody_batch_hierarchy.h"
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 #include "nbody.h"
 
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -527,6 +528,32 @@ public:
         bodies.resize((size_t)systems_ * (size_t)maxBodies_);
         check(nbody_batch_members(b_, dPositions, dVelocities, softening, maxIterations, initial, s.data(), bodies.data()),
               "nbody_batch_members");
+        return s;
+    }
+    // Hierarchies (nbody_batch_hierarchy.h): the nested bound pairs of every system from the state in the caller's buffers --
+    // per system the nodes made, the live roots, the levels evaluated (1 <= maxLevels <= 16) and the singles, binaries, triples,
+    // higher multiples and unstable roots.  A pair whose worst perturber's tide exceeds tidalTolerance of its own attraction is
+    // no node; +inf accepts every bound mutual pair.  The second form also fills numSystems x maxBodies node records and
+    // per-body records (parent, root, depth) laid out like the positions; the first copies 40 bytes per system alone.
+    // Changes nothing the handle keeps.
+    std::vector<nbody_batch_hierarchy_system> hierarchy(const float *dPositions, const float *dVelocities,
+                                                        double tidalTolerance = std::numeric_limits<double>::infinity(),
+                                                        int maxLevels = 8)
+    {
+        std::vector<nbody_batch_hierarchy_system> s((size_t)systems_);
+        check(nbody_batch_hierarchy(b_, dPositions, dVelocities, tidalTolerance, maxLevels, s.data(), nullptr, nullptr),
+              "nbody_batch_hierarchy");
+        return s;
+    }
+    std::vector<nbody_batch_hierarchy_system> hierarchy(const float *dPositions, const float *dVelocities, double tidalTolerance,
+                                                        int maxLevels, std::vector<nbody_batch_hierarchy_node> &nodes,
+                                                        std::vector<nbody_batch_hierarchy_body> &bodies)
+    {
+        std::vector<nbody_batch_hierarchy_system> s((size_t)systems_);
+        nodes.resize((size_t)systems_ * (size_t)maxBodies_);
+        bodies.resize((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_hierarchy(b_, dPositions, dVelocities, tidalTolerance, maxLevels, s.data(), nodes.data(), bodies.data()),
+              "nbody_batch_hierarchy");
         return s;
     }
     // per system {kinetic, potential, total} and {px, py, pz, mass}

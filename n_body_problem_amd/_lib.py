@@ -314,6 +314,35 @@ _MEMBERS_PROTOTYPES = {
 }
 
 
+BATCH_HIERARCHY_MAX_LEVELS = 16
+
+
+class BatchHierarchyNode(ctypes.Structure):
+    """``nbody_batch_hierarchy_node`` of include/nbody_batch_hierarchy.h."""
+    _fields_ = [("child", c_int * 2), ("parent", c_int), ("level", c_int), ("leaves", c_int), ("slot", c_int), ("stable", c_int),
+                ("reserved", c_int), ("mass", c_double), ("energy", c_double), ("semi_major_axis", c_double),
+                ("eccentricity", c_double), ("inclination", c_double), ("separation", c_double), ("perturbation", c_double),
+                ("mutual_inclination", c_double * 2), ("h", c_double * 3)]
+
+
+class BatchHierarchyBody(ctypes.Structure):
+    """``nbody_batch_hierarchy_body`` of include/nbody_batch_hierarchy.h."""
+    _fields_ = [("parent", c_int), ("root", c_int), ("depth", c_int), ("reserved", c_int)]
+
+
+class BatchHierarchySystem(ctypes.Structure):
+    """``nbody_batch_hierarchy_system`` of include/nbody_batch_hierarchy.h."""
+    _fields_ = [("nodes", c_int), ("roots", c_int), ("levels", c_int), ("converged", c_int), ("singles", c_int),
+                ("binaries", c_int), ("triples", c_int), ("higher", c_int), ("unstable", c_int), ("reserved", c_int)]
+
+
+#: the entry point of include/nbody_batch_hierarchy.h (hierarchies of batched ensembles), which nbody.h includes
+_HIERARCHY_PROTOTYPES = {
+    "nbody_batch_hierarchy": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, POINTER(BatchHierarchySystem),
+                                      POINTER(BatchHierarchyNode), POINTER(BatchHierarchyBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -341,7 +370,7 @@ def load() -> ctypes.CDLL:
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
-                list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()):
+                list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -407,6 +436,11 @@ def structure_names():
 def members_names():
     """The entry point of nbody_batch_members.h."""
     return list(_MEMBERS_PROTOTYPES)
+
+
+def hierarchy_names():
+    """The entry point of nbody_batch_hierarchy.h."""
+    return list(_HIERARCHY_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

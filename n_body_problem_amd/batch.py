@@ -49,6 +49,18 @@ MEMBER_SYSTEM_DTYPE = np.dtype([("bound_mass", np.float64), ("centre", np.float6
                                 ("iterations", np.int32), ("converged", np.int32)])
 assert MEMBER_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMemberBody) == 24
 assert MEMBER_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMemberSystem) == 88
+#: the records of :meth:`BatchedSystem.hierarchy`: numpy's views of ``nbody_batch_hierarchy_node``, ``_body`` and ``_system``
+HIERARCHY_NODE_DTYPE = np.dtype([("child", np.int32, 2), ("parent", np.int32), ("level", np.int32), ("leaves", np.int32),
+                                 ("slot", np.int32), ("stable", np.int32), ("reserved", np.int32), ("mass", np.float64),
+                                 ("energy", np.float64), ("semi_major_axis", np.float64), ("eccentricity", np.float64),
+                                 ("inclination", np.float64), ("separation", np.float64), ("perturbation", np.float64),
+                                 ("mutual_inclination", np.float64, 2), ("h", np.float64, 3)])
+HIERARCHY_BODY_DTYPE = np.dtype([("parent", np.int32), ("root", np.int32), ("depth", np.int32), ("reserved", np.int32)])
+HIERARCHY_SYSTEM_DTYPE = np.dtype([(name, np.int32) for name in ("nodes", "roots", "levels", "converged", "singles", "binaries",
+                                                                 "triples", "higher", "unstable", "reserved")])
+assert HIERARCHY_NODE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchyNode) == 128
+assert HIERARCHY_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchyBody) == 16
+assert HIERARCHY_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchySystem) == 40
 #: the weight of a body in :meth:`BatchedSystem.structure`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -529,6 +541,28 @@ class BatchedSystem:
             rec.ctypes.data_as(ctypes.POINTER(_lib.BatchMemberBody)) if bodies else None), self._h)
         return MemberResult(systems, rec, self._source_mass())
 
+    def hierarchy(self, tidal_tolerance: float = np.inf, max_levels: int = 8, nodes: bool = True,
+                  bodies: bool = True) -> "HierarchyResult":
+        """What every system has become, as nested bound pairs such as ``[[0 1] 2] 3`` (``include/nbody_batch_hierarchy.h``
+        states the rules), found on the device from the current state (waits for the queued work).  Level by level the live
+        roots look for partners as :meth:`pairs` does; two roots that choose each other, are bound, and whose worst
+        perturber's tide at apocentre is at most ``tidal_tolerance`` of their own attraction become a node with the merged
+        body's state, and the search runs again, ``max_levels`` (1 ... 16) times at the most.  Nested pairs are judged by the
+        stability criterion of Mardling & Aarseth (2001).  With massive counts (:meth:`set_massive_counts`) only massive
+        bodies are leaves.  ``nodes=False`` and ``bodies=False`` skip the 128 and 16 bytes per slot on their way to the host:
+        those arrays of the result are ``None``, the per-system ones the same bits.  Changes nothing: an :meth:`evolve` after
+        it is bit for bit the :meth:`evolve` without it."""
+        systems = np.zeros(self.num_systems, dtype=HIERARCHY_SYSTEM_DTYPE)
+        node = np.zeros((self.num_systems, self.max_bodies), dtype=HIERARCHY_NODE_DTYPE) if nodes else None
+        body = np.zeros((self.num_systems, self.max_bodies), dtype=HIERARCHY_BODY_DTYPE) if bodies else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_hierarchy(
+            self._h, _ptr(self.positions), _ptr(self.velocities), float(tidal_tolerance), int(max_levels),
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchHierarchySystem)),
+            node.ctypes.data_as(ctypes.POINTER(_lib.BatchHierarchyNode)) if nodes else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchHierarchyBody)) if bodies else None), self._h)
+        return HierarchyResult(systems, node, body, self.counts)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -746,4 +780,68 @@ def interactions_per_step(counts, massive=None) -> int:
     return int((c * m).sum())
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+SYSTEM_FIELDS = ("nodes", "roots", "levels", "singles", "binaries", "triples", "higher", "unstable")
+NODE_FIELDS = ("child", "parent", "level", "leaves", "slot", "mass", "energy", "semi_major_axis", "eccentricity", "inclination",
+               "separation", "perturbation", "mutual_inclination", "h")
+
+
+class HierarchyResult:
+    """What :meth:`BatchedSystem.hierarchy` found.  Per system (``(B,)`` int32 arrays): ``nodes`` (made), ``roots`` (live at the
+    end, leaves only), ``levels`` (evaluated), ``singles``, ``binaries``, ``triples``, ``higher`` (roots with 1, 2, 3 and >= 4
+    leaves), ``unstable`` (roots with ``stable == 0``), and ``converged`` (bool).  ``counts``: the body counts the call saw; a
+    leaf's id is its index and node ``k`` of system ``s`` has the id ``counts[s] + k``.  Per node, ``(B, max_bodies)`` arrays
+    or ``None`` without ``nodes`` (entry ``k`` is node ``k``; beyond ``nodes[s]`` zeros, ``child`` and ``parent`` -1):
+    ``child`` (``(B, max_bodies, 2)``, the lower slot's first), ``node_parent``, ``level``, ``leaves``, ``slot``, ``stable``
+    (bool), ``mass``, ``energy``, ``semi_major_axis``, ``eccentricity``, ``inclination``, ``separation``, ``perturbation``,
+    ``mutual_inclination`` (``(B, max_bodies, 2)``) and ``h`` (``(B, max_bodies, 3)``).  Per body, ``(B, max_bodies)`` int32
+    arrays or ``None`` without ``bodies``: ``parent``, ``root`` and ``depth``.  ``systems``, ``node_records`` and
+    ``body_records`` are the records themselves."""
+
+    def __init__(self, systems, nodes, bodies, counts):
+        self.systems, self.node_records, self.body_records = systems, nodes, bodies
+        self.counts = np.asarray(counts, dtype=np.int64)
+        for name in SYSTEM_FIELDS:
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.converged = systems["converged"] != 0
+        for name in NODE_FIELDS:
+            setattr(self, "node_parent" if name == "parent" else name, None if nodes is None else np.ascontiguousarray(nodes[name]))
+        self.stable = None if nodes is None else nodes["stable"] != 0
+        self.nodes = np.ascontiguousarray(systems["nodes"])       # the per-system count, not the records
+        self.parent = self.root = self.depth = None
+        if bodies is not None:
+            self.parent, self.root, self.depth = (np.ascontiguousarray(bodies[name]) for name in ("parent", "root", "depth"))
+
+    def multiplicity(self) -> np.ndarray:
+        """``(B, 4)`` int32: singles, binaries, triples and higher multiples among the roots of every system."""
+        return np.stack([self.singles, self.binaries, self.triples, self.higher], axis=1)
+
+    def roots_of(self, s: int) -> list:
+        """The ids of system ``s``'s roots in ascending slot (needs the node records)."""
+        if self.node_records is None:
+            raise ValueError("roots_of needs the node records: call hierarchy(nodes=True)")
+        n, made = int(self.counts[s]), int(self.nodes[s])
+        rec = self.node_records[s, :made]
+        leaves = made + int(self.roots[s])              # every node takes one root away; test particles are no roots
+        child = set(rec["child"].ravel().tolist())
+        roots = [(i, i) for i in range(leaves) if i not in child]
+        roots += [(int(rec["slot"][k]), n + k) for k in range(made) if rec["parent"][k] < 0]
+        return [i for _, i in sorted(roots)]
+
+    def describe(self, s: int) -> str:
+        """System ``s`` Fewbody style: the roots in ascending slot, a node as ``[a b]`` with the lower-slot child first, e.g.
+        ``"[[0 2] 5] 1 [3 4]"``."""
+        n = int(self.counts[s])
+
+        def text(i):
+            if i < n:
+                return str(i)
+            a, b = self.node_records[s, i - n]["child"]
+            return f"[{text(int(a))} {text(int(b))}]"
+        return " ".join(text(i) for i in self.roots_of(s))
+
+    def __repr__(self):
+        return (f"HierarchyResult(multiplicity={self.multiplicity().tolist()}, unstable={self.unstable.tolist()}, "
+                f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
+
+
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

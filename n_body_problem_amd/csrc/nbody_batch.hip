@@ -14,6 +14,7 @@
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
+#include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radii_check.h"
@@ -3802,6 +3803,340 @@ hipError_t launch_batch_members(const float4 *pos, const float4 *vel, const int 
     }
 }
 
+// ---- hierarchies (include/nbody_batch_hierarchy.h): nested bound pairs.  Level by level the live roots of a system look for
+// partners as batch_pairs_kernel's rows do, the mutual bound pairs that their worst perturber lets stand become nodes with the
+// merged body's state, and the search runs again over what is left.  A sibling of batch_pairs_kernel: one workgroup per
+// system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  The levels run
+// inside the kernel.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchHierarchyNode) == sizeof(nbody_batch_hierarchy_node) && sizeof(nbody_batch_hierarchy_node) == 128 &&
+                  offsetof(BatchHierarchyNode, parent) == offsetof(nbody_batch_hierarchy_node, parent) &&
+                  offsetof(BatchHierarchyNode, stable) == offsetof(nbody_batch_hierarchy_node, stable) &&
+                  offsetof(BatchHierarchyNode, mass) == offsetof(nbody_batch_hierarchy_node, mass) &&
+                  offsetof(BatchHierarchyNode, perturbation) == offsetof(nbody_batch_hierarchy_node, perturbation) &&
+                  offsetof(BatchHierarchyNode, mutual_inclination) == offsetof(nbody_batch_hierarchy_node, mutual_inclination) &&
+                  offsetof(BatchHierarchyNode, h) == offsetof(nbody_batch_hierarchy_node, h),
+              "nbody_batch_hierarchy_math.h mirrors the node record of nbody_batch_hierarchy.h");
+static_assert(sizeof(BatchHierarchyBody) == sizeof(nbody_batch_hierarchy_body) && sizeof(nbody_batch_hierarchy_body) == 16 &&
+                  offsetof(BatchHierarchyBody, depth) == offsetof(nbody_batch_hierarchy_body, depth),
+              "nbody_batch_hierarchy_math.h mirrors the body record of nbody_batch_hierarchy.h");
+static_assert(sizeof(BatchHierarchySystem) == sizeof(nbody_batch_hierarchy_system) && sizeof(nbody_batch_hierarchy_system) == 40 &&
+                  offsetof(BatchHierarchySystem, singles) == offsetof(nbody_batch_hierarchy_system, singles) &&
+                  offsetof(BatchHierarchySystem, unstable) == offsetof(nbody_batch_hierarchy_system, unstable),
+              "nbody_batch_hierarchy_math.h mirrors the system record of nbody_batch_hierarchy.h");
+static_assert(kHierarchyMaxLevels == NBODY_BATCH_HIERARCHY_MAX_LEVELS, "nbody_batch_hierarchy_math.h mirrors the limit of nbody_batch_hierarchy.h");
+
+constexpr size_t kHierarchyBytesPerBody = 2 * kBatchBytesPerBody + sizeof(int);  // position, velocity, the slot's node id
+
+// LDS: sh[2 j] = {x, y, z, m} and sh[2 j + 1] = {vx, vy, vz, word} of the root in slot j < m (batch_pairs_kernel's layout,
+// 128 KiB at 4096 bodies), then nid[j], the id of that root or -1 for a dead slot (16 KiB): 144 KiB, with the few hundred
+// bytes of made and red inside the 160 KiB of a workgroup.  The fourth word of the velocity holds the slot's partner after
+// walk 1 and, in the higher slot of a mutual pair, the pair's g after walk 2.
+// Dead slots: the mass word of a dead slot is NaN, and so is the row mass of a lane whose row is dead or no leaf.  mu, eps
+// and s are then NaN and the searches' own comparisons never take them: no branch, no predicate beside the pairs kernel's.
+// What a node needs of a composite child (a, h, stable, leaves) is read back from the node records in global memory, which
+// this workgroup wrote at an earlier level with barriers between; LDS holds no per-node array.
+// The level loop holds barriers, so its trip count is workgroup-uniform: m, max_levels and t are, and the nodes a level made
+// are summed by every lane from the same words of `made`.  The record loop is kept rolled (the fp64 arithmetic is
+// instantiated once); the creation order over r = q * T + lane is a ballot within the wave, the waves' counts in LDS and a
+// running offset over q.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_hierarchy_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, int max_bodies, double tolerance, int max_levels,
+    int fill, BatchHierarchyNode *nodes, BatchHierarchyBody *bodies, BatchHierarchySystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ int made[16];
+    __shared__ double red[16 * 5];
+    int *nid = reinterpret_cast<int *>(sh + 2 * (size_t)max_bodies);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float dead = __builtin_nanf("");
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < m) {
+            const float4 w = vel[base + r];
+            sh[2 * r] = pos[base + r];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            nid[r] = r;
+        }
+    }
+    int nodes_made = 0, levels = 0, converged = 1;  // a system of fewer than two leaves evaluates no level
+    if (m >= 2) {
+        for (int t = 1;; ++t) {
+            __syncthreads();  // the roots of this level are in place
+            float4 x[RPL];    // {x, y, z, m} of the row's root; m is NaN for a dead slot and for a row that is no leaf
+            float3 v[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                x[q] = make_float4(0.f, 0.f, 0.f, dead);
+                v[q] = make_float3(0.f, 0.f, 0.f);
+                if (r < m) {
+                    x[q] = sh[2 * r];
+                    const float4 w = sh[2 * r + 1];
+                    v[q] = make_float3(w.x, w.y, w.z);
+                }
+            }
+            // Walk 1: batch_pairs_kernel's search.
+            float best[RPL];
+            int bj[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                best[q] = __builtin_inff();
+                bj[q] = -1;
+            }
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+                const float4 pj = sh[2 * j], vj = sh[2 * j + 1];  // wave-uniform addresses: broadcast ds_read_b128
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+                    const float wx = vj.x - v[q].x, wy = vj.y - v[q].y, wz = vj.z - v[q].z;
+                    const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    const float v2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+                    const float inv = __builtin_amdgcn_rsqf(r2);
+                    const float mu = pj.w + x[q].w;
+                    const float eps = __builtin_fmaf(-mu, inv, 0.5f * v2);
+                    const bool take = r2 > 0.f && eps < best[q];  // r2 == 0: the root itself and coincident roots
+                    best[q] = take ? eps : best[q];
+                    bj[q] = take ? j : bj[q];
+                }
+            }
+            __syncthreads();  // every lane is done with the columns before the partners replace the fourth words
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < m)
+                    sh[2 * r + 1].w = __int_as_float(bj[q]);
+            }
+            __syncthreads();
+            // The mutual pairs, owned by the lane of the lower slot, and the position X of the node each would make.
+            unsigned mut = 0;
+            float3 X[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid, j = bj[q];
+                X[q] = make_float3(x[q].x, x[q].y, x[q].z);
+                if (j > r) {
+                    const float4 pj = sh[2 * j];
+                    if (__float_as_int(sh[2 * j + 1].w) == r) {
+                        const double M = (double)x[q].w + (double)pj.w;
+                        mut |= 1u << q;
+                        X[q].x = hierarchy_merged(x[q].w, x[q].x, pj.w, pj.x, M);
+                        X[q].y = hierarchy_merged(x[q].w, x[q].y, pj.w, pj.y, M);
+                        X[q].z = hierarchy_merged(x[q].w, x[q].z, pj.w, pj.z, M);
+                    }
+                }
+            }
+            __syncthreads();  // every lane has read its partner's word before a pair's g replaces it
+            // Walk 2: the worst perturber of every mutual pair (an unbound pair's g is dropped with the pair).
+            float g[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                g[q] = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < m; ++k) {
+                const float4 pk = sh[2 * k];
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const float dx = pk.x - X[q].x, dy = pk.y - X[q].y, dz = pk.z - X[q].z;
+                    const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    const float inv = __builtin_amdgcn_rsqf(r2);
+                    const float s = (pk.w * inv) * (inv * inv);
+                    const bool take = (k != q * T + tid) & (k != bj[q]) & (s > g[q]);  // one predicate, no branch; a dead slot's s is NaN
+                    g[q] = take ? s : g[q];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                if ((mut >> q) & 1u)
+                    sh[2 * bj[q] + 1].w = g[q];
+            __syncthreads();  // every lane is done with the columns before the new nodes replace them
+            // The records and the new nodes, one row at a time from LDS.  A pair's two slots are read and written by the
+            // lane that owns the pair alone.
+            int level_made = 0;
+#pragma unroll 1
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                bool accept = false;
+                BatchHierarchyNode rec = hierarchy_empty_node();
+                float4 xi = make_float4(0.f, 0.f, 0.f, 0.f), vi = xi, xj = xi, vj = xi;
+                int j = -1;
+                if ((mut >> q) & 1u) {
+                    xi = sh[2 * r], vi = sh[2 * r + 1];
+                    j = __float_as_int(vi.w);
+                    xj = sh[2 * j], vj = sh[2 * j + 1];
+                    const float pi[3] = {xi.x, xi.y, xi.z}, wi[3] = {vi.x, vi.y, vi.z};
+                    const float pj[3] = {xj.x, xj.y, xj.z}, wj[3] = {vj.x, vj.y, vj.z};
+                    hierarchy_elements(pi, wi, xi.w, pj, wj, xj.w, rec);
+                    rec.perturbation = hierarchy_perturbation(vj.w, rec.semi_major_axis, rec.eccentricity, (double)xj.w + (double)xi.w);
+                    accept = hierarchy_accepts(rec.energy, rec.perturbation, tolerance);
+                }
+                // creation order: the accepted rows before this one in the wave, in the waves before, at the q before
+                const unsigned long long votes = __ballot(accept);
+                const int before = __popcll(votes & ((1ull << lane) - 1ull));
+                __syncthreads();  // every lane has read the counts of the q before
+                if (lane == 0)
+                    made[wave] = __popcll(votes);
+                __syncthreads();
+                int lower = 0, total = 0;
+                for (int w = 0; w < T / 64; ++w) {
+                    const int c = made[w];
+                    lower += w < wave ? c : 0;
+                    total += c;
+                }
+                if (accept) {
+                    const int k = nodes_made + level_made + lower + before, id = n + k;
+                    const int ci = nid[r], cj = nid[j];
+                    BatchHierarchyNode *out = nodes + base + k;
+                    rec.child[0] = ci;
+                    rec.child[1] = cj;
+                    rec.level = t;
+                    rec.slot = r;
+                    *out = rec;  // leaves, stable and the mutual inclinations follow below: little is live across them
+                    const float mass = xi.w + xj.w;
+                    const double M = (double)xi.w + (double)xj.w;
+                    sh[2 * r] = make_float4(hierarchy_merged(xi.w, xi.x, xj.w, xj.x, M), hierarchy_merged(xi.w, xi.y, xj.w, xj.y, M),
+                                            hierarchy_merged(xi.w, xi.z, xj.w, xj.z, M), mass);
+                    sh[2 * r + 1] = make_float4(hierarchy_merged(xi.w, vi.x, xj.w, vj.x, M), hierarchy_merged(xi.w, vi.y, xj.w, vj.y, M),
+                                                hierarchy_merged(xi.w, vi.z, xj.w, vj.z, M), 0.f);
+                    sh[2 * j].w = dead;
+                    nid[r] = id;
+                    nid[j] = -1;
+                    int leaves = 0, stable = 1;
+#pragma unroll 1
+                    for (int c = 0; c < 2; ++c) {
+                        const int cid = c ? cj : ci;
+                        if (cid < n) {
+                            leaves += 1;
+                            continue;
+                        }
+                        BatchHierarchyNode *child = nodes + base + (cid - n);
+                        const double mc = c ? (double)xj.w : (double)xi.w, mo = c ? (double)xi.w : (double)xj.w;
+                        const double hc[3] = {child->h[0], child->h[1], child->h[2]};
+                        const double imut = hierarchy_mutual_inclination(rec.h, hc);
+                        const bool passes = hierarchy_child_passes(rec.semi_major_axis, rec.eccentricity, child->semi_major_axis,
+                                                                   mo / mc, imut);
+                        stable = (passes && child->stable) ? stable : 0;
+                        leaves += child->leaves;
+                        out->mutual_inclination[c] = imut;
+                        child->parent = id;
+                    }
+                    out->leaves = leaves;
+                    out->stable = stable;
+                }
+                level_made += total;
+            }
+            // The same words of `made` in every lane of every wave: the exit is the workgroup's.
+            const int level_nodes = __builtin_amdgcn_readfirstlane(level_made);
+            nodes_made += level_nodes;
+            levels = t;
+            converged = (level_nodes == 0 || m - nodes_made < 2) ? 1 : 0;
+            if (converged || t >= max_levels)
+                break;
+        }
+    }
+    __syncthreads();  // the node records and ids of the last level are in place
+    // The roots: singles, binaries, triples, higher, unstable.
+    double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const int id = r < m ? nid[r] : -1;
+        if (id >= 0) {
+            int leaves = 1, stable = 1;
+            if (id >= n) {
+                leaves = nodes[base + (id - n)].leaves;
+                stable = nodes[base + (id - n)].stable;
+            }
+            c[0] += leaves == 1 ? 1.0 : 0.0;
+            c[1] += leaves == 2 ? 1.0 : 0.0;
+            c[2] += leaves == 3 ? 1.0 : 0.0;
+            c[3] += leaves >= 4 ? 1.0 : 0.0;
+            c[4] += stable ? 0.0 : 1.0;
+        }
+    }
+    structure_block_sum(c, red, tid, T);
+    if (tid == 0)
+        systems[blockIdx.x] = BatchHierarchySystem{nodes_made, m - nodes_made, levels, converged, (int)c[0], (int)c[1], (int)c[2],
+                                                   (int)c[3], (int)c[4], 0};
+    if (fill) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r >= nodes_made && r < max_bodies)
+                nodes[base + r] = hierarchy_empty_node();
+        }
+    }
+    if (bodies) {
+        // Every leaf's parent from the nodes' children, in the LDS the roots no longer need; then every leaf climbs.
+        int *up = reinterpret_cast<int *>(sh);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                up[r] = -1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < nodes_made) {
+                const int c0 = nodes[base + r].child[0], c1 = nodes[base + r].child[1];
+                if (c0 < n)
+                    up[c0] = n + r;
+                if (c1 < n)
+                    up[c1] = n + r;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r >= max_bodies)
+                continue;
+            BatchHierarchyBody rec = hierarchy_empty_body();
+            if (r < n) {
+                rec.parent = up[r];
+                rec.root = r;
+                for (int p = rec.parent; p >= 0; p = nodes[base + (p - n)].parent) {
+                    rec.root = p;
+                    rec.depth += 1;
+                }
+            }
+            bodies[base + r] = rec;
+        }
+    }
+}
+
+// One launch over all systems.  36 bytes of dynamic LDS per body, 144 KiB at 4096 bodies: the limit is raised first, as
+// launch_batch_pairs does.  massive and bodies may be NULL; fill: write the empty records from the node count on.
+hipError_t launch_batch_hierarchy(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                                  int max_bodies, double tolerance, int max_levels, bool fill, BatchHierarchyNode *nodes,
+                                  BatchHierarchyBody *bodies, BatchHierarchySystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kHierarchyBytesPerBody * (size_t)max_bodies;
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, vel, counts, massive, max_bodies, tolerance,
+                           max_levels, fill ? 1 : 0, nodes, bodies, systems);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_hierarchy_kernel<1>);
+    case 2: return launch(batch_hierarchy_kernel<2>);
+    default: return launch(batch_hierarchy_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -3942,6 +4277,10 @@ struct nbody_batch {
     BatchMemberSystem *members_systems_dev = nullptr;  // [n_systems]
     BatchMemberBody *members_bodies_dev = nullptr;     // [n_systems][max_bodies]
     unsigned char *members_initial_dev = nullptr;      // [n_systems][max_bodies]
+    // nbody_batch_hierarchy: the records of the last call, allocated by the first call
+    BatchHierarchySystem *hierarchy_systems_dev = nullptr;  // [n_systems]
+    BatchHierarchyNode *hierarchy_nodes_dev = nullptr;      // [n_systems][max_bodies]; the kernel reads its own nodes back
+    BatchHierarchyBody *hierarchy_bodies_dev = nullptr;     // [n_systems][max_bodies], only once bodies were asked for
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -4186,6 +4525,9 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->members_systems_dev) (void)hipFree(b->members_systems_dev);
     if (b->members_bodies_dev) (void)hipFree(b->members_bodies_dev);
     if (b->members_initial_dev) (void)hipFree(b->members_initial_dev);
+    if (b->hierarchy_systems_dev) (void)hipFree(b->hierarchy_systems_dev);
+    if (b->hierarchy_nodes_dev) (void)hipFree(b->hierarchy_nodes_dev);
+    if (b->hierarchy_bodies_dev) (void)hipFree(b->hierarchy_bodies_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -4916,6 +5258,41 @@ int nbody_batch_members(nbody_batch *b, const float *d_pos, const float *d_vel, 
     BATCH_TRY(b, hipMemcpyAsync(systems_out, b->members_systems_dev, sizeof(BatchMemberSystem) * B, hipMemcpyDeviceToHost, b->stream));
     if (bodies_out)
         BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->members_bodies_dev, sizeof(BatchMemberBody) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_hierarchy(nbody_batch *b, const float *d_pos, const float *d_vel, double tidal_tolerance, int max_levels,
+                          nbody_batch_hierarchy_system *systems_out, nbody_batch_hierarchy_node *nodes_out,
+                          nbody_batch_hierarchy_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_hierarchy: batch is NULL");
+    if (!d_pos || !d_vel || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: NULL argument");
+    if (max_levels < 1 || max_levels > NBODY_BATCH_HIERARCHY_MAX_LEVELS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: max_levels must be 1 ... 16");
+    if (!(tidal_tolerance >= 0.0))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: tidal_tolerance must be >= 0 (+inf accepts every pair), not NaN");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->hierarchy_systems_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->hierarchy_systems_dev, sizeof(BatchHierarchySystem) * B));
+    if (!b->hierarchy_nodes_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->hierarchy_nodes_dev, sizeof(BatchHierarchyNode) * slots));
+    if (bodies_out && !b->hierarchy_bodies_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->hierarchy_bodies_dev, sizeof(BatchHierarchyBody) * slots));
+    BATCH_TRY(b, launch_batch_hierarchy(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                        b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                        tidal_tolerance, max_levels, nodes_out != nullptr, b->hierarchy_nodes_dev,
+                                        bodies_out ? b->hierarchy_bodies_dev : nullptr, b->hierarchy_systems_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(systems_out, b->hierarchy_systems_dev, sizeof(BatchHierarchySystem) * B, hipMemcpyDeviceToHost, b->stream));
+    if (nodes_out)
+        BATCH_TRY(b, hipMemcpyAsync(nodes_out, b->hierarchy_nodes_dev, sizeof(BatchHierarchyNode) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    if (bodies_out)
+        BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->hierarchy_bodies_dev, sizeof(BatchHierarchyBody) * slots, hipMemcpyDeviceToHost,
                                     b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

@@ -71,7 +71,14 @@ iterations): members(0) with the per-body records, with bodies=False, and with b
 and pairs() on the same state -- all synchronous calls, wall clock, alternated, medians and spreads.  An iteration is one
 n x n walk of fp32 pair terms summed in fp64, energy()'s own terms: the one-iteration call is one iteration of every system,
 and the difference of the two lean calls is given over the further iterations of the slowest system and of the mean.  The
-kernel's time alone comes from a traced run of this mode."""
+kernel's time alone comes from a traced run of this mode.
+
+--hierarchy: instead, the hierarchies (BatchedSystem.hierarchy).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one line per
+case on the state of tests/hermite_hierarchy_ref.py (singles, binaries, triples, 2 + 2 and (2 + 1) + 1 objects on a jittered
+lattice; 64 distinct systems, the rest copies): hierarchy(max_levels=16) with the node and body records, with neither, and with
+neither at tidal_tolerance = 0.01, against pairs() on the same state -- all synchronous calls, wall clock, alternated, medians
+and spreads -- and the levels evaluated.  A level is one pairs search and one shorter walk over the live roots.  The kernels'
+times alone come from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -115,6 +122,8 @@ ap.add_argument("--structure", action="store_true", help="structure() with and w
                 "and pairs() on the same state, wall clock")
 ap.add_argument("--members", action="store_true", help="members() with and without the per-body records and with one iteration "
                 "against energy() and pairs() on the same boosted state, wall clock, and the time per iteration")
+ap.add_argument("--hierarchy", action="store_true", help="hierarchy() with and without the node and body records against "
+                "pairs() on the same state of nested objects, wall clock, and the levels evaluated")
 args = ap.parse_args()
 
 
@@ -735,6 +744,70 @@ def members_lines():
         print(json.dumps(line), flush=True)
 
 
+def nested_ensemble(n, B):
+    """B systems of n bodies from the generator of tests/hermite_hierarchy_ref.py: objects(n, seed=s), 64 distinct systems, the
+    rest copies."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import hermite_hierarchy_ref as href
+    P = np.zeros((B, n, 4), np.float32)
+    V = np.zeros((B, n, 4), np.float32)
+    for s in range(B):
+        if s < 64:
+            P[s], V[s] = href.objects(n, 500 + s)
+        else:
+            P[s], V[s] = P[s % 64], V[s % 64]
+    return P, V
+
+
+def hierarchy_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = nested_ensemble(n, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"hierarchy": lambda: batch.hierarchy(max_levels=16),
+                     "hierarchy_lean": lambda: batch.hierarchy(max_levels=16, nodes=False, bodies=False),
+                     "hierarchy_lean_tolerance_0.01": lambda: batch.hierarchy(0.01, max_levels=16, nodes=False, bodies=False),
+                     "pairs": batch.pairs}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            kept = {}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    kept[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        free, strict = kept["hierarchy_lean"], kept["hierarchy_lean_tolerance_0.01"]
+        line.update({"levels_mean": round(float(free.levels.mean()), 3), "levels_max": int(free.levels.max()),
+                     "levels_mean_tolerance_0.01": round(float(strict.levels.mean()), 3),
+                     "levels_max_tolerance_0.01": int(strict.levels.max()), "converged": int(free.converged.sum()),
+                     "nodes_mean": round(float(free.nodes.mean()), 1), "multiplicity_mean": free.multiplicity().mean(axis=0).round(1).tolist(),
+                     "unstable_mean": round(float(free.unstable.mean()), 1),
+                     "lean_over_pairs_call": round(med["hierarchy_lean"] / med["pairs"], 3),
+                     "record_megabytes": round(B * n * (128 + 16) / 1e6, 1), "system_kilobytes": round(B * 40 / 1e3, 1)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.hierarchy:
+    hierarchy_lines()
+    sys.exit(0)
 if args.members:
     members_lines()
     sys.exit(0)
