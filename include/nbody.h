@@ -542,6 +542,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 /* bound members: per-body potentials and energies by iterative unbinding, the bound mass and its frame of every system */
 #include "nbody_batch_members.h"
 #include "nbody_batch_hierarchy.h"
+/* gravity at points: the acceleration, potential and tidal tensor of every system at its own bodies or at sample points */
+#include "nbody_batch_gravity.h"
 
 #ifdef __cplusplus
 }

@@ -556,6 +556,28 @@ public:
               "nbody_batch_hierarchy");
         return s;
     }
+    // Gravity at points (nbody_batch_gravity.h): the acceleration and potential that every system's sources exert at its own
+    // bodies (dPoints == nullptr: numSystems x maxBodies records, each body skipping itself) or at numPoints device points
+    // {x, y, z, ignored} per system (pointCounts: numSystems values in [0, numPoints], or nullptr for numPoints everywhere).
+    // The second form also fills six floats {xx, xy, xz, yy, yz, zz} of the tidal tensor per row.  Changes nothing the handle
+    // keeps.
+    std::vector<nbody_batch_gravity_record> gravityAt(const float *dPositions, float softening, const float *dPoints = nullptr,
+                                                      int64_t numPoints = 0, const int64_t *pointCounts = nullptr)
+    {
+        std::vector<nbody_batch_gravity_record> r((size_t)systems_ * (size_t)(dPoints ? numPoints : maxBodies_));
+        check(nbody_batch_gravity(b_, dPositions, dPoints, numPoints, pointCounts, softening, r.data(), nullptr),
+              "nbody_batch_gravity");
+        return r;
+    }
+    std::vector<nbody_batch_gravity_record> gravityAt(const float *dPositions, float softening, const float *dPoints,
+                                                      int64_t numPoints, const int64_t *pointCounts, std::vector<float> &tidal)
+    {
+        std::vector<nbody_batch_gravity_record> r((size_t)systems_ * (size_t)(dPoints ? numPoints : maxBodies_));
+        tidal.resize(r.size() * 6);
+        check(nbody_batch_gravity(b_, dPositions, dPoints, numPoints, pointCounts, softening, r.data(), tidal.data()),
+              "nbody_batch_gravity");
+        return r;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

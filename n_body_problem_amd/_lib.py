@@ -343,6 +343,21 @@ _HIERARCHY_PROTOTYPES = {
 }
 
 
+BATCH_GRAVITY_MAX_POINTS = 1048576
+
+
+class BatchGravityRecord(ctypes.Structure):
+    """``nbody_batch_gravity_record`` of include/nbody_batch_gravity.h."""
+    _fields_ = [("acceleration", c_float * 3), ("reserved", c_float), ("potential", c_double)]
+
+
+#: the entry point of include/nbody_batch_gravity.h (gravity at points of batched ensembles), which nbody.h includes
+_GRAVITY_PROTOTYPES = {
+    "nbody_batch_gravity": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_float, POINTER(BatchGravityRecord),
+                                    POINTER(c_float)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -370,7 +385,8 @@ def load() -> ctypes.CDLL:
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_EVOLVE_PROTOTYPES.items()) + list(_STOP_PROTOTYPES.items()) + \
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
-                list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()):
+                list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
+                list(_GRAVITY_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -441,6 +457,11 @@ def members_names():
 def hierarchy_names():
     """The entry point of nbody_batch_hierarchy.h."""
     return list(_HIERARCHY_PROTOTYPES)
+
+
+def gravity_names():
+    """The entry point of nbody_batch_gravity.h."""
+    return list(_GRAVITY_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

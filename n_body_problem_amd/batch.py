@@ -61,6 +61,9 @@ HIERARCHY_SYSTEM_DTYPE = np.dtype([(name, np.int32) for name in ("nodes", "roots
 assert HIERARCHY_NODE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchyNode) == 128
 assert HIERARCHY_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchyBody) == 16
 assert HIERARCHY_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchySystem) == 40
+#: one record of :meth:`BatchedSystem.gravity_at`: numpy's view of ``nbody_batch_gravity_record``
+GRAVITY_RECORD_DTYPE = np.dtype([("acceleration", np.float32, 3), ("reserved", np.float32), ("potential", np.float64)])
+assert GRAVITY_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGravityRecord) == 24
 #: the weight of a body in :meth:`BatchedSystem.structure`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -563,6 +566,46 @@ class BatchedSystem:
             body.ctypes.data_as(ctypes.POINTER(_lib.BatchHierarchyBody)) if bodies else None), self._h)
         return HierarchyResult(systems, node, body, self.counts)
 
+    def gravity_at(self, points=None, softening: float = SOFTENING_VERSION3, tidal: bool = False,
+                   point_counts=None) -> "GravityResult":
+        """The field of every system at its own bodies or at sample points (``include/nbody_batch_gravity.h`` states the
+        rules), summed on the device from the current state (waits for the queued work): the acceleration (the fp32 pair
+        terms and chains of the step kernels, so the bits a ``kick_drift`` step uses), the potential (:meth:`members`' fp32
+        terms in fp64 sums) and, with ``tidal``, the tidal tensor ``T_ab = d a_a / d x_b``.  ``points=None``: the rows are the
+        bodies of every system, test particles included, each skipping itself, and ``P = max_bodies``.  Otherwise ``points``
+        is ``(B, P, 3)`` or ``(B, P, 4)`` (a fourth word is ignored), numpy or torch, with ``1 <= P <= 1048576``; a float32
+        device tensor of shape ``(B, P, 4)`` is used in place.  ``point_counts``: ``B`` values in ``[0, P]`` for ragged point
+        sets, or ``None`` for ``P`` everywhere.  With massive counts (:meth:`set_massive_counts`) only massive bodies are
+        sources.  An external field (:meth:`set_external_field`) is not part of it.  Changes nothing: an :meth:`evolve` after
+        it is bit for bit the :meth:`evolve` without it."""
+        torch = _torch()
+        B = self.num_systems
+        dev, P = None, self.max_bodies
+        if points is not None:
+            p = points if isinstance(points, torch.Tensor) else torch.as_tensor(np.asarray(points))
+            if p.dim() != 3 or p.shape[0] != B or p.shape[2] not in (3, 4) or p.shape[1] < 1:
+                raise ValueError(f"points must have shape ({B}, P >= 1, 3) or ({B}, P >= 1, 4), got {tuple(p.shape)}")
+            P = int(p.shape[1])
+            if p.shape[2] == 4 and p.dtype == torch.float32 and p.device == self.device and p.is_contiguous():
+                dev = p                                            # in place
+            else:
+                dev = torch.zeros((B, P, 4), dtype=torch.float32, device=self.device)
+                dev[:, :, :p.shape[2]].copy_(p.to(device=self.device, dtype=torch.float32))
+        pc = None
+        if point_counts is not None:
+            pc = np.ascontiguousarray(np.asarray(point_counts).reshape(-1), dtype=np.int64)
+            if pc.shape[0] != B:
+                raise ValueError(f"expected {B} point counts, got {pc.shape[0]}")
+        rec = np.zeros((B, P), dtype=GRAVITY_RECORD_DTYPE)
+        tid = np.zeros((B, P, 6), dtype=np.float32) if tidal else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_gravity(
+            self._h, _ptr(self.positions), _ptr(dev) if dev is not None else None, P if dev is not None else 0,
+            pc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if pc is not None else None, float(softening),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchGravityRecord)),
+            tid.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tidal else None), self._h)
+        return GravityResult(rec, tid)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -770,6 +813,25 @@ class MemberResult:
                 f"iterations={self.iterations.tolist()}, converged={self.converged.tolist()})")
 
 
+class GravityResult:
+    """What :meth:`BatchedSystem.gravity_at` found, per system and row (``P`` rows: the points given, or ``max_bodies``
+    without points): ``acceleration`` (``(B, P, 3)`` float32, ``G = 1``), ``potential`` (``(B, P)`` float64, ``<= 0``) and
+    ``tidal`` (``(B, P, 3, 3)`` float32, symmetric: ``T_ab = d a_a / d x_b``, whose trace is ``-3 eps^2 sum m (r^2 + eps^2)^-5/2``
+    and zero without softening), or ``None`` without ``tidal``.  Rows from the point count or body count on read 0."""
+
+    #: where the six words {xx, xy, xz, yy, yz, zz} of a row go in its 3 x 3 tensor
+    TIDAL_INDEX = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])
+
+    def __init__(self, records, tidal):
+        self.acceleration = np.ascontiguousarray(records["acceleration"])
+        self.potential = np.ascontiguousarray(records["potential"])
+        self.tidal = None if tidal is None else np.ascontiguousarray(tidal[..., self.TIDAL_INDEX])
+
+    def __repr__(self):
+        B, P = self.potential.shape
+        return f"GravityResult(systems={B}, rows={P}, tidal={self.tidal is not None})"
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -844,4 +906,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -14,6 +14,7 @@
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
+#include "nbody_batch_gravity_math.h"
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_pairs_elements.h"
@@ -3803,6 +3804,120 @@ hipError_t launch_batch_members(const float4 *pos, const float4 *vel, const int 
     }
 }
 
+// ---- gravity at points (include/nbody_batch_gravity.h): the acceleration, the potential and the tidal tensor of every system
+// at its own bodies (SELF) or at the caller's points.  A sibling of batch_members_kernel with a second grid dimension: a
+// workgroup serves one system and one block of rows (gravity_plan_own / gravity_plan_points of nbody_batch_gravity_math.h),
+// with the system's m sources in LDS as {x, y, z, m}, read by wave-uniform broadcasts; each lane holds RPL rows in registers,
+// row gravity_row(block, RPL, T, q, lane).  Every pair and every sum goes through gravity_pair and GravityRow of that header,
+// which are batch_forces' r2, inv, s and chain and members_columns' fp64 sum: a loop of its own, so that every kernel above
+// stays the code it is (see batch_forces_jerks on OWN).  No atomics, no reduction: a row's outputs are its lane's alone.  It
+// reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchGravityRecord) == sizeof(nbody_batch_gravity_record) && sizeof(nbody_batch_gravity_record) == 24 &&
+                  offsetof(BatchGravityRecord, acceleration) == offsetof(nbody_batch_gravity_record, acceleration) &&
+                  offsetof(BatchGravityRecord, reserved) == offsetof(nbody_batch_gravity_record, reserved) &&
+                  offsetof(BatchGravityRecord, potential) == offsetof(nbody_batch_gravity_record, potential),
+              "nbody_batch_gravity_math.h mirrors the record of nbody_batch_gravity.h");
+static_assert(kGravityMaxPoints == NBODY_BATCH_GRAVITY_MAX_POINTS, "nbody_batch_gravity_math.h mirrors the limit of nbody_batch_gravity.h");
+
+// SELF: the rows are the bodies r < n of pos and `stride` is max_bodies; otherwise the rows are the points r < point_counts[s]
+// (n_points where point_counts is null) of `points` and `stride` is n_points.  Rows from the count on up to `stride` receive the
+// empty record; a block without a row below the count writes those and returns before it loads a source.  One row per lane is
+// held to the 64 registers of eight waves per SIMD, as batch_members_kernel<1> is.
+template <int RPL, bool GUARD, bool SELF, bool TIDAL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_gravity_kernel(
+    const float4 *pos, const float4 *points, const int *counts, const int *massive, const int *point_counts, int max_bodies,
+    int stride, float eps2, BatchGravityRecord *records, float *tidal)
+{
+    extern __shared__ float4 sh[];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int pc = SELF ? n : (point_counts ? point_counts[blockIdx.x] : stride);
+    const int rows = pc < stride ? pc : stride;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const int first = gravity_row(blockIdx.y, RPL, T, 0, 0);
+    const size_t src = (size_t)blockIdx.x * (size_t)max_bodies, base = (size_t)blockIdx.x * (size_t)stride;
+    if (first >= rows) {  // workgroup-uniform: no barrier is passed
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+            if (r < stride) {
+                records[base + r] = gravity_empty_record();
+                if (TIDAL) {
+#pragma unroll
+                    for (int c = 0; c < kGravityTidalWords; ++c)
+                        tidal[(base + r) * kGravityTidalWords + c] = 0.f;
+                }
+            }
+        }
+        return;
+    }
+    for (int j = tid; j < m; j += T)
+        sh[j] = pos[src + j];
+    float4 x[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < rows)
+            x[q] = SELF ? pos[src + r] : points[base + r];
+    }
+    __syncthreads();
+    GravityRow<TIDAL> row[RPL];
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[j];  // wave-uniform address: broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            row[q].add(gravity_pair<GUARD, TIDAL>(x[q].x, x[q].y, x[q].z, pj.x, pj.y, pj.z, pj.w, eps2,
+                                                  SELF && j == gravity_row(blockIdx.y, RPL, T, q, tid)));
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+        if (r < stride) {
+            float t[kGravityTidalWords] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (TIDAL && r < rows)
+                row[q].tidal(t);
+            records[base + r] = r < rows ? row[q].record() : gravity_empty_record();
+            if (TIDAL) {
+#pragma unroll
+                for (int c = 0; c < kGravityTidalWords; ++c)
+                    tidal[(base + r) * kGravityTidalWords + c] = t[c];
+            }
+        }
+    }
+}
+
+// One launch over all systems and row blocks.  64 KiB of dynamic LDS at 4096 bodies: the limit is raised first, as
+// launch_batch_members does.  points null: own-bodies mode.  massive, point_counts and tidal may be null.
+hipError_t launch_batch_gravity(const float4 *pos, const float4 *points, const int *counts, const int *massive,
+                                const int *point_counts, int n_systems, int max_bodies, int n_points, float eps2,
+                                BatchGravityRecord *records, float *tidal, hipStream_t stream)
+{
+    const bool self = points == nullptr;
+    const GravityPlan plan = self ? gravity_plan_own(max_bodies) : gravity_plan_points(n_points);
+    const int stride = self ? max_bodies : n_points;
+    const size_t lds = gravity_lds_bytes(max_bodies);
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems, plan.blocks), dim3(plan.threads), lds, stream, pos, points, counts, massive,
+                           point_counts, max_bodies, stride, eps2, records, tidal);
+        return hipGetLastError();
+    };
+    const auto with_modes = [&](auto rpl, auto guard) {
+        constexpr int R = decltype(rpl)::value;
+        constexpr bool G = decltype(guard)::value;
+        if (self)
+            return tidal ? launch(batch_gravity_kernel<R, G, true, true>) : launch(batch_gravity_kernel<R, G, true, false>);
+        return tidal ? launch(batch_gravity_kernel<R, G, false, true>) : launch(batch_gravity_kernel<R, G, false, false>);
+    };
+    return with_shape(plan.rpl, !(eps2 > 0.f), with_modes);
+}
+
 // ---- hierarchies (include/nbody_batch_hierarchy.h): nested bound pairs.  Level by level the live roots of a system look for
 // partners as batch_pairs_kernel's rows do, the mutual bound pairs that their worst perturber lets stand become nodes with the
 // merged body's state, and the search runs again over what is left.  A sibling of batch_pairs_kernel: one workgroup per
@@ -4281,6 +4396,13 @@ struct nbody_batch {
     BatchHierarchySystem *hierarchy_systems_dev = nullptr;  // [n_systems]
     BatchHierarchyNode *hierarchy_nodes_dev = nullptr;      // [n_systems][max_bodies]; the kernel reads its own nodes back
     BatchHierarchyBody *hierarchy_bodies_dev = nullptr;     // [n_systems][max_bodies], only once bodies were asked for
+    // nbody_batch_gravity: the records and tidal words of the last call, allocated on first use and grown when a call needs more
+    // rows; the device copy of the point counts
+    BatchGravityRecord *gravity_records_dev = nullptr;  // [gravity_rows]
+    float *gravity_tidal_dev = nullptr;                 // [gravity_tidal_rows][6]
+    size_t gravity_rows = 0, gravity_tidal_rows = 0;
+    int *gravity_counts_dev = nullptr;                  // [n_systems]
+    std::vector<int> gravity_counts;                    // host copy of the last call's point counts
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -4528,6 +4650,9 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->hierarchy_systems_dev) (void)hipFree(b->hierarchy_systems_dev);
     if (b->hierarchy_nodes_dev) (void)hipFree(b->hierarchy_nodes_dev);
     if (b->hierarchy_bodies_dev) (void)hipFree(b->hierarchy_bodies_dev);
+    if (b->gravity_records_dev) (void)hipFree(b->gravity_records_dev);
+    if (b->gravity_tidal_dev) (void)hipFree(b->gravity_tidal_dev);
+    if (b->gravity_counts_dev) (void)hipFree(b->gravity_counts_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -5293,6 +5418,65 @@ int nbody_batch_hierarchy(nbody_batch *b, const float *d_pos, const float *d_vel
                                     b->stream));
     if (bodies_out)
         BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->hierarchy_bodies_dev, sizeof(BatchHierarchyBody) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_gravity(nbody_batch *b, const float *d_pos, const float *d_points, int64_t n_points, const int64_t *host_point_counts,
+                        float softening, nbody_batch_gravity_record *records_out, float *tidal_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_gravity: batch is NULL");
+    if (!d_pos || !records_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: NULL argument");
+    if (!d_points && (n_points != 0 || host_point_counts))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: n_points or host_point_counts given without points (own-bodies mode "
+                                           "takes n_points = 0 and no point counts)");
+    if (d_points && (n_points < 1 || n_points > NBODY_BATCH_GRAVITY_MAX_POINTS))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: n_points must be 1 ... NBODY_BATCH_GRAVITY_MAX_POINTS (1048576)");
+    const size_t B = (size_t)b->n_systems;
+    if (host_point_counts)
+        for (size_t s = 0; s < B; ++s)
+            if (host_point_counts[s] < 0 || host_point_counts[s] > n_points)
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: the point count of system " + std::to_string(s) + " is " +
+                                                       std::to_string(host_point_counts[s]) + ", outside [0, n_points]");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    const size_t rows = B * (size_t)(d_points ? n_points : b->max_bodies);
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (rows > b->gravity_rows) {
+        if (b->gravity_records_dev)
+            (void)hipFree(b->gravity_records_dev);
+        b->gravity_records_dev = nullptr;
+        b->gravity_rows = 0;
+        BATCH_TRY(b, hipMalloc((void **)&b->gravity_records_dev, sizeof(BatchGravityRecord) * rows));
+        b->gravity_rows = rows;
+    }
+    if (tidal_out && rows > b->gravity_tidal_rows) {
+        if (b->gravity_tidal_dev)
+            (void)hipFree(b->gravity_tidal_dev);
+        b->gravity_tidal_dev = nullptr;
+        b->gravity_tidal_rows = 0;
+        BATCH_TRY(b, hipMalloc((void **)&b->gravity_tidal_dev, sizeof(float) * kGravityTidalWords * rows));
+        b->gravity_tidal_rows = rows;
+    }
+    if (host_point_counts) {
+        if (!b->gravity_counts_dev)
+            BATCH_TRY(b, hipMalloc((void **)&b->gravity_counts_dev, sizeof(int) * B));
+        b->gravity_counts.assign(B, 0);
+        for (size_t s = 0; s < B; ++s)
+            b->gravity_counts[s] = (int)host_point_counts[s];
+        BATCH_TRY(b, hipMemcpyAsync(b->gravity_counts_dev, b->gravity_counts.data(), sizeof(int) * B, hipMemcpyHostToDevice, b->stream));
+    }
+    BATCH_TRY(b, launch_batch_gravity(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_points), b->counts_dev,
+                                      b->config.massive_set ? b->massive_dev : nullptr,
+                                      host_point_counts ? b->gravity_counts_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                      (int)n_points, softening * softening, b->gravity_records_dev,
+                                      tidal_out ? b->gravity_tidal_dev : nullptr, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(records_out, b->gravity_records_dev, sizeof(BatchGravityRecord) * rows, hipMemcpyDeviceToHost, b->stream));
+    if (tidal_out)
+        BATCH_TRY(b, hipMemcpyAsync(tidal_out, b->gravity_tidal_dev, sizeof(float) * kGravityTidalWords * rows, hipMemcpyDeviceToHost,
                                     b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

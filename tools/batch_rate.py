@@ -78,7 +78,14 @@ case on the state of tests/hermite_hierarchy_ref.py (singles, binaries, triples,
 lattice; 64 distinct systems, the rest copies): hierarchy(max_levels=16) with the node and body records, with neither, and with
 neither at tidal_tolerance = 0.01, against pairs() on the same state -- all synchronous calls, wall clock, alternated, medians
 and spreads -- and the levels evaluated.  A level is one pairs search and one shorter walk over the live roots.  The kernels'
-times alone come from a traced run of this mode."""
+times alone come from a traced run of this mode.
+
+--gravity: instead, gravity at points (BatchedSystem.gravity_at).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one line
+per case on the boosted Plummer spheres of --members: gravity_at() in own-bodies mode with the tidal tensor and without it,
+against members(max_iterations=1, bodies=False) and energy() at the same softening on the same state; then one line for a
+65536-point grid per system at n x B = 1024 x 64, with and without the tensor.  All synchronous calls, wall clock, alternated,
+medians and spreads.  A call is one n x n (or points x n) walk and returns 24 bytes per row, 48 with the tensor: the copy to the
+host is part of the wall time, so the kernel's time alone comes from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -124,6 +131,8 @@ ap.add_argument("--members", action="store_true", help="members() with and witho
                 "against energy() and pairs() on the same boosted state, wall clock, and the time per iteration")
 ap.add_argument("--hierarchy", action="store_true", help="hierarchy() with and without the node and body records against "
                 "pairs() on the same state of nested objects, wall clock, and the levels evaluated")
+ap.add_argument("--gravity", action="store_true", help="gravity_at() at the systems' own bodies with and without the tidal tensor "
+                "against members(max_iterations=1) and energy() on the same state, and a 65536-point grid per system, wall clock")
 args = ap.parse_args()
 
 
@@ -805,6 +814,70 @@ def hierarchy_lines():
         print(json.dumps(line), flush=True)
 
 
+def gravity_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+
+    def measure(batch, calls):
+        def wall(fn):
+            batch.sync()
+            t0 = time.perf_counter()
+            fn()
+            return (time.perf_counter() - t0) * 1e3
+
+        for fn in calls.values():                       # the first calls allocate the records and set the kernels' LDS limits
+            wall(fn)
+        times = {name: [] for name in calls}
+        for _ in range(args.repeats):                   # alternated
+            for name, fn in calls.items():
+                times[name].append(wall(fn))
+        return times, {name: statistics.median(ts) for name, ts in times.items()}
+
+    def report(line, calls, times, med):
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = boosted_ensemble(n, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+            calls = {"gravity_own_tidal": lambda: batch.gravity_at(softening=args.eps, tidal=True),
+                     "gravity_own": lambda: batch.gravity_at(softening=args.eps),
+                     "members_lean_one_iteration": lambda: batch.members(args.eps, max_iterations=1, bodies=False),
+                     "members_one_iteration": lambda: batch.members(args.eps, max_iterations=1),
+                     "energy": lambda: batch.energy(args.eps)}
+            times, med = measure(batch, calls)
+        line = {"n": n, "B": B, "softening": args.eps,
+                "own_over_members_one_iteration": round(med["gravity_own"] / med["members_one_iteration"], 3),
+                "tidal_over_own": round(med["gravity_own_tidal"] / med["gravity_own"], 3),
+                "pair_evaluations_per_s_own": float(f"{B * n * n / (med['gravity_own'] * 1e-3):.4g}"),
+                "record_megabytes": round(B * n * 24 / 1e6, 1), "tidal_megabytes": round(B * n * 24 / 1e6, 1)}
+        report(line, calls, times, med)
+    n, B, side = 1024, 64, 256                          # a 256 x 256 grid in the plane z = 0 of every system
+    P, V = boosted_ensemble(n, B)
+    axis = np.linspace(-2.0, 2.0, side, dtype=np.float32)
+    grid = torch.zeros((B, side * side, 4), dtype=torch.float32, device="cuda")
+    grid[:, :, 0] = torch.as_tensor(np.repeat(axis, side)).to("cuda")
+    grid[:, :, 1] = torch.as_tensor(np.tile(axis, side)).to("cuda")
+    with nb.BatchedSystem(B, n) as batch:
+        batch.set_state(P, V)
+        calls = {"gravity_grid_tidal": lambda: batch.gravity_at(grid, softening=args.eps, tidal=True),
+                 "gravity_grid": lambda: batch.gravity_at(grid, softening=args.eps)}
+        times, med = measure(batch, calls)
+    line = {"n": n, "B": B, "points_per_system": side * side, "softening": args.eps,
+            "pair_evaluations_per_s_grid": float(f"{B * side * side * n / (med['gravity_grid'] * 1e-3):.4g}"),
+            "record_megabytes": round(B * side * side * 24 / 1e6, 1), "tidal_megabytes": round(B * side * side * 24 / 1e6, 1)}
+    report(line, calls, times, med)
+
+
+if args.gravity:
+    gravity_lines()
+    sys.exit(0)
 if args.hierarchy:
     hierarchy_lines()
     sys.exit(0)
