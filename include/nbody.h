@@ -544,6 +544,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_hierarchy.h"
 /* gravity at points: the acceleration, potential and tidal tensor of every system at its own bodies or at sample points */
 #include "nbody_batch_gravity.h"
+/* groups: friends-of-friends clumps at a linking length, the members, centre and velocity of every piece of every system */
+#include "nbody_batch_groups.h"
 
 #ifdef __cplusplus
 }

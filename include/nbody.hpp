@@ -578,6 +578,29 @@ public:
               "nbody_batch_gravity");
         return r;
     }
+    // Groups (nbody_batch_groups.h): friends-of-friends clumps from the state in the caller's buffers.  linkingLengths: one
+    // value per system (host).  Per system the groups with at least minMembers members, the bodies in them, the singles, the
+    // largest group, the sweeps run (1 <= maxSweeps <= 64) and whether they converged.  groups and bodies, where given, are
+    // resized to numSystems x maxBodies and take the per-slot group records (filled at a group's root) and the per-body
+    // {group, size}; nullptr skips that copy.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_group_system> groups(const float *dPositions, const float *dVelocities,
+                                                 const std::vector<float> &linkingLengths, int minMembers = 2,
+                                                 int weight = NBODY_BATCH_WEIGHT_MASS, int maxSweeps = NBODY_BATCH_GROUPS_MAX_SWEEPS,
+                                                 std::vector<nbody_batch_group_record> *groups = nullptr,
+                                                 std::vector<nbody_batch_group_body> *bodies = nullptr)
+    {
+        if (linkingLengths.size() != (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::groups: one linking length per system");
+        std::vector<nbody_batch_group_system> s((size_t)systems_);
+        if (groups)
+            groups->resize((size_t)systems_ * (size_t)maxBodies_);
+        if (bodies)
+            bodies->resize((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_groups(b_, dPositions, dVelocities, linkingLengths.data(), minMembers, weight, maxSweeps, s.data(),
+                                 groups ? groups->data() : nullptr, bodies ? bodies->data() : nullptr),
+              "nbody_batch_groups");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -358,6 +358,32 @@ _GRAVITY_PROTOTYPES = {
 }
 
 
+BATCH_GROUPS_MAX_SWEEPS = 64
+
+
+class BatchGroupBody(ctypes.Structure):
+    """``nbody_batch_group_body`` of include/nbody_batch_groups.h."""
+    _fields_ = [("group", c_int), ("size", c_int)]
+
+
+class BatchGroupRecord(ctypes.Structure):
+    """``nbody_batch_group_record`` of include/nbody_batch_groups.h."""
+    _fields_ = [("weight", c_double), ("centre", c_double * 3), ("velocity", c_double * 3), ("count", c_int), ("sources", c_int)]
+
+
+class BatchGroupSystem(ctypes.Structure):
+    """``nbody_batch_group_system`` of include/nbody_batch_groups.h."""
+    _fields_ = [("groups", c_int), ("grouped", c_int), ("singles", c_int), ("largest", c_int), ("largest_count", c_int),
+                ("sweeps", c_int), ("converged", c_int), ("reserved", c_int)]
+
+
+#: the entry point of include/nbody_batch_groups.h (friends-of-friends groups of batched ensembles), which nbody.h includes
+_GROUPS_PROTOTYPES = {
+    "nbody_batch_groups": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(BatchGroupSystem),
+                                   POINTER(BatchGroupRecord), POINTER(BatchGroupBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -386,7 +412,7 @@ def load() -> ctypes.CDLL:
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
-                list(_GRAVITY_PROTOTYPES.items()):
+                list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -462,6 +488,11 @@ def hierarchy_names():
 def gravity_names():
     """The entry point of nbody_batch_gravity.h."""
     return list(_GRAVITY_PROTOTYPES)
+
+
+def groups_names():
+    """The entry point of nbody_batch_groups.h."""
+    return list(_GROUPS_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

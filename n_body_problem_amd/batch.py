@@ -64,7 +64,16 @@ assert HIERARCHY_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchHierarchySyste
 #: one record of :meth:`BatchedSystem.gravity_at`: numpy's view of ``nbody_batch_gravity_record``
 GRAVITY_RECORD_DTYPE = np.dtype([("acceleration", np.float32, 3), ("reserved", np.float32), ("potential", np.float64)])
 assert GRAVITY_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGravityRecord) == 24
-#: the weight of a body in :meth:`BatchedSystem.structure`: its mass word, or 1
+#: the records of :meth:`BatchedSystem.groups`: numpy's views of ``nbody_batch_group_body``, ``_record`` and ``_system``
+GROUP_BODY_DTYPE = np.dtype([("group", np.int32), ("size", np.int32)])
+GROUP_RECORD_DTYPE = np.dtype([("weight", np.float64), ("centre", np.float64, 3), ("velocity", np.float64, 3),
+                               ("count", np.int32), ("sources", np.int32)])
+GROUP_SYSTEM_DTYPE = np.dtype([(name, np.int32) for name in ("groups", "grouped", "singles", "largest", "largest_count", "sweeps",
+                                                             "converged", "reserved")])
+assert GROUP_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupBody) == 8
+assert GROUP_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupRecord) == 64
+assert GROUP_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupSystem) == 32
+#: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
 
@@ -606,6 +615,37 @@ class BatchedSystem:
             tid.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tidal else None), self._h)
         return GravityResult(rec, tid)
 
+    def groups(self, linking_length, min_members: int = 2, weight: str = "mass", max_sweeps: int = _lib.BATCH_GROUPS_MAX_SWEEPS,
+               records: bool = True, bodies: bool = True) -> "BatchGroups":
+        """Into which pieces every system has fallen (``include/nbody_batch_groups.h`` states the rules): friends-of-friends
+        groups on the device from the current state (waits for the queued work).  Two bodies are friends where their fp32
+        distance is at most ``linking_length`` (a scalar, or ``B`` values, one per system); a group is a connected set of
+        friends, named by the lowest index among its members.  All bodies link, test particles included; with massive counts
+        (:meth:`set_massive_counts`) and ``weight="mass"`` only massive bodies weigh, and the tracers' mass words are not read;
+        ``weight="number"`` weighs every body 1.  ``min_members`` sets which groups ``groups`` and ``grouped`` count and
+        :meth:`BatchGroups.groups_of` lists; the labels and records do not depend on it.  ``max_sweeps`` (1 ... 64) bounds the
+        label sweeps; a handful converge.  ``records=False`` and ``bodies=False`` skip the 64 bytes per slot and the 8 bytes
+        per body on their way to the host: those arrays of the result are ``None``, the per-system ones the same bits.  Changes
+        nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+        b = np.asarray(linking_length, dtype=np.float32)
+        if b.ndim == 0:
+            b = np.full(self.num_systems, b, dtype=np.float32)
+        b = np.ascontiguousarray(b.reshape(-1))
+        if b.shape[0] != self.num_systems:
+            raise ValueError(f"expected one linking length or {self.num_systems}, got {b.shape[0]}")
+        systems = np.zeros(self.num_systems, dtype=GROUP_SYSTEM_DTYPE)
+        rec = np.zeros((self.num_systems, self.max_bodies), dtype=GROUP_RECORD_DTYPE) if records else None
+        body = np.zeros((self.num_systems, self.max_bodies), dtype=GROUP_BODY_DTYPE) if bodies else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_groups(
+            self._h, _ptr(self.positions), _ptr(self.velocities), b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            int(min_members), WEIGHTS[weight], int(max_sweeps), systems.ctypes.data_as(ctypes.POINTER(_lib.BatchGroupSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchGroupRecord)) if records else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchGroupBody)) if bodies else None), self._h)
+        return BatchGroups(systems, rec, body, b, int(min_members), weight)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -832,6 +872,61 @@ class GravityResult:
         return f"GravityResult(systems={B}, rows={P}, tidal={self.tidal is not None})"
 
 
+class BatchGroups:
+    """What :meth:`BatchedSystem.groups` found.  Per system (``(B,)`` int32 arrays): ``groups`` (those with at least
+    ``min_members`` members), ``grouped`` (the bodies in them), ``singles`` (groups of one body), ``largest`` (the root of the
+    group with the most members, ties to the lower root; -1 for an empty system), ``largest_count``, ``sweeps`` (the label
+    sweeps run) and ``converged`` (bool: the last sweep lowered no label).  Per body, ``(B, max_bodies)`` int32 arrays or ``None``
+    without ``bodies``: ``group`` (the root of the body's group, the lowest index among its members; -1 from the count on) and
+    ``size`` (its members; 0 from the count on).  Per slot, ``(B, max_bodies)`` arrays or ``None`` without ``records``, filled
+    at a group's root and 0 elsewhere: ``weight`` (float64), ``centre`` and ``velocity`` (``(B, max_bodies, 3)`` float64: the
+    weighted means; 0 where the weight is 0), ``count`` and ``sources`` (int32: all members, and the massive ones).
+    ``linking_length`` (``(B,)`` float32), ``min_members`` and ``weight_kind`` are the call's arguments."""
+
+    def __init__(self, systems, records, bodies, linking_length, min_members, weight):
+        self.systems, self.group_records, self.body_records = systems, records, bodies
+        self.linking_length, self.min_members, self.weight_kind = np.asarray(linking_length, dtype=np.float32), int(min_members), weight
+        for name in ("groups", "grouped", "singles", "largest", "largest_count", "sweeps"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.converged = systems["converged"] != 0
+        self.group = self.size = None
+        if bodies is not None:
+            self.group, self.size = np.ascontiguousarray(bodies["group"]), np.ascontiguousarray(bodies["size"])
+        self.weight = self.centre = self.velocity = self.count = self.sources = None
+        if records is not None:
+            for name in ("weight", "centre", "velocity", "count", "sources"):
+                setattr(self, name, np.ascontiguousarray(records[name]))
+
+    def _need_bodies(self, what):
+        if self.group is None:
+            raise ValueError(f"{what} needs the per-body records: call groups(bodies=True)")
+
+    def roots(self, s: int) -> np.ndarray:
+        """The roots of all groups of system ``s`` in ascending order, groups of one body included."""
+        self._need_bodies("roots")
+        g = self.group[s]
+        return np.flatnonzero(g == np.arange(g.shape[0])).astype(np.int32)
+
+    def groups_of(self, s: int) -> list:
+        """The member index arrays (ascending) of system ``s``'s groups with at least ``min_members`` members, the largest
+        group first, ties by the lower root."""
+        self._need_bodies("groups_of")
+        g, size = self.group[s], self.size[s]
+        roots = [int(r) for r in self.roots(s) if size[r] >= self.min_members]
+        roots.sort(key=lambda r: (-int(size[r]), r))
+        return [np.flatnonzero(g == r) for r in roots]
+
+    def largest_mask(self) -> np.ndarray:
+        """``(B, max_bodies)`` bool: the members of every system's largest group -- a starting set for
+        :meth:`BatchedSystem.members` (``initial=``)."""
+        self._need_bodies("largest_mask")
+        return (self.group == self.largest[:, None]) & (self.group >= 0)
+
+    def __repr__(self):
+        return (f"BatchGroups(groups={self.groups.tolist()}, largest_count={self.largest_count.tolist()}, "
+                f"sweeps={self.sweeps.tolist()}, converged={self.converged.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -906,4 +1001,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

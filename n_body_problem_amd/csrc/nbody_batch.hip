@@ -15,6 +15,7 @@
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
 #include "nbody_batch_gravity_math.h"
+#include "nbody_batch_groups_math.h"
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_pairs_elements.h"
@@ -4252,6 +4253,251 @@ hipError_t launch_batch_hierarchy(const float4 *pos, const float4 *vel, const in
     }
 }
 
+// ---- groups (include/nbody_batch_groups.h): friends-of-friends clumps at a linking length.  Every row's label is lowered to
+// the smallest label among its friends, its root is hooked below, the labels are compressed, and again until a sweep lowers
+// nothing; then every row sums its group's weight, position and velocity in fp64 and the roots write the records.  A sibling of
+// batch_members_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane
+// at r = q * T + lane.  The labels never leave the CU.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchGroupBody) == sizeof(nbody_batch_group_body) && sizeof(nbody_batch_group_body) == 8 &&
+                  offsetof(BatchGroupBody, group) == offsetof(nbody_batch_group_body, group) &&
+                  offsetof(BatchGroupBody, size) == offsetof(nbody_batch_group_body, size),
+              "nbody_batch_groups_math.h mirrors the body record of nbody_batch_groups.h");
+static_assert(sizeof(BatchGroupRecord) == sizeof(nbody_batch_group_record) && sizeof(nbody_batch_group_record) == 64 &&
+                  offsetof(BatchGroupRecord, weight) == offsetof(nbody_batch_group_record, weight) &&
+                  offsetof(BatchGroupRecord, centre) == offsetof(nbody_batch_group_record, centre) &&
+                  offsetof(BatchGroupRecord, velocity) == offsetof(nbody_batch_group_record, velocity) &&
+                  offsetof(BatchGroupRecord, count) == offsetof(nbody_batch_group_record, count) &&
+                  offsetof(BatchGroupRecord, sources) == offsetof(nbody_batch_group_record, sources),
+              "nbody_batch_groups_math.h mirrors the group record of nbody_batch_groups.h");
+static_assert(sizeof(BatchGroupSystem) == sizeof(nbody_batch_group_system) && sizeof(nbody_batch_group_system) == 32 &&
+                  offsetof(BatchGroupSystem, groups) == offsetof(nbody_batch_group_system, groups) &&
+                  offsetof(BatchGroupSystem, grouped) == offsetof(nbody_batch_group_system, grouped) &&
+                  offsetof(BatchGroupSystem, singles) == offsetof(nbody_batch_group_system, singles) &&
+                  offsetof(BatchGroupSystem, largest) == offsetof(nbody_batch_group_system, largest) &&
+                  offsetof(BatchGroupSystem, largest_count) == offsetof(nbody_batch_group_system, largest_count) &&
+                  offsetof(BatchGroupSystem, sweeps) == offsetof(nbody_batch_group_system, sweeps) &&
+                  offsetof(BatchGroupSystem, converged) == offsetof(nbody_batch_group_system, converged) &&
+                  offsetof(BatchGroupSystem, reserved) == offsetof(nbody_batch_group_system, reserved),
+              "nbody_batch_groups_math.h mirrors the system record of nbody_batch_groups.h");
+static_assert(kGroupsMaxSweeps == NBODY_BATCH_GROUPS_MAX_SWEEPS && kGroupsWeightMass == NBODY_BATCH_WEIGHT_MASS &&
+                  kGroupsWeightNumber == NBODY_BATCH_WEIGHT_NUMBER,
+              "nbody_batch_groups_math.h mirrors the limit of nbody_batch_groups.h and the weights of nbody_batch_structure.h");
+static_assert(sizeof(int4) == kGroupsWords * sizeof(int) && kBatchBytesPerBody == sizeof(int4), "a column is one 16-byte read");
+
+// The image {x, y, z, label} and, for the records, the labels in an array of their own while the image holds {x, y, z, w} and
+// then {vx, vy, vz, w}: 20 bytes per body.
+constexpr size_t kGroupsBytesPerBody = kBatchBytesPerBody + sizeof(int);
+
+// Whether any lane of the workgroup says so: a ballot per wave, the waves through flags[16].  Every lane returns the same
+// word, so a loop that leaves on it is left by the whole workgroup.  Its first barrier also ends the reads the lanes did
+// before the call.
+__device__ inline bool groups_block_any(bool mine, int *flags, int tid, int T)
+{
+    const int wave = __ballot(mine) != 0 ? 1 : 0;
+    __syncthreads();  // every lane is done with what it read before, the flags of the call before among it
+    if ((tid & 63) == 0)
+        flags[tid >> 6] = wave;
+    __syncthreads();
+    int any = 0;
+    for (int w = 0; w < T / 64; ++w)
+        any |= flags[w];
+    return __builtin_amdgcn_readfirstlane(any) != 0;
+}
+
+// LDS: img[j] = {x, y, z, label} of body j as four words, one ds_read_b128 per column (64 KiB at 4096 bodies), and lab[j]
+// behind it for the records (16 KiB more; the limit is raised before the launch).  Rows from the count on carry NaN
+// coordinates: they link to nothing, are lowered by nothing and write nothing.
+// Every loop that holds a barrier has a workgroup-uniform trip count: n, t and max_sweeps are uniform, and "a label was
+// lowered" and "a pass changed a label" come out of groups_block_any; no lane leaves on data of its own.
+// One row per lane is held to the 64 registers of eight waves per SIMD, as in batch_members_kernel<1>.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_groups_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, const float *linking2, int max_bodies,
+    int min_members, int weight, int max_sweeps, BatchGroupBody *bodies, BatchGroupRecord *records, BatchGroupSystem *systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int flags[16];
+    __shared__ int tally[4];  // groups, grouped, singles, the largest key
+    int *words = reinterpret_cast<int *>(img);
+    int *lab = words + kGroupsWords * max_bodies;
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const float b2 = linking2[blockIdx.x];
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the mass word}
+    int L[RPL];     // the row's label
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const float none = __int_as_float(0x7fc00000);
+        x[q] = make_float4(none, none, none, 0.f);
+        L[q] = r;
+        if (r < n) {
+            x[q] = pos[base + r];
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), r);
+        }
+    }
+    if (tid == 0) {
+        tally[0] = tally[1] = tally[2] = 0;
+        tally[3] = kGroupsKeyNone;
+    }
+    // Phase 1, the sweeps.
+    int sweeps = 0, converged = 1;  // a system without bodies runs no sweep
+    if (n > 0) {
+        for (int t = 1;; ++t) {
+            __syncthreads();  // the image, or the labels the sweep before left, are in place
+            int c[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                c[q] = L[q];
+#pragma unroll 4
+            for (int j = 0; j < n; ++j) {
+                const int4 pj = img[j];
+                const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+                for (int q = 0; q < RPL; ++q)
+                    c[q] = groups_link(c[q], x[q].x, x[q].y, x[q].z, xj, yj, zj, pj.w, b2);
+            }
+            bool low = false;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                low = low || groups_lowered(c[q], L[q]);
+            const bool lowered = groups_block_any(low, flags, tid, T);  // its barriers: every lane is done reading the labels
+            sweeps = t;
+            converged = lowered ? 0 : 1;
+            if (!lowered)
+                break;
+            // Hook: the roots take the minimum of what their rows found.  An LDS integer atomic: the order does not matter.
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                if (groups_lowered(c[q], L[q]))
+                    groups_hook(words, q * T + tid, L[q], c[q], [](int *address, int value) { atomicMin(address, value); });
+            }
+            // Compress: every row reads its root's label, then every row writes, until a pass changes nothing.
+            for (;;) {
+                __syncthreads();  // the hooks, or the pass before, are in place
+                int next[RPL];
+                bool moved = false;
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const int r = q * T + tid;
+                    next[q] = L[q];
+                    if (r < n) {
+                        const int now = words[groups_label_at(r)];
+                        next[q] = groups_compress(words, now);
+                        moved = moved || next[q] != now;
+                    }
+                }
+                const bool again = groups_block_any(moved, flags, tid, T);  // its barriers: every row has read
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const int r = q * T + tid;
+                    L[q] = next[q];
+                    if (r < n)
+                        words[groups_label_at(r)] = next[q];
+                }
+                if (!again)
+                    break;
+            }
+            if (t >= max_sweeps)
+                break;
+        }
+    }
+    // Phase 2, the records: the image takes the weights, the labels move behind it.
+    __syncthreads();  // every lane is done with the labels in the image
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            x[q].w = groups_weight(weight, x[q].w, r < m);
+            words[groups_label_at(r)] = __float_as_int(x[q].w);
+            lab[r] = L[q];
+        }
+    }
+    __syncthreads();
+    GroupSums sum[RPL];
+#pragma unroll 2
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[j];
+        const int lj = lab[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            groups_add_position(sum[q], lj == L[q], j < m, __int_as_float(pj.w), __int_as_float(pj.x), __int_as_float(pj.y),
+                                __int_as_float(pj.z));
+    }
+    if (records) {  // the same for every lane: a kernel argument
+        __syncthreads();  // every lane is done with the positions
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float4 v = vel[base + r];
+                img[r] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), __float_as_int(x[q].w));
+            }
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const int lj = lab[j];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                groups_add_velocity(sum[q], lj == L[q], __int_as_float(pj.w), __int_as_float(pj.x), __int_as_float(pj.y),
+                                    __int_as_float(pj.z));
+        }
+    }
+    // The roots write their group's record and add themselves to the summary: integers, in any order.
+    GroupTally mine;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const bool root = r < n && L[q] == r;
+        if (root)
+            groups_tally_root(mine, sum[q].count, r, min_members);
+        if (r < max_bodies) {
+            if (records)
+                records[base + r] = root ? groups_record(sum[q]) : groups_empty_record();
+            if (bodies)
+                bodies[base + r] = r < n ? BatchGroupBody{L[q], sum[q].count} : groups_empty_body();
+        }
+    }
+    if (mine.key != kGroupsKeyNone) {
+        atomicAdd(&tally[0], mine.groups);
+        atomicAdd(&tally[1], mine.grouped);
+        atomicAdd(&tally[2], mine.singles);
+        atomicMax(&tally[3], mine.key);
+    }
+    __syncthreads();
+    if (tid == 0)
+        systems[blockIdx.x] = groups_summary(GroupTally{tally[0], tally[1], tally[2], tally[3]}, sweeps, converged);
+}
+
+// One launch over all systems.  20 bytes of dynamic LDS per body, 80 KiB at 4096 bodies: the limit is raised first, as
+// launch_batch_members does.  massive, bodies and records may be NULL; without records the velocities are not read.
+hipError_t launch_batch_groups(const float4 *pos, const float4 *vel, const int *counts, const int *massive, const float *linking2,
+                               int n_systems, int max_bodies, int min_members, int weight, int max_sweeps, BatchGroupBody *bodies,
+                               BatchGroupRecord *records, BatchGroupSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kGroupsBytesPerBody * (size_t)max_bodies;
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, vel, counts, massive, linking2, max_bodies,
+                           min_members, weight, max_sweeps, bodies, records, systems);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_groups_kernel<1>);
+    case 2: return launch(batch_groups_kernel<2>);
+    default: return launch(batch_groups_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -4403,6 +4649,13 @@ struct nbody_batch {
     size_t gravity_rows = 0, gravity_tidal_rows = 0;
     int *gravity_counts_dev = nullptr;                  // [n_systems]
     std::vector<int> gravity_counts;                    // host copy of the last call's point counts
+    // nbody_batch_groups: the records of the last call and the squared linking lengths, each allocated by the first call that
+    // asks for it
+    BatchGroupSystem *groups_systems_dev = nullptr;  // [n_systems]
+    BatchGroupRecord *groups_records_dev = nullptr;  // [n_systems][max_bodies]
+    BatchGroupBody *groups_bodies_dev = nullptr;     // [n_systems][max_bodies]
+    float *groups_linking2_dev = nullptr;            // [n_systems]
+    std::vector<float> groups_linking2;              // host copy of the last call's b[s] b[s]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -4653,6 +4906,10 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->gravity_records_dev) (void)hipFree(b->gravity_records_dev);
     if (b->gravity_tidal_dev) (void)hipFree(b->gravity_tidal_dev);
     if (b->gravity_counts_dev) (void)hipFree(b->gravity_counts_dev);
+    if (b->groups_systems_dev) (void)hipFree(b->groups_systems_dev);
+    if (b->groups_records_dev) (void)hipFree(b->groups_records_dev);
+    if (b->groups_bodies_dev) (void)hipFree(b->groups_bodies_dev);
+    if (b->groups_linking2_dev) (void)hipFree(b->groups_linking2_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -5477,6 +5734,54 @@ int nbody_batch_gravity(nbody_batch *b, const float *d_pos, const float *d_point
     BATCH_TRY(b, hipMemcpyAsync(records_out, b->gravity_records_dev, sizeof(BatchGravityRecord) * rows, hipMemcpyDeviceToHost, b->stream));
     if (tidal_out)
         BATCH_TRY(b, hipMemcpyAsync(tidal_out, b->gravity_tidal_dev, sizeof(float) * kGravityTidalWords * rows, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_groups(nbody_batch *b, const float *d_pos, const float *d_vel, const float *linking_lengths, int min_members,
+                       int weight, int max_sweeps, nbody_batch_group_system *systems_out, nbody_batch_group_record *groups_out,
+                       nbody_batch_group_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_groups: batch is NULL");
+    if (!d_pos || !d_vel || !linking_lengths || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: NULL argument");
+    if (min_members < 1)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: min_members must be >= 1");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (max_sweeps < 1 || max_sweeps > NBODY_BATCH_GROUPS_MAX_SWEEPS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: max_sweeps must be 1 ... 64");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    for (size_t s = 0; s < B; ++s) {
+        if (!std::isfinite(linking_lengths[s]) || linking_lengths[s] < 0.f)
+            return bfail(b, NBODY_ERR_INVALID,
+                         "nbody_batch_groups: the linking length of system " + std::to_string(s) + " must be finite and >= 0");
+    }
+    b->groups_linking2.resize(B);
+    for (size_t s = 0; s < B; ++s)
+        b->groups_linking2[s] = linking_lengths[s] * linking_lengths[s];  // b2: one fp32 product
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->groups_systems_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->groups_systems_dev, sizeof(BatchGroupSystem) * B));
+    if (!b->groups_linking2_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->groups_linking2_dev, sizeof(float) * B));
+    if (groups_out && !b->groups_records_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->groups_records_dev, sizeof(BatchGroupRecord) * slots));
+    if (bodies_out && !b->groups_bodies_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->groups_bodies_dev, sizeof(BatchGroupBody) * slots));
+    BATCH_TRY(b, hipMemcpyAsync(b->groups_linking2_dev, b->groups_linking2.data(), sizeof(float) * B, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_groups(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                     b->config.massive_set ? b->massive_dev : nullptr, b->groups_linking2_dev, (int)b->n_systems,
+                                     (int)b->max_bodies, min_members, weight, max_sweeps, bodies_out ? b->groups_bodies_dev : nullptr,
+                                     groups_out ? b->groups_records_dev : nullptr, b->groups_systems_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(systems_out, b->groups_systems_dev, sizeof(BatchGroupSystem) * B, hipMemcpyDeviceToHost, b->stream));
+    if (groups_out)
+        BATCH_TRY(b, hipMemcpyAsync(groups_out, b->groups_records_dev, sizeof(BatchGroupRecord) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    if (bodies_out)
+        BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->groups_bodies_dev, sizeof(BatchGroupBody) * slots, hipMemcpyDeviceToHost,
                                     b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

@@ -85,7 +85,15 @@ per case on the boosted Plummer spheres of --members: gravity_at() in own-bodies
 against members(max_iterations=1, bodies=False) and energy() at the same softening on the same state; then one line for a
 65536-point grid per system at n x B = 1024 x 64, with and without the tensor.  All synchronous calls, wall clock, alternated,
 medians and spreads.  A call is one n x n (or points x n) walk and returns 24 bytes per row, 48 with the tensor: the copy to the
-host is part of the wall time, so the kernel's time alone comes from a traced run of this mode."""
+host is part of the wall time, so the kernel's time alone comes from a traced run of this mode.
+
+--groups: instead, the friends-of-friends groups (BatchedSystem.groups).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases), one
+line per case on Plummer spheres, at linking lengths of 0.2 and 1.0 mean interparticle spacings within the half-mass radius:
+groups() without the per-slot and per-body records (32 bytes per system come back: the kernel, its launch and the wait for it),
+with the per-body records, and with both, against pairs() on the same state -- all synchronous calls, wall clock, alternated,
+medians and spreads -- and the sweeps run.  A sweep is one n x n walk of nine fp32 and integer operations per pair; the records
+take two more walks with fp64 sums, the second only where the per-slot records are asked for.  The kernel's time alone comes
+from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -133,6 +141,8 @@ ap.add_argument("--hierarchy", action="store_true", help="hierarchy() with and w
                 "pairs() on the same state of nested objects, wall clock, and the levels evaluated")
 ap.add_argument("--gravity", action="store_true", help="gravity_at() at the systems' own bodies with and without the tidal tensor "
                 "against members(max_iterations=1) and energy() on the same state, and a 65536-point grid per system, wall clock")
+ap.add_argument("--groups", action="store_true", help="groups() at 0.2 and 1.0 mean spacings with and without the per-slot and "
+                "per-body records against pairs() on the same Plummer spheres, wall clock, and the sweeps run")
 args = ap.parse_args()
 
 
@@ -875,6 +885,60 @@ def gravity_lines():
     report(line, calls, times, med)
 
 
+def groups_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        # the mean interparticle spacing within the half-mass radius (1.3048 scale radii) of a Plummer sphere of n bodies
+        spacing = (4.0 / 3.0 * np.pi * 1.3048 ** 3 / (n / 2.0)) ** (1.0 / 3.0)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"pairs": batch.pairs}
+            for tag, f in (("0.2", 0.2), ("1.0", 1.0)):
+                b = float(np.float32(f * spacing))
+                calls["groups_lean_" + tag] = lambda b=b: batch.groups(b, records=False, bodies=False)
+                calls["groups_bodies_" + tag] = lambda b=b: batch.groups(b, records=False)
+                calls["groups_" + tag] = lambda b=b: batch.groups(b)
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    if name.startswith("groups_lean_"):
+                        found[name[len("groups_lean_"):]] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B, "mean_spacing": round(spacing, 5)}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for tag, res in found.items():
+            line.update({f"sweeps_mean_{tag}": round(float(res.sweeps.mean()), 3), f"sweeps_max_{tag}": int(res.sweeps.max()),
+                         f"converged_{tag}": int(res.converged.sum()), f"groups_mean_{tag}": round(float(res.groups.mean()), 1),
+                         f"largest_count_mean_{tag}": round(float(res.largest_count.mean()), 1),
+                         f"lean_over_pairs_{tag}": round(med["groups_lean_" + tag] / med["pairs"], 3),
+                         f"ms_per_walk_{tag}": round(med["groups_lean_" + tag] / (float(res.sweeps.mean()) + 1.0), 4)})
+        line.update({"record_megabytes": round(B * n * 64 / 1e6, 1), "body_megabytes": round(B * n * 8 / 1e6, 1),
+                     "system_kilobytes": round(B * 32 / 1e3, 1)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.groups:
+    groups_lines()
+    sys.exit(0)
 if args.gravity:
     gravity_lines()
     sys.exit(0)
