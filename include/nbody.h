@@ -546,6 +546,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_gravity.h"
 /* groups: friends-of-friends clumps at a linking length, the members, centre and velocity of every piece of every system */
 #include "nbody_batch_groups.h"
+/* spanning trees: the Euclidean minimum spanning tree of every system or of a subset of its bodies, edges in ascending order */
+#include "nbody_batch_span.h"
 
 #ifdef __cplusplus
 }

@@ -601,6 +601,29 @@ public:
               "nbody_batch_groups");
         return s;
     }
+    // Spanning trees (nbody_batch_span.h): the Euclidean minimum spanning tree of every system from the positions in the
+    // caller's buffer.  subset: empty for all bodies, or numSystems x maxBodies bytes (host), non-zero where a body is a
+    // vertex.  Per system the edges, the selected bodies, the rounds run, the total and the longest length and, with
+    // separations, the mean separation of the selected bodies.  edges and bodies, where given, are resized to
+    // numSystems x maxBodies and take the per-slot edges in ascending order and the per-body {degree, nearest}; nullptr skips
+    // that copy.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_span_system> spanningTree(const float *dPositions, const std::vector<unsigned char> &subset = {},
+                                                      bool separations = false,
+                                                      std::vector<nbody_batch_span_edge> *edges = nullptr,
+                                                      std::vector<nbody_batch_span_body> *bodies = nullptr)
+    {
+        if (!subset.empty() && subset.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::spanningTree: one subset byte per slot, or none");
+        std::vector<nbody_batch_span_system> s((size_t)systems_);
+        if (edges)
+            edges->resize((size_t)systems_ * (size_t)maxBodies_);
+        if (bodies)
+            bodies->resize((size_t)systems_ * (size_t)maxBodies_);
+        check(nbody_batch_span(b_, dPositions, subset.empty() ? nullptr : subset.data(), separations ? 1 : 0, s.data(),
+                               edges ? edges->data() : nullptr, bodies ? bodies->data() : nullptr),
+              "nbody_batch_span");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -384,6 +384,32 @@ _GROUPS_PROTOTYPES = {
 }
 
 
+BATCH_SPAN_MAX_ROUNDS = 13
+
+
+class BatchSpanSystem(ctypes.Structure):
+    """``nbody_batch_span_system`` of include/nbody_batch_span.h."""
+    _fields_ = [("edges", c_int), ("selected", c_int), ("rounds", c_int), ("reserved", c_int), ("total_length", c_double),
+                ("longest", c_double), ("mean_separation", c_double)]
+
+
+class BatchSpanEdge(ctypes.Structure):
+    """``nbody_batch_span_edge`` of include/nbody_batch_span.h."""
+    _fields_ = [("i", c_int), ("j", c_int), ("r2", c_float), ("reserved", c_int)]
+
+
+class BatchSpanBody(ctypes.Structure):
+    """``nbody_batch_span_body`` of include/nbody_batch_span.h."""
+    _fields_ = [("degree", c_int), ("nearest", c_int)]
+
+
+#: the entry point of include/nbody_batch_span.h (minimum spanning trees of batched ensembles), which nbody.h includes
+_SPAN_PROTOTYPES = {
+    "nbody_batch_span": (c_int, [c_void_p, c_void_p, POINTER(ctypes.c_ubyte), c_int, POINTER(BatchSpanSystem),
+                                 POINTER(BatchSpanEdge), POINTER(BatchSpanBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -412,7 +438,7 @@ def load() -> ctypes.CDLL:
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
-                list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()):
+                list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -493,6 +519,11 @@ def gravity_names():
 def groups_names():
     """The entry point of nbody_batch_groups.h."""
     return list(_GROUPS_PROTOTYPES)
+
+
+def span_names():
+    """The entry point of nbody_batch_span.h."""
+    return list(_SPAN_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

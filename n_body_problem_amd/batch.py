@@ -73,6 +73,14 @@ GROUP_SYSTEM_DTYPE = np.dtype([(name, np.int32) for name in ("groups", "grouped"
 assert GROUP_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupBody) == 8
 assert GROUP_RECORD_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupRecord) == 64
 assert GROUP_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchGroupSystem) == 32
+#: the records of :meth:`BatchedSystem.spanning_tree`: numpy's views of ``nbody_batch_span_system``, ``_edge`` and ``_body``
+SPAN_SYSTEM_DTYPE = np.dtype([("edges", np.int32), ("selected", np.int32), ("rounds", np.int32), ("reserved", np.int32),
+                              ("total_length", np.float64), ("longest", np.float64), ("mean_separation", np.float64)])
+SPAN_EDGE_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("r2", np.float32), ("reserved", np.int32)])
+SPAN_BODY_DTYPE = np.dtype([("degree", np.int32), ("nearest", np.int32)])
+assert SPAN_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanSystem) == 40
+assert SPAN_EDGE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanEdge) == 16
+assert SPAN_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanBody) == 8
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -646,6 +654,38 @@ class BatchedSystem:
             body.ctypes.data_as(ctypes.POINTER(_lib.BatchGroupBody)) if bodies else None), self._h)
         return BatchGroups(systems, rec, body, b, int(min_members), weight)
 
+    def spanning_tree(self, subset=None, separations: bool = False, edges: bool = True, bodies: bool = True) -> "SpanResult":
+        """The Euclidean minimum spanning tree of every system (``include/nbody_batch_span.h`` states the rules), found on the
+        device from the current state (waits for the queued work).  All bodies below the count are vertices, test particles
+        included; ``subset``, a ``(B, max_bodies)`` bool or uint8 array, selects the vertices of each system instead.  Edges are
+        ordered by their fp32 squared length, ties by the lower first and then the lower second index, so the tree is unique
+        and its edges come sorted: cut those longer than ``b`` and the pieces are :meth:`groups` at ``b``.
+        ``separations=True`` also gives the mean separation of the selected bodies, which :meth:`SpanResult.q_parameter`
+        needs, for one more pass over the pairs.  ``edges=False`` and ``bodies=False`` skip the 16 bytes per slot and the 8
+        bytes per body on their way to the host: those arrays of the result are ``None``, the per-system ones the same bits.
+        Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        sub = None
+        if subset is not None:
+            sub = np.ascontiguousarray(np.asarray(subset))
+            if sub.dtype != np.bool_ and sub.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {sub.dtype}")
+            if sub.shape != (self.num_systems, self.max_bodies):
+                raise ValueError(f"subset must have shape ({self.num_systems}, {self.max_bodies}), got {tuple(sub.shape)}")
+            sub = sub.view(np.uint8)
+        systems = np.zeros(self.num_systems, dtype=SPAN_SYSTEM_DTYPE)
+        edge = np.zeros((self.num_systems, self.max_bodies), dtype=SPAN_EDGE_DTYPE) if edges else None
+        body = np.zeros((self.num_systems, self.max_bodies), dtype=SPAN_BODY_DTYPE) if bodies else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_span(
+            self._h, _ptr(self.positions), sub.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if sub is not None else None,
+            1 if separations else 0, systems.ctypes.data_as(ctypes.POINTER(_lib.BatchSpanSystem)),
+            edge.ctypes.data_as(ctypes.POINTER(_lib.BatchSpanEdge)) if edges else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchSpanBody)) if bodies else None), self._h)
+        vertices = np.arange(self.max_bodies)[None, :] < np.asarray(self.counts).reshape(-1, 1)
+        if sub is not None:
+            vertices = vertices & (sub != 0)
+        return SpanResult(systems, edge, body, bool(separations), vertices)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -927,6 +967,111 @@ class BatchGroups:
                 f"sweeps={self.sweeps.tolist()}, converged={self.converged.tolist()})")
 
 
+class SpanResult:
+    """What :meth:`BatchedSystem.spanning_tree` found.  Per system (``(B,)`` arrays): ``edges`` (int32: ``selected - 1``, or 0
+    below two selected bodies), ``selected`` (int32: the vertices), ``rounds`` (int32: the rounds the search ran),
+    ``total_length`` and ``longest`` (float64: the sum of the edge lengths in ascending order, and the last of them) and
+    ``mean_separation`` (float64: the mean distance of two selected bodies; 0 without ``separations``).  Per slot,
+    ``(B, max_bodies)`` arrays or ``None`` without ``edges``: ``i``, ``j`` (int32, ``i < j``) and ``r2`` (float32: the squared
+    length) of the ``e``-th shortest edge; -1, -1 and 0 from ``edges`` on.  Per body, ``(B, max_bodies)`` int32 arrays or
+    ``None`` without ``bodies``: ``degree`` (the tree edges at the body) and ``nearest`` (its nearest selected body, always a
+    tree neighbour); 0 and -1 for a body that is not selected, beyond the count or alone."""
+
+    def __init__(self, systems, edges, bodies, separations, vertices):
+        self.systems, self.edge_records, self.body_records, self.separations = systems, edges, bodies, bool(separations)
+        self.vertices = vertices
+        for name in ("edges", "selected", "rounds", "total_length", "longest", "mean_separation"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.i = self.j = self.r2 = self.degree = self.nearest = None
+        if edges is not None:
+            self.i, self.j, self.r2 = (np.ascontiguousarray(edges[name]) for name in ("i", "j", "r2"))
+        if bodies is not None:
+            self.degree, self.nearest = np.ascontiguousarray(bodies["degree"]), np.ascontiguousarray(bodies["nearest"])
+
+    def _need_edges(self, what):
+        if self.i is None:
+            raise ValueError(f"{what} needs the per-slot records: call spanning_tree(edges=True)")
+
+    def edges_of(self, s: int):
+        """``(ends, lengths)`` of system ``s``: an ``(E, 2)`` int32 array of the edges' ends in ascending order of length, and
+        their float64 lengths, the terms of ``total_length``."""
+        self._need_edges("edges_of")
+        E = int(self.edges[s])
+        ends = np.stack([self.i[s, :E], self.j[s, :E]], axis=1).astype(np.int32)
+        return ends, np.sqrt(self.r2[s, :E].astype(np.float64))
+
+    def _b2(self, b):
+        """The fp32 product ``b b`` that :meth:`BatchedSystem.groups` compares with; a scalar or one value per system."""
+        b = np.asarray(b, dtype=np.float32)
+        if b.ndim == 0:
+            b = np.full(self.edges.shape[0], b, dtype=np.float32)
+        b = b.reshape(-1)
+        if b.shape[0] != self.edges.shape[0]:
+            raise ValueError(f"expected one linking length or {self.edges.shape[0]}, got {b.shape[0]}")
+        return b * b
+
+    def group_count(self, b) -> np.ndarray:
+        """``(B,)`` int32: into how many pieces every system falls at the linking length ``b`` (a scalar, or one per system):
+        1 + the edges with ``r2 > b2``; 0 without selected bodies.  This is ``groups(b, min_members=1).groups`` where all
+        bodies are selected."""
+        self._need_edges("group_count")
+        b2 = self._b2(b)
+        live = np.arange(self.r2.shape[1])[None, :] < self.edges[:, None]
+        cut = (live & (self.r2 > b2[:, None])).sum(axis=1)
+        return np.where(self.selected > 0, 1 + cut, 0).astype(np.int32)
+
+    def labels_at(self, s: int, b) -> np.ndarray:
+        """``(max_bodies,)`` int32: for every selected body of system ``s`` the lowest index of its piece at the linking length
+        ``b`` -- :meth:`BatchedSystem.groups`' ``group`` where all bodies are selected; -1 for a body that is not selected or
+        beyond the count.  A union-find over the edges with ``r2 <= b2``."""
+        self._need_edges("labels_at")
+        b2 = self._b2(b)[s]
+        n = self.r2.shape[1]
+        parent = list(range(n))
+
+        def find(a):
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            return a
+
+        E = int(self.edges[s])
+        for a, c, r2 in zip(self.i[s, :E].tolist(), self.j[s, :E].tolist(), self.r2[s, :E].tolist()):
+            if np.float32(r2) <= b2:
+                ra, rc = find(a), find(c)
+                parent[max(ra, rc)] = min(ra, rc)
+        labels = np.array([find(a) for a in range(n)], dtype=np.int32)
+        return np.where(self.vertices[s], labels, -1).astype(np.int32)
+
+    def linking_length_for(self, pieces: int) -> np.ndarray:
+        """``(B,)`` float64: the length of the ``(pieces - 1)``-th longest edge: at linking lengths below it, down to the next
+        edge, a system is in ``pieces`` pieces.  NaN where a system has fewer than ``pieces - 1`` edges."""
+        self._need_edges("linking_length_for")
+        if pieces < 2:
+            raise ValueError("pieces must be at least 2")
+        at = self.edges.astype(np.int64) - (pieces - 1)
+        r2 = np.take_along_axis(self.r2, np.clip(at, 0, self.r2.shape[1] - 1)[:, None], axis=1)[:, 0].astype(np.float64)
+        return np.where(at >= 0, np.sqrt(r2), np.nan)
+
+    def q_parameter(self, radius) -> np.ndarray:
+        """``(B,)`` float64: the Q of Cartwright & Whitworth (2004), ``m / s`` with ``m = total_length / (N^2 V)^(1/3)``,
+        ``V = 4 pi R^3 / 3``, ``s = mean_separation / R`` and ``N = selected``.  ``radius`` is the cluster radius ``R``, a
+        scalar or one value per system.  Needs ``spanning_tree(separations=True)``.  Q above 0.8 speaks for a central
+        concentration, below for substructure.  NaN below two selected bodies."""
+        if not self.separations:
+            raise ValueError("q_parameter needs the mean separation: call spanning_tree(separations=True)")
+        R = np.broadcast_to(np.asarray(radius, dtype=np.float64), self.total_length.shape)
+        N = self.selected.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = self.total_length / np.cbrt(N * N * (4.0 * np.pi * R ** 3 / 3.0))
+            s = self.mean_separation / R
+            return np.where(self.selected >= 2, m / s, np.nan)
+
+    def __repr__(self):
+        return (f"SpanResult(edges={self.edges.tolist()}, total_length={self.total_length.tolist()}, "
+                f"rounds={self.rounds.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -1001,4 +1146,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -16,6 +16,7 @@
 #include "nbody_batch_choice.h"
 #include "nbody_batch_gravity_math.h"
 #include "nbody_batch_groups_math.h"
+#include "nbody_batch_span_math.h"
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_pairs_elements.h"
@@ -4498,6 +4499,295 @@ hipError_t launch_batch_groups(const float4 *pos, const float4 *vel, const int *
     }
 }
 
+// ---- spanning trees (include/nbody_batch_span.h): the Euclidean minimum spanning tree of every system's selected bodies by
+// Boruvka's rounds.  Every row finds the cheapest edge that leaves its component, the components take the minimum of their
+// rows' keys with a 64-bit LDS integer min, the roots decide, hook and record, the labels are compressed, and again until one
+// component is left; then the recorded keys are sorted in LDS and the lengths summed in order.  A sibling of
+// batch_groups_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane
+// at r = q * T + lane.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchSpanSystem) == sizeof(nbody_batch_span_system) && sizeof(nbody_batch_span_system) == 40 &&
+                  offsetof(BatchSpanSystem, edges) == offsetof(nbody_batch_span_system, edges) &&
+                  offsetof(BatchSpanSystem, selected) == offsetof(nbody_batch_span_system, selected) &&
+                  offsetof(BatchSpanSystem, rounds) == offsetof(nbody_batch_span_system, rounds) &&
+                  offsetof(BatchSpanSystem, reserved) == offsetof(nbody_batch_span_system, reserved) &&
+                  offsetof(BatchSpanSystem, total_length) == offsetof(nbody_batch_span_system, total_length) &&
+                  offsetof(BatchSpanSystem, longest) == offsetof(nbody_batch_span_system, longest) &&
+                  offsetof(BatchSpanSystem, mean_separation) == offsetof(nbody_batch_span_system, mean_separation),
+              "nbody_batch_span_math.h mirrors the system record of nbody_batch_span.h");
+static_assert(sizeof(BatchSpanEdge) == sizeof(nbody_batch_span_edge) && sizeof(nbody_batch_span_edge) == 16 &&
+                  offsetof(BatchSpanEdge, i) == offsetof(nbody_batch_span_edge, i) &&
+                  offsetof(BatchSpanEdge, j) == offsetof(nbody_batch_span_edge, j) &&
+                  offsetof(BatchSpanEdge, r2) == offsetof(nbody_batch_span_edge, r2) &&
+                  offsetof(BatchSpanEdge, reserved) == offsetof(nbody_batch_span_edge, reserved),
+              "nbody_batch_span_math.h mirrors the edge record of nbody_batch_span.h");
+static_assert(sizeof(BatchSpanBody) == sizeof(nbody_batch_span_body) && sizeof(nbody_batch_span_body) == 8 &&
+                  offsetof(BatchSpanBody, degree) == offsetof(nbody_batch_span_body, degree) &&
+                  offsetof(BatchSpanBody, nearest) == offsetof(nbody_batch_span_body, nearest),
+              "nbody_batch_span_math.h mirrors the body record of nbody_batch_span.h");
+static_assert(kSpanMaxRounds == NBODY_BATCH_SPAN_MAX_ROUNDS, "nbody_batch_span_math.h mirrors the limit of nbody_batch_span.h");
+static_assert(NBODY_BATCH_MAX_BODIES <= (1 << kSpanIndexBits), "an index fills 12 bits of the key");
+static_assert(sizeof(SpanKey) == 8 && sizeof(double) == 8, "a 64-bit word holds a key, then a length");
+
+// The image {x, y, z, component}, 16 bytes per body, and behind it one 64-bit word per slot of the sort, whose length is the
+// capacity rounded up to a power of two: 24 bytes per body and 96 KiB at 4096 bodies.
+inline size_t span_lds_bytes(int max_bodies)
+{
+    return kBatchBytesPerBody * (size_t)max_bodies + sizeof(SpanKey) * (size_t)span_sort_length(max_bodies);
+}
+
+// LDS: img[j] = {x, y, z, component} of body j as four words, one ds_read_b128 per column, and key[] behind it: a component's
+// minimum at its root's slot while the rounds run, the row sums of the separations before them, the recorded keys and then the
+// lengths after them.  Unselected rows carry kSpanNoComponent and are skipped as columns; rows from the count on are no columns.
+// Every loop that holds a barrier has a workgroup-uniform trip count: n, the sort's length and the separations flag are
+// uniform, the components left are read from LDS behind a barrier, and "a pass changed a label" comes out of groups_block_any.
+// The edge a component records lives in rec[q] of the lane that owns the row of its root: a root is absorbed once.
+// One row per lane is held to the 64 registers of eight waves per SIMD, as in batch_groups_kernel<1>.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_span_kernel(
+    const float4 *pos, const int *counts, const unsigned char *subset, int max_bodies, int separations, BatchSpanEdge *edges,
+    BatchSpanBody *bodies, BatchSpanSystem *systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int flags[16];
+    __shared__ int left;  // the components left; before the rounds, the selected bodies
+    int *words = reinterpret_cast<int *>(img);
+    SpanKey *key = reinterpret_cast<SpanKey *>(img + max_bodies);
+    double *term = reinterpret_cast<double *>(key);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];      // {x, y, z, the mass word}
+    int L[RPL];         // the row's component; kSpanNoComponent for a row that is not selected
+    int nearest[RPL];   // the first round's row result
+    SpanKey rec[RPL];   // the edge the row's component recorded when it was absorbed
+    if (tid == 0)
+        left = 0;
+    __syncthreads();
+    int mine = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        L[q] = kSpanNoComponent;
+        nearest[q] = -1;
+        rec[q] = kSpanNoKey;
+        if (r < n) {
+            x[q] = pos[base + r];
+            L[q] = !subset || subset[base + r] != 0 ? r : kSpanNoComponent;
+            mine += L[q] != kSpanNoComponent ? 1 : 0;
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), L[q]);
+        }
+    }
+    if (mine)
+        atomicAdd(&left, mine);
+    __syncthreads();  // the image and the count are in place
+    const int selected = left;
+    // The separations: every row's sum in ascending j, then thread 0 adds the rows in ascending i.
+    double separation = 0.0;
+    if (separations && selected > 1) {  // the same for every lane
+        double sum[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            sum[q] = 0.0;
+#pragma unroll 2
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                sum[q] += span_separation(pj.w != kSpanNoComponent && j != q * T + tid,
+                                          groups_r2(x[q].x, x[q].y, x[q].z, xj, yj, zj));
+        }
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                term[r] = L[q] != kSpanNoComponent ? sum[q] : 0.0;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int i = 0; i < n; ++i)
+                separation += term[i];
+        }
+    }
+    // The rounds.
+    int rounds = 0;
+    for (;;) {
+        __syncthreads();  // the labels and the count the round before left are in place; the words are free
+        const int components = left;
+        if (components <= 1 || rounds >= kSpanMaxRounds)
+            break;
+        ++rounds;
+        SpanBest best[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                key[r] = kSpanNoKey;
+        }
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                span_step(best[q], L[q], x[q].x, x[q].y, x[q].z, xj, yj, zj, pj.w, j);
+        }
+        __syncthreads();  // every word is cleared
+        // The components' minima: an LDS integer atomic, so the order does not matter.
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            if (L[q] != kSpanNoComponent) {
+                if (rounds == 1)
+                    nearest[q] = best[q].j;
+                const SpanKey k = span_row_key(best[q], q * T + tid);
+                if (k != kSpanNoKey)
+                    atomicMin(&key[L[q]], k);
+            }
+        }
+        __syncthreads();  // the minima are in place
+        // The roots decide: reads alone.
+        int under[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            under[q] = kSpanNoComponent;
+            if (L[q] == r) {  // a selected root
+                const SpanKey k = key[r];
+                if (k != kSpanNoKey) {
+                    const int o = span_other(r, words[groups_label_at(span_key_i(k))], words[groups_label_at(span_key_j(k))]);
+                    if (span_hooks(k, key[o], r, o)) {
+                        under[q] = o;
+                        rec[q] = k;
+                    }
+                }
+            }
+        }
+        __syncthreads();  // every root has read
+        int hooked = 0;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            if (under[q] != kSpanNoComponent) {
+                words[groups_label_at(q * T + tid)] = under[q];
+                ++hooked;
+            }
+        }
+        if (hooked)
+            atomicSub(&left, hooked);
+        // Compress: every row reads its root's label, then every row writes, until a pass changes nothing.
+        for (;;) {
+            __syncthreads();  // the hooks, or the pass before, are in place
+            int next[RPL];
+            bool moved = false;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                next[q] = L[q];
+                if (L[q] != kSpanNoComponent) {
+                    const int now = words[groups_label_at(r)];
+                    next[q] = span_compress(words, now);
+                    moved = moved || next[q] != now;
+                }
+            }
+            const bool again = groups_block_any(moved, flags, tid, T);  // its barriers: every row has read
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (L[q] != kSpanNoComponent) {
+                    L[q] = next[q];
+                    words[groups_label_at(r)] = next[q];
+                }
+            }
+            if (!again)
+                break;
+        }
+    }
+    // The sort: the recorded keys into the words, padded with all-ones keys to a power of two, and the image's fourth word
+    // cleared for the degrees.  The last barrier of the rounds stands before this: every lane is done with the labels.
+    const int recorded = selected - left;  // selected - 1 where the rounds ended with one component
+    const int length = span_sort_length(n);
+    for (int r = tid; r < length; r += T)
+        key[r] = kSpanNoKey;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            words[groups_label_at(r)] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        if (rec[q] != kSpanNoKey)
+            key[q * T + tid] = rec[q];
+    }
+    __syncthreads();
+    for (int k = 2; k <= length; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < length / 2; t += T)
+                span_exchange(key, t, k, j);
+            __syncthreads();
+        }
+    }
+    // Slot e holds the e-th edge: its record, its ends' degrees (integer LDS adds) and, in its word, its length.
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int e = q * T + tid;
+        if (e < max_bodies) {
+            const SpanKey k = e < length ? key[e] : kSpanNoKey;
+            const BatchSpanEdge edge = span_edge(k);
+            if (k != kSpanNoKey) {
+                atomicAdd(&words[groups_label_at(edge.i)], 1);
+                atomicAdd(&words[groups_label_at(edge.j)], 1);
+                term[e] = span_length(edge.r2);
+            }
+            if (edges)
+                edges[base + e] = edge;
+        }
+    }
+    __syncthreads();
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = L[q] != kSpanNoComponent ? BatchSpanBody{words[groups_label_at(r)], nearest[q]} : span_empty_body();
+        }
+    }
+    if (tid == 0) {
+        double total = 0.0, longest = 0.0;
+        for (int e = 0; e < recorded; ++e) {
+            longest = term[e];
+            total += longest;
+        }
+        systems[blockIdx.x] = BatchSpanSystem{recorded, selected, rounds, 0, total, longest, span_mean_separation(separation, selected)};
+    }
+}
+
+// One launch over all systems.  24 bytes of dynamic LDS per body at a power-of-two capacity, 96 KiB at 4096 bodies: the limit is
+// raised first, as launch_batch_groups does.  subset, edges and bodies may be NULL.
+hipError_t launch_batch_span(const float4 *pos, const int *counts, const unsigned char *subset, int n_systems, int max_bodies,
+                             int separations, BatchSpanEdge *edges, BatchSpanBody *bodies, BatchSpanSystem *systems,
+                             hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = span_lds_bytes(max_bodies);
+    const auto launch = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(sh.threads), lds, stream, pos, counts, subset, max_bodies, separations,
+                           edges, bodies, systems);
+        return hipGetLastError();
+    };
+    switch (sh.rpl) {
+    case 1: return launch(batch_span_kernel<1>);
+    case 2: return launch(batch_span_kernel<2>);
+    default: return launch(batch_span_kernel<4>);
+    }
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;
@@ -4656,6 +4946,12 @@ struct nbody_batch {
     BatchGroupBody *groups_bodies_dev = nullptr;     // [n_systems][max_bodies]
     float *groups_linking2_dev = nullptr;            // [n_systems]
     std::vector<float> groups_linking2;              // host copy of the last call's b[s] b[s]
+    // nbody_batch_span: the records of the last call and the device copy of `subset`, each allocated by the first call that
+    // needs it.
+    BatchSpanSystem *span_systems_dev = nullptr;  // [n_systems]
+    BatchSpanEdge *span_edges_dev = nullptr;      // [n_systems][max_bodies]
+    BatchSpanBody *span_bodies_dev = nullptr;     // [n_systems][max_bodies]
+    unsigned char *span_subset_dev = nullptr;     // [n_systems][max_bodies]
     double *diag_dev = nullptr;   // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     hipStream_t own_stream = nullptr;
@@ -4910,6 +5206,10 @@ int nbody_batch_destroy(nbody_batch *b)
     if (b->groups_records_dev) (void)hipFree(b->groups_records_dev);
     if (b->groups_bodies_dev) (void)hipFree(b->groups_bodies_dev);
     if (b->groups_linking2_dev) (void)hipFree(b->groups_linking2_dev);
+    if (b->span_systems_dev) (void)hipFree(b->span_systems_dev);
+    if (b->span_edges_dev) (void)hipFree(b->span_edges_dev);
+    if (b->span_bodies_dev) (void)hipFree(b->span_bodies_dev);
+    if (b->span_subset_dev) (void)hipFree(b->span_subset_dev);
     if (b->diag_dev) (void)hipFree(b->diag_dev);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -5782,6 +6082,40 @@ int nbody_batch_groups(nbody_batch *b, const float *d_pos, const float *d_vel, c
                                     b->stream));
     if (bodies_out)
         BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->groups_bodies_dev, sizeof(BatchGroupBody) * slots, hipMemcpyDeviceToHost,
+                                    b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_span(nbody_batch *b, const float *d_pos, const unsigned char *subset, int separations,
+                     nbody_batch_span_system *systems_out, nbody_batch_span_edge *edges_out, nbody_batch_span_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_span: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_span: NULL argument");
+    if (separations != 0 && separations != 1)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_span: separations must be 0 or 1");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    if (!b->span_systems_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->span_systems_dev, sizeof(BatchSpanSystem) * B));
+    if (subset && !b->span_subset_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->span_subset_dev, slots));
+    if (edges_out && !b->span_edges_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->span_edges_dev, sizeof(BatchSpanEdge) * slots));
+    if (bodies_out && !b->span_bodies_dev)
+        BATCH_TRY(b, hipMalloc((void **)&b->span_bodies_dev, sizeof(BatchSpanBody) * slots));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(b->span_subset_dev, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_span(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, subset ? b->span_subset_dev : nullptr,
+                                   (int)b->n_systems, (int)b->max_bodies, separations, edges_out ? b->span_edges_dev : nullptr,
+                                   bodies_out ? b->span_bodies_dev : nullptr, b->span_systems_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(systems_out, b->span_systems_dev, sizeof(BatchSpanSystem) * B, hipMemcpyDeviceToHost, b->stream));
+    if (edges_out)
+        BATCH_TRY(b, hipMemcpyAsync(edges_out, b->span_edges_dev, sizeof(BatchSpanEdge) * slots, hipMemcpyDeviceToHost, b->stream));
+    if (bodies_out)
+        BATCH_TRY(b, hipMemcpyAsync(bodies_out, b->span_bodies_dev, sizeof(BatchSpanBody) * slots, hipMemcpyDeviceToHost,
                                     b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

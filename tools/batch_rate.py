@@ -93,7 +93,15 @@ groups() without the per-slot and per-body records (32 bytes per system come bac
 with the per-body records, and with both, against pairs() on the same state -- all synchronous calls, wall clock, alternated,
 medians and spreads -- and the sweeps run.  A sweep is one n x n walk of nine fp32 and integer operations per pair; the records
 take two more walks with fp64 sums, the second only where the per-slot records are asked for.  The kernel's time alone comes
-from a traced run of this mode."""
+from a traced run of this mode.
+
+--span: instead, the minimum spanning trees (BatchedSystem.spanning_tree).  For n x B = 1024 x 1024 and 4096 x 256 (or --cases),
+one line per case on Plummer spheres: spanning_tree() without the per-slot and per-body records (40 bytes per system come back:
+the kernel, its launch and the wait for it), the same with separations, the whole call with both records, and a call with
+subsets of 20 random bodies per system, against groups() without its records at one mean spacing and pairs() on the same
+state -- all synchronous calls, wall clock, alternated, medians and spreads -- and the rounds run.  A round is one n x n walk of
+about a dozen fp32 and integer operations per pair; the separations take one more walk with an fp32 square root and an fp64
+add per pair.  The kernel's time alone comes from a traced run of this mode."""
 import argparse
 import json
 import os
@@ -143,6 +151,8 @@ ap.add_argument("--gravity", action="store_true", help="gravity_at() at the syst
                 "against members(max_iterations=1) and energy() on the same state, and a 65536-point grid per system, wall clock")
 ap.add_argument("--groups", action="store_true", help="groups() at 0.2 and 1.0 mean spacings with and without the per-slot and "
                 "per-body records against pairs() on the same Plummer spheres, wall clock, and the sweeps run")
+ap.add_argument("--span", action="store_true", help="spanning_tree() with and without the separations, the records and subsets "
+                "of 20 bodies against groups() and pairs() on the same Plummer spheres, wall clock, and the rounds run")
 args = ap.parse_args()
 
 
@@ -936,6 +946,66 @@ def groups_lines():
         print(json.dumps(line), flush=True)
 
 
+def span_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        spacing = (4.0 / 3.0 * np.pi * 1.3048 ** 3 / (n / 2.0)) ** (1.0 / 3.0)   # as in --groups
+        rng = np.random.default_rng(7)
+        subset = np.zeros((B, n), np.uint8)
+        for s in range(B):
+            subset[s, rng.choice(n, size=min(20, n), replace=False)] = 1
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            b = float(np.float32(spacing))
+            calls = {"pairs": batch.pairs,
+                     "groups_lean": lambda: batch.groups(b, records=False, bodies=False),
+                     "span_lean": lambda: batch.spanning_tree(edges=False, bodies=False),
+                     "span_lean_separations": lambda: batch.spanning_tree(separations=True, edges=False, bodies=False),
+                     "span": lambda: batch.spanning_tree(),
+                     "span_subsets_of_20": lambda: batch.spanning_tree(subset=subset, edges=False, bodies=False)}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        tree, sweeps = found["span_lean"], found["groups_lean"].sweeps
+        line.update({"rounds_mean": round(float(tree.rounds.mean()), 3), "rounds_max": int(tree.rounds.max()),
+                     "rounds_subsets_mean": round(float(found["span_subsets_of_20"].rounds.mean()), 3),
+                     "groups_sweeps_mean": round(float(sweeps.mean()), 3),
+                     "ms_per_round": round(med["span_lean"] / max(float(tree.rounds.mean()), 1.0), 4),
+                     "ms_per_groups_walk": round(med["groups_lean"] / (float(sweeps.mean()) + 1.0), 4),
+                     "separations_ms": round(med["span_lean_separations"] - med["span_lean"], 3),
+                     "lean_over_pairs": round(med["span_lean"] / med["pairs"], 3),
+                     "lean_over_groups_lean": round(med["span_lean"] / med["groups_lean"], 3),
+                     "edge_megabytes": round(B * n * 16 / 1e6, 1), "body_megabytes": round(B * n * 8 / 1e6, 1),
+                     "system_kilobytes": round(B * 40 / 1e3, 1)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.span:
+    span_lines()
+    sys.exit(0)
 if args.groups:
     groups_lines()
     sys.exit(0)
