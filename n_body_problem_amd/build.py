@@ -13,10 +13,12 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
-SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip"]
+SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip",
+           "nbody_batch_analysis.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
            os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
-           os.path.join(CSRC, "nbody_batch_choice.h"), os.path.join(CSRC, "nbody_batch_pairs_elements.h"),
+           os.path.join(CSRC, "nbody_batch_choice.h"), os.path.join(CSRC, "nbody_batch_handle.h"),
+           os.path.join(CSRC, "nbody_batch_pairs_elements.h"),
            os.path.join(CSRC, "nbody_batch_structure_math.h"), os.path.join(CSRC, "nbody_batch_members_math.h"),
            os.path.join(CSRC, "nbody_batch_hierarchy_math.h"), os.path.join(CSRC, "nbody_batch_gravity_math.h"),
            os.path.join(CSRC, "nbody_batch_groups_math.h"), os.path.join(CSRC, "nbody_batch_span_math.h"),
@@ -59,7 +61,7 @@ def is_stale() -> bool:
 #: per-source extra flags.  The force kernels are built without SLP vectorisation: v_pk_*_f32 buys nothing on gfx950
 #: (4 cycles for two lanes' worth) and the packing moves break their hand-ordered instruction phases.
 EXTRA_FLAGS = {"nbody_symmetric.hip": ["-fno-slp-vectorize"], "nbody_kernels.hip": ["-fno-slp-vectorize"],
-               "nbody_batch.hip": ["-fno-slp-vectorize"]}
+               "nbody_batch.hip": ["-fno-slp-vectorize"], "nbody_batch_analysis.hip": ["-fno-slp-vectorize"]}
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:

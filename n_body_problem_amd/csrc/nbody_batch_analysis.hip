@@ -1,0 +1,2035 @@
+// nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
+// structure, bound members, gravity at points, hierarchies, groups, spanning trees, energy and momentum (include/nbody.h,
+// nbody_batch_pairs.h ... nbody_batch_span.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
+// integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
+// integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
+#include "nbody_batch_gravity_math.h"
+#include "nbody_batch_groups_math.h"
+#include "nbody_batch_handle.h"
+#include "nbody_batch_hierarchy_math.h"
+#include "nbody_batch_members_math.h"
+#include "nbody_batch_pairs_elements.h"
+#include "nbody_batch_span_math.h"
+#include "nbody_batch_structure_math.h"
+#include "nbody_kernels.h"
+
+#include <cmath>
+#include <new>
+
+namespace nbody {
+namespace {
+
+// One launch of an analysis kernel with `lds` bytes of dynamic LDS.  The limit is raised first, always: positions and
+// velocities of 4096 bodies are 128 KiB, above the default 64 KiB from 2049 bodies on.
+template <class... P, class... A>
+hipError_t launch_analysis_kernel(void (*kernel)(P...), dim3 grid, int threads, size_t lds, hipStream_t stream, const A &...args)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, stream, args...);
+    return hipGetLastError();
+}
+
+// Rows per lane (batch_shape's 1, 2 or 4) as a template argument: f(integral_constant<int, RPL>).
+template <class F>
+hipError_t with_rpl(int rpl, F &&f)
+{
+    switch (rpl) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
+// The workgroup's sums of N values in a fixed order -- the lanes of a wave by shuffles, the waves in ascending order through
+// red[16][N] -- returned to every lane.
+template <int N>
+__device__ inline void block_sum(double (&v)[N], double *red, int tid, int T)
+{
+#pragma unroll
+    for (int c = 0; c < N; ++c)
+        for (int off = 32; off > 0; off >>= 1)
+            v[c] += __shfl_down(v[c], off, 64);
+    __syncthreads();  // every lane has read what red held before
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            red[(tid >> 6) * N + c] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        double s = red[c];
+        for (int w = 1; w < T / 64; ++w)
+            s += red[w * N + c];
+        v[c] = s;
+    }
+}
+
+// The workgroup's minimum, returned to every lane.
+__device__ inline double block_min(double v, double *red, int tid, int T)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v = fmin(v, __shfl_down(v, off, 64));
+    __syncthreads();
+    if ((tid & 63) == 0)
+        red[tid >> 6] = v;
+    __syncthreads();
+    double m = red[0];
+    for (int w = 1; w < T / 64; ++w)
+        m = fmin(m, red[w]);
+    return m;
+}
+
+// Whether any lane of the workgroup says so: a ballot per wave, the waves through flags[16].  Every lane returns the same
+// word, so a loop that leaves on it is left by the whole workgroup.  Its first barrier also ends the reads the lanes did
+// before the call.
+__device__ inline bool block_any(bool mine, int *flags, int tid, int T)
+{
+    const int wave = __ballot(mine) != 0 ? 1 : 0;
+    __syncthreads();  // every lane is done with what it read before, the flags of the call before among it
+    if ((tid & 63) == 0)
+        flags[tid >> 6] = wave;
+    __syncthreads();
+    int any = 0;
+    for (int w = 0; w < T / 64; ++w)
+        any |= flags[w];
+    return __builtin_amdgcn_readfirstlane(any) != 0;
+}
+
+// ---- bound pairs (include/nbody_batch_pairs.h): every row's partner by the smallest two-body energy, the fp64 record of the
+// pair, and the binaries of every system.  A sibling of the force kernels: one workgroup per system with batch_shape's
+// workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  It reads the state and writes only the
+// handle's records and counts.
+
+static_assert(sizeof(BatchPairRecord) == sizeof(nbody_batch_pair_record) && sizeof(nbody_batch_pair_record) == 48 &&
+                  offsetof(BatchPairRecord, mutual) == offsetof(nbody_batch_pair_record, mutual) &&
+                  offsetof(BatchPairRecord, energy) == offsetof(nbody_batch_pair_record, energy) &&
+                  offsetof(BatchPairRecord, separation) == offsetof(nbody_batch_pair_record, separation),
+              "nbody_batch_pairs_elements.h mirrors the record of nbody_batch_pairs.h");
+
+// LDS: sh[2 j] = {x, y, z, m} and sh[2 j + 1] = {vx, vy, vz, partner} of body j (the Hermite families' layout, 128 KiB at
+// 4096 bodies); the partner's bits replace the unused fourth word of the velocity after the search.
+// m: the candidates are the columns j < m (the massive ones, or all n); a row r >= m is a test particle and adds no mass.
+// The search needs few registers at every RPL; the rolled fp64 record sets the kernel's count.  One row per lane is held to
+// the 64 registers of eight waves per SIMD, batch_hermite_kernel<1>'s; the other two shapes are below theirs unasked.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_pairs_kernel(const float4 *pos, const float4 *vel, const int *counts,
+                                                           const int *massive, int max_bodies, BatchPairRecord *records,
+                                                           int *binaries)
+{
+    extern __shared__ float4 sh[];
+    __shared__ int wave_binaries[16];
+    const int n = counts[blockIdx.x];
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the mass this row adds to mu}
+    float3 v[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = make_float3(0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            sh[2 * r] = x[q];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            if (r >= m)
+                x[q].w = 0.f;
+        }
+    }
+    __syncthreads();
+    float best[RPL];
+    int bj[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        best[q] = __builtin_inff();
+        bj[q] = -1;
+    }
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[2 * j], vj = sh[2 * j + 1];  // wave-uniform addresses: broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float wx = vj.x - v[q].x, wy = vj.y - v[q].y, wz = vj.z - v[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const float v2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+            const float inv = __builtin_amdgcn_rsqf(r2);
+            const float mu = pj.w + x[q].w;
+            const float eps = __builtin_fmaf(-mu, inv, 0.5f * v2);
+            const bool take = r2 > 0.f && eps < best[q];  // r2 == 0: the self pair and coincident bodies are no candidates
+            best[q] = take ? eps : best[q];
+            bj[q] = take ? j : bj[q];
+        }
+    }
+    __syncthreads();  // every lane is done with the columns before the partners replace the velocities' fourth words
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            sh[2 * r + 1].w = __int_as_float(bj[q]);
+    }
+    __syncthreads();
+    // The records, one row at a time from LDS (the loop is kept rolled: the fp64 arithmetic is instantiated once).
+    int mine = 0;
+#pragma unroll 1
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r >= max_bodies)
+            break;
+        BatchPairRecord rec = batch_pair_empty();
+        if (r < n) {
+            const float4 xi = sh[2 * r], vi = sh[2 * r + 1];
+            const int j = __float_as_int(vi.w);
+            if (j >= 0) {
+                const float4 xj = sh[2 * j], vj = sh[2 * j + 1];
+                const int mutual = __float_as_int(vj.w) == r ? 1 : 0;
+                const float pi[3] = {xi.x, xi.y, xi.z}, wi[3] = {vi.x, vi.y, vi.z};
+                const float pj[3] = {xj.x, xj.y, xj.z}, wj[3] = {vj.x, vj.y, vj.z};
+                const double mu = r < m ? (double)xj.w + (double)xi.w : (double)xj.w;
+                rec = batch_pair_record(j, mutual, pi, wi, pj, wj, mu);
+                mine += (mutual && rec.energy < 0.0 && r < j) ? 1 : 0;
+            }
+        }
+        records[base + r] = rec;
+    }
+    // binaries of the system: lanes -> wave -> workgroup
+    for (int off = 32; off > 0; off >>= 1)
+        mine += __shfl_down(mine, off, 64);
+    if ((tid & 63) == 0)
+        wave_binaries[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < T / 64; ++w)
+            total += wave_binaries[w];
+        binaries[blockIdx.x] = total;
+    }
+}
+
+// One launch over all systems.  Positions and velocities of a system's bodies in dynamic LDS, 128 KiB at 4096 bodies.
+hipError_t launch_batch_pairs(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                              int max_bodies, BatchPairRecord *records, int *binaries, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = 2 * kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_pairs_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, vel, counts, massive,
+                                      max_bodies, records, binaries);
+    });
+}
+
+// ---- cluster structure (include/nbody_batch_structure.h): every row's k-th neighbour distance, neighbour weight and density,
+// and per system the density centre, core radius and density, and the Lagrangian radii about the centre.  A sibling of
+// batch_pairs_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per
+// lane at r = q * T + lane.  It reads the positions and writes only the handle's records.
+
+static_assert(sizeof(BatchStructureBody) == sizeof(nbody_batch_structure_body) && sizeof(nbody_batch_structure_body) == 40 &&
+                  offsetof(BatchStructureBody, radius) == offsetof(nbody_batch_structure_body, radius) &&
+                  offsetof(BatchStructureBody, enclosed) == offsetof(nbody_batch_structure_body, enclosed) &&
+                  offsetof(BatchStructureBody, neighbour_r2) == offsetof(nbody_batch_structure_body, neighbour_r2) &&
+                  offsetof(BatchStructureBody, neighbour_weight) == offsetof(nbody_batch_structure_body, neighbour_weight) &&
+                  offsetof(BatchStructureBody, inside) == offsetof(nbody_batch_structure_body, inside),
+              "nbody_batch_structure_math.h mirrors the body record of nbody_batch_structure.h");
+static_assert(sizeof(BatchStructureSystem) == sizeof(nbody_batch_structure_system) && sizeof(nbody_batch_structure_system) == 120 &&
+                  offsetof(BatchStructureSystem, core_radius) == offsetof(nbody_batch_structure_system, core_radius) &&
+                  offsetof(BatchStructureSystem, core_density) == offsetof(nbody_batch_structure_system, core_density) &&
+                  offsetof(BatchStructureSystem, total_weight) == offsetof(nbody_batch_structure_system, total_weight) &&
+                  offsetof(BatchStructureSystem, lagrange) == offsetof(nbody_batch_structure_system, lagrange) &&
+                  offsetof(BatchStructureSystem, estimated) == offsetof(nbody_batch_structure_system, estimated),
+              "nbody_batch_structure_math.h mirrors the system record of nbody_batch_structure.h");
+static_assert(kStructureMaxNeighbour == NBODY_BATCH_STRUCTURE_MAX_NEIGHBOUR && kStructureFractions == NBODY_BATCH_STRUCTURE_FRACTIONS,
+              "nbody_batch_structure_math.h mirrors the limits of nbody_batch_structure.h");
+
+struct BatchStructureArgs {
+    double fraction[kStructureFractions];
+    int n_fractions, k, weight;
+};
+
+constexpr int kStructureSums = 10;  // sum rho, rho x, rho y, rho z, rho^2, w, w x, w y, w z, and the bodies with a k-th neighbour
+
+// LDS: sh[j] = {x, y, z, w_j} of body j (64 KiB at 4096 bodies; with the reduction words above the default limit, which is
+// raised before the launch); after the densities the same bytes hold {s_j, (double)w_j}, 16 bytes per body again.
+// The eight smallest r2 of every row stay in registers (structure_insert); one row per lane is held to the 64 registers of
+// eight waves per SIMD, batch_hermite_kernel<1>'s.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_structure_kernel(
+    const float4 *pos, const int *counts, int max_bodies, BatchStructureArgs p, BatchStructureBody *bodies, BatchStructureSystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ double red[16 * kStructureSums];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float inf = __builtin_inff();
+    float4 x[RPL];  // {x, y, z, w}
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            if (p.weight == NBODY_BATCH_WEIGHT_NUMBER)
+                x[q].w = 1.f;
+            sh[r] = x[q];
+        }
+    }
+    __syncthreads();
+    // Phase 1: the k-th smallest r2 > 0 of every row.
+    float r2k[RPL];
+    {
+        float a[RPL][kStructureMaxNeighbour];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+#pragma unroll
+            for (int t = 0; t < kStructureMaxNeighbour; ++t)
+                a[q][t] = inf;
+        // Measured on an MI355X (profiles/batch_rate_structure.txt): unrolled by 4 the kernel is 4 % faster than by 2, and a
+        // wave-uniform skip of the insertion (no lane's r2 below its list's largest; the same bits) costs 19 - 25 % at 1024
+        // bodies and 2 - 7 % at 4096 -- some lane of 64 nearly always inserts, and the vote and branch are paid per column.
+        // So: 4, no skip.
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const float4 pj = sh[j];  // a wave-uniform address: one broadcast LDS read (ds_read_b96: the weight is not needed)
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+                const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                structure_insert(a[q], r2 > 0.f ? r2 : inf);  // the self pair, coincident bodies and NaN are no neighbour pairs
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            r2k[q] = structure_kth(a[q], p.k);
+    }
+    // Phase 2: the pairs strictly inside the k-th distance, and their weight in ascending j.
+    int inside[RPL];
+    float nw[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        inside[q] = 0;
+        nw[q] = 0.f;
+    }
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = sh[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const bool in = r2 > 0.f && r2 < r2k[q];
+            inside[q] += in ? 1 : 0;
+            nw[q] += in ? pj.w : 0.f;  // + 0 leaves the sum's bits: no branch
+        }
+    }
+    // Phase 3: densities, the system's sums, the centre.
+    double rho[RPL], sum[kStructureSums];
+#pragma unroll
+    for (int c = 0; c < kStructureSums; ++c)
+        sum[c] = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const bool live = q * T + tid < n;
+        rho[q] = live ? structure_density(r2k[q], nw[q]) : 0.0;
+        const double w = live ? (double)x[q].w : 0.0;
+        sum[0] += rho[q];
+        sum[1] += rho[q] * (double)x[q].x;
+        sum[2] += rho[q] * (double)x[q].y;
+        sum[3] += rho[q] * (double)x[q].z;
+        sum[4] += rho[q] * rho[q];
+        sum[5] += w;
+        sum[6] += w * (double)x[q].x;
+        sum[7] += w * (double)x[q].y;
+        sum[8] += w * (double)x[q].z;
+        sum[9] += live && r2k[q] < inf ? 1.0 : 0.0;
+    }
+    block_sum(sum, red, tid, T);  // its barriers: every lane is done with the columns
+    const bool none = sum[0] == 0.0, zero = none && sum[5] == 0.0;
+    double cx = 0.0, cy = 0.0, cz = 0.0;
+    if (!zero) {
+        cx = none ? sum[6] / sum[5] : sum[1] / sum[0];
+        cy = none ? sum[7] / sum[5] : sum[2] / sum[0];
+        cz = none ? sum[8] / sum[5] : sum[3] / sum[0];
+    }
+    // Phase 4: radii about the centre, the core radius, the enclosed weights and the Lagrangian radii.
+    double2 *sd = reinterpret_cast<double2 *>(sh);
+    double s[RPL], core[1] = {0.0};
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const double dx = (double)x[q].x - cx, dy = (double)x[q].y - cy, dz = (double)x[q].z - cz;
+        s[q] = r < n ? dx * dx + dy * dy + dz * dz : 0.0;
+        core[0] += rho[q] * rho[q] * s[q];
+        if (r < n)
+            sd[r] = make_double2(s[q], (double)x[q].w);
+    }
+    block_sum(core, red, tid, T);  // its barriers: the {s_j, w_j} are in place
+    double enc[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        enc[q] = 0.0;
+#pragma unroll 2
+    for (int j = 0; j < n; ++j) {
+        const double2 cj = sd[j];  // broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            enc[q] += cj.x <= s[q] ? cj.y : 0.0;
+    }
+    double radius[RPL], far = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        radius[q] = sqrt(s[q]);
+        far = fmax(far, radius[q]);  // rows from the count on have s = 0
+    }
+    far = 0.0 - block_min(-far, red, tid, T);  // the largest radius; 0 without bodies
+    // The system record, field by field: a record indexed by the fraction would live in scratch memory.
+    BatchStructureSystem *out = systems + blockIdx.x;
+    if (tid == 0) {
+        out->centre[0] = cx;
+        out->centre[1] = cy;
+        out->centre[2] = cz;
+        out->core_radius = none ? 0.0 : sqrt(core[0] / sum[4]);
+        out->core_density = none ? 0.0 : sum[4] / sum[0];
+        out->total_weight = zero ? 0.0 : sum[5];
+        out->estimated = (int)sum[9];
+        out->reserved = 0;
+    }
+#pragma unroll 1
+    for (int f = 0; f < p.n_fractions; ++f) {
+        const double target = p.fraction[f] * sum[5];
+        double m = (double)inf;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            m = (q * T + tid < n && enc[q] >= target) ? fmin(m, radius[q]) : m;
+        m = block_min(m, red, tid, T);
+        if (tid == 0)
+            out->lagrange[f] = zero ? 0.0 : (m < (double)inf ? m : far);
+    }
+    if (tid == 0)
+        for (int f = p.n_fractions; f < kStructureFractions; ++f)
+            out->lagrange[f] = 0.0;  // unused slots
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = r < n ? BatchStructureBody{rho[q], radius[q], enc[q], r2k[q], nw[q], inside[q], 0}
+                                         : structure_empty_body();
+        }
+    }
+}
+
+// One launch over all systems.  64 KiB of dynamic LDS at 4096 bodies beside the reduction words.  bodies may be NULL: the
+// per-body records are then not stored.
+hipError_t launch_batch_structure(const float4 *pos, const int *counts, int n_systems, int max_bodies, const BatchStructureArgs &p,
+                                  BatchStructureBody *bodies, BatchStructureSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_structure_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, counts, max_bodies, p,
+                                      bodies, systems);
+    });
+}
+
+// ---- bound members (include/nbody_batch_members.h): iterative unbinding.  Every row's potential from the member sources and
+// its energy in their rest frame, the rows with e >= 0 dropped, again with the survivors until nothing changes; then the bound
+// mass, centre, velocity and energies of what is left.  A sibling of batch_structure_kernel: one workgroup per system with
+// batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  The iterations run inside
+// the kernel: the member mask and the frame never leave the CU.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchMemberBody) == sizeof(nbody_batch_member_body) && sizeof(nbody_batch_member_body) == 24 &&
+                  offsetof(BatchMemberBody, energy) == offsetof(nbody_batch_member_body, energy) &&
+                  offsetof(BatchMemberBody, member) == offsetof(nbody_batch_member_body, member) &&
+                  offsetof(BatchMemberBody, removed_at) == offsetof(nbody_batch_member_body, removed_at),
+              "nbody_batch_members_math.h mirrors the body record of nbody_batch_members.h");
+static_assert(sizeof(BatchMemberSystem) == sizeof(nbody_batch_member_system) && sizeof(nbody_batch_member_system) == 88 &&
+                  offsetof(BatchMemberSystem, centre) == offsetof(nbody_batch_member_system, centre) &&
+                  offsetof(BatchMemberSystem, velocity) == offsetof(nbody_batch_member_system, velocity) &&
+                  offsetof(BatchMemberSystem, kinetic) == offsetof(nbody_batch_member_system, kinetic) &&
+                  offsetof(BatchMemberSystem, potential) == offsetof(nbody_batch_member_system, potential) &&
+                  offsetof(BatchMemberSystem, members) == offsetof(nbody_batch_member_system, members) &&
+                  offsetof(BatchMemberSystem, sources) == offsetof(nbody_batch_member_system, sources) &&
+                  offsetof(BatchMemberSystem, iterations) == offsetof(nbody_batch_member_system, iterations) &&
+                  offsetof(BatchMemberSystem, converged) == offsetof(nbody_batch_member_system, converged),
+              "nbody_batch_members_math.h mirrors the system record of nbody_batch_members.h");
+static_assert(kMembersMaxIterations == NBODY_BATCH_MEMBERS_MAX_ITERATIONS, "nbody_batch_members_math.h mirrors the limit of nbody_batch_members.h");
+
+// The final set's sums: mass, m x, m y, m z, m vx, m vy, m vz, kinetic, potential, members, member sources.
+constexpr int kMembersSums = 11;
+
+// One pass over the sources j < m for RPL rows: sum[q] += (double)(m_j inv) in ascending j, the fp32 term batch_diag_kernel
+// forms for nbody_batch_energy (GUARD: the eps = 0 guard).  sh[j].w is the source's mass word, or 0 for a non-member: its
+// term is +0, no branch.  Column reads are wave-uniform broadcasts.
+template <int RPL, bool GUARD>
+__device__ __forceinline__ void members_columns(const float4 *sh, int m, const float4 (&x)[RPL], int tid, int T, float eps2,
+                                                double (&sum)[RPL])
+{
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, eps2)));
+            float inv = __builtin_amdgcn_rsqf(GUARD ? guard_r2(r2) : r2);
+            inv = j != q * T + tid ? inv : 0.f;
+            sum[q] += (double)(pj.w * inv);
+        }
+    }
+}
+
+// LDS: sh[j] = {x, y, z, masked mass} of body j (64 KiB at 4096 bodies; with the reduction words above the default limit,
+// which is raised before the launch).  The velocities stay in the rows' registers: only the frame needs them.
+// The iteration loop holds barriers, so its trip count is workgroup-uniform: n, max_iterations and t are, and "removed" and
+// "left" come out of one block_sum, which hands every lane the same words of red; no lane leaves on data of its own.
+// One row per lane is held to the 64 registers of eight waves per SIMD, batch_hermite_kernel<1>'s.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_members_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, int max_bodies, float eps2, int max_iterations,
+    const unsigned char *initial, BatchMemberBody *bodies, BatchMemberSystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ double red[16 * kMembersSums];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the row's mass word as a source; 0 for a test particle}
+    float3 v[RPL];
+    bool in[RPL];   // member of the current set; never for a row from the count on
+    int gone[RPL];  // the iteration that removed the row
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = make_float3(0.f, 0.f, 0.f);
+        in[q] = false;
+        gone[q] = 0;
+        if (r < n) {
+            x[q] = pos[base + r];
+            const float4 w = vel[base + r];
+            v[q] = make_float3(w.x, w.y, w.z);
+            in[q] = initial ? initial[base + r] != 0 : true;
+            if (r >= m)
+                x[q].w = 0.f;
+            sh[r] = make_float4(x[q].x, x[q].y, x[q].z, in[q] ? x[q].w : 0.f);
+        }
+    }
+    double phi[RPL], e[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        phi[q] = e[q] = 0.0;
+    double Vx = 0.0, Vy = 0.0, Vz = 0.0;
+    int iterations = 0, converged = 1;  // a system without bodies evaluates nothing
+    if (n > 0) {
+        for (int t = 1;; ++t) {
+            // The frame of the member sources.
+            double f[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const double w = in[q] ? (double)x[q].w : 0.0;
+                f[0] += w;
+                f[1] += w * (double)v[q].x;
+                f[2] += w * (double)v[q].y;
+                f[3] += w * (double)v[q].z;
+            }
+            block_sum(f, red, tid, T);  // its barriers: the masked mass words are in place
+            const bool massless = f[0] == 0.0;
+            Vx = massless ? 0.0 : f[1] / f[0];
+            Vy = massless ? 0.0 : f[2] / f[0];
+            Vz = massless ? 0.0 : f[3] / f[0];
+            // The potentials, the energies, the decision.
+            double sum[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                sum[q] = 0.0;
+            if (eps2 > 0.f)
+                members_columns<RPL, false>(sh, m, x, tid, T, eps2, sum);
+            else
+                members_columns<RPL, true>(sh, m, x, tid, T, eps2, sum);
+            double c[2] = {0.0, 0.0};  // removed by this iteration, members left
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                phi[q] = 0.0 - sum[q];
+                e[q] = members_energy(v[q].x, v[q].y, v[q].z, Vx, Vy, Vz, phi[q]);
+                const bool stays = members_stays(in[q], e[q]);
+                const bool leaves = in[q] && !stays;
+                gone[q] = leaves ? t : gone[q];
+                in[q] = stays;
+                c[0] += leaves ? 1.0 : 0.0;
+                c[1] += stays ? 1.0 : 0.0;
+            }
+            block_sum(c, red, tid, T);  // its barriers: every lane is done with the columns
+            // The same two words of red in every lane of every wave: the exit is the workgroup's.
+            const int removed = __builtin_amdgcn_readfirstlane((int)c[0]), left = __builtin_amdgcn_readfirstlane((int)c[1]);
+            iterations = t;
+            converged = (removed == 0 || left == 0) ? 1 : 0;
+            if (converged || t >= max_iterations)
+                break;
+            // Every lane masks its own rows' mass words for the next iteration; the next sum's barriers publish them.
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < m)
+                    sh[r].w = in[q] ? x[q].w : 0.f;
+            }
+        }
+    }
+    // The final set.
+    double g[kMembersSums];
+#pragma unroll
+    for (int c = 0; c < kMembersSums; ++c)
+        g[c] = 0.0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const double w = in[q] ? (double)x[q].w : 0.0;
+        g[0] += w;
+        g[1] += w * (double)x[q].x;
+        g[2] += w * (double)x[q].y;
+        g[3] += w * (double)x[q].z;
+        g[4] += w * (double)v[q].x;
+        g[5] += w * (double)v[q].y;
+        g[6] += w * (double)v[q].z;
+        g[7] += in[q] ? w * members_kinetic(v[q].x, v[q].y, v[q].z, Vx, Vy, Vz) : 0.0;
+        g[8] += in[q] ? 0.5 * w * phi[q] : 0.0;
+        g[9] += in[q] ? 1.0 : 0.0;
+        g[10] += in[q] && q * T + tid < m ? 1.0 : 0.0;
+    }
+    block_sum(g, red, tid, T);
+    if (tid == 0) {
+        const bool massless = g[0] == 0.0;
+        BatchMemberSystem *out = systems + blockIdx.x;
+        out->bound_mass = g[0];
+        out->centre[0] = massless ? 0.0 : g[1] / g[0];
+        out->centre[1] = massless ? 0.0 : g[2] / g[0];
+        out->centre[2] = massless ? 0.0 : g[3] / g[0];
+        out->velocity[0] = massless ? 0.0 : g[4] / g[0];
+        out->velocity[1] = massless ? 0.0 : g[5] / g[0];
+        out->velocity[2] = massless ? 0.0 : g[6] / g[0];
+        out->kinetic = g[7];
+        out->potential = g[8];
+        out->members = (int)g[9];
+        out->sources = (int)g[10];
+        out->iterations = iterations;
+        out->converged = converged;
+    }
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = r < n ? BatchMemberBody{phi[q], e[q], in[q] ? 1 : 0, gone[q]} : members_empty_body();
+        }
+    }
+}
+
+// One launch over all systems.  64 KiB of dynamic LDS at 4096 bodies beside the reduction words.  massive, initial and bodies
+// may be NULL.
+hipError_t launch_batch_members(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                                int max_bodies, float eps2, int max_iterations, const unsigned char *initial, BatchMemberBody *bodies,
+                                BatchMemberSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_members_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, vel, counts, massive,
+                                      max_bodies, eps2, max_iterations, initial, bodies, systems);
+    });
+}
+
+// ---- gravity at points (include/nbody_batch_gravity.h): the acceleration, the potential and the tidal tensor of every system
+// at its own bodies (SELF) or at the caller's points.  A sibling of batch_members_kernel with a second grid dimension: a
+// workgroup serves one system and one block of rows (gravity_plan_own / gravity_plan_points of nbody_batch_gravity_math.h),
+// with the system's m sources in LDS as {x, y, z, m}, read by wave-uniform broadcasts; each lane holds RPL rows in registers,
+// row gravity_row(block, RPL, T, q, lane).  Every pair and every sum goes through gravity_pair and GravityRow of that header,
+// which are batch_forces' r2, inv, s and chain and members_columns' fp64 sum: a loop of its own, so that every kernel above
+// stays the code it is (see batch_forces_jerks on OWN).  No atomics, no reduction: a row's outputs are its lane's alone.  It
+// reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchGravityRecord) == sizeof(nbody_batch_gravity_record) && sizeof(nbody_batch_gravity_record) == 24 &&
+                  offsetof(BatchGravityRecord, acceleration) == offsetof(nbody_batch_gravity_record, acceleration) &&
+                  offsetof(BatchGravityRecord, reserved) == offsetof(nbody_batch_gravity_record, reserved) &&
+                  offsetof(BatchGravityRecord, potential) == offsetof(nbody_batch_gravity_record, potential),
+              "nbody_batch_gravity_math.h mirrors the record of nbody_batch_gravity.h");
+static_assert(kGravityMaxPoints == NBODY_BATCH_GRAVITY_MAX_POINTS, "nbody_batch_gravity_math.h mirrors the limit of nbody_batch_gravity.h");
+
+// SELF: the rows are the bodies r < n of pos and `stride` is max_bodies; otherwise the rows are the points r < point_counts[s]
+// (n_points where point_counts is null) of `points` and `stride` is n_points.  Rows from the count on up to `stride` receive the
+// empty record; a block without a row below the count writes those and returns before it loads a source.  One row per lane is
+// held to the 64 registers of eight waves per SIMD, as batch_members_kernel<1> is.
+template <int RPL, bool GUARD, bool SELF, bool TIDAL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_gravity_kernel(
+    const float4 *pos, const float4 *points, const int *counts, const int *massive, const int *point_counts, int max_bodies,
+    int stride, float eps2, BatchGravityRecord *records, float *tidal)
+{
+    extern __shared__ float4 sh[];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int pc = SELF ? n : (point_counts ? point_counts[blockIdx.x] : stride);
+    const int rows = pc < stride ? pc : stride;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const int first = gravity_row(blockIdx.y, RPL, T, 0, 0);
+    const size_t src = (size_t)blockIdx.x * (size_t)max_bodies, base = (size_t)blockIdx.x * (size_t)stride;
+    if (first >= rows) {  // workgroup-uniform: no barrier is passed
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+            if (r < stride) {
+                records[base + r] = gravity_empty_record();
+                if (TIDAL) {
+#pragma unroll
+                    for (int c = 0; c < kGravityTidalWords; ++c)
+                        tidal[(base + r) * kGravityTidalWords + c] = 0.f;
+                }
+            }
+        }
+        return;
+    }
+    for (int j = tid; j < m; j += T)
+        sh[j] = pos[src + j];
+    float4 x[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < rows)
+            x[q] = SELF ? pos[src + r] : points[base + r];
+    }
+    __syncthreads();
+    GravityRow<TIDAL> row[RPL];
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const float4 pj = sh[j];  // wave-uniform address: broadcast ds_read_b128
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            row[q].add(gravity_pair<GUARD, TIDAL>(x[q].x, x[q].y, x[q].z, pj.x, pj.y, pj.z, pj.w, eps2,
+                                                  SELF && j == gravity_row(blockIdx.y, RPL, T, q, tid)));
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = gravity_row(blockIdx.y, RPL, T, q, tid);
+        if (r < stride) {
+            float t[kGravityTidalWords] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (TIDAL && r < rows)
+                row[q].tidal(t);
+            records[base + r] = r < rows ? row[q].record() : gravity_empty_record();
+            if (TIDAL) {
+#pragma unroll
+                for (int c = 0; c < kGravityTidalWords; ++c)
+                    tidal[(base + r) * kGravityTidalWords + c] = t[c];
+            }
+        }
+    }
+}
+
+// One launch over all systems and row blocks.  64 KiB of dynamic LDS at 4096 bodies.  points null: own-bodies mode.  massive,
+// point_counts and tidal may be null.
+hipError_t launch_batch_gravity(const float4 *pos, const float4 *points, const int *counts, const int *massive,
+                                const int *point_counts, int n_systems, int max_bodies, int n_points, float eps2,
+                                BatchGravityRecord *records, float *tidal, hipStream_t stream)
+{
+    const bool self = points == nullptr;
+    const GravityPlan plan = self ? gravity_plan_own(max_bodies) : gravity_plan_points(n_points);
+    const int stride = self ? max_bodies : n_points;
+    const size_t lds = gravity_lds_bytes(max_bodies);
+    const auto launch = [&](auto kernel) {
+        return launch_analysis_kernel(kernel, dim3(n_systems, plan.blocks), plan.threads, lds, stream, pos, points, counts, massive,
+                                      point_counts, max_bodies, stride, eps2, records, tidal);
+    };
+    const auto with_modes = [&](auto rpl, auto guard) {
+        constexpr int R = decltype(rpl)::value;
+        constexpr bool G = decltype(guard)::value;
+        if (self)
+            return tidal ? launch(batch_gravity_kernel<R, G, true, true>) : launch(batch_gravity_kernel<R, G, true, false>);
+        return tidal ? launch(batch_gravity_kernel<R, G, false, true>) : launch(batch_gravity_kernel<R, G, false, false>);
+    };
+    return with_shape(plan.rpl, !(eps2 > 0.f), with_modes);
+}
+
+// ---- hierarchies (include/nbody_batch_hierarchy.h): nested bound pairs.  Level by level the live roots of a system look for
+// partners as batch_pairs_kernel's rows do, the mutual bound pairs that their worst perturber lets stand become nodes with the
+// merged body's state, and the search runs again over what is left.  A sibling of batch_pairs_kernel: one workgroup per
+// system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  The levels run
+// inside the kernel.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchHierarchyNode) == sizeof(nbody_batch_hierarchy_node) && sizeof(nbody_batch_hierarchy_node) == 128 &&
+                  offsetof(BatchHierarchyNode, parent) == offsetof(nbody_batch_hierarchy_node, parent) &&
+                  offsetof(BatchHierarchyNode, stable) == offsetof(nbody_batch_hierarchy_node, stable) &&
+                  offsetof(BatchHierarchyNode, mass) == offsetof(nbody_batch_hierarchy_node, mass) &&
+                  offsetof(BatchHierarchyNode, perturbation) == offsetof(nbody_batch_hierarchy_node, perturbation) &&
+                  offsetof(BatchHierarchyNode, mutual_inclination) == offsetof(nbody_batch_hierarchy_node, mutual_inclination) &&
+                  offsetof(BatchHierarchyNode, h) == offsetof(nbody_batch_hierarchy_node, h),
+              "nbody_batch_hierarchy_math.h mirrors the node record of nbody_batch_hierarchy.h");
+static_assert(sizeof(BatchHierarchyBody) == sizeof(nbody_batch_hierarchy_body) && sizeof(nbody_batch_hierarchy_body) == 16 &&
+                  offsetof(BatchHierarchyBody, depth) == offsetof(nbody_batch_hierarchy_body, depth),
+              "nbody_batch_hierarchy_math.h mirrors the body record of nbody_batch_hierarchy.h");
+static_assert(sizeof(BatchHierarchySystem) == sizeof(nbody_batch_hierarchy_system) && sizeof(nbody_batch_hierarchy_system) == 40 &&
+                  offsetof(BatchHierarchySystem, singles) == offsetof(nbody_batch_hierarchy_system, singles) &&
+                  offsetof(BatchHierarchySystem, unstable) == offsetof(nbody_batch_hierarchy_system, unstable),
+              "nbody_batch_hierarchy_math.h mirrors the system record of nbody_batch_hierarchy.h");
+static_assert(kHierarchyMaxLevels == NBODY_BATCH_HIERARCHY_MAX_LEVELS, "nbody_batch_hierarchy_math.h mirrors the limit of nbody_batch_hierarchy.h");
+
+constexpr size_t kHierarchyBytesPerBody = 2 * kBatchBytesPerBody + sizeof(int);  // position, velocity, the slot's node id
+
+// LDS: sh[2 j] = {x, y, z, m} and sh[2 j + 1] = {vx, vy, vz, word} of the root in slot j < m (batch_pairs_kernel's layout,
+// 128 KiB at 4096 bodies), then nid[j], the id of that root or -1 for a dead slot (16 KiB): 144 KiB, with the few hundred
+// bytes of made and red inside the 160 KiB of a workgroup.  The fourth word of the velocity holds the slot's partner after
+// walk 1 and, in the higher slot of a mutual pair, the pair's g after walk 2.
+// Dead slots: the mass word of a dead slot is NaN, and so is the row mass of a lane whose row is dead or no leaf.  mu, eps
+// and s are then NaN and the searches' own comparisons never take them: no branch, no predicate beside the pairs kernel's.
+// What a node needs of a composite child (a, h, stable, leaves) is read back from the node records in global memory, which
+// this workgroup wrote at an earlier level with barriers between; LDS holds no per-node array.
+// The level loop holds barriers, so its trip count is workgroup-uniform: m, max_levels and t are, and the nodes a level made
+// are summed by every lane from the same words of `made`.  The record loop is kept rolled (the fp64 arithmetic is
+// instantiated once); the creation order over r = q * T + lane is a ballot within the wave, the waves' counts in LDS and a
+// running offset over q.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_hierarchy_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, int max_bodies, double tolerance, int max_levels,
+    int fill, BatchHierarchyNode *nodes, BatchHierarchyBody *bodies, BatchHierarchySystem *systems)
+{
+    extern __shared__ float4 sh[];
+    __shared__ int made[16];
+    __shared__ double red[16 * 5];
+    int *nid = reinterpret_cast<int *>(sh + 2 * (size_t)max_bodies);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float dead = __builtin_nanf("");
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < m) {
+            const float4 w = vel[base + r];
+            sh[2 * r] = pos[base + r];
+            sh[2 * r + 1] = make_float4(w.x, w.y, w.z, 0.f);
+            nid[r] = r;
+        }
+    }
+    int nodes_made = 0, levels = 0, converged = 1;  // a system of fewer than two leaves evaluates no level
+    if (m >= 2) {
+        for (int t = 1;; ++t) {
+            __syncthreads();  // the roots of this level are in place
+            float4 x[RPL];    // {x, y, z, m} of the row's root; m is NaN for a dead slot and for a row that is no leaf
+            float3 v[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                x[q] = make_float4(0.f, 0.f, 0.f, dead);
+                v[q] = make_float3(0.f, 0.f, 0.f);
+                if (r < m) {
+                    x[q] = sh[2 * r];
+                    const float4 w = sh[2 * r + 1];
+                    v[q] = make_float3(w.x, w.y, w.z);
+                }
+            }
+            // Walk 1: batch_pairs_kernel's search.
+            float best[RPL];
+            int bj[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                best[q] = __builtin_inff();
+                bj[q] = -1;
+            }
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+                const float4 pj = sh[2 * j], vj = sh[2 * j + 1];  // wave-uniform addresses: broadcast ds_read_b128
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const float dx = pj.x - x[q].x, dy = pj.y - x[q].y, dz = pj.z - x[q].z;
+                    const float wx = vj.x - v[q].x, wy = vj.y - v[q].y, wz = vj.z - v[q].z;
+                    const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    const float v2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+                    const float inv = __builtin_amdgcn_rsqf(r2);
+                    const float mu = pj.w + x[q].w;
+                    const float eps = __builtin_fmaf(-mu, inv, 0.5f * v2);
+                    const bool take = r2 > 0.f && eps < best[q];  // r2 == 0: the root itself and coincident roots
+                    best[q] = take ? eps : best[q];
+                    bj[q] = take ? j : bj[q];
+                }
+            }
+            __syncthreads();  // every lane is done with the columns before the partners replace the fourth words
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (r < m)
+                    sh[2 * r + 1].w = __int_as_float(bj[q]);
+            }
+            __syncthreads();
+            // The mutual pairs, owned by the lane of the lower slot, and the position X of the node each would make.
+            unsigned mut = 0;
+            float3 X[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid, j = bj[q];
+                X[q] = make_float3(x[q].x, x[q].y, x[q].z);
+                if (j > r) {
+                    const float4 pj = sh[2 * j];
+                    if (__float_as_int(sh[2 * j + 1].w) == r) {
+                        const double M = (double)x[q].w + (double)pj.w;
+                        mut |= 1u << q;
+                        X[q].x = hierarchy_merged(x[q].w, x[q].x, pj.w, pj.x, M);
+                        X[q].y = hierarchy_merged(x[q].w, x[q].y, pj.w, pj.y, M);
+                        X[q].z = hierarchy_merged(x[q].w, x[q].z, pj.w, pj.z, M);
+                    }
+                }
+            }
+            __syncthreads();  // every lane has read its partner's word before a pair's g replaces it
+            // Walk 2: the worst perturber of every mutual pair (an unbound pair's g is dropped with the pair).
+            float g[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                g[q] = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < m; ++k) {
+                const float4 pk = sh[2 * k];
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const float dx = pk.x - X[q].x, dy = pk.y - X[q].y, dz = pk.z - X[q].z;
+                    const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    const float inv = __builtin_amdgcn_rsqf(r2);
+                    const float s = (pk.w * inv) * (inv * inv);
+                    const bool take = (k != q * T + tid) & (k != bj[q]) & (s > g[q]);  // one predicate, no branch; a dead slot's s is NaN
+                    g[q] = take ? s : g[q];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                if ((mut >> q) & 1u)
+                    sh[2 * bj[q] + 1].w = g[q];
+            __syncthreads();  // every lane is done with the columns before the new nodes replace them
+            // The records and the new nodes, one row at a time from LDS.  A pair's two slots are read and written by the
+            // lane that owns the pair alone.
+            int level_made = 0;
+#pragma unroll 1
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                bool accept = false;
+                BatchHierarchyNode rec = hierarchy_empty_node();
+                float4 xi = make_float4(0.f, 0.f, 0.f, 0.f), vi = xi, xj = xi, vj = xi;
+                int j = -1;
+                if ((mut >> q) & 1u) {
+                    xi = sh[2 * r], vi = sh[2 * r + 1];
+                    j = __float_as_int(vi.w);
+                    xj = sh[2 * j], vj = sh[2 * j + 1];
+                    const float pi[3] = {xi.x, xi.y, xi.z}, wi[3] = {vi.x, vi.y, vi.z};
+                    const float pj[3] = {xj.x, xj.y, xj.z}, wj[3] = {vj.x, vj.y, vj.z};
+                    hierarchy_elements(pi, wi, xi.w, pj, wj, xj.w, rec);
+                    rec.perturbation = hierarchy_perturbation(vj.w, rec.semi_major_axis, rec.eccentricity, (double)xj.w + (double)xi.w);
+                    accept = hierarchy_accepts(rec.energy, rec.perturbation, tolerance);
+                }
+                // creation order: the accepted rows before this one in the wave, in the waves before, at the q before
+                const unsigned long long votes = __ballot(accept);
+                const int before = __popcll(votes & ((1ull << lane) - 1ull));
+                __syncthreads();  // every lane has read the counts of the q before
+                if (lane == 0)
+                    made[wave] = __popcll(votes);
+                __syncthreads();
+                int lower = 0, total = 0;
+                for (int w = 0; w < T / 64; ++w) {
+                    const int c = made[w];
+                    lower += w < wave ? c : 0;
+                    total += c;
+                }
+                if (accept) {
+                    const int k = nodes_made + level_made + lower + before, id = n + k;
+                    const int ci = nid[r], cj = nid[j];
+                    BatchHierarchyNode *out = nodes + base + k;
+                    rec.child[0] = ci;
+                    rec.child[1] = cj;
+                    rec.level = t;
+                    rec.slot = r;
+                    *out = rec;  // leaves, stable and the mutual inclinations follow below: little is live across them
+                    const float mass = xi.w + xj.w;
+                    const double M = (double)xi.w + (double)xj.w;
+                    sh[2 * r] = make_float4(hierarchy_merged(xi.w, xi.x, xj.w, xj.x, M), hierarchy_merged(xi.w, xi.y, xj.w, xj.y, M),
+                                            hierarchy_merged(xi.w, xi.z, xj.w, xj.z, M), mass);
+                    sh[2 * r + 1] = make_float4(hierarchy_merged(xi.w, vi.x, xj.w, vj.x, M), hierarchy_merged(xi.w, vi.y, xj.w, vj.y, M),
+                                                hierarchy_merged(xi.w, vi.z, xj.w, vj.z, M), 0.f);
+                    sh[2 * j].w = dead;
+                    nid[r] = id;
+                    nid[j] = -1;
+                    int leaves = 0, stable = 1;
+#pragma unroll 1
+                    for (int c = 0; c < 2; ++c) {
+                        const int cid = c ? cj : ci;
+                        if (cid < n) {
+                            leaves += 1;
+                            continue;
+                        }
+                        BatchHierarchyNode *child = nodes + base + (cid - n);
+                        const double mc = c ? (double)xj.w : (double)xi.w, mo = c ? (double)xi.w : (double)xj.w;
+                        const double hc[3] = {child->h[0], child->h[1], child->h[2]};
+                        const double imut = hierarchy_mutual_inclination(rec.h, hc);
+                        const bool passes = hierarchy_child_passes(rec.semi_major_axis, rec.eccentricity, child->semi_major_axis,
+                                                                   mo / mc, imut);
+                        stable = (passes && child->stable) ? stable : 0;
+                        leaves += child->leaves;
+                        out->mutual_inclination[c] = imut;
+                        child->parent = id;
+                    }
+                    out->leaves = leaves;
+                    out->stable = stable;
+                }
+                level_made += total;
+            }
+            // The same words of `made` in every lane of every wave: the exit is the workgroup's.
+            const int level_nodes = __builtin_amdgcn_readfirstlane(level_made);
+            nodes_made += level_nodes;
+            levels = t;
+            converged = (level_nodes == 0 || m - nodes_made < 2) ? 1 : 0;
+            if (converged || t >= max_levels)
+                break;
+        }
+    }
+    __syncthreads();  // the node records and ids of the last level are in place
+    // The roots: singles, binaries, triples, higher, unstable.
+    double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const int id = r < m ? nid[r] : -1;
+        if (id >= 0) {
+            int leaves = 1, stable = 1;
+            if (id >= n) {
+                leaves = nodes[base + (id - n)].leaves;
+                stable = nodes[base + (id - n)].stable;
+            }
+            c[0] += leaves == 1 ? 1.0 : 0.0;
+            c[1] += leaves == 2 ? 1.0 : 0.0;
+            c[2] += leaves == 3 ? 1.0 : 0.0;
+            c[3] += leaves >= 4 ? 1.0 : 0.0;
+            c[4] += stable ? 0.0 : 1.0;
+        }
+    }
+    block_sum(c, red, tid, T);
+    if (tid == 0)
+        systems[blockIdx.x] = BatchHierarchySystem{nodes_made, m - nodes_made, levels, converged, (int)c[0], (int)c[1], (int)c[2],
+                                                   (int)c[3], (int)c[4], 0};
+    if (fill) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r >= nodes_made && r < max_bodies)
+                nodes[base + r] = hierarchy_empty_node();
+        }
+    }
+    if (bodies) {
+        // Every leaf's parent from the nodes' children, in the LDS the roots no longer need; then every leaf climbs.
+        int *up = reinterpret_cast<int *>(sh);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                up[r] = -1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < nodes_made) {
+                const int c0 = nodes[base + r].child[0], c1 = nodes[base + r].child[1];
+                if (c0 < n)
+                    up[c0] = n + r;
+                if (c1 < n)
+                    up[c1] = n + r;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r >= max_bodies)
+                continue;
+            BatchHierarchyBody rec = hierarchy_empty_body();
+            if (r < n) {
+                rec.parent = up[r];
+                rec.root = r;
+                for (int p = rec.parent; p >= 0; p = nodes[base + (p - n)].parent) {
+                    rec.root = p;
+                    rec.depth += 1;
+                }
+            }
+            bodies[base + r] = rec;
+        }
+    }
+}
+
+// One launch over all systems.  36 bytes of dynamic LDS per body, 144 KiB at 4096 bodies.  massive and bodies may be NULL;
+// fill: write the empty records from the node count on.
+hipError_t launch_batch_hierarchy(const float4 *pos, const float4 *vel, const int *counts, const int *massive, int n_systems,
+                                  int max_bodies, double tolerance, int max_levels, bool fill, BatchHierarchyNode *nodes,
+                                  BatchHierarchyBody *bodies, BatchHierarchySystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kHierarchyBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_hierarchy_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, vel, counts, massive,
+                                      max_bodies, tolerance, max_levels, fill ? 1 : 0, nodes, bodies, systems);
+    });
+}
+
+// ---- groups (include/nbody_batch_groups.h): friends-of-friends clumps at a linking length.  Every row's label is lowered to
+// the smallest label among its friends, its root is hooked below, the labels are compressed, and again until a sweep lowers
+// nothing; then every row sums its group's weight, position and velocity in fp64 and the roots write the records.  A sibling of
+// batch_members_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane
+// at r = q * T + lane.  The labels never leave the CU.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchGroupBody) == sizeof(nbody_batch_group_body) && sizeof(nbody_batch_group_body) == 8 &&
+                  offsetof(BatchGroupBody, group) == offsetof(nbody_batch_group_body, group) &&
+                  offsetof(BatchGroupBody, size) == offsetof(nbody_batch_group_body, size),
+              "nbody_batch_groups_math.h mirrors the body record of nbody_batch_groups.h");
+static_assert(sizeof(BatchGroupRecord) == sizeof(nbody_batch_group_record) && sizeof(nbody_batch_group_record) == 64 &&
+                  offsetof(BatchGroupRecord, weight) == offsetof(nbody_batch_group_record, weight) &&
+                  offsetof(BatchGroupRecord, centre) == offsetof(nbody_batch_group_record, centre) &&
+                  offsetof(BatchGroupRecord, velocity) == offsetof(nbody_batch_group_record, velocity) &&
+                  offsetof(BatchGroupRecord, count) == offsetof(nbody_batch_group_record, count) &&
+                  offsetof(BatchGroupRecord, sources) == offsetof(nbody_batch_group_record, sources),
+              "nbody_batch_groups_math.h mirrors the group record of nbody_batch_groups.h");
+static_assert(sizeof(BatchGroupSystem) == sizeof(nbody_batch_group_system) && sizeof(nbody_batch_group_system) == 32 &&
+                  offsetof(BatchGroupSystem, groups) == offsetof(nbody_batch_group_system, groups) &&
+                  offsetof(BatchGroupSystem, grouped) == offsetof(nbody_batch_group_system, grouped) &&
+                  offsetof(BatchGroupSystem, singles) == offsetof(nbody_batch_group_system, singles) &&
+                  offsetof(BatchGroupSystem, largest) == offsetof(nbody_batch_group_system, largest) &&
+                  offsetof(BatchGroupSystem, largest_count) == offsetof(nbody_batch_group_system, largest_count) &&
+                  offsetof(BatchGroupSystem, sweeps) == offsetof(nbody_batch_group_system, sweeps) &&
+                  offsetof(BatchGroupSystem, converged) == offsetof(nbody_batch_group_system, converged) &&
+                  offsetof(BatchGroupSystem, reserved) == offsetof(nbody_batch_group_system, reserved),
+              "nbody_batch_groups_math.h mirrors the system record of nbody_batch_groups.h");
+static_assert(kGroupsMaxSweeps == NBODY_BATCH_GROUPS_MAX_SWEEPS && kGroupsWeightMass == NBODY_BATCH_WEIGHT_MASS &&
+                  kGroupsWeightNumber == NBODY_BATCH_WEIGHT_NUMBER,
+              "nbody_batch_groups_math.h mirrors the limit of nbody_batch_groups.h and the weights of nbody_batch_structure.h");
+static_assert(sizeof(int4) == kGroupsWords * sizeof(int) && kBatchBytesPerBody == sizeof(int4), "a column is one 16-byte read");
+
+// The image {x, y, z, label} and, for the records, the labels in an array of their own while the image holds {x, y, z, w} and
+// then {vx, vy, vz, w}: 20 bytes per body.
+constexpr size_t kGroupsBytesPerBody = kBatchBytesPerBody + sizeof(int);
+
+// LDS: img[j] = {x, y, z, label} of body j as four words, one ds_read_b128 per column (64 KiB at 4096 bodies), and lab[j]
+// behind it for the records (16 KiB more; the limit is raised before the launch).  Rows from the count on carry NaN
+// coordinates: they link to nothing, are lowered by nothing and write nothing.
+// Every loop that holds a barrier has a workgroup-uniform trip count: n, t and max_sweeps are uniform, and "a label was
+// lowered" and "a pass changed a label" come out of block_any; no lane leaves on data of its own.
+// One row per lane is held to the 64 registers of eight waves per SIMD, as in batch_members_kernel<1>.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_groups_kernel(
+    const float4 *pos, const float4 *vel, const int *counts, const int *massive, const float *linking2, int max_bodies,
+    int min_members, int weight, int max_sweeps, BatchGroupBody *bodies, BatchGroupRecord *records, BatchGroupSystem *systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int flags[16];
+    __shared__ int tally[4];  // groups, grouped, singles, the largest key
+    int *words = reinterpret_cast<int *>(img);
+    int *lab = words + kGroupsWords * max_bodies;
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int m = massive ? (massive[blockIdx.x] < n ? massive[blockIdx.x] : n) : n;
+    const float b2 = linking2[blockIdx.x];
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];  // {x, y, z, the mass word}
+    int L[RPL];     // the row's label
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const float none = __int_as_float(0x7fc00000);
+        x[q] = make_float4(none, none, none, 0.f);
+        L[q] = r;
+        if (r < n) {
+            x[q] = pos[base + r];
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), r);
+        }
+    }
+    if (tid == 0) {
+        tally[0] = tally[1] = tally[2] = 0;
+        tally[3] = kGroupsKeyNone;
+    }
+    // Phase 1, the sweeps.
+    int sweeps = 0, converged = 1;  // a system without bodies runs no sweep
+    if (n > 0) {
+        for (int t = 1;; ++t) {
+            __syncthreads();  // the image, or the labels the sweep before left, are in place
+            int c[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                c[q] = L[q];
+#pragma unroll 4
+            for (int j = 0; j < n; ++j) {
+                const int4 pj = img[j];
+                const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+                for (int q = 0; q < RPL; ++q)
+                    c[q] = groups_link(c[q], x[q].x, x[q].y, x[q].z, xj, yj, zj, pj.w, b2);
+            }
+            bool low = false;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                low = low || groups_lowered(c[q], L[q]);
+            const bool lowered = block_any(low, flags, tid, T);  // its barriers: every lane is done reading the labels
+            sweeps = t;
+            converged = lowered ? 0 : 1;
+            if (!lowered)
+                break;
+            // Hook: the roots take the minimum of what their rows found.  An LDS integer atomic: the order does not matter.
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                if (groups_lowered(c[q], L[q]))
+                    groups_hook(words, q * T + tid, L[q], c[q], [](int *address, int value) { atomicMin(address, value); });
+            }
+            // Compress: every row reads its root's label, then every row writes, until a pass changes nothing.
+            for (;;) {
+                __syncthreads();  // the hooks, or the pass before, are in place
+                int next[RPL];
+                bool moved = false;
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const int r = q * T + tid;
+                    next[q] = L[q];
+                    if (r < n) {
+                        const int now = words[groups_label_at(r)];
+                        next[q] = groups_compress(words, now);
+                        moved = moved || next[q] != now;
+                    }
+                }
+                const bool again = block_any(moved, flags, tid, T);  // its barriers: every row has read
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const int r = q * T + tid;
+                    L[q] = next[q];
+                    if (r < n)
+                        words[groups_label_at(r)] = next[q];
+                }
+                if (!again)
+                    break;
+            }
+            if (t >= max_sweeps)
+                break;
+        }
+    }
+    // Phase 2, the records: the image takes the weights, the labels move behind it.
+    __syncthreads();  // every lane is done with the labels in the image
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n) {
+            x[q].w = groups_weight(weight, x[q].w, r < m);
+            words[groups_label_at(r)] = __float_as_int(x[q].w);
+            lab[r] = L[q];
+        }
+    }
+    __syncthreads();
+    GroupSums sum[RPL];
+#pragma unroll 2
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[j];
+        const int lj = lab[j];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            groups_add_position(sum[q], lj == L[q], j < m, __int_as_float(pj.w), __int_as_float(pj.x), __int_as_float(pj.y),
+                                __int_as_float(pj.z));
+    }
+    if (records) {  // the same for every lane: a kernel argument
+        __syncthreads();  // every lane is done with the positions
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n) {
+                const float4 v = vel[base + r];
+                img[r] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), __float_as_int(x[q].w));
+            }
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const int lj = lab[j];
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                groups_add_velocity(sum[q], lj == L[q], __int_as_float(pj.w), __int_as_float(pj.x), __int_as_float(pj.y),
+                                    __int_as_float(pj.z));
+        }
+    }
+    // The roots write their group's record and add themselves to the summary: integers, in any order.
+    GroupTally mine;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        const bool root = r < n && L[q] == r;
+        if (root)
+            groups_tally_root(mine, sum[q].count, r, min_members);
+        if (r < max_bodies) {
+            if (records)
+                records[base + r] = root ? groups_record(sum[q]) : groups_empty_record();
+            if (bodies)
+                bodies[base + r] = r < n ? BatchGroupBody{L[q], sum[q].count} : groups_empty_body();
+        }
+    }
+    if (mine.key != kGroupsKeyNone) {
+        atomicAdd(&tally[0], mine.groups);
+        atomicAdd(&tally[1], mine.grouped);
+        atomicAdd(&tally[2], mine.singles);
+        atomicMax(&tally[3], mine.key);
+    }
+    __syncthreads();
+    if (tid == 0)
+        systems[blockIdx.x] = groups_summary(GroupTally{tally[0], tally[1], tally[2], tally[3]}, sweeps, converged);
+}
+
+// One launch over all systems.  20 bytes of dynamic LDS per body, 80 KiB at 4096 bodies.  massive, bodies and records may be
+// NULL; without records the velocities are not read.
+hipError_t launch_batch_groups(const float4 *pos, const float4 *vel, const int *counts, const int *massive, const float *linking2,
+                               int n_systems, int max_bodies, int min_members, int weight, int max_sweeps, BatchGroupBody *bodies,
+                               BatchGroupRecord *records, BatchGroupSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kGroupsBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_groups_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, vel, counts, massive,
+                                      linking2, max_bodies, min_members, weight, max_sweeps, bodies, records, systems);
+    });
+}
+
+// ---- spanning trees (include/nbody_batch_span.h): the Euclidean minimum spanning tree of every system's selected bodies by
+// Boruvka's rounds.  Every row finds the cheapest edge that leaves its component, the components take the minimum of their
+// rows' keys with a 64-bit LDS integer min, the roots decide, hook and record, the labels are compressed, and again until one
+// component is left; then the recorded keys are sorted in LDS and the lengths summed in order.  A sibling of
+// batch_groups_kernel: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane
+// at r = q * T + lane.  It reads the state and writes only the handle's records.
+
+static_assert(sizeof(BatchSpanSystem) == sizeof(nbody_batch_span_system) && sizeof(nbody_batch_span_system) == 40 &&
+                  offsetof(BatchSpanSystem, edges) == offsetof(nbody_batch_span_system, edges) &&
+                  offsetof(BatchSpanSystem, selected) == offsetof(nbody_batch_span_system, selected) &&
+                  offsetof(BatchSpanSystem, rounds) == offsetof(nbody_batch_span_system, rounds) &&
+                  offsetof(BatchSpanSystem, reserved) == offsetof(nbody_batch_span_system, reserved) &&
+                  offsetof(BatchSpanSystem, total_length) == offsetof(nbody_batch_span_system, total_length) &&
+                  offsetof(BatchSpanSystem, longest) == offsetof(nbody_batch_span_system, longest) &&
+                  offsetof(BatchSpanSystem, mean_separation) == offsetof(nbody_batch_span_system, mean_separation),
+              "nbody_batch_span_math.h mirrors the system record of nbody_batch_span.h");
+static_assert(sizeof(BatchSpanEdge) == sizeof(nbody_batch_span_edge) && sizeof(nbody_batch_span_edge) == 16 &&
+                  offsetof(BatchSpanEdge, i) == offsetof(nbody_batch_span_edge, i) &&
+                  offsetof(BatchSpanEdge, j) == offsetof(nbody_batch_span_edge, j) &&
+                  offsetof(BatchSpanEdge, r2) == offsetof(nbody_batch_span_edge, r2) &&
+                  offsetof(BatchSpanEdge, reserved) == offsetof(nbody_batch_span_edge, reserved),
+              "nbody_batch_span_math.h mirrors the edge record of nbody_batch_span.h");
+static_assert(sizeof(BatchSpanBody) == sizeof(nbody_batch_span_body) && sizeof(nbody_batch_span_body) == 8 &&
+                  offsetof(BatchSpanBody, degree) == offsetof(nbody_batch_span_body, degree) &&
+                  offsetof(BatchSpanBody, nearest) == offsetof(nbody_batch_span_body, nearest),
+              "nbody_batch_span_math.h mirrors the body record of nbody_batch_span.h");
+static_assert(kSpanMaxRounds == NBODY_BATCH_SPAN_MAX_ROUNDS, "nbody_batch_span_math.h mirrors the limit of nbody_batch_span.h");
+static_assert(NBODY_BATCH_MAX_BODIES <= (1 << kSpanIndexBits), "an index fills 12 bits of the key");
+static_assert(sizeof(SpanKey) == 8 && sizeof(double) == 8, "a 64-bit word holds a key, then a length");
+
+// The image {x, y, z, component}, 16 bytes per body, and behind it one 64-bit word per slot of the sort, whose length is the
+// capacity rounded up to a power of two: 24 bytes per body and 96 KiB at 4096 bodies.
+inline size_t span_lds_bytes(int max_bodies)
+{
+    return kBatchBytesPerBody * (size_t)max_bodies + sizeof(SpanKey) * (size_t)span_sort_length(max_bodies);
+}
+
+// LDS: img[j] = {x, y, z, component} of body j as four words, one ds_read_b128 per column, and key[] behind it: a component's
+// minimum at its root's slot while the rounds run, the row sums of the separations before them, the recorded keys and then the
+// lengths after them.  Unselected rows carry kSpanNoComponent and are skipped as columns; rows from the count on are no columns.
+// Every loop that holds a barrier has a workgroup-uniform trip count: n, the sort's length and the separations flag are
+// uniform, the components left are read from LDS behind a barrier, and "a pass changed a label" comes out of block_any.
+// The edge a component records lives in rec[q] of the lane that owns the row of its root: a root is absorbed once.
+// One row per lane is held to the 64 registers of eight waves per SIMD, as in batch_groups_kernel<1>.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_span_kernel(
+    const float4 *pos, const int *counts, const unsigned char *subset, int max_bodies, int separations, BatchSpanEdge *edges,
+    BatchSpanBody *bodies, BatchSpanSystem *systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int flags[16];
+    __shared__ int left;  // the components left; before the rounds, the selected bodies
+    int *words = reinterpret_cast<int *>(img);
+    SpanKey *key = reinterpret_cast<SpanKey *>(img + max_bodies);
+    double *term = reinterpret_cast<double *>(key);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    float4 x[RPL];      // {x, y, z, the mass word}
+    int L[RPL];         // the row's component; kSpanNoComponent for a row that is not selected
+    int nearest[RPL];   // the first round's row result
+    SpanKey rec[RPL];   // the edge the row's component recorded when it was absorbed
+    if (tid == 0)
+        left = 0;
+    __syncthreads();
+    int mine = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        L[q] = kSpanNoComponent;
+        nearest[q] = -1;
+        rec[q] = kSpanNoKey;
+        if (r < n) {
+            x[q] = pos[base + r];
+            L[q] = !subset || subset[base + r] != 0 ? r : kSpanNoComponent;
+            mine += L[q] != kSpanNoComponent ? 1 : 0;
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), L[q]);
+        }
+    }
+    if (mine)
+        atomicAdd(&left, mine);
+    __syncthreads();  // the image and the count are in place
+    const int selected = left;
+    // The separations: every row's sum in ascending j, then thread 0 adds the rows in ascending i.
+    double separation = 0.0;
+    if (separations && selected > 1) {  // the same for every lane
+        double sum[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            sum[q] = 0.0;
+#pragma unroll 2
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                sum[q] += span_separation(pj.w != kSpanNoComponent && j != q * T + tid,
+                                          groups_r2(x[q].x, x[q].y, x[q].z, xj, yj, zj));
+        }
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                term[r] = L[q] != kSpanNoComponent ? sum[q] : 0.0;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int i = 0; i < n; ++i)
+                separation += term[i];
+        }
+    }
+    // The rounds.
+    int rounds = 0;
+    for (;;) {
+        __syncthreads();  // the labels and the count the round before left are in place; the words are free
+        const int components = left;
+        if (components <= 1 || rounds >= kSpanMaxRounds)
+            break;
+        ++rounds;
+        SpanBest best[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < n)
+                key[r] = kSpanNoKey;
+        }
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const int4 pj = img[j];
+            const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                span_step(best[q], L[q], x[q].x, x[q].y, x[q].z, xj, yj, zj, pj.w, j);
+        }
+        __syncthreads();  // every word is cleared
+        // The components' minima: an LDS integer atomic, so the order does not matter.
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            if (L[q] != kSpanNoComponent) {
+                if (rounds == 1)
+                    nearest[q] = best[q].j;
+                const SpanKey k = span_row_key(best[q], q * T + tid);
+                if (k != kSpanNoKey)
+                    atomicMin(&key[L[q]], k);
+            }
+        }
+        __syncthreads();  // the minima are in place
+        // The roots decide: reads alone.
+        int under[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            under[q] = kSpanNoComponent;
+            if (L[q] == r) {  // a selected root
+                const SpanKey k = key[r];
+                if (k != kSpanNoKey) {
+                    const int o = span_other(r, words[groups_label_at(span_key_i(k))], words[groups_label_at(span_key_j(k))]);
+                    if (span_hooks(k, key[o], r, o)) {
+                        under[q] = o;
+                        rec[q] = k;
+                    }
+                }
+            }
+        }
+        __syncthreads();  // every root has read
+        int hooked = 0;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            if (under[q] != kSpanNoComponent) {
+                words[groups_label_at(q * T + tid)] = under[q];
+                ++hooked;
+            }
+        }
+        if (hooked)
+            atomicSub(&left, hooked);
+        // Compress: every row reads its root's label, then every row writes, until a pass changes nothing.
+        for (;;) {
+            __syncthreads();  // the hooks, or the pass before, are in place
+            int next[RPL];
+            bool moved = false;
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                next[q] = L[q];
+                if (L[q] != kSpanNoComponent) {
+                    const int now = words[groups_label_at(r)];
+                    next[q] = span_compress(words, now);
+                    moved = moved || next[q] != now;
+                }
+            }
+            const bool again = block_any(moved, flags, tid, T);  // its barriers: every row has read
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                if (L[q] != kSpanNoComponent) {
+                    L[q] = next[q];
+                    words[groups_label_at(r)] = next[q];
+                }
+            }
+            if (!again)
+                break;
+        }
+    }
+    // The sort: the recorded keys into the words, padded with all-ones keys to a power of two, and the image's fourth word
+    // cleared for the degrees.  The last barrier of the rounds stands before this: every lane is done with the labels.
+    const int recorded = selected - left;  // selected - 1 where the rounds ended with one component
+    const int length = span_sort_length(n);
+    for (int r = tid; r < length; r += T)
+        key[r] = kSpanNoKey;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            words[groups_label_at(r)] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        if (rec[q] != kSpanNoKey)
+            key[q * T + tid] = rec[q];
+    }
+    __syncthreads();
+    for (int k = 2; k <= length; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < length / 2; t += T)
+                span_exchange(key, t, k, j);
+            __syncthreads();
+        }
+    }
+    // Slot e holds the e-th edge: its record, its ends' degrees (integer LDS adds) and, in its word, its length.
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int e = q * T + tid;
+        if (e < max_bodies) {
+            const SpanKey k = e < length ? key[e] : kSpanNoKey;
+            const BatchSpanEdge edge = span_edge(k);
+            if (k != kSpanNoKey) {
+                atomicAdd(&words[groups_label_at(edge.i)], 1);
+                atomicAdd(&words[groups_label_at(edge.j)], 1);
+                term[e] = span_length(edge.r2);
+            }
+            if (edges)
+                edges[base + e] = edge;
+        }
+    }
+    __syncthreads();
+    if (bodies) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies)
+                bodies[base + r] = L[q] != kSpanNoComponent ? BatchSpanBody{words[groups_label_at(r)], nearest[q]} : span_empty_body();
+        }
+    }
+    if (tid == 0) {
+        double total = 0.0, longest = 0.0;
+        for (int e = 0; e < recorded; ++e) {
+            longest = term[e];
+            total += longest;
+        }
+        systems[blockIdx.x] = BatchSpanSystem{recorded, selected, rounds, 0, total, longest, span_mean_separation(separation, selected)};
+    }
+}
+
+// One launch over all systems.  24 bytes of dynamic LDS per body at a power-of-two capacity, 96 KiB at 4096 bodies.  subset,
+// edges and bodies may be NULL.
+hipError_t launch_batch_span(const float4 *pos, const int *counts, const unsigned char *subset, int n_systems, int max_bodies,
+                             int separations, BatchSpanEdge *edges, BatchSpanBody *bodies, BatchSpanSystem *systems,
+                             hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_span_kernel<rpl()>, n_systems, sh.threads, span_lds_bytes(max_bodies), stream, pos,
+                                      counts, subset, max_bodies, separations, edges, bodies, systems);
+    });
+}
+
+// ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
+// nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
+constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
+
+// POT = false: momentum and mass only (no pair loop).
+template <bool GUARD, bool POT>
+__global__ __launch_bounds__(kDiagThreads) void batch_diag_kernel(const float4 *pos, const float4 *vel, const int *counts,
+                                                                  int max_bodies, float eps2, double *out)
+{
+    extern __shared__ float4 sp[];
+    __shared__ double red[kDiagValues][kDiagThreads / 64];
+    const int n = counts[blockIdx.x];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    for (int j = tid; j < n; j += kDiagThreads)
+        sp[j] = pos[base + j];
+    __syncthreads();
+    double acc[kDiagValues] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += kDiagThreads) {
+        const float4 pi = sp[i];
+        const float4 w = vel[base + i];
+        double phi = 0.0;
+        for (int j = 0; j < (POT ? n : 0); ++j) {
+            const float4 pj = sp[j];
+            const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, eps2)));
+            float inv = __builtin_amdgcn_rsqf(GUARD ? guard_r2(r2) : r2);
+            inv = j != i ? inv : 0.f;
+            phi += (double)(pj.w * inv);
+        }
+        acc[0] += 0.5 * (double)pi.w * ((double)w.x * w.x + (double)w.y * w.y + (double)w.z * w.z);
+        acc[1] += -0.5 * (double)pi.w * phi;
+        acc[2] += (double)pi.w * w.x;
+        acc[3] += (double)pi.w * w.y;
+        acc[4] += (double)pi.w * w.z;
+        acc[5] += (double)pi.w;
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int c = 0; c < kDiagValues; ++c) {
+        double s = acc[c];
+        for (int off = 32; off > 0; off >>= 1)
+            s += __shfl_down(s, off, 64);
+        if (lane == 0)
+            red[c][wave] = s;
+    }
+    __syncthreads();
+    if (tid < kDiagValues) {
+        double s = 0.0;
+        for (int q = 0; q < kDiagThreads / 64; ++q)
+            s += red[tid][q];
+        out[(size_t)blockIdx.x * kDiagValues + tid] = s;
+    }
+}
+
+hipError_t launch_batch_diag(const float4 *pos, const float4 *vel, const int *counts, int n_systems, int max_bodies,
+                             float eps2, bool potential, double *out, hipStream_t stream)
+{
+    const size_t lds = sizeof(float4) * (size_t)max_bodies;
+    const auto kernel = !potential    ? batch_diag_kernel<false, false>
+                        : eps2 > 0.f ? batch_diag_kernel<false, true> : batch_diag_kernel<true, true>;
+    hipLaunchKernelGGL(kernel, dim3(n_systems), dim3(kDiagThreads), lds, stream, pos, vel, counts, max_bodies, eps2, out);
+    return hipGetLastError();
+}
+
+// ---- what the calls keep on the handle, and the calls (the C ABI) ----------------------------------------------------------
+
+// A device array of T that its owner frees: a pointer and the elements it has room for.
+template <class T>
+struct DeviceArray {
+    T *ptr = nullptr;
+    size_t capacity = 0;
+
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    ~DeviceArray() { release(); }
+
+    // Room for `count` elements: nothing to do while the capacity suffices (0, an output the call was not asked for: always;
+    // a size fixed per handle: after the first call that asked); otherwise a new array in place of the old one, whose contents
+    // no call needs (gravity's rows grow with the call).  A failed allocation leaves no array.
+    hipError_t ensure(size_t count)
+    {
+        if (count <= capacity)
+            return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&ptr, sizeof(T) * count);
+        if (e == hipSuccess)
+            capacity = count;
+        return e;
+    }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        capacity = 0;
+    }
+};
+
+// `count` elements of a device array to the caller's host array, behind the launches on the handle's stream; no `host`, no copy.
+template <class T>
+hipError_t copy_out(const nbody_batch *b, void *host, const DeviceArray<T> &array, size_t count)
+{
+    return host ? hipMemcpyAsync(host, array.ptr, sizeof(T) * count, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
+}
+
+}  // namespace
+
+// What the analysis calls keep on a handle: the records of each call's last launch, allocated by the first call that asks for
+// them, and the host copies that outlive a call.  Nothing forgets them and no integrator reads them.
+struct BatchAnalysis {
+    DeviceArray<BatchPairRecord> pairs;  // [n_systems][max_bodies]
+    DeviceArray<int> pairs_binaries;     // [n_systems]
+    std::vector<int> pairs_binaries_host;  // the last call's, empty before any call (nbody_batch_pairs_binaries)
+    DeviceArray<BatchStructureSystem> structure_systems;  // [n_systems]
+    DeviceArray<BatchStructureBody> structure_bodies;     // [n_systems][max_bodies]
+    DeviceArray<BatchMemberSystem> members_systems;  // [n_systems]
+    DeviceArray<BatchMemberBody> members_bodies;     // [n_systems][max_bodies]
+    DeviceArray<unsigned char> members_initial;      // [n_systems][max_bodies], the device copy of `initial`
+    DeviceArray<BatchHierarchySystem> hierarchy_systems;  // [n_systems]
+    DeviceArray<BatchHierarchyNode> hierarchy_nodes;      // [n_systems][max_bodies]; the kernel reads its own nodes back
+    DeviceArray<BatchHierarchyBody> hierarchy_bodies;     // [n_systems][max_bodies]
+    DeviceArray<BatchGravityRecord> gravity_records;  // one per row of the largest call so far
+    DeviceArray<float> gravity_tidal;                 // kGravityTidalWords per row of the largest call that asked for them
+    DeviceArray<int> gravity_counts;                  // [n_systems], the device copy of the point counts
+    std::vector<int> gravity_counts_host;             // the last call's point counts: the copy's source until the stream is idle
+    DeviceArray<BatchGroupSystem> groups_systems;  // [n_systems]
+    DeviceArray<BatchGroupRecord> groups_records;  // [n_systems][max_bodies]
+    DeviceArray<BatchGroupBody> groups_bodies;     // [n_systems][max_bodies]
+    DeviceArray<float> groups_linking2;            // [n_systems]
+    std::vector<float> groups_linking2_host;       // the last call's b[s] b[s]
+    DeviceArray<BatchSpanSystem> span_systems;  // [n_systems]
+    DeviceArray<BatchSpanEdge> span_edges;      // [n_systems][max_bodies]
+    DeviceArray<BatchSpanBody> span_bodies;     // [n_systems][max_bodies]
+    DeviceArray<unsigned char> span_subset;     // [n_systems][max_bodies], the device copy of `subset`
+};
+
+// Every member frees itself, in one walk that no new array can be left out of.
+void batch_analysis_destroy(nbody_batch *b)
+{
+    delete b->analysis;
+    b->analysis = nullptr;
+}
+
+}  // namespace nbody
+
+using namespace nbody;
+
+// The handle's analysis state in `a`, created by the first analysis call.
+static hipError_t batch_analysis(nbody_batch *b, BatchAnalysis *&a)
+{
+    if (!b->analysis)
+        b->analysis = new (std::nothrow) BatchAnalysis;
+    a = b->analysis;
+    return a ? hipSuccess : hipErrorOutOfMemory;  // which BATCH_TRY returns as NBODY_ERR_ALLOC
+}
+
+extern "C" {
+
+int nbody_batch_pairs(nbody_batch *b, const float *d_pos, const float *d_vel, nbody_batch_pair_record *records_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_pairs: batch is NULL");
+    if (!d_pos || !d_vel || !records_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pairs: NULL argument");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->pairs.ensure(slots));
+    BATCH_TRY(b, a->pairs_binaries.ensure(B));
+    std::vector<int> found;
+    found.assign(B, 0);
+    BATCH_TRY(b, launch_batch_pairs(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                    b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                    a->pairs.ptr, a->pairs_binaries.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, records_out, a->pairs, slots));
+    BATCH_TRY(b, copy_out(b, found.data(), a->pairs_binaries, B));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    a->pairs_binaries_host.swap(found);
+    return NBODY_OK;
+}
+
+int nbody_batch_pairs_binaries(nbody_batch *b, int64_t *count_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_pairs_binaries: batch is NULL");
+    if (!count_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pairs_binaries: NULL argument");
+    if (!b->analysis || b->analysis->pairs_binaries_host.empty())
+        return bfail(b, NBODY_ERR_STATE, "nbody_batch_pairs_binaries: no nbody_batch_pairs call has been made");
+    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
+        count_out[s] = b->analysis->pairs_binaries_host[s];
+    return NBODY_OK;
+}
+
+int nbody_batch_structure(nbody_batch *b, const float *d_pos, int k, int weight, const double *fractions, int n_fractions,
+                          nbody_batch_structure_system *systems_out, nbody_batch_structure_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_structure: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: NULL argument");
+    if (k < 1 || k > NBODY_BATCH_STRUCTURE_MAX_NEIGHBOUR)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: k must be 1 ... 8");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (n_fractions < 0 || n_fractions > NBODY_BATCH_STRUCTURE_FRACTIONS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: n_fractions must be 0 ... 8");
+    if (n_fractions > 0 && !fractions)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: fractions is NULL");
+    BatchStructureArgs p{};
+    p.n_fractions = n_fractions;
+    p.k = k;
+    p.weight = weight;
+    for (int q = 0; q < n_fractions; ++q) {
+        if (!(fractions[q] > 0.0 && fractions[q] <= 1.0))  // NaN is refused too
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_structure: a fraction must be in (0, 1]");
+        p.fraction[q] = fractions[q];
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->structure_systems.ensure(B));
+    BATCH_TRY(b, a->structure_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, launch_batch_structure(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, (int)b->n_systems, (int)b->max_bodies, p,
+                                        bodies_out ? a->structure_bodies.ptr : nullptr, a->structure_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->structure_systems, B));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->structure_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_members(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, int max_iterations,
+                        const unsigned char *initial, nbody_batch_member_system *systems_out, nbody_batch_member_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_members: batch is NULL");
+    if (!d_pos || !d_vel || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: NULL argument");
+    if (max_iterations < 1 || max_iterations > NBODY_BATCH_MEMBERS_MAX_ITERATIONS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: max_iterations must be 1 ... 64");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_members: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->members_systems.ensure(B));
+    BATCH_TRY(b, a->members_bodies.ensure(bodies_out ? slots : 0));
+    if (initial) {
+        BATCH_TRY(b, a->members_initial.ensure(slots));
+        BATCH_TRY(b, hipMemcpyAsync(a->members_initial.ptr, initial, slots, hipMemcpyHostToDevice, b->stream));
+    }
+    BATCH_TRY(b, launch_batch_members(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                      b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                      softening * softening, max_iterations, initial ? a->members_initial.ptr : nullptr,
+                                      bodies_out ? a->members_bodies.ptr : nullptr, a->members_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->members_systems, B));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->members_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_hierarchy(nbody_batch *b, const float *d_pos, const float *d_vel, double tidal_tolerance, int max_levels,
+                          nbody_batch_hierarchy_system *systems_out, nbody_batch_hierarchy_node *nodes_out,
+                          nbody_batch_hierarchy_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_hierarchy: batch is NULL");
+    if (!d_pos || !d_vel || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: NULL argument");
+    if (max_levels < 1 || max_levels > NBODY_BATCH_HIERARCHY_MAX_LEVELS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: max_levels must be 1 ... 16");
+    if (!(tidal_tolerance >= 0.0))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_hierarchy: tidal_tolerance must be >= 0 (+inf accepts every pair), not NaN");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->hierarchy_systems.ensure(B));
+    BATCH_TRY(b, a->hierarchy_nodes.ensure(slots));
+    BATCH_TRY(b, a->hierarchy_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, launch_batch_hierarchy(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                        b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                        tidal_tolerance, max_levels, nodes_out != nullptr, a->hierarchy_nodes.ptr,
+                                        bodies_out ? a->hierarchy_bodies.ptr : nullptr, a->hierarchy_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->hierarchy_systems, B));
+    BATCH_TRY(b, copy_out(b, nodes_out, a->hierarchy_nodes, slots));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->hierarchy_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_gravity(nbody_batch *b, const float *d_pos, const float *d_points, int64_t n_points, const int64_t *host_point_counts,
+                        float softening, nbody_batch_gravity_record *records_out, float *tidal_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_gravity: batch is NULL");
+    if (!d_pos || !records_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: NULL argument");
+    if (!d_points && (n_points != 0 || host_point_counts))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: n_points or host_point_counts given without points (own-bodies mode "
+                                           "takes n_points = 0 and no point counts)");
+    if (d_points && (n_points < 1 || n_points > NBODY_BATCH_GRAVITY_MAX_POINTS))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: n_points must be 1 ... NBODY_BATCH_GRAVITY_MAX_POINTS (1048576)");
+    const size_t B = (size_t)b->n_systems;
+    if (host_point_counts)
+        for (size_t s = 0; s < B; ++s)
+            if (host_point_counts[s] < 0 || host_point_counts[s] > n_points)
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: the point count of system " + std::to_string(s) + " is " +
+                                                       std::to_string(host_point_counts[s]) + ", outside [0, n_points]");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_gravity: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t rows = B * (size_t)(d_points ? n_points : b->max_bodies);
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->gravity_records.ensure(rows));  // these two grow when a call needs more rows
+    BATCH_TRY(b, a->gravity_tidal.ensure(tidal_out ? kGravityTidalWords * rows : 0));
+    if (host_point_counts) {
+        BATCH_TRY(b, a->gravity_counts.ensure(B));
+        a->gravity_counts_host.assign(B, 0);
+        for (size_t s = 0; s < B; ++s)
+            a->gravity_counts_host[s] = (int)host_point_counts[s];
+        BATCH_TRY(b, hipMemcpyAsync(a->gravity_counts.ptr, a->gravity_counts_host.data(), sizeof(int) * B, hipMemcpyHostToDevice,
+                                    b->stream));
+    }
+    BATCH_TRY(b, launch_batch_gravity(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_points), b->counts_dev,
+                                      b->config.massive_set ? b->massive_dev : nullptr,
+                                      host_point_counts ? a->gravity_counts.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies,
+                                      (int)n_points, softening * softening, a->gravity_records.ptr,
+                                      tidal_out ? a->gravity_tidal.ptr : nullptr, b->stream));
+    BATCH_TRY(b, copy_out(b, records_out, a->gravity_records, rows));
+    BATCH_TRY(b, copy_out(b, tidal_out, a->gravity_tidal, kGravityTidalWords * rows));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_groups(nbody_batch *b, const float *d_pos, const float *d_vel, const float *linking_lengths, int min_members,
+                       int weight, int max_sweeps, nbody_batch_group_system *systems_out, nbody_batch_group_record *groups_out,
+                       nbody_batch_group_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_groups: batch is NULL");
+    if (!d_pos || !d_vel || !linking_lengths || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: NULL argument");
+    if (min_members < 1)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: min_members must be >= 1");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (max_sweeps < 1 || max_sweeps > NBODY_BATCH_GROUPS_MAX_SWEEPS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_groups: max_sweeps must be 1 ... 64");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    for (size_t s = 0; s < B; ++s) {
+        if (!std::isfinite(linking_lengths[s]) || linking_lengths[s] < 0.f)
+            return bfail(b, NBODY_ERR_INVALID,
+                         "nbody_batch_groups: the linking length of system " + std::to_string(s) + " must be finite and >= 0");
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->groups_linking2_host.assign(linking_lengths, linking_lengths + B);
+    for (float &l : a->groups_linking2_host)
+        l = l * l;  // b2: one fp32 product
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->groups_systems.ensure(B));
+    BATCH_TRY(b, a->groups_linking2.ensure(B));
+    BATCH_TRY(b, a->groups_records.ensure(groups_out ? slots : 0));
+    BATCH_TRY(b, a->groups_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, hipMemcpyAsync(a->groups_linking2.ptr, a->groups_linking2_host.data(), sizeof(float) * B, hipMemcpyHostToDevice,
+                                b->stream));
+    BATCH_TRY(b, launch_batch_groups(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                     b->config.massive_set ? b->massive_dev : nullptr, a->groups_linking2.ptr, (int)b->n_systems,
+                                     (int)b->max_bodies, min_members, weight, max_sweeps, bodies_out ? a->groups_bodies.ptr : nullptr,
+                                     groups_out ? a->groups_records.ptr : nullptr, a->groups_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->groups_systems, B));
+    BATCH_TRY(b, copy_out(b, groups_out, a->groups_records, slots));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->groups_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_span(nbody_batch *b, const float *d_pos, const unsigned char *subset, int separations,
+                     nbody_batch_span_system *systems_out, nbody_batch_span_edge *edges_out, nbody_batch_span_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_span: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_span: NULL argument");
+    if (separations != 0 && separations != 1)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_span: separations must be 0 or 1");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->span_systems.ensure(B));
+    BATCH_TRY(b, a->span_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->span_edges.ensure(edges_out ? slots : 0));
+    BATCH_TRY(b, a->span_bodies.ensure(bodies_out ? slots : 0));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->span_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_span(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, subset ? a->span_subset.ptr : nullptr,
+                                   (int)b->n_systems, (int)b->max_bodies, separations, edges_out ? a->span_edges.ptr : nullptr,
+                                   bodies_out ? a->span_bodies.ptr : nullptr, a->span_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->span_systems, B));
+    BATCH_TRY(b, copy_out(b, edges_out, a->span_edges, slots));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->span_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+static int batch_diag(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, bool potential)
+{
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, launch_batch_diag(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
+                                   (int)b->n_systems, (int)b->max_bodies, softening * softening, potential, b->diag_dev, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(b->diag_host.data(), b->diag_dev, sizeof(double) * b->diag_host.size(), hipMemcpyDeviceToHost,
+                                b->stream));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_energy(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, double *out3B)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_energy: batch is NULL");
+    if (!d_pos || !d_vel || !out3B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: NULL argument");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_energy: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    const int rc = batch_diag(b, d_pos, d_vel, softening, true);
+    if (rc != NBODY_OK)
+        return rc;
+    for (int64_t s = 0; s < b->n_systems; ++s) {
+        const double *d = &b->diag_host[(size_t)s * kDiagValues];
+        out3B[3 * s] = d[0];
+        out3B[3 * s + 1] = d[1];
+        out3B[3 * s + 2] = d[0] + d[1];
+    }
+    return NBODY_OK;
+}
+
+int nbody_batch_momentum(nbody_batch *b, const float *d_pos, const float *d_vel, double *out4B)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_momentum: batch is NULL");
+    if (!d_pos || !d_vel || !out4B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_momentum: NULL argument");
+    const int rc = batch_diag(b, d_pos, d_vel, 1.f, false);
+    if (rc != NBODY_OK)
+        return rc;
+    for (int64_t s = 0; s < b->n_systems; ++s)
+        for (int c = 0; c < 4; ++c)
+            out4B[4 * s + c] = b->diag_host[(size_t)s * kDiagValues + 2 + c];
+    return NBODY_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // nbody_batch_gravity_math.h -- the arithmetic of nbody_batch_gravity (include/nbody_batch_gravity.h) that needs no GPU: the
 // record and the empty record, the pair term of one row from one source with its tidal products, the sums of a row, and the
-// launch plan for P rows.  Plain C++17 without HIP, like nbody_batch_members_math.h: batch_gravity_kernel (nbody_batch.hip)
+// launch plan for P rows.  Plain C++17 without HIP, like nbody_batch_members_math.h: batch_gravity_kernel (nbody_batch_analysis.hip)
 // forms every pair and every sum through these functions, and a stand-alone driver (tests/batch_gravity_driver.cpp) calls them
 // on the CPU, where tests/test_batch_gravity_cpu.py checks hand-picked rows and the plan.  On the device the reciprocal square
 // root is v_rsq_f32; on the host it is 1 / sqrtf.  Internal; the public surface is include/nbody_batch_gravity.h.
@@ -23,7 +23,7 @@ namespace nbody {
 constexpr int64_t kGravityMaxPoints = 1048576;  // NBODY_BATCH_GRAVITY_MAX_POINTS
 constexpr int kGravityTidalWords = 6;           // {xx, xy, xz, yy, yz, zz}
 
-// nbody_batch_gravity_record's layout (nbody_batch.hip asserts it): 24 bytes.
+// nbody_batch_gravity_record's layout (nbody_batch_analysis.hip asserts it): 24 bytes.
 struct BatchGravityRecord {
     float acceleration[3], reserved;
     double potential;

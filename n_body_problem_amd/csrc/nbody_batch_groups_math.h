@@ -1,7 +1,7 @@
 // nbody_batch_groups_math.h -- the arithmetic of nbody_batch_groups (include/nbody_batch_groups.h) that needs no GPU: the
 // three records and their empty values, the link predicate, the Link, Hook and Compress steps of one row on an array of
 // labels, the fp64 sums of one group and the system summary.  Plain C++17 without HIP, like nbody_batch_members_math.h:
-// batch_groups_kernel (nbody_batch.hip) calls these per row with the labels in LDS, and a stand-alone driver
+// batch_groups_kernel (nbody_batch_analysis.hip) calls these per row with the labels in LDS, and a stand-alone driver
 // (tests/batch_groups_driver.cpp) runs whole systems through the same functions in sequential loops on the CPU, where
 // tests/test_batch_groups_cpu.py compares them with a union-find.  Internal; the public surface is
 // include/nbody_batch_groups.h.
@@ -25,18 +25,18 @@ constexpr int kGroupsWeightMass = 0, kGroupsWeightNumber = 1;  // NBODY_BATCH_WE
 constexpr int kGroupsWords = 4, kGroupsLabelWord = 3;
 NBODY_HD inline int groups_label_at(int j) { return kGroupsWords * j + kGroupsLabelWord; }
 
-// nbody_batch_group_body's layout (nbody_batch.hip asserts it): 8 bytes.
+// nbody_batch_group_body's layout (nbody_batch_analysis.hip asserts it): 8 bytes.
 struct BatchGroupBody {
     int group, size;
 };
 
-// nbody_batch_group_record's layout (nbody_batch.hip asserts it): 64 bytes.
+// nbody_batch_group_record's layout (nbody_batch_analysis.hip asserts it): 64 bytes.
 struct BatchGroupRecord {
     double weight, centre[3], velocity[3];
     int count, sources;
 };
 
-// nbody_batch_group_system's layout (nbody_batch.hip asserts it): 32 bytes.
+// nbody_batch_group_system's layout (nbody_batch_analysis.hip asserts it): 32 bytes.
 struct BatchGroupSystem {
     int groups, grouped, singles, largest, largest_count, sweeps, converged, reserved;
 };

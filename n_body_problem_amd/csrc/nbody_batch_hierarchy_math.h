@@ -2,7 +2,7 @@
 // GPU: the three records and their empty values, the merged state of a new node (nbody_batch_merge.h's arithmetic), the
 // pair's elements and angular momentum (nbody_batch_pairs_elements.h's formulas), the perturbation scaling, the mutual
 // inclination and the Mardling & Aarseth stability comparison.  Plain C++17 without HIP, like nbody_batch_members_math.h:
-// batch_hierarchy_kernel (nbody_batch.hip) calls it once per candidate pair, and a stand-alone driver
+// batch_hierarchy_kernel (nbody_batch_analysis.hip) calls it once per candidate pair, and a stand-alone driver
 // (tests/batch_hierarchy_driver.cpp) calls it on the CPU, where tests/test_batch_hierarchy_cpu.py checks it against closed
 // forms.  Internal; the public surface is include/nbody_batch_hierarchy.h.
 #pragma once
@@ -16,7 +16,7 @@ namespace nbody {
 
 constexpr int kHierarchyMaxLevels = 16;  // NBODY_BATCH_HIERARCHY_MAX_LEVELS
 
-// nbody_batch_hierarchy_node's layout (nbody_batch.hip asserts it): 128 bytes.
+// nbody_batch_hierarchy_node's layout (nbody_batch_analysis.hip asserts it): 128 bytes.
 struct BatchHierarchyNode {
     int child[2], parent, level, leaves, slot, stable, reserved;
     double mass, energy, semi_major_axis, eccentricity, inclination, separation, perturbation, mutual_inclination[2], h[3];

@@ -1,7 +1,7 @@
 // nbody_batch_members_math.h -- the arithmetic of nbody_batch_members (include/nbody_batch_members.h) that needs no GPU: the
 // two records, the empty records, and the fp64 energy and decision of one row from its fp32 velocity, the frame's fp64
 // velocity and the row's fp64 potential.  Plain C++17 without HIP, like nbody_batch_structure_math.h: batch_members_kernel
-// (nbody_batch.hip) calls it per row and iteration, and a stand-alone driver (tests/batch_members_driver.cpp) calls it on the
+// (nbody_batch_analysis.hip) calls it per row and iteration, and a stand-alone driver (tests/batch_members_driver.cpp) calls it on the
 // CPU, where tests/test_batch_members_cpu.py checks hand-picked rows.  Internal; the public surface is
 // include/nbody_batch_members.h.
 #pragma once
@@ -18,13 +18,13 @@ namespace nbody {
 
 constexpr int kMembersMaxIterations = 64;  // NBODY_BATCH_MEMBERS_MAX_ITERATIONS
 
-// nbody_batch_member_body's layout (nbody_batch.hip asserts it): 24 bytes.
+// nbody_batch_member_body's layout (nbody_batch_analysis.hip asserts it): 24 bytes.
 struct BatchMemberBody {
     double potential, energy;
     int member, removed_at;
 };
 
-// nbody_batch_member_system's layout (nbody_batch.hip asserts it): 88 bytes.
+// nbody_batch_member_system's layout (nbody_batch_analysis.hip asserts it): 88 bytes.
 struct BatchMemberSystem {
     double bound_mass, centre[3], velocity[3], kinetic, potential;
     int members, sources, iterations, converged;

@@ -1,6 +1,6 @@
 // nbody_batch_pairs_elements.h -- the fp64 record of one pair of nbody_batch_pairs (include/nbody_batch_pairs.h, "The
 // record"): differences, mu -> energy, semi-major axis, eccentricity, inclination and separation, with the header's special
-// cases.  Plain C++17 without HIP, like nbody_sym_plan.h: batch_pairs_kernel (nbody_batch.hip) calls it once per row, and a
+// cases.  Plain C++17 without HIP, like nbody_sym_plan.h: batch_pairs_kernel (nbody_batch_analysis.hip) calls it once per row, and a
 // stand-alone driver (tests/batch_pairs_driver.cpp) calls it on the CPU, where tests/test_batch_pairs_cpu.py checks it against
 // closed forms.  Internal; the public surface is include/nbody_batch_pairs.h.
 #pragma once
@@ -18,7 +18,7 @@
 
 namespace nbody {
 
-// nbody_batch_pair_record's layout (nbody_batch.hip asserts it): 48 bytes.
+// nbody_batch_pair_record's layout (nbody_batch_analysis.hip asserts it): 48 bytes.
 struct BatchPairRecord {
     int partner, mutual;
     double energy, semi_major_axis, eccentricity, inclination, separation;

@@ -2,7 +2,7 @@
 // records and their empty values, the 64-bit key of an edge and its fields, the step of one row over one column, the decision
 // of one component given its own minimum and the other's, one Compress pass, the compare-exchange of the sort, and the length
 // and separation terms.  Plain C++17 without HIP, like nbody_batch_groups_math.h, whose r2 and image layout it reuses:
-// batch_span_kernel (nbody_batch.hip) calls these per row with the image in LDS, and a stand-alone driver
+// batch_span_kernel (nbody_batch_analysis.hip) calls these per row with the image in LDS, and a stand-alone driver
 // (tests/batch_span_driver.cpp) runs whole systems through the same functions in sequential loops on the CPU, where
 // tests/test_batch_span_cpu.py compares them with Prim's algorithm.  Internal; the public surface is
 // include/nbody_batch_span.h.
@@ -14,20 +14,20 @@ namespace nbody {
 
 constexpr int kSpanMaxRounds = 13;  // NBODY_BATCH_SPAN_MAX_ROUNDS
 
-// nbody_batch_span_system's layout (nbody_batch.hip asserts it): 40 bytes.
+// nbody_batch_span_system's layout (nbody_batch_analysis.hip asserts it): 40 bytes.
 struct BatchSpanSystem {
     int edges, selected, rounds, reserved;
     double total_length, longest, mean_separation;
 };
 
-// nbody_batch_span_edge's layout (nbody_batch.hip asserts it): 16 bytes.
+// nbody_batch_span_edge's layout (nbody_batch_analysis.hip asserts it): 16 bytes.
 struct BatchSpanEdge {
     int i, j;
     float r2;
     int reserved;
 };
 
-// nbody_batch_span_body's layout (nbody_batch.hip asserts it): 8 bytes.
+// nbody_batch_span_body's layout (nbody_batch_analysis.hip asserts it): 8 bytes.
 struct BatchSpanBody {
     int degree, nearest;
 };

@@ -1,7 +1,7 @@
 // nbody_batch_structure_math.h -- the arithmetic of nbody_batch_structure (include/nbody_batch_structure.h) that needs no GPU:
 // the two records, the sorted list of a row's eight smallest squared distances, the k-th of it, and the density of one body
 // from its k-th distance and neighbour weight.  Plain C++17 without HIP, like nbody_batch_pairs_elements.h:
-// batch_structure_kernel (nbody_batch.hip) calls it per pair and per row, and a stand-alone driver
+// batch_structure_kernel (nbody_batch_analysis.hip) calls it per pair and per row, and a stand-alone driver
 // (tests/batch_structure_driver.cpp) calls it on the CPU, where tests/test_batch_structure_cpu.py checks it against std::sort
 // and the formula.  Internal; the public surface is include/nbody_batch_structure.h.
 #pragma once
@@ -22,14 +22,14 @@ constexpr int kStructureMaxNeighbour = 8;  // NBODY_BATCH_STRUCTURE_MAX_NEIGHBOU
 constexpr int kStructureFractions = 8;     // NBODY_BATCH_STRUCTURE_FRACTIONS
 constexpr double kFourPiOverThree = 4.1887902047863909846;
 
-// nbody_batch_structure_body's layout (nbody_batch.hip asserts it): 40 bytes.
+// nbody_batch_structure_body's layout (nbody_batch_analysis.hip asserts it): 40 bytes.
 struct BatchStructureBody {
     double density, radius, enclosed;
     float neighbour_r2, neighbour_weight;
     int inside, reserved;
 };
 
-// nbody_batch_structure_system's layout (nbody_batch.hip asserts it): 120 bytes.
+// nbody_batch_structure_system's layout (nbody_batch_analysis.hip asserts it): 120 bytes.
 struct BatchStructureSystem {
     double centre[3], core_radius, core_density, total_weight;
     double lagrange[kStructureFractions];

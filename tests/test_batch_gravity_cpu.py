@@ -174,7 +174,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     assert any(os.path.basename(h) == "nbody_batch_gravity.h" for h in build.HEADERS)
     text = open(os.path.join(CSRC, "nbody_batch_gravity_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and "1.f / sqrtf(r2)" in text
-    hip = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    hip = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     assert '#include "nbody_batch_gravity_math.h"' in hip
     # the kernel forms its pairs, sums, rows and empty records with the header's functions, not with copies of them
     kernel = hip[hip.index("void batch_gravity_kernel("):hip.index("hipError_t launch_batch_gravity(")]
@@ -184,7 +184,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     launcher = hip[hip.index("hipError_t launch_batch_gravity("):hip.index("// ---- hierarchies")]
     assert "gravity_plan_own(" in launcher and "gravity_plan_points(" in launcher and "gravity_lds_bytes(" in launcher
     # batch_forces has the callers it had: the step kernels and their massive siblings
-    assert len(re.findall(r"\bbatch_forces<", hip)) == 6
+    assert len(re.findall(r"\bbatch_forces<", open(os.path.join(CSRC, "nbody_batch.hip")).read())) == 6
 
 
 # ---- the arithmetic and the plan, through the driver ------------------------------------------------------------------------

@@ -221,7 +221,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     text = open(os.path.join(CSRC, "nbody_batch_groups_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and "return r2 <= b2;" in text
     assert "__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx))" in text
-    hip = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    hip = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     assert '#include "nbody_batch_groups_math.h"' in hip
     # the kernel links, hooks, compresses and sums with the header's functions, not with copies of them
     kernel = hip[hip.index("void batch_groups_kernel("):hip.index("hipError_t launch_batch_groups(")]

@@ -203,7 +203,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     text = open(os.path.join(CSRC, "nbody_batch_hierarchy_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and '#include "nbody_batch_pairs_elements.h"' in text
     assert "batch_pair_record(" in text                       # the elements are the pairs header's, not a copy
-    hip = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    hip = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     assert '#include "nbody_batch_hierarchy_math.h"' in hip
     kernel = hip[hip.index("void batch_hierarchy_kernel("):hip.index("hipError_t launch_batch_hierarchy(")]
     for call in ("hierarchy_elements(", "hierarchy_merged(", "hierarchy_perturbation(", "hierarchy_accepts(",

@@ -196,7 +196,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     assert any(os.path.basename(h) == "nbody_batch_members.h" for h in build.HEADERS)
     text = open(os.path.join(CSRC, "nbody_batch_members_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and "member && energy < 0.0" in text
-    hip = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    hip = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     assert '#include "nbody_batch_members_math.h"' in hip
     # the kernel decides with the header's functions, not with copies of them
     kernel = hip[hip.index("void batch_members_kernel("):hip.index("hipError_t launch_batch_members(")]

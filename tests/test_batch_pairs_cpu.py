@@ -155,7 +155,7 @@ def test_the_elements_header_is_a_build_dependency_and_free_of_hip():
     assert any(os.path.basename(h) == "nbody_batch_pairs.h" for h in build.HEADERS)
     text = open(os.path.join(CSRC, "nbody_batch_pairs_elements.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text
-    assert '#include "nbody_batch_pairs_elements.h"' in open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    assert '#include "nbody_batch_pairs_elements.h"' in open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
 
 
 # ---- the elements, through the driver -------------------------------------------------------------------------------------

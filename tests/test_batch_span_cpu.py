@@ -136,7 +136,7 @@ def test_the_abi_stays_at_version_5_and_the_errors_of_the_header_are_refused_wit
     out = (_lib.BatchSpanSystem * 1)()
     assert lib.nbody_batch_span(None, None, None, 0, out, None, None) == _lib.NBODY_ERR_INVALID
     assert b"nbody_batch_span: batch is NULL" in lib.nbody_batch_last_error(None)
-    source = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    source = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     body = source[source.index("int nbody_batch_span("):]
     body = body[:body.index("\n}\n")]
     for message in ("nbody_batch_span: batch is NULL", "nbody_batch_span: NULL argument",
@@ -151,10 +151,10 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip_a
     text = open(os.path.join(CSRC, "nbody_batch_span_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and '#include "nbody_batch_groups_math.h"' in text
     assert "groups_r2(" in text and "fmaf" not in text.replace("fmaf(dz", "")       # the chain is reused, not restated
-    kernel = open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    kernel = open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
     kernel = kernel[kernel.index("void batch_span_kernel("):kernel.index("hipError_t launch_batch_span(")]
     for call in ("span_step(", "span_row_key(", "span_other(", "span_hooks(", "span_compress(", "span_exchange(", "span_edge(",
-                 "span_length(", "span_separation(", "span_mean_separation(", "groups_block_any(", "atomicMin(&key["):
+                 "span_length(", "span_separation(", "span_mean_separation(", "block_any(", "atomicMin(&key["):
         assert call in kernel, call
 
 

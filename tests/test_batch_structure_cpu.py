@@ -193,7 +193,7 @@ def test_the_headers_are_build_dependencies_and_the_math_header_is_free_of_hip()
     text = open(os.path.join(CSRC, "nbody_batch_structure_math.h")).read()
     assert "hip/" not in text and "NBODY_HD inline" in text and "4.1887902047863909846" in text
     assert "lo = fminf(a[t], c)" in text and "c = fmaxf(a[t], c)" in text and "a[t] = lo" in text
-    assert '#include "nbody_batch_structure_math.h"' in open(os.path.join(CSRC, "nbody_batch.hip")).read()
+    assert '#include "nbody_batch_structure_math.h"' in open(os.path.join(CSRC, "nbody_batch_analysis.hip")).read()
 
 
 # ---- the arithmetic, through the driver ------------------------------------------------------------------------------------
