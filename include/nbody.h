@@ -458,8 +458,8 @@ nbody_ctx *nbody_multi_shard(nbody_multi *m, int local_index);
 float *nbody_multi_positions_device(nbody_multi *m, int local_index);
 float *nbody_multi_velocities_device(nbody_multi *m, int local_index);
 
-/* ======== batched ensembles: many independent small systems, one launch (csrc/nbody_batch.hip, nbody_batch_analysis.hip)
- * ========
+/* ======== batched ensembles: many independent small systems, one launch (csrc/nbody_batch.hip, nbody_batch_capi.hip,
+ * nbody_batch_analysis.hip) ========
  * Everything above steps ONE system.  Below NBODY_BATCH_MAX_BODIES bodies one system cannot fill the GPU -- a 256- or
  * 4096-body step is ~0.02 ms of almost pure launch overhead -- while ensemble users (realisations of a cluster, parameter
  * sweeps, stability surveys, training data) want many such systems.  A nbody_batch steps B independent systems of up to

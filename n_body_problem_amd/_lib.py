@@ -121,7 +121,7 @@ _PROTOTYPES = {
     "nbody_multi_shard": (c_void_p, [c_void_p, c_int]),
     "nbody_multi_positions_device": (c_void_p, [c_void_p, c_int]),
     "nbody_multi_velocities_device": (c_void_p, [c_void_p, c_int]),
-    # batched ensembles (csrc/nbody_batch.hip, csrc/nbody_batch_analysis.hip)
+    # batched ensembles (csrc/nbody_batch_capi.hip over csrc/nbody_batch.hip, csrc/nbody_batch_analysis.hip)
     "nbody_batch_create": (c_int, [POINTER(c_void_p), c_int, c_int64, c_int64]),
     "nbody_batch_destroy": (c_int, [c_void_p]),
     "nbody_batch_last_error": (c_char_p, [c_void_p]),

@@ -1,5 +1,6 @@
 """Batched ensembles: many independent small systems stepped together, one launch per call (``nbody_batch_*`` of
-``include/nbody.h``, kernels in ``csrc/nbody_batch.hip`` and ``csrc/nbody_batch_analysis.hip``).
+``include/nbody.h``, kernels in ``csrc/nbody_batch.hip`` and ``csrc/nbody_batch_analysis.hip``, the integrators' host code in
+``csrc/nbody_batch_capi.hip``).
 
 One :class:`NBodySystem` below a few thousand bodies cannot fill the GPU: its step is ~0.02 ms of launch overhead.  A
 :class:`BatchedSystem` holds ``B`` systems of up to ``max_bodies`` (at most :data:`BATCH_MAX_BODIES`) bodies each -- system

@@ -12,15 +12,11 @@
 // The update is update_kernel's: v <- (float)fma((double)a, (double)dt, (double)v), x <- (float)fma((double)v, ...).
 // Hermite (NBODY_INTEGRATOR_HERMITE) runs a sibling kernel, batch_hermite_kernel: the same order, with the jerk summed
 // beside the acceleration and a fourth-order predict-evaluate-correct step (see there).
-// Here: the integrators and the handle's C ABI.  What a state can be asked (pairs ... spanning trees, energy, momentum) is in
-// nbody_batch_analysis.hip; both see the handle through nbody_batch_handle.h.
-#include "nbody_batch_handle.h"
-#include "nbody_batch_radii_check.h"
+// Here: the integrators' kernels and their launchers.  The host code behind their C ABI is in nbody_batch_capi.hip, which
+// reaches them through nbody_batch_launch.h; what a state can be asked (pairs ... spanning trees, energy, momentum) is in
+// nbody_batch_analysis.hip.
+#include "nbody_batch_launch.h"
 #include "nbody_kernels.h"
-
-#include <algorithm>
-#include <cmath>
-#include <cstring>
 
 namespace nbody {
 namespace {
@@ -29,20 +25,7 @@ static_assert(NBODY_BATCH_MAX_BODIES == 4096, "LDS per workgroup: 64 KiB of posi
                                               "CU's 160 KiB), 128 KiB of positions and velocities for the Hermite families");
 static_assert(sizeof(float4) == kBatchBytesPerBody, "nbody_batch_choice.h counts the dynamic LDS in float4");
 
-// What the launches of a call share: the choice, the systems, the stream, the caller's state and the handle's arrays (those a
-// family does not read may be null).
-struct BatchLaunch {
-    BatchChoice choice;
-    int n_systems, max_bodies;
-    hipStream_t stream;
-    float4 *pos, *vel, *acc, *jerk;
-    int *counts;
-    const int *massive;
-    BatchEvolveState *state;
-    int *counters;
-    BatchStopReport *report;
-    const BatchFieldTerm *field;  // nbody_batch_field.h: [n_systems][4], null while no field is set
-};
+// BatchLaunch, what the launches of a call share: nbody_batch_launch.h.
 
 // One launch of a batch kernel, one workgroup per system, with the choice's workgroup and dynamic LDS.  The Hermite families
 // raise their limit first: above the default 64 KiB of dynamic LDS from 2049 bodies on (128 KiB at 4096).
@@ -300,11 +283,7 @@ __device__ __forceinline__ void hermite_correct(float &x, float &v, float a0, fl
     v = v1;
 }
 
-// Stopping conditions (include/nbody_batch_stop.h) as the kernels take them, formed once on the host in fp32.
-struct BatchStopArgs {
-    float thr;  // a pair collides when its r^2 + eps^2 <= thr = fma(R_c, R_c, eps^2); -1: never
-    float re2;  // a body has escaped when |x|^2 > re2 = R_e R_e; +inf: never
-};
+// BatchStopArgs, the stopping conditions as the kernels take them: nbody_batch_launch.h.
 constexpr int kStopCollision = 1, kStopEscape = 2;
 
 // What the wave found in one row per lane, wave-uniform: kStopCollision when a row r < n (valid) saw a second column within
@@ -462,21 +441,7 @@ hipError_t launch_batch_hermite(const BatchLaunch &l, int k, float dt, float eps
 
 // BatchEvolveState, per system in HBM between launches and calls: nbody_batch_handle.h, whose handle keeps a host copy.
 
-struct BatchEvolveArgs {
-    // dt_max and what every step needs of it, formed once on the host in fp64: a level only scales them by a power of two,
-    // which is exact, so h / 3, 1 / h^2 ... are the values the division would give for h = dt_max 2^-L
-    double dt, dt_half, dt_third, dt_sixth, dt_six;  // dt_max, dt_max / 2, dt_max / 3, dt_max / 6, 6 dt_max
-    double dt2, inv_dt2, inv_dt3;                     // dt_max^2, 1 / dt_max^2, 1 / dt_max^3
-    double eta, eta_start2;  // eta_start^2
-    long long target, max_steps;
-    float eps2;
-    int levels, budget;  // steps per launch at most
-    int have_acc, have_level;
-    int new_call;    // first launch of a call: the call's counters start at 0
-    int reset_tick;  // ... and the tick too (not when the call resumes one that ran out of steps)
-};
-
-constexpr int kEvolveNoLevel = 1 << 30;
+// BatchEvolveArgs, dt_max and what every step needs of it: nbody_batch_launch.h.  kEvolveNoLevel: nbody_batch_handle.h.
 
 // A value every lane holds, moved to scalar registers: the step constants must not cost vector registers.  The empty asm
 // statement pins the result there (the compiler otherwise folds the readfirstlane of a value it knows to be uniform and
@@ -986,12 +951,7 @@ __global__ __launch_bounds__(1024) void batch_hermite_stop_kernel(float4 *pos, f
 
 // ---- mergers (include/nbody_batch_merge.h): a system whose bodies collide merges the pair and carries its run on.
 
-// Per launch: the systems' merger counts and logs (events: [n_systems][capacity], nullptr for capacity 0).
-struct BatchMergeArgs {
-    int *merges;
-    nbody_batch_merge_event *events;
-    int capacity;
-};
+// BatchMergeArgs, per launch the systems' merger counts and logs: nbody_batch_launch.h.
 
 // One component of the merged body: fp64 from the fp32 operands, rounded once; M = (double)m_i + (double)m_j.
 __device__ __forceinline__ float merge_mean(float mi, float ui, float mj, float uj, double M)
@@ -1297,11 +1257,7 @@ hipError_t launch_batch_merge(const BatchLaunch &l, const BatchEvolveArgs &p, co
 
 // ---- per-body radii (include/nbody_batch_radii.h): a pair collides when it is within the sum of its own two radii.
 
-// Per launch: the radii ([n_systems][max_bodies], laid out like the positions) and the collision action, workgroup-uniform.
-struct BatchRadiiArgs {
-    float *radii;
-    int merge;  // NBODY_BATCH_ON_COLLISION_MERGE: merge the pair and carry on; otherwise stop and report
-};
+// BatchRadiiArgs, per launch the radii and the collision action: nbody_batch_launch.h.
 
 // hermite_evaluate<.., CORRECT = false, STOP = true> and hermite_evaluate_request<.., STOP = true> with radii: siblings, so
 // that those stay the code they are for the kernels above.  The same row groups; a row's radius is read with its predicted
@@ -2529,16 +2485,8 @@ __global__ __launch_bounds__(256) void batch_field_potential_kernel(const float4
 // A test particle that touches a massive body or leaves the escape radius is removed -- frozen, with a fate -- and its system
 // carries on; a collision among the massive bodies or a massive escaper stops the system as batch_hermite_stop_kernel does.
 
-// Per launch.  One kernel serves both kinds of radius: a shared R_c rides as the radius R_c / 2 of every body, whose fp32 sum
-// is R_c exactly, so the threshold is fmaf(R_c, R_c, eps^2) as nbody_batch_stop.h states it.  The fates (BatchFate,
-// nbody_batch_handle.h) are laid out like the positions; all zero: alive.
+// BatchFateArgs, per launch; one kernel serves both kinds of radius: nbody_batch_launch.h.
 constexpr int kFateHit = 1, kFateEscaped = 2;
-struct BatchFateArgs {
-    float *radii;        // [n_systems][max_bodies], or nullptr: every body has the radius half_rc (written by accretion only)
-    float half_rc;
-    int collide;         // a collision radius or radii are set (otherwise the column loop's masks are dropped)
-    BatchFate *fates;    // one pointer: the kernel's scalar registers are all taken
-};
 
 // The cold path of a tracer that is removed, by its own lane only: the massive body of smallest r^2 + eps^2 among those
 // within the pair's threshold (ties to the smallest index: the scan ascends and replaces on less-than only), with the
@@ -2871,11 +2819,7 @@ hipError_t launch_batch_fate(const BatchLaunch &l, const BatchEvolveArgs &p, con
 
 // ---- accreting tracers (include/nbody_batch_accrete.h): a tracer that hits a massive body gives it its mass word.
 
-// Per launch: the mass each tracer gave ([n_systems][max_bodies], laid out like the positions) and the systems' accretions.
-struct BatchAccreteArgs {
-    float *given;
-    int *accretions;
-};
+// BatchAccreteArgs, per launch what each tracer gave and the systems' accretions: nbody_batch_launch.h.
 constexpr int kFoundHit = 4;        // beside kStopCollision | kStopEscape in the waves' findings: a tracer hit at this evaluation
 constexpr int kAccreteWords = NBODY_BATCH_MAX_BODIES / 32;  // a bit per row
 
@@ -3136,130 +3080,10 @@ hipError_t launch_batch_accrete(const BatchLaunch &l, const BatchEvolveArgs &p, 
 }
 
 }  // namespace
-}  // namespace nbody
 
-using namespace nbody;
+// ---- the entry points (nbody_batch_launch.h) -------------------------------------------------------------------------------
 
-// ---- the C ABI (the analysis calls: nbody_batch_analysis.hip; the handle: nbody_batch_handle.h) ---------------------------
-
-static thread_local std::string g_batch_create_error;
-
-int nbody::bfail(nbody_batch *b, int status, const std::string &msg)
-{
-    if (b)
-        b->err = msg;
-    else
-        g_batch_create_error = msg;
-    return status;
-}
-
-// The caches are forgotten, and with them the levels (nbody_batch_evolve_on sees to those) and the stops.
-static void forget_caches(nbody_batch *b)
-{
-    b->acc_valid = false;
-    b->stop_forgotten = true;
-}
-
-// nbody_batch_evolve_on's buffers: the caches and the per-system state, and what the mode keeps beside them -- merger counts and
-// logs, stop reports, fates, accretions -- allocated on first use and zeroed where the stops count as forgotten.
-static int evolve_prepare_buffers(nbody_batch *b, const BatchMode &mode)
-{
-    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
-    if (!b->acc)
-        BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
-    if (!b->jerk)
-        BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
-    if (!b->evolve_state) {
-        BATCH_TRY(b, hipMalloc((void **)&b->evolve_state, sizeof(BatchEvolveState) * B));
-        BATCH_TRY(b, hipMemsetAsync(b->evolve_state, 0, sizeof(BatchEvolveState) * B, b->stream));
-    }
-    if (!b->evolve_counters)
-        BATCH_TRY(b, hipMalloc((void **)&b->evolve_counters, 2 * sizeof(int)));
-    if (mode.merging) {  // nbody_batch_merge.h: counts and logs that start from zero where the reports do
-        if (!b->merge_count) {
-            BATCH_TRY(b, hipMalloc((void **)&b->merge_count, sizeof(int) * B));
-            b->stop_forgotten = true;
-        }
-        if (b->merge_capacity > 0 && !b->merge_log) {
-            BATCH_TRY(b, hipMalloc((void **)&b->merge_log, sizeof(nbody_batch_merge_event) * B * (size_t)b->merge_capacity));
-            b->stop_forgotten = true;
-        }
-        if (b->stop_forgotten)
-            BATCH_TRY(b, hipMemsetAsync(b->merge_count, 0, sizeof(int) * B, b->stream));
-    }
-    if (mode.stopping) {  // nbody_batch_stop.h: reports that start from zero
-        if (!b->stop_report) {
-            BATCH_TRY(b, hipMalloc((void **)&b->stop_report, sizeof(BatchStopReport) * B));
-            b->stop_forgotten = true;
-        }
-        if (b->stop_forgotten)
-            BATCH_TRY(b, hipMemsetAsync(b->stop_report, 0, sizeof(BatchStopReport) * B, b->stream));
-        if (b->stop_forgotten && mode.fates)  // nbody_batch_fate.h: the fates are forgotten where the stops are
-            BATCH_TRY(b, hipMemsetAsync(b->fates, 0, sizeof(BatchFate) * slots, b->stream));
-        if (b->stop_forgotten && mode.accreting) {  // nbody_batch_accrete.h: zeroed exactly where the fates are
-            BATCH_TRY(b, hipMemsetAsync(b->given, 0, sizeof(float) * slots, b->stream));
-            BATCH_TRY(b, hipMemsetAsync(b->accretions, 0, sizeof(int) * B, b->stream));
-        }
-        b->stop_forgotten = false;
-    }
-    return NBODY_OK;
-}
-
-// What one nbody_batch_evolve_on call hands its kernel; p's have_acc, have_level, new_call and reset_tick change per launch.
-struct BatchEvolveLaunch {
-    BatchEvolveArgs p;
-    BatchStopArgs sa;
-    BatchMergeArgs ma;
-    BatchRadiiArgs ra;
-    BatchFateArgs fa;
-    BatchAccreteArgs aa;
-};
-
-// The arguments from the handle's settings and the call's (after evolve_prepare_buffers: they carry its pointers).
-static BatchEvolveLaunch evolve_launch_args(const nbody_batch *b, const BatchMode &mode, const nbody_batch_evolve_config *cfg,
-                                            int64_t target, int64_t max_steps)
-{
-    const BatchConfig &c = b->config;
-    BatchEvolveLaunch a;
-    BatchEvolveArgs &p = a.p;
-    p.dt = (double)cfg->dt_max;
-    p.dt_half = 0.5 * p.dt;
-    p.dt_six = 6.0 * p.dt;
-    p.dt_third = p.dt / 3.0;
-    p.dt_sixth = p.dt / 6.0;
-    p.dt2 = p.dt * p.dt;
-    p.inv_dt2 = 1.0 / (p.dt * p.dt);
-    p.inv_dt3 = 1.0 / (p.dt * p.dt * p.dt);
-    p.eta = (double)cfg->eta;
-    p.eta_start2 = (double)cfg->eta_start * (double)cfg->eta_start;
-    p.target = target;
-    p.max_steps = max_steps;
-    p.eps2 = cfg->softening * cfg->softening;
-    p.levels = cfg->levels;
-    p.budget = b->evolve_launch_steps;
-    // stopping conditions (nbody_batch_stop.h): the thresholds in fp32; radii (nbody_batch_radii.h) watch collisions without one
-    a.sa = BatchStopArgs{-1.f, __builtin_inff()};
-    if (c.collision_radius > 0.f)
-        a.sa.thr = std::fmaf(c.collision_radius, c.collision_radius, cfg->softening * cfg->softening);
-    if (c.escape_radius > 0.f)
-        a.sa.re2 = c.escape_radius * c.escape_radius;
-    a.ma = BatchMergeArgs{b->merge_count, b->merge_log, b->merge_capacity};
-    a.ra = BatchRadiiArgs{b->radii, mode.merging ? 1 : 0};
-    a.fa = BatchFateArgs{c.radii_set ? b->radii : nullptr, 0.5f * c.collision_radius, mode.collisions ? 1 : 0, b->fates};
-    a.aa = BatchAccreteArgs{b->given, b->accretions};
-    return a;
-}
-
-// What every launch of a call on these buffers shares.
-static BatchLaunch batch_launch(const nbody_batch *b, const BatchChoice &choice, float *d_pos, float *d_vel)
-{
-    return BatchLaunch{choice, (int)b->n_systems, (int)b->max_bodies, b->stream, reinterpret_cast<float4 *>(d_pos),
-                       reinterpret_cast<float4 *>(d_vel), b->acc, b->jerk, b->counts_dev, b->massive_dev, b->evolve_state,
-                       b->evolve_counters, b->stop_report, b->field_dev};
-}
-
-// One launch of nbody_batch_evolve_on by the chosen family.
-static hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLaunch &a)
+hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLaunch &a)
 {
     if (l.choice.field)  // nbody_batch_field.h: the two families without conditions, through their sibling with the field
         return l.choice.kernel == BatchKernel::adaptive_massive || l.choice.kernel == BatchKernel::adaptive
@@ -3277,8 +3101,7 @@ static hipError_t launch_batch_evolve(const BatchLaunch &l, const BatchEvolveLau
     }
 }
 
-// One launch of nbody_batch_step_n_async by the chosen family: `run` steps of every system.  Kick-drift keeps no accelerations.
-static hipError_t launch_batch_steps(const BatchLaunch &l, bool kdk, int run, float dt, float eps2, bool acc_valid)
+hipError_t launch_batch_steps(const BatchLaunch &l, bool kdk, int run, float dt, float eps2, bool acc_valid)
 {
     switch (l.choice.kernel) {
     case BatchKernel::hermite_massive: return launch_batch_hermite_massive(l, run, dt, eps2, acc_valid ? 1 : 0);
@@ -3289,716 +3112,13 @@ static hipError_t launch_batch_steps(const BatchLaunch &l, bool kdk, int run, fl
     }
 }
 
-extern "C" {
-
-int nbody_batch_create(nbody_batch **out, int device, int64_t n_systems, int64_t max_bodies)
+// One thread per slot, a row of workgroups per system.
+hipError_t launch_batch_field_potential(const float4 *pos, const int *counts, const nbody_batch_field_component *comps,
+                                        int n_components, int n_systems, int max_bodies, double *phi, hipStream_t stream)
 {
-    if (!out)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: out is NULL");
-    *out = nullptr;
-    if (n_systems <= 0 || n_systems > ((int64_t)1 << 30))
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: n_systems out of range [1, 2^30]");
-    if (max_bodies <= 0 || max_bodies > NBODY_BATCH_MAX_BODIES)
-        return bfail(nullptr, NBODY_ERR_INVALID,
-                     "nbody_batch_create: max_bodies out of range [1, NBODY_BATCH_MAX_BODIES = 4096] (larger systems: nbody_create)");
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-        return bfail(nullptr, NBODY_ERR_NO_DEVICE,
-                     std::string("nbody_batch_create: no HIP device (") + hipGetErrorString(e) + "); this library has no CPU path");
-    if (device < 0 || device >= ndev)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_create: device index out of range");
-    BATCH_TRY(nullptr, hipSetDevice(device));
-    hipDeviceProp_t prop;
-    BATCH_TRY(nullptr, hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return bfail(nullptr, NBODY_ERR_NO_DEVICE,
-                     std::string("nbody_batch_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    nbody_batch *b = new (std::nothrow) nbody_batch;
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_ALLOC, "nbody_batch_create: host allocation failed");
-    b->device = device;
-    b->n_systems = n_systems;
-    b->max_bodies = max_bodies;
-    b->counts.assign((size_t)n_systems, (int)max_bodies);
-    b->diag_host.resize((size_t)n_systems * kDiagValues);
-    hipError_t he = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
-    if (he == hipSuccess)
-        he = hipMalloc((void **)&b->counts_dev, sizeof(int) * (size_t)n_systems);
-    if (he == hipSuccess)
-        he = hipMalloc((void **)&b->diag_dev, sizeof(double) * b->diag_host.size());
-    if (he == hipSuccess)
-        he = hipMemcpy(b->counts_dev, b->counts.data(), sizeof(int) * (size_t)n_systems, hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        const int rc = bfail(nullptr, he == hipErrorOutOfMemory ? NBODY_ERR_ALLOC : NBODY_ERR_DEVICE,
-                             std::string("nbody_batch_create: ") + hipGetErrorString(he));
-        nbody_batch_destroy(b);
-        return rc;
-    }
-    b->stream = b->own_stream;
-    *out = b;
-    return NBODY_OK;
+    hipLaunchKernelGGL(batch_field_potential_kernel, dim3((unsigned)((max_bodies + 255) / 256), (unsigned)n_systems), dim3(256), 0,
+                       stream, pos, counts, comps, n_components, max_bodies, phi);
+    return hipGetLastError();
 }
 
-int nbody_batch_destroy(nbody_batch *b)
-{
-    if (!b)
-        return NBODY_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream)
-        (void)hipStreamSynchronize(b->stream);
-    if (b->own_stream && b->own_stream != b->stream)
-        (void)hipStreamSynchronize(b->own_stream);
-    batch_analysis_destroy(b);  // nbody_batch_analysis.hip: what the analysis calls keep
-    if (b->counts_dev) (void)hipFree(b->counts_dev);
-    if (b->acc) (void)hipFree(b->acc);
-    if (b->jerk) (void)hipFree(b->jerk);
-    if (b->evolve_state) (void)hipFree(b->evolve_state);
-    if (b->evolve_counters) (void)hipFree(b->evolve_counters);
-    if (b->stop_report) (void)hipFree(b->stop_report);
-    if (b->merge_count) (void)hipFree(b->merge_count);
-    if (b->merge_log) (void)hipFree(b->merge_log);
-    if (b->radii) (void)hipFree(b->radii);
-    if (b->massive_dev) (void)hipFree(b->massive_dev);
-    if (b->fates) (void)hipFree(b->fates);
-    if (b->given) (void)hipFree(b->given);
-    if (b->accretions) (void)hipFree(b->accretions);
-    if (b->field_dev) (void)hipFree(b->field_dev);
-    if (b->field_raw_dev) (void)hipFree(b->field_raw_dev);
-    if (b->diag_dev) (void)hipFree(b->diag_dev);
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
-    delete b;
-    return NBODY_OK;
-}
-
-const char *nbody_batch_last_error(const nbody_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
-
-int nbody_batch_set_counts(nbody_batch *b, const int64_t *host_counts)
-{
-    if (!b || !host_counts)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_counts: NULL argument");
-    for (int64_t s = 0; s < b->n_systems; ++s)
-        if (host_counts[s] < 0 || host_counts[s] > b->max_bodies)
-            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_counts: count of system " + std::to_string(s) + " (" +
-                                                   std::to_string(host_counts[s]) + ") outside [0, max_bodies = " +
-                                                   std::to_string(b->max_bodies) + "]");
-    for (int64_t s = 0; s < b->n_systems; ++s)
-        b->counts[(size_t)s] = (int)host_counts[s];
-    BATCH_TRY(b, hipSetDevice(b->device));
-    BATCH_TRY(b, hipMemcpyAsync(b->counts_dev, b->counts.data(), sizeof(int) * b->counts.size(), hipMemcpyHostToDevice, b->stream));
-    BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
-    forget_caches(b);
-    return NBODY_OK;
-}
-
-int nbody_batch_set_integrator(nbody_batch *b, int integrator)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_integrator: batch is NULL");
-    if (integrator != NBODY_INTEGRATOR_KICK_DRIFT && integrator != NBODY_INTEGRATOR_KDK && integrator != NBODY_INTEGRATOR_HERMITE)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_set_integrator: unknown integrator (KICK_DRIFT = 0, KDK = 1, HERMITE = 2)");
-    if (integrator != b->config.integrator)
-        forget_caches(b);
-    b->config.integrator = integrator;
-    return NBODY_OK;
-}
-
-int nbody_batch_invalidate_forces(nbody_batch *b)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_invalidate_forces: batch is NULL");
-    forget_caches(b);
-    return NBODY_OK;
-}
-
-int nbody_batch_set_stream(nbody_batch *b, void *hip_stream)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_set_stream: batch is NULL");
-    b->stream = (hipStream_t)hip_stream;  // verbatim: NULL is the HIP default stream
-    return NBODY_OK;
-}
-
-int nbody_batch_step_n_async(nbody_batch *b, float *d_pos, float *d_vel, int k, float dt, float softening)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_step_n: batch is NULL");
-    if (!d_pos || !d_vel)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: NULL buffer");
-    if (k < 0)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: k < 0");
-    if (!std::isfinite(dt))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: dt must be finite");
-    if (!batch_softening_ok(softening))
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_step_n: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9): "
-                                           "0 < softening < 1e-9 would overflow fp32 (eps^-3 x mass of the self pair)");
-    const BatchChoice choice = batch_step_choice(b->config, (int)b->max_bodies, softening);
-    if (choice.refusal != BatchRefusal::none)  // nbody_batch_field.h: no fixed-step kernel takes a field
-        return bfail(b, batch_refusal_status(choice.refusal), batch_refusal_message(choice.refusal));
-    if (k == 0)
-        return NBODY_OK;
-    if (b->evolve_pending && b->acc_valid && b->config.integrator == NBODY_INTEGRATOR_HERMITE)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_step_n: the last nbody_batch_evolve_on ran out of steps and its systems sit at "
-                                         "different times: complete it, or nbody_batch_invalidate_forces to drop it");
-    b->level_valid = false;  // fixed steps leave the levels behind, and the stops
-    b->stop_forgotten = true;
-    BATCH_TRY(b, hipSetDevice(b->device));
-    const bool kdk = b->config.integrator == NBODY_INTEGRATOR_KDK, hermite = b->config.integrator == NBODY_INTEGRATOR_HERMITE;
-    const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
-    if (kdk || hermite) {
-        if (!b->acc)
-            BATCH_TRY(b, hipMalloc((void **)&b->acc, sizeof(float4) * slots));
-        if (hermite && !b->jerk)
-            BATCH_TRY(b, hipMalloc((void **)&b->jerk, sizeof(float4) * slots));
-        // KDK's accelerations come without jerks: a cache is used only by the integrator that filled it
-        if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != softening || b->acc_integrator != b->config.integrator)
-            b->acc_valid = false;
-    }
-    const BatchLaunch launch = batch_launch(b, choice, d_pos, d_vel);
-    const float eps2 = softening * softening;
-    for (int done = 0; done < k; done += kBatchStepsPerLaunch) {
-        const int run = std::min(kBatchStepsPerLaunch, k - done);
-        BATCH_TRY(b, launch_batch_steps(launch, kdk, run, dt, eps2, b->acc_valid));
-        if (kdk || hermite) {
-            b->acc_integrator = b->config.integrator;
-            b->acc_valid = true;
-            b->acc_pos = d_pos;
-            b->acc_vel = d_vel;
-            b->acc_softening = softening;
-        }
-    }
-    return NBODY_OK;
-}
-
-int nbody_batch_sync(nbody_batch *b)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_sync: batch is NULL");
-    BATCH_TRY(b, hipSetDevice(b->device));
-    BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    BATCH_TRY(b, hipGetLastError());
-    return NBODY_OK;
-}
-
-int nbody_batch_step_n_on(nbody_batch *b, float *d_pos, float *d_vel, int k, float dt, float softening)
-{
-    const int rc = nbody_batch_step_n_async(b, d_pos, d_vel, k, dt, softening);
-    return rc != NBODY_OK ? rc : nbody_batch_sync(b);
-}
-
-int nbody_batch_evolve_launch_steps(nbody_batch *b, int steps_per_launch)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve_launch_steps: batch is NULL");
-    if (steps_per_launch < 1 || steps_per_launch > 4096)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve_launch_steps: steps_per_launch outside [1, 4096]");
-    b->evolve_launch_steps = steps_per_launch;
-    return NBODY_OK;
-}
-
-int nbody_batch_evolve_on(nbody_batch *b, float *d_pos, float *d_vel, int64_t n_intervals, const nbody_batch_evolve_config *cfg)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve: batch is NULL");
-    if (!d_pos || !d_vel || !cfg)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: NULL argument");
-    const BatchMode mode = batch_mode(b->config);
-    const BatchChoice choice = batch_evolve_choice(b->config, (int)b->max_bodies, cfg->softening);
-    if (choice.refusal != BatchRefusal::none)
-        return bfail(b, batch_refusal_status(choice.refusal), batch_refusal_message(choice.refusal));
-    if (const char *msg = batch_evolve_args_error(cfg->levels, n_intervals, cfg->dt_max, cfg->eta, cfg->eta_start, cfg->softening))
-        return bfail(b, NBODY_ERR_INVALID, msg);
-    const int64_t max_steps = cfg->max_steps > 0 ? cfg->max_steps : NBODY_BATCH_EVOLVE_DEFAULT_MAX_STEPS;
-    const int64_t target = n_intervals << cfg->levels;
-    if (b->acc_pos != d_pos || b->acc_vel != d_vel || b->acc_softening != cfg->softening || b->acc_integrator != b->config.integrator)
-        b->acc_valid = false;
-    if (!b->acc_valid) {
-        b->level_valid = b->evolve_pending = false;
-        b->stop_forgotten = true;
-    }
-    const bool same_axis = b->level_valid && b->level_dt_max == cfg->dt_max && b->level_levels == cfg->levels;
-    const bool resume = b->evolve_pending;
-    if (resume) {
-        if (!same_axis)
-            return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: the last call ran out of steps; complete it with the same dt_max and "
-                                             "levels, or nbody_batch_invalidate_forces to drop it");
-        for (int64_t s = 0; s < b->n_systems; ++s)
-            if (b->counts[(size_t)s] > 0 && b->evolve_host[(size_t)s].tick > target)
-                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_evolve: n_intervals ends before the time system " + std::to_string(s) +
-                                                       " reached in the call this one resumes");
-    }
-    const size_t B = (size_t)b->n_systems;
-    if (b->evolve_host.size() != B)
-        b->evolve_host.assign(B, BatchEvolveState{0, 0, 0, 0, kEvolveNoLevel, -1, 0});
-    if (!resume)
-        for (BatchEvolveState &st : b->evolve_host)
-            st = BatchEvolveState{0, 0, 0, 0, kEvolveNoLevel, -1, 0};
-    b->evolve_target = target;
-    if (target == 0)
-        return NBODY_OK;
-    BATCH_TRY(b, hipSetDevice(b->device));
-    if (const int rc = evolve_prepare_buffers(b, mode); rc != NBODY_OK)
-        return rc;
-    const BatchLaunch launch = batch_launch(b, choice, d_pos, d_vel);
-    BatchEvolveLaunch args = evolve_launch_args(b, mode, cfg, target, max_steps);
-    BatchEvolveArgs &p = args.p;
-    int counters[2] = {0, 0};
-    for (bool first = true;; first = false) {
-        p.have_acc = b->acc_valid ? 1 : 0;
-        p.have_level = !first || same_axis ? 1 : 0;
-        p.new_call = first ? 1 : 0;
-        p.reset_tick = first && !resume ? 1 : 0;
-        BATCH_TRY(b, hipMemsetAsync(b->evolve_counters, 0, sizeof(counters), b->stream));
-        BATCH_TRY(b, launch_batch_evolve(launch, args));
-        b->acc_integrator = b->config.integrator;
-        b->acc_valid = b->level_valid = true;
-        b->acc_pos = d_pos;
-        b->acc_vel = d_vel;
-        b->acc_softening = cfg->softening;
-        b->level_dt_max = cfg->dt_max;
-        b->level_levels = cfg->levels;
-        b->evolve_pending = true;  // until every system is seen at the target
-        BATCH_TRY(b, hipMemcpyAsync(counters, b->evolve_counters, sizeof(counters), hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-        if (counters[0] == 0 || counters[0] == counters[1])
-            break;
-    }
-    if (mode.merging)  // the kernel's own changes of the counts; the caches stay: the restarts have refilled them
-        BATCH_TRY(b, hipMemcpyAsync(b->counts.data(), b->counts_dev, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
-    BATCH_TRY(b, hipMemcpyAsync(b->evolve_host.data(), b->evolve_state, sizeof(BatchEvolveState) * B, hipMemcpyDeviceToHost, b->stream));
-    BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    for (size_t s = 0; s < B; ++s)
-        if (b->counts[s] <= 0)
-            b->evolve_host[s] = BatchEvolveState{target, 0, 0, 0, kEvolveNoLevel, -1, 0};
-    if (counters[0] == 0) {
-        b->evolve_pending = false;
-        return NBODY_OK;
-    }
-    std::vector<BatchStopReport> stopped(mode.stopping ? B : 0);  // a stopped system sits before the target too, finished
-    if (mode.stopping) {
-        BATCH_TRY(b, hipMemcpyAsync(stopped.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    size_t first_unfinished = 0;
-    while (first_unfinished < B && (b->evolve_host[first_unfinished].tick >= target || (mode.stopping && stopped[first_unfinished].reason)))
-        ++first_unfinished;
-    return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve: system " + std::to_string(first_unfinished) + " is unfinished after max_steps = " +
-                                         std::to_string(max_steps) + " steps (tick " +
-                                         std::to_string(first_unfinished < B ? b->evolve_host[first_unfinished].tick : 0) + " of " +
-                                         std::to_string(target) + "); " + std::to_string(counters[0]) + " of " + std::to_string(B) +
-                                         " systems are unfinished; the same call again continues from here");
-}
-
-int nbody_batch_evolve_stats(nbody_batch *b, int64_t *steps, int *min_level, int *max_level, int64_t *clamped, int64_t *ticks)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_evolve_stats: batch is NULL");
-    if (b->evolve_host.size() != (size_t)b->n_systems)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_evolve_stats: no nbody_batch_evolve_on call yet");
-    for (size_t s = 0; s < b->evolve_host.size(); ++s) {
-        const BatchEvolveState &st = b->evolve_host[s];
-        if (steps) steps[s] = st.steps;
-        if (min_level) min_level[s] = st.steps > 0 ? st.min_level : 0;
-        if (max_level) max_level[s] = st.steps > 0 ? st.max_level : 0;
-        if (clamped) clamped[s] = st.clamped;
-        if (ticks) ticks[s] = st.tick;
-    }
-    return NBODY_OK;
-}
-
-int nbody_batch_stop_set(nbody_batch *b, const nbody_batch_stop_config *cfg)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_set: batch is NULL");
-    const float rc = cfg ? cfg->collision_radius : 0.f, re = cfg ? cfg->escape_radius : 0.f;
-    if (!std::isfinite(rc) || rc < 0.f || !std::isfinite(re) || re < 0.f)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_stop_set: collision_radius and escape_radius must be finite and >= 0 (0: off)");
-    b->config.collision_radius = rc;
-    b->config.escape_radius = re;
-    forget_caches(b);  // the next nbody_batch_evolve_on starts with an evaluation, which examines the conditions
-    return NBODY_OK;
-}
-
-int nbody_batch_stop_read(nbody_batch *b, int *reason, int64_t *tick, int *pair_i, int *pair_j, float *separation, int *escaper)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_read: batch is NULL");
-    const size_t B = (size_t)b->n_systems;
-    std::vector<BatchStopReport> rep(B, BatchStopReport{0, 0, 0, 0, 0, 0.f, 0});
-    if (batch_mode(b->config).stopping && b->stop_report && !b->stop_forgotten) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        BATCH_TRY(b, hipMemcpyAsync(rep.data(), b->stop_report, sizeof(BatchStopReport) * B, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    for (size_t s = 0; s < B; ++s) {
-        const BatchStopReport r = b->counts[s] > 0 ? rep[s] : BatchStopReport{0, 0, 0, 0, 0, 0.f, 0};
-        if (reason) reason[s] = r.reason;
-        if (tick) tick[s] = r.tick;
-        if (pair_i) pair_i[s] = r.pair_i;
-        if (pair_j) pair_j[s] = r.pair_j;
-        if (separation) separation[s] = r.separation;
-        if (escaper) escaper[s] = r.escaper;
-    }
-    return NBODY_OK;
-}
-
-int nbody_batch_stop_count(nbody_batch *b, int64_t *stopped)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_stop_count: batch is NULL");
-    if (!stopped)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_stop_count: NULL argument");
-    std::vector<int> reason((size_t)b->n_systems);
-    const int rc = nbody_batch_stop_read(b, reason.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (rc != NBODY_OK)
-        return rc;
-    *stopped = 0;
-    for (int r : reason)
-        *stopped += r != 0;
-    return NBODY_OK;
-}
-
-int nbody_batch_merge_set(nbody_batch *b, const nbody_batch_merge_config *cfg)
-{
-    const int action = cfg ? cfg->on_collision : NBODY_BATCH_ON_COLLISION_STOP, capacity = cfg ? cfg->log_capacity : 0;
-    if (action != NBODY_BATCH_ON_COLLISION_STOP && action != NBODY_BATCH_ON_COLLISION_MERGE)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_merge_set: unknown collision action (STOP = 0, MERGE = 1)");
-    if (capacity < 0 || capacity > NBODY_BATCH_MAX_BODIES - 1)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_merge_set: log_capacity outside [0, NBODY_BATCH_MAX_BODIES - 1 = 4095]");
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_set: batch is NULL");
-    if (capacity != b->merge_capacity && b->merge_log) {  // allocated anew by the next evolve that merges
-        BATCH_TRY(b, hipSetDevice(b->device));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-        BATCH_TRY(b, hipFree(b->merge_log));
-        b->merge_log = nullptr;
-    }
-    b->config.collision_action = action;
-    b->merge_capacity = capacity;
-    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
-    return NBODY_OK;
-}
-
-int nbody_batch_merge_read(nbody_batch *b, int64_t *n_merges, nbody_batch_merge_event *events)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_merge_read: batch is NULL");
-    const size_t B = (size_t)b->n_systems, cap = (size_t)b->merge_capacity;
-    std::vector<int> count(B, 0);
-    const bool kept = batch_mode(b->config).merging && b->merge_count && !b->stop_forgotten;
-    if (events)
-        std::memset(events, 0, sizeof(nbody_batch_merge_event) * B * cap);
-    if (kept) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        BATCH_TRY(b, hipMemcpyAsync(count.data(), b->merge_count, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-        if (events && cap > 0 && b->merge_log) {
-            std::vector<nbody_batch_merge_event> log(B * cap);
-            BATCH_TRY(b, hipMemcpyAsync(log.data(), b->merge_log, sizeof(nbody_batch_merge_event) * B * cap, hipMemcpyDeviceToHost, b->stream));
-            BATCH_TRY(b, hipStreamSynchronize(b->stream));
-            for (size_t s = 0; s < B; ++s)  // entries beyond a system's count were never written
-                for (size_t e = 0; e < cap && e < (size_t)count[s]; ++e)
-                    events[s * cap + e] = log[s * cap + e];
-        }
-    }
-    if (n_merges)
-        for (size_t s = 0; s < B; ++s)
-            n_merges[s] = count[s];
-    return NBODY_OK;
-}
-
-int nbody_batch_radii_set(nbody_batch *b, const float *host_radii)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radii_set: batch is NULL");
-    if (host_radii) {
-        std::string msg;
-        if (!batch_radii_ok(host_radii, b->counts.data(), b->n_systems, b->max_bodies, &msg))
-            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radii_set: " + msg);
-        const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
-        BATCH_TRY(b, hipSetDevice(b->device));
-        if (!b->radii)
-            BATCH_TRY(b, hipMalloc((void **)&b->radii, sizeof(float) * slots));
-        BATCH_TRY(b, hipMemcpyAsync(b->radii, host_radii, sizeof(float) * slots, hipMemcpyHostToDevice, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the caller's array may change with the next call
-    }
-    b->config.radii_set = host_radii != nullptr;
-    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
-    return NBODY_OK;
-}
-
-int nbody_batch_radii_read(nbody_batch *b, float *host_radii)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radii_read: batch is NULL");
-    if (!host_radii)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radii_read: NULL argument");
-    if (!b->config.radii_set)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_radii_read: no radii are set (nbody_batch_radii_set)");
-    BATCH_TRY(b, hipSetDevice(b->device));
-    BATCH_TRY(b, hipMemcpyAsync(host_radii, b->radii, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies,
-                                hipMemcpyDeviceToHost, b->stream));
-    BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    return NBODY_OK;
-}
-
-int nbody_batch_massive_set(nbody_batch *b, const int64_t *host_massive)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_massive_set: batch is NULL");
-    if (host_massive) {
-        for (int64_t s = 0; s < b->n_systems; ++s)
-            if (host_massive[s] < 0 || host_massive[s] > b->max_bodies)
-                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_massive_set: massive count of system " + std::to_string(s) + " (" +
-                                                       std::to_string(host_massive[s]) + ") outside [0, max_bodies = " +
-                                                       std::to_string(b->max_bodies) + "]");
-        b->massive.resize((size_t)b->n_systems);
-        for (int64_t s = 0; s < b->n_systems; ++s)
-            b->massive[(size_t)s] = (int)host_massive[s];
-        BATCH_TRY(b, hipSetDevice(b->device));
-        if (!b->massive_dev)
-            BATCH_TRY(b, hipMalloc((void **)&b->massive_dev, sizeof(int) * b->massive.size()));
-        BATCH_TRY(b, hipMemcpyAsync(b->massive_dev, b->massive.data(), sizeof(int) * b->massive.size(), hipMemcpyHostToDevice, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copy may change with the next call
-    }
-    b->config.massive_set = host_massive != nullptr;
-    forget_caches(b);  // as nbody_batch_set_counts: the cached accelerations and jerks belong to the old columns
-    return NBODY_OK;
-}
-
-int nbody_batch_massive_read(nbody_batch *b, int64_t *host_massive)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_massive_read: batch is NULL");
-    if (!host_massive)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_massive_read: NULL argument");
-    if (!b->config.massive_set)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_massive_read: no massive counts are set (nbody_batch_massive_set)");
-    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
-        host_massive[s] = b->massive[s];
-    return NBODY_OK;
-}
-
-int nbody_batch_fate_set(nbody_batch *b, const nbody_batch_fate_config *cfg)
-{
-    const int action = cfg ? cfg->action : NBODY_BATCH_TRACERS_REFUSE;
-    if (action != NBODY_BATCH_TRACERS_REFUSE && action != NBODY_BATCH_TRACERS_REMOVE)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_fate_set: unknown tracer action (REFUSE = 0, REMOVE = 1)");
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_set: batch is NULL");
-    if (action == NBODY_BATCH_TRACERS_REMOVE && !b->fates) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        BATCH_TRY(b, hipMalloc((void **)&b->fates, sizeof(BatchFate) * (size_t)b->n_systems * (size_t)b->max_bodies));
-    }
-    b->config.tracer_action = action;
-    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
-    return NBODY_OK;
-}
-
-// Whether the fate arrays hold what the last nbody_batch_evolve_on calls found (otherwise every body reads alive).  Asked under
-// the tracer action REMOVE only: nbody_batch_fate_read refuses REFUSE first.
-static bool fates_kept(const nbody_batch *b)
-{
-    return batch_mode(b->config).fates && b->fates && !b->stop_forgotten;
-}
-
-int nbody_batch_fate_read(nbody_batch *b, int *fate, int64_t *tick, int *target, float *separation, float *relative_speed)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_read: batch is NULL");
-    if (b->config.tracer_action != NBODY_BATCH_TRACERS_REMOVE)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_read: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
-    const size_t B = (size_t)b->n_systems, cap = (size_t)b->max_bodies, slots = B * cap;
-    std::vector<BatchFate> f(slots, BatchFate{0, 0, 0, 0.f, 0.f});
-    if (fates_kept(b)) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        BATCH_TRY(b, hipMemcpyAsync(f.data(), b->fates, sizeof(BatchFate) * slots, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    for (size_t s = 0; s < B; ++s)
-        for (size_t i = 0; i < cap; ++i) {
-            const size_t k = s * cap + i;
-            const bool gone = (int64_t)i < (int64_t)b->counts[s] && f[k].fate != 0;  // alive, massive or beyond the count: 0, 0, -1, 0, 0
-            if (fate) fate[k] = gone ? f[k].fate : NBODY_BATCH_FATE_ALIVE;
-            if (tick) tick[k] = gone ? f[k].tick : 0;
-            if (target) target[k] = gone ? f[k].target : -1;
-            if (separation) separation[k] = gone ? f[k].separation : 0.f;
-            if (relative_speed) relative_speed[k] = gone ? f[k].speed : 0.f;
-        }
-    return NBODY_OK;
-}
-
-int nbody_batch_fate_count(nbody_batch *b, int64_t *hit, int64_t *escaped)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_fate_count: batch is NULL");
-    if (b->config.tracer_action != NBODY_BATCH_TRACERS_REMOVE)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_fate_count: the tracer action is REFUSE (nbody_batch_fate_set): no fates are kept");
-    std::vector<int> fate((size_t)b->n_systems * (size_t)b->max_bodies);
-    const int rc = nbody_batch_fate_read(b, fate.data(), nullptr, nullptr, nullptr, nullptr);
-    if (rc != NBODY_OK)
-        return rc;
-    for (size_t s = 0; s < (size_t)b->n_systems; ++s) {
-        int64_t h = 0, e = 0;
-        for (size_t i = 0; i < (size_t)b->max_bodies; ++i) {
-            h += fate[s * (size_t)b->max_bodies + i] == NBODY_BATCH_FATE_HIT;
-            e += fate[s * (size_t)b->max_bodies + i] == NBODY_BATCH_FATE_ESCAPED;
-        }
-        if (hit) hit[s] = h;
-        if (escaped) escaped[s] = e;
-    }
-    return NBODY_OK;
-}
-
-int nbody_batch_accrete_set(nbody_batch *b, const nbody_batch_accrete_config *cfg)
-{
-    const int on_hit = cfg ? cfg->on_hit : NBODY_BATCH_ON_HIT_REMOVE;
-    if (on_hit != NBODY_BATCH_ON_HIT_REMOVE && on_hit != NBODY_BATCH_ON_HIT_ACCRETE)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_accrete_set: unknown hit action (REMOVE = 0, ACCRETE = 1)");
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_accrete_set: batch is NULL (refused as an unknown hit action is)");
-    if (on_hit == NBODY_BATCH_ON_HIT_ACCRETE && (!b->given || !b->accretions)) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        if (!b->given)
-            BATCH_TRY(b, hipMalloc((void **)&b->given, sizeof(float) * (size_t)b->n_systems * (size_t)b->max_bodies));
-        if (!b->accretions)
-            BATCH_TRY(b, hipMalloc((void **)&b->accretions, sizeof(int) * (size_t)b->n_systems));
-    }
-    b->config.hit_action = on_hit;
-    forget_caches(b);  // as nbody_batch_stop_set: the next nbody_batch_evolve_on starts with an evaluation
-    return NBODY_OK;
-}
-
-int nbody_batch_accrete_read(nbody_batch *b, float *given, int64_t *accretions)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_accrete_read: batch is NULL");
-    if (b->config.hit_action != NBODY_BATCH_ON_HIT_ACCRETE)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_accrete_read: the hit action is REMOVE (nbody_batch_accrete_set): no accretions are kept");
-    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
-    // kept: the arrays hold what the last nbody_batch_evolve_on calls found; otherwise nobody gave anything
-    const bool kept = batch_mode(b->config).accreting && b->given && b->accretions && !b->stop_forgotten;
-    std::vector<int> count(B, 0);
-    if (given)
-        std::fill(given, given + slots, 0.f);
-    if (kept) {
-        BATCH_TRY(b, hipSetDevice(b->device));
-        if (given)
-            BATCH_TRY(b, hipMemcpyAsync(given, b->given, sizeof(float) * slots, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipMemcpyAsync(count.data(), b->accretions, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    if (accretions)
-        for (size_t s = 0; s < B; ++s)
-            accretions[s] = count[s];
-    return NBODY_OK;
-}
-
-// What the kernels take of one component (BatchFieldTerm): the squares and 1 / (q q) in fp32, formed here once.
-static BatchFieldTerm field_term(const nbody_batch_field_component &u)
-{
-    switch (u.kind) {
-    case NBODY_BATCH_FIELD_PLUMMER: return BatchFieldTerm{u.kind, u.p[0], u.p[1] * u.p[1], 0.f};
-    case NBODY_BATCH_FIELD_LOG_HALO: return BatchFieldTerm{u.kind, u.p[0] * u.p[0], u.p[1] * u.p[1], 1.f / (u.p[2] * u.p[2])};
-    case NBODY_BATCH_FIELD_MIYAMOTO_NAGAI: return BatchFieldTerm{u.kind, u.p[0], u.p[1], u.p[2] * u.p[2]};
-    default: return BatchFieldTerm{NBODY_BATCH_FIELD_NONE, 0.f, 0.f, 0.f};
-    }
-}
-
-int nbody_batch_field_set(nbody_batch *b, const nbody_batch_field_component *host, int n_components)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_set: batch is NULL");
-    if (host) {
-        if (n_components < 1 || n_components > NBODY_BATCH_FIELD_MAX_COMPONENTS)
-            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_set: n_components (" + std::to_string(n_components) +
-                                                   ") outside [1, NBODY_BATCH_FIELD_MAX_COMPONENTS = 4]");
-        const size_t B = (size_t)b->n_systems, C = (size_t)n_components;
-        for (size_t s = 0; s < B; ++s)
-            for (size_t c = 0; c < C; ++c) {
-                const nbody_batch_field_component &u = host[s * C + c];
-                if (const char *msg = batch_field_component_error(u.kind, u.p))
-                    return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_set: system " + std::to_string(s) + ", component " +
-                                                           std::to_string(c) + " (kind " + std::to_string(u.kind) + ", p = " +
-                                                           std::to_string(u.p[0]) + ", " + std::to_string(u.p[1]) + ", " +
-                                                           std::to_string(u.p[2]) + "): " + msg);
-            }
-        // padded to four components per system with NONE, for the kernels and for the potential
-        std::vector<BatchFieldTerm> terms(B * NBODY_BATCH_FIELD_MAX_COMPONENTS, BatchFieldTerm{NBODY_BATCH_FIELD_NONE, 0.f, 0.f, 0.f});
-        std::vector<nbody_batch_field_component> raw(B * NBODY_BATCH_FIELD_MAX_COMPONENTS,
-                                                     nbody_batch_field_component{NBODY_BATCH_FIELD_NONE, {0.f, 0.f, 0.f}});
-        for (size_t s = 0; s < B; ++s)
-            for (size_t c = 0; c < C; ++c) {
-                terms[s * NBODY_BATCH_FIELD_MAX_COMPONENTS + c] = field_term(host[s * C + c]);
-                raw[s * NBODY_BATCH_FIELD_MAX_COMPONENTS + c] = host[s * C + c];
-            }
-        BATCH_TRY(b, hipSetDevice(b->device));
-        if (!b->field_dev)
-            BATCH_TRY(b, hipMalloc((void **)&b->field_dev, sizeof(BatchFieldTerm) * terms.size()));
-        if (!b->field_raw_dev)
-            BATCH_TRY(b, hipMalloc((void **)&b->field_raw_dev, sizeof(nbody_batch_field_component) * raw.size()));
-        BATCH_TRY(b, hipMemcpyAsync(b->field_dev, terms.data(), sizeof(BatchFieldTerm) * terms.size(), hipMemcpyHostToDevice, b->stream));
-        BATCH_TRY(b, hipMemcpyAsync(b->field_raw_dev, raw.data(), sizeof(nbody_batch_field_component) * raw.size(),
-                                    hipMemcpyHostToDevice, b->stream));
-        BATCH_TRY(b, hipStreamSynchronize(b->stream));  // the host copies end with this call
-        b->field.assign(host, host + B * C);
-        b->field_components = n_components;
-    }
-    b->config.field_set = host != nullptr;
-    forget_caches(b);  // as nbody_batch_massive_set: the cached accelerations and jerks belong to the old field
-    return NBODY_OK;
-}
-
-int nbody_batch_field_read(nbody_batch *b, nbody_batch_field_component *host, int *n_components)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_read: batch is NULL");
-    if (!host || !n_components)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_read: NULL argument");
-    if (!b->config.field_set)
-        return bfail(b, NBODY_ERR_STATE, "nbody_batch_field_read: no field is set (nbody_batch_field_set)");
-    std::copy(b->field.begin(), b->field.end(), host);
-    *n_components = b->field_components;
-    return NBODY_OK;
-}
-
-int nbody_batch_field_potential(nbody_batch *b, const float *d_pos, double *host_phi)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_field_potential: batch is NULL");
-    if (!d_pos || !host_phi)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_potential: NULL argument");
-    const size_t slots = (size_t)b->n_systems * (size_t)b->max_bodies;
-    std::fill(host_phi, host_phi + slots, 0.0);
-    if (!b->config.field_set)
-        return NBODY_OK;
-    if (b->n_systems > 65535)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_field_potential: more than 65535 systems");
-    BATCH_TRY(b, hipSetDevice(b->device));
-    double *phi = nullptr;
-    BATCH_TRY(b, hipMalloc((void **)&phi, sizeof(double) * slots));
-    hipLaunchKernelGGL(batch_field_potential_kernel, dim3((unsigned)((b->max_bodies + 255) / 256), (unsigned)b->n_systems), dim3(256), 0,
-                       b->stream, reinterpret_cast<const float4 *>(d_pos), b->counts_dev, b->field_raw_dev,
-                       NBODY_BATCH_FIELD_MAX_COMPONENTS, (int)b->max_bodies, phi);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(host_phi, phi, sizeof(double) * slots, hipMemcpyDeviceToHost, b->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(b->stream);
-    (void)hipFree(phi);
-    BATCH_TRY(b, e);
-    return NBODY_OK;
-}
-
-int nbody_batch_get_counts(nbody_batch *b, int64_t *counts)
-{
-    if (!b)
-        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_get_counts: batch is NULL");
-    if (!counts)
-        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_get_counts: NULL argument");
-    for (size_t s = 0; s < (size_t)b->n_systems; ++s)
-        counts[s] = b->counts[s];
-    return NBODY_OK;
-}
-
-}  // extern "C"
+}  // namespace nbody

@@ -1641,44 +1641,7 @@ hipError_t launch_batch_diag(const float4 *pos, const float4 *vel, const int *co
 
 // ---- what the calls keep on the handle, and the calls (the C ABI) ----------------------------------------------------------
 
-// A device array of T that its owner frees: a pointer and the elements it has room for.
-template <class T>
-struct DeviceArray {
-    T *ptr = nullptr;
-    size_t capacity = 0;
-
-    DeviceArray() = default;
-    DeviceArray(const DeviceArray &) = delete;
-    DeviceArray &operator=(const DeviceArray &) = delete;
-    ~DeviceArray() { release(); }
-
-    // Room for `count` elements: nothing to do while the capacity suffices (0, an output the call was not asked for: always;
-    // a size fixed per handle: after the first call that asked); otherwise a new array in place of the old one, whose contents
-    // no call needs (gravity's rows grow with the call).  A failed allocation leaves no array.
-    hipError_t ensure(size_t count)
-    {
-        if (count <= capacity)
-            return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void **)&ptr, sizeof(T) * count);
-        if (e == hipSuccess)
-            capacity = count;
-        return e;
-    }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        capacity = 0;
-    }
-};
-
-// `count` elements of a device array to the caller's host array, behind the launches on the handle's stream; no `host`, no copy.
-template <class T>
-hipError_t copy_out(const nbody_batch *b, void *host, const DeviceArray<T> &array, size_t count)
-{
-    return host ? hipMemcpyAsync(host, array.ptr, sizeof(T) * count, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
-}
+// DeviceArray, a device array that its owner frees, and copy_out: nbody_batch_handle.h, whose handle holds its arrays so too.
 
 }  // namespace
 
@@ -1747,8 +1710,8 @@ int nbody_batch_pairs(nbody_batch *b, const float *d_pos, const float *d_vel, nb
     BATCH_TRY(b, a->pairs_binaries.ensure(B));
     std::vector<int> found;
     found.assign(B, 0);
-    BATCH_TRY(b, launch_batch_pairs(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
-                                    b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+    BATCH_TRY(b, launch_batch_pairs(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                    b->config.massive_set ? b->massive_dev.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies,
                                     a->pairs.ptr, a->pairs_binaries.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, records_out, a->pairs, slots));
     BATCH_TRY(b, copy_out(b, found.data(), a->pairs_binaries, B));
@@ -1800,7 +1763,7 @@ int nbody_batch_structure(nbody_batch *b, const float *d_pos, int k, int weight,
     BATCH_TRY(b, hipSetDevice(b->device));
     BATCH_TRY(b, a->structure_systems.ensure(B));
     BATCH_TRY(b, a->structure_bodies.ensure(bodies_out ? slots : 0));
-    BATCH_TRY(b, launch_batch_structure(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, (int)b->n_systems, (int)b->max_bodies, p,
+    BATCH_TRY(b, launch_batch_structure(reinterpret_cast<const float4 *>(d_pos), b->counts_dev.ptr, (int)b->n_systems, (int)b->max_bodies, p,
                                         bodies_out ? a->structure_bodies.ptr : nullptr, a->structure_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->structure_systems, B));
     BATCH_TRY(b, copy_out(b, bodies_out, a->structure_bodies, slots));
@@ -1829,8 +1792,8 @@ int nbody_batch_members(nbody_batch *b, const float *d_pos, const float *d_vel, 
         BATCH_TRY(b, a->members_initial.ensure(slots));
         BATCH_TRY(b, hipMemcpyAsync(a->members_initial.ptr, initial, slots, hipMemcpyHostToDevice, b->stream));
     }
-    BATCH_TRY(b, launch_batch_members(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
-                                      b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+    BATCH_TRY(b, launch_batch_members(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                      b->config.massive_set ? b->massive_dev.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies,
                                       softening * softening, max_iterations, initial ? a->members_initial.ptr : nullptr,
                                       bodies_out ? a->members_bodies.ptr : nullptr, a->members_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->members_systems, B));
@@ -1858,8 +1821,8 @@ int nbody_batch_hierarchy(nbody_batch *b, const float *d_pos, const float *d_vel
     BATCH_TRY(b, a->hierarchy_systems.ensure(B));
     BATCH_TRY(b, a->hierarchy_nodes.ensure(slots));
     BATCH_TRY(b, a->hierarchy_bodies.ensure(bodies_out ? slots : 0));
-    BATCH_TRY(b, launch_batch_hierarchy(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
-                                        b->config.massive_set ? b->massive_dev : nullptr, (int)b->n_systems, (int)b->max_bodies,
+    BATCH_TRY(b, launch_batch_hierarchy(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                        b->config.massive_set ? b->massive_dev.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies,
                                         tidal_tolerance, max_levels, nodes_out != nullptr, a->hierarchy_nodes.ptr,
                                         bodies_out ? a->hierarchy_bodies.ptr : nullptr, a->hierarchy_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->hierarchy_systems, B));
@@ -1903,8 +1866,8 @@ int nbody_batch_gravity(nbody_batch *b, const float *d_pos, const float *d_point
         BATCH_TRY(b, hipMemcpyAsync(a->gravity_counts.ptr, a->gravity_counts_host.data(), sizeof(int) * B, hipMemcpyHostToDevice,
                                     b->stream));
     }
-    BATCH_TRY(b, launch_batch_gravity(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_points), b->counts_dev,
-                                      b->config.massive_set ? b->massive_dev : nullptr,
+    BATCH_TRY(b, launch_batch_gravity(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_points), b->counts_dev.ptr,
+                                      b->config.massive_set ? b->massive_dev.ptr : nullptr,
                                       host_point_counts ? a->gravity_counts.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies,
                                       (int)n_points, softening * softening, a->gravity_records.ptr,
                                       tidal_out ? a->gravity_tidal.ptr : nullptr, b->stream));
@@ -1946,8 +1909,8 @@ int nbody_batch_groups(nbody_batch *b, const float *d_pos, const float *d_vel, c
     BATCH_TRY(b, a->groups_bodies.ensure(bodies_out ? slots : 0));
     BATCH_TRY(b, hipMemcpyAsync(a->groups_linking2.ptr, a->groups_linking2_host.data(), sizeof(float) * B, hipMemcpyHostToDevice,
                                 b->stream));
-    BATCH_TRY(b, launch_batch_groups(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
-                                     b->config.massive_set ? b->massive_dev : nullptr, a->groups_linking2.ptr, (int)b->n_systems,
+    BATCH_TRY(b, launch_batch_groups(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                     b->config.massive_set ? b->massive_dev.ptr : nullptr, a->groups_linking2.ptr, (int)b->n_systems,
                                      (int)b->max_bodies, min_members, weight, max_sweeps, bodies_out ? a->groups_bodies.ptr : nullptr,
                                      groups_out ? a->groups_records.ptr : nullptr, a->groups_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->groups_systems, B));
@@ -1976,7 +1939,7 @@ int nbody_batch_span(nbody_batch *b, const float *d_pos, const unsigned char *su
     BATCH_TRY(b, a->span_bodies.ensure(bodies_out ? slots : 0));
     if (subset)
         BATCH_TRY(b, hipMemcpyAsync(a->span_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
-    BATCH_TRY(b, launch_batch_span(reinterpret_cast<const float4 *>(d_pos), b->counts_dev, subset ? a->span_subset.ptr : nullptr,
+    BATCH_TRY(b, launch_batch_span(reinterpret_cast<const float4 *>(d_pos), b->counts_dev.ptr, subset ? a->span_subset.ptr : nullptr,
                                    (int)b->n_systems, (int)b->max_bodies, separations, edges_out ? a->span_edges.ptr : nullptr,
                                    bodies_out ? a->span_bodies.ptr : nullptr, a->span_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->span_systems, B));
@@ -1989,9 +1952,9 @@ int nbody_batch_span(nbody_batch *b, const float *d_pos, const unsigned char *su
 static int batch_diag(nbody_batch *b, const float *d_pos, const float *d_vel, float softening, bool potential)
 {
     BATCH_TRY(b, hipSetDevice(b->device));
-    BATCH_TRY(b, launch_batch_diag(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev,
-                                   (int)b->n_systems, (int)b->max_bodies, softening * softening, potential, b->diag_dev, b->stream));
-    BATCH_TRY(b, hipMemcpyAsync(b->diag_host.data(), b->diag_dev, sizeof(double) * b->diag_host.size(), hipMemcpyDeviceToHost,
+    BATCH_TRY(b, launch_batch_diag(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                   (int)b->n_systems, (int)b->max_bodies, softening * softening, potential, b->diag_dev.ptr, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(b->diag_host.data(), b->diag_dev.ptr, sizeof(double) * b->diag_host.size(), hipMemcpyDeviceToHost,
                                 b->stream));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;

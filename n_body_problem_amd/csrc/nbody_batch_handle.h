@@ -1,10 +1,12 @@
-// nbody_batch_handle.h -- the handle of a batched ensemble (include/nbody.h, nbody_batch_*), as the two sources behind it see
-// it: nbody_batch.hip (the integrators, their settings and records) and nbody_batch_analysis.hip (the kernels that read a state
-// and write only records of their own).  Internal: nothing here crosses the C ABI.
+// nbody_batch_handle.h -- the handle of a batched ensemble (include/nbody.h, nbody_batch_*), as the three sources behind it see
+// it: nbody_batch.hip (the integrators' kernels and launchers), nbody_batch_capi.hip (the host code behind the integrators' C
+// ABI: their settings and records) and nbody_batch_analysis.hip (the kernels that read a state and write only records of their
+// own, and their calls).  Internal: nothing here crosses the C ABI.
 //
-// Ownership: what the integrators keep lives in the handle, allocated by nbody_batch_create, a setter or the first evolve, and
-// freed by nbody_batch_destroy.  What the analysis calls keep lives in one BatchAnalysis behind `analysis`, created by the first
-// analysis call and freed by batch_analysis_destroy; no integrator reads it and no analysis call writes anything else.
+// Ownership: every device array is a DeviceArray, which frees itself.  What the integrators keep lives in the handle, allocated
+// by nbody_batch_create, a setter or the first evolve, and freed when nbody_batch_destroy deletes the handle.  What the analysis
+// calls keep lives in one BatchAnalysis behind `analysis`, created by the first analysis call and freed by
+// batch_analysis_destroy; no integrator reads it and no analysis call writes anything else.
 #pragma once
 
 #include "../../include/nbody.h"
@@ -12,6 +14,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -51,6 +54,9 @@ struct BatchEvolveState {
     long long steps, clamped;
     int level, min_level, max_level, pad;
 };
+constexpr int kEvolveNoLevel = 1 << 30;
+// A system that has not stepped in this call, at tick 0.
+constexpr BatchEvolveState kEvolveStateFresh{0, 0, 0, 0, kEvolveNoLevel, -1, 0};
 
 // Per system, beside BatchEvolveState: what a stopping condition found (include/nbody_batch_stop.h).  All zero: the system
 // has not stopped.  A system whose reason is set is frozen: later launches leave it alone.
@@ -61,6 +67,7 @@ struct BatchStopReport {
     float separation;
     int pad;
 };
+constexpr BatchStopReport kNotStopped{0, 0, 0, 0, 0, 0.f, 0};
 
 // Per slot: what became of a test particle (include/nbody_batch_fate.h).  All zero: alive.
 struct BatchFate {
@@ -75,6 +82,38 @@ struct BatchFate {
 struct BatchFieldTerm {
     int kind;
     float c0, c1, c2;
+};
+
+// A device array of T that its owner frees: a pointer and the elements it has room for.
+template <class T>
+struct DeviceArray {
+    T *ptr = nullptr;
+    size_t capacity = 0;
+
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    ~DeviceArray() { release(); }
+
+    // Room for `count` elements: nothing to do while the capacity suffices (0, an output the call was not asked for: always;
+    // a size fixed per handle: after the first call that asked); otherwise a new array in place of the old one, whose contents
+    // no call needs (gravity's rows grow with the call).  A failed allocation leaves no array.
+    hipError_t ensure(size_t count)
+    {
+        if (count <= capacity)
+            return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&ptr, sizeof(T) * count);
+        if (e == hipSuccess)
+            capacity = count;
+        return e;
+    }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        capacity = 0;
+    }
 };
 
 struct BatchAnalysis;  // nbody_batch_analysis.hip
@@ -102,19 +141,19 @@ struct nbody_batch {
     int device = 0;
     int64_t n_systems = 0, max_bodies = 0;
     std::vector<int> counts;      // host copy of the per-system body counts
-    int *counts_dev = nullptr;    // [n_systems]
+    nbody::DeviceArray<int> counts_dev;  // [n_systems]
     // what picks the kernels (nbody_batch_choice.h): the integrator, whether massive counts and radii are set, the stopping
     // conditions, the collision action and the tracer action, each written by its setter
     nbody::BatchConfig config;
-    float4 *acc = nullptr;        // KDK, Hermite: [n_systems][max_bodies] accelerations at the current state (slots < n_b)
-    float4 *jerk = nullptr;       // Hermite: [n_systems][max_bodies] jerks at the current state, allocated on first use
+    nbody::DeviceArray<float4> acc;   // KDK, Hermite: [n_systems][max_bodies] accelerations at the current state (slots < n_b)
+    nbody::DeviceArray<float4> jerk;  // Hermite: [n_systems][max_bodies] jerks at the current state, allocated on first use
     bool acc_valid = false;
     int acc_integrator = -1;      // the integrator that filled the cache
     const void *acc_pos = nullptr, *acc_vel = nullptr;  // the buffers and softening the cache belongs to
     float acc_softening = 0.f;
     // nbody_batch_evolve_on: the per-system level and tick beside the caches, valid only while acc_valid
-    nbody::BatchEvolveState *evolve_state = nullptr;  // [n_systems]
-    int *evolve_counters = nullptr;                   // {unfinished, unfinished and out of steps} of the last launch
+    nbody::DeviceArray<nbody::BatchEvolveState> evolve_state;  // [n_systems]
+    nbody::DeviceArray<int> evolve_counters;          // {unfinished, unfinished and out of steps} of the last launch
     std::vector<nbody::BatchEvolveState> evolve_host; // the last call's, for nbody_batch_evolve_stats
     int64_t evolve_target = 0;
     bool level_valid = false;                  // the levels belong to level_dt_max and level_levels
@@ -123,32 +162,32 @@ struct nbody_batch {
     bool evolve_pending = false;               // the last call ran out of steps: systems sit at different ticks
     int evolve_launch_steps = nbody::kBatchStepsPerLaunch;
     // nbody_batch_stop_set: the per-system reports beside evolve_state
-    nbody::BatchStopReport *stop_report = nullptr;  // [n_systems], allocated by the first evolve with conditions
+    nbody::DeviceArray<nbody::BatchStopReport> stop_report;  // [n_systems], allocated by the first evolve with conditions
     bool stop_forgotten = true;                // the reports count as all zero: cleared before the next launch reads them
     // nbody_batch_merge_set: the per-system merger counts and logs beside the reports (forgotten with them)
     int merge_capacity = 0;
-    int *merge_count = nullptr;                     // [n_systems], allocated by the first evolve that merges
-    nbody_batch_merge_event *merge_log = nullptr;   // [n_systems][merge_capacity]
+    nbody::DeviceArray<int> merge_count;                    // [n_systems], allocated by the first evolve that merges
+    nbody::DeviceArray<nbody_batch_merge_event> merge_log;  // [n_systems][merge_capacity]
     // nbody_batch_radii_set: one radius per slot, laid out like the positions; a property of the slots, which only
     // nbody_batch_radii_set and the mergers change
-    float *radii = nullptr;       // [n_systems][max_bodies], allocated by the first nbody_batch_radii_set
+    nbody::DeviceArray<float> radii;  // [n_systems][max_bodies], allocated by the first nbody_batch_radii_set
     // nbody_batch_massive_set: per system the number of leading bodies that exert forces; a property of the handle, which only
     // nbody_batch_massive_set changes
     std::vector<int> massive;     // host copy, [n_systems] while config.massive_set
-    int *massive_dev = nullptr;   // [n_systems], allocated by the first nbody_batch_massive_set
+    nbody::DeviceArray<int> massive_dev;  // [n_systems], allocated by the first nbody_batch_massive_set
     // nbody_batch_fate_set: the per-body fates beside the reports (forgotten with them), laid out like the positions and
     // allocated by the first REMOVE
-    nbody::BatchFate *fates = nullptr;  // [n_systems][max_bodies]
+    nbody::DeviceArray<nbody::BatchFate> fates;  // [n_systems][max_bodies]
     // nbody_batch_accrete_set: what the tracers gave, beside the fates (forgotten with them) and allocated by the first ACCRETE
-    float *given = nullptr;       // [n_systems][max_bodies]
-    int *accretions = nullptr;    // [n_systems]
+    nbody::DeviceArray<float> given;     // [n_systems][max_bodies]
+    nbody::DeviceArray<int> accretions;  // [n_systems]
     // nbody_batch_field_set: the external field's components; a property of the handle, which only nbody_batch_field_set changes
     std::vector<nbody_batch_field_component> field;  // host copy as set, [n_systems][field_components] while config.field_set
     int field_components = 0;
-    nbody::BatchFieldTerm *field_dev = nullptr;            // [n_systems][4] as the kernels take them, allocated by the first set
-    nbody_batch_field_component *field_raw_dev = nullptr;  // [n_systems][4] as set, for nbody_batch_field_potential
+    nbody::DeviceArray<nbody::BatchFieldTerm> field_dev;  // [n_systems][4] as the kernels take them, allocated by the first set
+    nbody::DeviceArray<nbody_batch_field_component> field_raw_dev;  // [n_systems][4] as set, for nbody_batch_field_potential
     // nbody_batch_energy, nbody_batch_momentum: allocated by nbody_batch_create, so that a diagnostic never allocates
-    double *diag_dev = nullptr;   // [n_systems][kDiagValues]
+    nbody::DeviceArray<double> diag_dev;  // [n_systems][kDiagValues]
     std::vector<double> diag_host;
     // nbody_batch_pairs ... nbody_batch_span: the records of the last calls; they belong to no cache and nothing forgets them
     nbody::BatchAnalysis *analysis = nullptr;  // created by the first analysis call
@@ -156,3 +195,18 @@ struct nbody_batch {
     hipStream_t stream = nullptr;  // own_stream or the caller's (nbody_batch_set_stream)
     std::string err;
 };
+
+#pragma GCC visibility push(hidden)
+
+namespace nbody {
+
+// `count` elements of a device array to the caller's host array, behind the launches on the handle's stream; no `host`, no copy.
+template <class T>
+hipError_t copy_out(const nbody_batch *b, void *host, const DeviceArray<T> &array, size_t count)
+{
+    return host ? hipMemcpyAsync(host, array.ptr, sizeof(T) * count, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
+}
+
+}  // namespace nbody
+
+#pragma GCC visibility pop

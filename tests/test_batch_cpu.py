@@ -42,6 +42,24 @@ def test_batch_entry_points_are_declared_bound_and_exported(lib):
         assert hasattr(fake, name), name
 
 
+def test_the_three_batch_sources_and_their_headers_are_build_dependencies_and_the_c_abi_source_holds_no_kernel():
+    from n_body_problem_amd import build
+    csrc = os.path.join(ROOT, "n_body_problem_amd", "csrc")
+    text = {}
+    for source in ("nbody_batch.hip", "nbody_batch_capi.hip", "nbody_batch_analysis.hip"):
+        assert source in build.SOURCES
+        text[source] = open(os.path.join(csrc, source)).read()
+        for header in re.findall(r'^#include "([^"/]+)"', text[source], flags=re.M):
+            assert os.path.join(csrc, header) in build.HEADERS, (source, header)
+    assert os.path.join(csrc, "nbody_batch_launch.h") in build.HEADERS
+    for source in ("nbody_batch.hip", "nbody_batch_capi.hip"):      # the two meet in that header
+        assert '#include "nbody_batch_launch.h"' in text[source]
+    host = re.sub(r"//[^\n]*", "", text["nbody_batch_capi.hip"])
+    assert not re.search(r"__global__|__device__|hipLaunchKernelGGL|<<<|hipMalloc|hipFree", host)
+    assert "nbody_batch_capi.hip" not in build.EXTRA_FLAGS          # no device code, no device flags
+    assert 'extern "C"' not in text["nbody_batch.hip"]
+
+
 def test_max_bodies_constant_matches_the_python_mirror():
     import n_body_problem_amd as nb
     from n_body_problem_amd import batch
