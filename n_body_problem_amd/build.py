@@ -13,10 +13,11 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libnbody_amd.so")
-SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_multi.hip", "nbody_batch.hip",
-           "nbody_batch_capi.hip", "nbody_batch_analysis.hip"]
+SOURCES = ["nbody_kernels.hip", "nbody_symmetric.hip", "nbody_order.hip", "nbody_capi.hip", "nbody_capi_step.hip",
+           "nbody_capi_order.hip", "nbody_multi.hip", "nbody_batch.hip", "nbody_batch_capi.hip", "nbody_batch_analysis.hip"]
 HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_plan.h"),
-           os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
+           os.path.join(CSRC, "nbody_launch_choice.h"), os.path.join(CSRC, "nbody_device_owned.h"),
+           os.path.join(CSRC, "nbody_ctx.h"), os.path.join(CSRC, "nbody_batch_radii_check.h"),
            os.path.join(CSRC, "nbody_batch_choice.h"), os.path.join(CSRC, "nbody_batch_handle.h"),
            os.path.join(CSRC, "nbody_batch_launch.h"),
            os.path.join(CSRC, "nbody_batch_pairs_elements.h"),

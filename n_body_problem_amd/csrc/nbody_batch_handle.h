@@ -3,14 +3,15 @@
 // ABI: their settings and records) and nbody_batch_analysis.hip (the kernels that read a state and write only records of their
 // own, and their calls).  Internal: nothing here crosses the C ABI.
 //
-// Ownership: every device array is a DeviceArray, which frees itself.  What the integrators keep lives in the handle, allocated
-// by nbody_batch_create, a setter or the first evolve, and freed when nbody_batch_destroy deletes the handle.  What the analysis
+// Ownership: every device array is a DeviceArray (nbody_device_owned.h), which frees itself.  What the integrators keep lives in
+// the handle, allocated by nbody_batch_create, a setter or the first evolve, and freed when nbody_batch_destroy deletes it.  What the analysis
 // calls keep lives in one BatchAnalysis behind `analysis`, created by the first analysis call and freed by
 // batch_analysis_destroy; no integrator reads it and no analysis call writes anything else.
 #pragma once
 
 #include "../../include/nbody.h"
 #include "nbody_batch_choice.h"
+#include "nbody_device_owned.h"
 
 #include <hip/hip_runtime.h>
 
@@ -82,38 +83,6 @@ struct BatchFate {
 struct BatchFieldTerm {
     int kind;
     float c0, c1, c2;
-};
-
-// A device array of T that its owner frees: a pointer and the elements it has room for.
-template <class T>
-struct DeviceArray {
-    T *ptr = nullptr;
-    size_t capacity = 0;
-
-    DeviceArray() = default;
-    DeviceArray(const DeviceArray &) = delete;
-    DeviceArray &operator=(const DeviceArray &) = delete;
-    ~DeviceArray() { release(); }
-
-    // Room for `count` elements: nothing to do while the capacity suffices (0, an output the call was not asked for: always;
-    // a size fixed per handle: after the first call that asked); otherwise a new array in place of the old one, whose contents
-    // no call needs (gravity's rows grow with the call).  A failed allocation leaves no array.
-    hipError_t ensure(size_t count)
-    {
-        if (count <= capacity)
-            return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void **)&ptr, sizeof(T) * count);
-        if (e == hipSuccess)
-            capacity = count;
-        return e;
-    }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        capacity = 0;
-    }
 };
 
 struct BatchAnalysis;  // nbody_batch_analysis.hip

@@ -1,4 +1,4 @@
-// nbody_kernels.h -- launch interface between the C ABI (nbody_capi.hip) and the gfx950 kernels
+// nbody_kernels.h -- launch interface between the C ABI (nbody_capi*.hip) and the gfx950 kernels
 // (nbody_kernels.hip).  Internal; the public surface is include/nbody.h.
 #pragma once
 #include <hip/hip_runtime.h>

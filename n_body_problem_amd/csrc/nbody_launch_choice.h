@@ -1,7 +1,7 @@
 // nbody_launch_choice.h -- which force kernel a configuration runs and with what launch shape, the split-length rules and the
 // automatic graph-replay rule: pure functions of their arguments.  Plain C++17 without HIP, like nbody_sym_plan.h (which tiles, in
 // which order): the launchers (nbody_kernels.hip, nbody_symmetric.hip) look the chosen kernel up in their tables, the C ABI
-// (nbody_capi.hip) reads what its sequencing needs, and a CPU test (tests/test_launch_choice_cpu.py) checks every choice without
+// (nbody_capi_step.hip) reads what its sequencing needs, and a CPU test (tests/test_launch_choice_cpu.py) checks every choice without
 // a GPU.  Internal; the public surface is include/nbody.h.
 #pragma once
 #include <cstddef>

@@ -1,6 +1,6 @@
 // nbody_sym_plan.h -- the launch plan of the pair-once mode: which strips and diagonal tiles a force call launches, in which
 // order, cut into which summation parts, and where each part's partial sums go.  Plain C++17 without HIP: the kernels
-// (nbody_kernels.h includes this file) and the C ABI (nbody_capi.hip) share the geometry below, and a CPU test
+// (nbody_kernels.h includes this file) and the C ABI (nbody_capi_step.hip) share the geometry below, and a CPU test
 // (tests/test_sym_plan_cpu.py) checks the plan without a GPU.  Internal; the public surface is include/nbody.h.
 #pragma once
 #include "../../include/nbody.h"

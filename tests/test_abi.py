@@ -209,3 +209,47 @@ def test_the_rccl_test_double_build_is_the_same_library_without_librccl():
     needed = lambda path: subprocess.run(["readelf", "-d", path], capture_output=True, text=True).stdout  # noqa: E731
     assert "librccl" not in needed(build_fake_rccl.LIB)
     assert "librccl" in needed(build.LIB_PATH)
+
+
+CTX_SOURCES = ("nbody_capi.hip", "nbody_capi_step.hip", "nbody_capi_order.hip")
+
+
+def test_the_three_c_abi_sources_and_their_headers_are_build_dependencies_and_hold_no_kernel():
+    from n_body_problem_amd import build
+    csrc = os.path.join(ROOT, "n_body_problem_amd", "csrc")
+    for header in ("nbody_ctx.h", "nbody_device_owned.h"):
+        assert os.path.join(csrc, header) in build.HEADERS
+    assert '#include "nbody_device_owned.h"' in open(os.path.join(csrc, "nbody_batch_handle.h")).read()   # one owner type, shared
+    for source in CTX_SOURCES:
+        assert source in build.SOURCES
+        assert source not in build.EXTRA_FLAGS                      # no device code, no device flags
+        text = open(os.path.join(csrc, source)).read()
+        for header in ("nbody_ctx.h", "nbody_kernels.h"):
+            assert f'#include "{header}"' in text, (source, header)
+        for header in re.findall(r'^#include "([^"/]+)"', text, flags=re.M):
+            assert os.path.join(csrc, header) in build.HEADERS, (source, header)
+        host = re.sub(r"//[^\n]*", "", text)
+        assert not re.search(r"__global__|__device__|hipLaunchKernelGGL|<<<", host), source
+        assert not re.search(r"\bhipFree\b|\bhipEventDestroy\b|\bhipStreamDestroy\b|\bhipGraphExecDestroy\b", host), source
+    assert "hipFree" not in re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "nbody_ctx.h")).read())   # only the owner type frees
+
+
+def test_nbody_destroy_keeps_no_list_of_frees():
+    text = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "n_body_problem_amd", "csrc", "nbody_capi.hip")).read())
+    body = re.search(r"^int nbody_destroy\(nbody_ctx \*c\)\n\{\n(.*?)^\}", text, flags=re.S | re.M).group(1)
+    assert "delete c;" in body and "hipStreamSynchronize" in body
+    assert "hipFree" not in body and "hipEventDestroy" not in body
+
+
+def test_the_library_defines_exactly_the_names_it_defined_before_the_context_owned_its_arrays(lib):
+    """profiles/ctx_ownership_exports.txt: the strong dynamic symbols of the build before the split (its head says how it was
+    made and why weak symbols and the per-unit __hip_cuid_ markers are left out).  None of the owner types shows in any name."""
+    import subprocess
+    from n_body_problem_amd import build
+    out = subprocess.run(["nm", "-D", "--defined-only", build.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    symbols = [line.split() for line in out.splitlines() if len(line.split()) == 3]
+    strong = sorted(name for _, kind, name in symbols if kind not in "WV" and not name.startswith("__hip_cuid_"))
+    listed = [line.strip() for line in open(os.path.join(ROOT, "profiles", "ctx_ownership_exports.txt")) if not line.startswith("#")]
+    assert strong == sorted(listed) and len(strong) > 150
+    for _, _, name in symbols:
+        assert not re.search(r"DeviceArray|OwnedEvent|OwnedStream|OwnedGraphExec|TimedLaunch", name), name
