@@ -549,6 +549,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_groups.h"
 /* spanning trees: the Euclidean minimum spanning tree of every system or of a subset of its bodies, edges in ascending order */
 #include "nbody_batch_span.h"
+/* neighbours: every body's k nearest sources by index and squared distance, and how many lie within a radius */
+#include "nbody_batch_neighbours.h"
 
 #ifdef __cplusplus
 }

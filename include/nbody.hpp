@@ -624,6 +624,37 @@ public:
               "nbody_batch_span");
         return s;
     }
+    // Nearest-neighbour lists (nbody_batch_neighbours.h): for every body of every system its k (1 ... 8) nearest sources
+    // from the positions in the caller's buffer.  radii: empty, or one radius per system (host) for the bodies' `within`
+    // counts.  sources: empty for all bodies, or numSystems x maxBodies bytes (host), non-zero where a body is a source; every
+    // body gets a list all the same.  Per system the rows, the sources, the listed, complete and mutual rows and the mean
+    // nearest and k-th distances.  bodies, where given, is resized to numSystems x maxBodies and takes the per-body {found,
+    // within}; index and r2, given both or neither, are resized to numSystems x maxBodies x k and take the lists (-1 and +inf
+    // from `found` on); nullptr skips that copy.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_neighbour_system> neighbours(const float *dPositions, int k = 6, const std::vector<float> &radii = {},
+                                                         const std::vector<unsigned char> &sources = {},
+                                                         std::vector<nbody_batch_neighbour_body> *bodies = nullptr,
+                                                         std::vector<int> *index = nullptr, std::vector<float> *r2 = nullptr)
+    {
+        if (!radii.empty() && radii.size() != (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::neighbours: one radius per system, or none");
+        if (!sources.empty() && sources.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::neighbours: one source byte per slot, or none");
+        if (k < 1 || k > NBODY_BATCH_NEIGHBOURS_MAX)
+            throw std::invalid_argument("nbody::Batch::neighbours: k must be 1 ... 8");
+        std::vector<nbody_batch_neighbour_system> s((size_t)systems_);
+        if (bodies)
+            bodies->resize((size_t)systems_ * (size_t)maxBodies_);
+        if (index)
+            index->resize((size_t)systems_ * (size_t)maxBodies_ * (size_t)k);
+        if (r2)
+            r2->resize((size_t)systems_ * (size_t)maxBodies_ * (size_t)k);
+        check(nbody_batch_neighbours(b_, dPositions, k, radii.empty() ? nullptr : radii.data(),
+                                     sources.empty() ? nullptr : sources.data(), s.data(), bodies ? bodies->data() : nullptr,
+                                     index ? index->data() : nullptr, r2 ? r2->data() : nullptr),
+              "nbody_batch_neighbours");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

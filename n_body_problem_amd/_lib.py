@@ -410,6 +410,28 @@ _SPAN_PROTOTYPES = {
 }
 
 
+BATCH_NEIGHBOURS_MAX = 8
+
+
+class BatchNeighbourSystem(ctypes.Structure):
+    """``nbody_batch_neighbour_system`` of include/nbody_batch_neighbours.h."""
+    _fields_ = [("bodies", c_int), ("sources", c_int), ("listed", c_int), ("complete", c_int), ("mutual", c_int),
+                ("reserved", c_int), ("mean_nearest", c_double), ("mean_kth", c_double)]
+
+
+class BatchNeighbourBody(ctypes.Structure):
+    """``nbody_batch_neighbour_body`` of include/nbody_batch_neighbours.h."""
+    _fields_ = [("found", c_int), ("within", c_int)]
+
+
+#: the entry point of include/nbody_batch_neighbours.h (nearest-neighbour lists of batched ensembles), which nbody.h includes
+_NEIGHBOURS_PROTOTYPES = {
+    "nbody_batch_neighbours": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_float), POINTER(ctypes.c_ubyte),
+                                       POINTER(BatchNeighbourSystem), POINTER(BatchNeighbourBody), POINTER(c_int),
+                                       POINTER(c_float)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -438,7 +460,8 @@ def load() -> ctypes.CDLL:
                 list(_MERGE_PROTOTYPES.items()) + list(_RADII_PROTOTYPES.items()) + list(_MASSIVE_PROTOTYPES.items()) + list(_FATE_PROTOTYPES.items()) + \
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
-                list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()):
+                list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
+                list(_NEIGHBOURS_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -524,6 +547,11 @@ def groups_names():
 def span_names():
     """The entry point of nbody_batch_span.h."""
     return list(_SPAN_PROTOTYPES)
+
+
+def neighbours_names():
+    """The entry point of nbody_batch_neighbours.h."""
+    return list(_NEIGHBOURS_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -82,6 +82,13 @@ SPAN_BODY_DTYPE = np.dtype([("degree", np.int32), ("nearest", np.int32)])
 assert SPAN_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanSystem) == 40
 assert SPAN_EDGE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanEdge) == 16
 assert SPAN_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSpanBody) == 8
+#: the records of :meth:`BatchedSystem.neighbours`: numpy's views of ``nbody_batch_neighbour_system`` and ``_body``
+NEIGHBOUR_SYSTEM_DTYPE = np.dtype([("bodies", np.int32), ("sources", np.int32), ("listed", np.int32), ("complete", np.int32),
+                                   ("mutual", np.int32), ("reserved", np.int32), ("mean_nearest", np.float64),
+                                   ("mean_kth", np.float64)])
+NEIGHBOUR_BODY_DTYPE = np.dtype([("found", np.int32), ("within", np.int32)])
+assert NEIGHBOUR_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchNeighbourSystem) == 40
+assert NEIGHBOUR_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchNeighbourBody) == 8
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -687,6 +694,51 @@ class BatchedSystem:
             vertices = vertices & (sub != 0)
         return SpanResult(systems, edge, body, bool(separations), vertices)
 
+    def neighbours(self, k: int = 6, radius=None, sources=None, lists: bool = True, bodies: bool = True) -> "NeighbourResult":
+        """Who is next to whom (``include/nbody_batch_neighbours.h`` states the rules): for every body of every system the
+        indices and fp32 squared distances of its ``k`` (1 ... 8) nearest sources, found on the device from the current state
+        (waits for the queued work).  All bodies below the count are rows, test particles included.  ``sources``, a
+        ``(B, max_bodies)`` bool or uint8 array, selects the bodies that can be neighbours (all, without it); every body gets a
+        list all the same, so with the massive bodies as sources the lists are every planetesimal's nearest planets.  A list
+        is ordered by distance, ties by the lower index; a coincident body is a neighbour, the body itself never.  ``radius``
+        (a scalar, or ``B`` values, one per system) also counts the sources within it, ``within``; without it that is 0.
+        ``lists=False`` and ``bodies=False`` skip the ``8 k`` bytes and the 8 bytes per body on their way to the host: those
+        arrays of the result are ``None``, the per-system ones the same bits.  Changes nothing: an :meth:`evolve` after it is
+        bit for bit the :meth:`evolve` without it."""
+        k = int(k)
+        if not 1 <= k <= _lib.BATCH_NEIGHBOURS_MAX:
+            raise ValueError(f"k must be 1 ... {_lib.BATCH_NEIGHBOURS_MAX}, not {k}")
+        B, n = self.num_systems, self.max_bodies
+        b = None
+        if radius is not None:
+            b = np.asarray(radius, dtype=np.float32)
+            if b.ndim == 0:
+                b = np.full(B, b, dtype=np.float32)
+            b = np.ascontiguousarray(b.reshape(-1))
+            if b.shape[0] != B:
+                raise ValueError(f"expected one radius or {B}, got {b.shape[0]}")
+        src = None
+        if sources is not None:
+            src = np.ascontiguousarray(np.asarray(sources))
+            if src.dtype != np.bool_ and src.dtype != np.uint8:
+                raise ValueError(f"sources must be bool or uint8, not {src.dtype}")
+            if src.shape != (B, n):
+                raise ValueError(f"sources must have shape ({B}, {n}), got {tuple(src.shape)}")
+            src = src.view(np.uint8)
+        systems = np.zeros(B, dtype=NEIGHBOUR_SYSTEM_DTYPE)
+        body = np.zeros((B, n), dtype=NEIGHBOUR_BODY_DTYPE) if bodies else None
+        index = np.zeros((B, n, k), dtype=np.int32) if lists else None
+        r2 = np.zeros((B, n, k), dtype=np.float32) if lists else None
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_neighbours(
+            self._h, _ptr(self.positions), k, b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if b is not None else None,
+            src.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if src is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchNeighbourSystem)),
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchNeighbourBody)) if bodies else None,
+            index.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if lists else None,
+            r2.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if lists else None), self._h)
+        return NeighbourResult(systems, body, index, r2, k)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1073,6 +1125,47 @@ class SpanResult:
                 f"rounds={self.rounds.tolist()})")
 
 
+class NeighbourResult:
+    """What :meth:`BatchedSystem.neighbours` found.  Per list slot, ``(B, max_bodies, k)`` arrays or ``None`` without
+    ``lists``: ``index`` (int32: the ``t``-th nearest source of the body; -1 from ``found`` on and beyond the count), ``r2``
+    (float32: its squared distance; +inf there) and ``distance`` (float64: ``sqrt`` of it, formed on the host).  Per body,
+    ``(B, max_bodies)`` int32 arrays or ``None`` without ``bodies``: ``found`` (the filled slots, ``min(k, candidates)``) and
+    ``within`` (the sources within ``radius``; 0 without one).  Per system (``(B,)`` arrays): ``bodies`` (int32: the rows),
+    ``sources`` (the selected bodies), ``listed`` (rows with a neighbour), ``complete`` (rows with ``k``), ``mutual`` (rows
+    whose nearest body's nearest they are), ``mean_nearest`` and ``mean_kth`` (float64: the mean distance to the nearest
+    source over the listed rows, and to the ``k``-th over the complete ones).  ``systems`` and ``body_records`` are the
+    records themselves; ``k`` is the list length asked for."""
+
+    def __init__(self, systems, bodies, index, r2, k):
+        self.systems, self.body_records, self.index, self.r2, self.k = systems, bodies, index, r2, int(k)
+        for name in ("bodies", "sources", "listed", "complete", "mutual", "mean_nearest", "mean_kth"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.distance = None if r2 is None else np.sqrt(r2.astype(np.float64))
+        self.found = self.within = None
+        if bodies is not None:
+            self.found, self.within = np.ascontiguousarray(bodies["found"]), np.ascontiguousarray(bodies["within"])
+
+    def gather(self, values, fill=np.nan) -> np.ndarray:
+        """``values``, a ``(B, max_bodies, ...)`` array of one entry per body, at the neighbours' indices:
+        ``(B, max_bodies, k, ...)``, with ``fill`` where a slot is empty.  The velocity dispersion about every body's
+        neighbours is ``res.gather(v).std(axis=2)``.  Integer ``values`` need an integer ``fill``."""
+        if self.index is None:
+            raise ValueError("gather needs the lists: call neighbours(lists=True)")
+        values = np.asarray(values)
+        B, n, k = self.index.shape
+        if values.shape[:2] != (B, n):
+            raise ValueError(f"values must have shape ({B}, {n}, ...), got {tuple(values.shape)}")
+        empty = self.index < 0
+        out = values[np.arange(B)[:, None, None], np.where(empty, 0, self.index)]
+        out = out.astype(np.result_type(out.dtype, np.asarray(fill).dtype), copy=True)
+        out[empty] = fill
+        return out
+
+    def __repr__(self):
+        return (f"NeighbourResult(k={self.k}, listed={self.listed.tolist()}, complete={self.complete.tolist()}, "
+                f"mutual={self.mutual.tolist()}, mean_nearest={self.mean_nearest.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -1147,4 +1240,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -1,6 +1,6 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
-// structure, bound members, gravity at points, hierarchies, groups, spanning trees, energy and momentum (include/nbody.h,
-// nbody_batch_pairs.h ... nbody_batch_span.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, energy and momentum
+// (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_neighbours.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
@@ -9,6 +9,7 @@
 #include "nbody_batch_handle.h"
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
+#include "nbody_batch_neighbours_math.h"
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_span_math.h"
 #include "nbody_batch_structure_math.h"
@@ -1574,6 +1575,176 @@ hipError_t launch_batch_span(const float4 *pos, const int *counts, const unsigne
     });
 }
 
+// ---- neighbours (include/nbody_batch_neighbours.h): every row's k nearest sources by index and squared distance, the sources
+// within a radius, and per system the listed, complete and mutual rows and the mean nearest and k-th distances.  A sibling of
+// batch_structure_kernel, whose first phase this is with the indices kept: one workgroup per system with batch_shape's
+// workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  It reads the positions and writes only
+// the handle's records.
+
+static_assert(sizeof(BatchNeighbourSystem) == sizeof(nbody_batch_neighbour_system) && sizeof(nbody_batch_neighbour_system) == 40 &&
+                  offsetof(BatchNeighbourSystem, bodies) == offsetof(nbody_batch_neighbour_system, bodies) &&
+                  offsetof(BatchNeighbourSystem, sources) == offsetof(nbody_batch_neighbour_system, sources) &&
+                  offsetof(BatchNeighbourSystem, listed) == offsetof(nbody_batch_neighbour_system, listed) &&
+                  offsetof(BatchNeighbourSystem, complete) == offsetof(nbody_batch_neighbour_system, complete) &&
+                  offsetof(BatchNeighbourSystem, mutual) == offsetof(nbody_batch_neighbour_system, mutual) &&
+                  offsetof(BatchNeighbourSystem, reserved) == offsetof(nbody_batch_neighbour_system, reserved) &&
+                  offsetof(BatchNeighbourSystem, mean_nearest) == offsetof(nbody_batch_neighbour_system, mean_nearest) &&
+                  offsetof(BatchNeighbourSystem, mean_kth) == offsetof(nbody_batch_neighbour_system, mean_kth),
+              "nbody_batch_neighbours_math.h mirrors the system record of nbody_batch_neighbours.h");
+static_assert(sizeof(BatchNeighbourBody) == sizeof(nbody_batch_neighbour_body) && sizeof(nbody_batch_neighbour_body) == 8 &&
+                  offsetof(BatchNeighbourBody, found) == offsetof(nbody_batch_neighbour_body, found) &&
+                  offsetof(BatchNeighbourBody, within) == offsetof(nbody_batch_neighbour_body, within),
+              "nbody_batch_neighbours_math.h mirrors the body record of nbody_batch_neighbours.h");
+static_assert(kNeighboursMax == NBODY_BATCH_NEIGHBOURS_MAX, "nbody_batch_neighbours_math.h mirrors the limit of nbody_batch_neighbours.h");
+
+constexpr int kNeighbourTallies = 4;  // sources, listed, complete, mutual
+
+// LDS: img[j] = {x, y, z, source flag} of body j as four words, one ds_read_b128 per column (64 KiB at 4096 bodies; with the
+// tallies above the default limit, which is raised before the launch).  After the walk the same bytes hold every row's nearest
+// index, one word per row, for `mutual`, and after that every row's two terms of the means, 16 bytes per row again.
+// The eight nearest (r2, index) pairs of every row stay in registers (neighbours_insert); one row per lane is held to the 64
+// registers of eight waves per SIMD, batch_hermite_kernel<1>'s.  radius2 is b2 per system, or NULL; index and r2 are NULL
+// together; bodies may be NULL.
+template <int RPL>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_neighbours_kernel(
+    const float4 *pos, const int *counts, const unsigned char *sources, const float *radius2, int max_bodies, int k,
+    BatchNeighbourBody *bodies, int *index, float *r2, BatchNeighbourSystem *systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int tally[kNeighbourTallies];
+    int *nearest = reinterpret_cast<int *>(img);
+    double2 *term = reinterpret_cast<double2 *>(img);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float b2 = radius2 ? radius2[blockIdx.x] : kNeighboursNoRadius2;
+    float4 x[RPL];  // {x, y, z, the mass word}
+    if (tid < kNeighbourTallies)
+        tally[tid] = 0;
+    __syncthreads();
+    int mine = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < n) {
+            x[q] = pos[base + r];
+            const int flag = !sources || sources[base + r] != 0 ? 1 : 0;
+            mine += flag;
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), flag);
+        }
+    }
+    if (mine)
+        atomicAdd(&tally[0], mine);
+    __syncthreads();  // the image is in place
+    NeighbourList list[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        neighbours_clear(list[q]);
+    // Measured on an MI355X (profiles/batch_rate_neighbours.txt, the lean call at k = 6): with the insertion for every column
+    // 1.41 ms at 1024 x 1024 and 5.40 ms at 4096 x 256; skipped where no lane of the wave wants it for any of its rows (one
+    // vote per column) 1.40 and 4.31; skipped per row group q (one vote per column and q: 64 rows, not 256, have to agree) 1.18
+    // and 3.06.  The same bits all three.  Unlike in structure(), whose insertion is 16 operations, the 40 saved here pay for
+    // the vote and the branch once the lists have settled, from a few hundred columns on.  So: a skip per row group.
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[j];  // a wave-uniform address: one broadcast LDS read
+        if (__builtin_amdgcn_readfirstlane(pj.w) == 0)
+            continue;  // no source: the flag is the same in every lane, so the branch is a scalar one
+        const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const float c = neighbours_measure(list[q], q * T + tid, x[q].x, x[q].y, x[q].z, xj, yj, zj, true, j, b2);
+            if (__ballot(neighbours_wanted(list[q], c)) != 0)
+                neighbours_insert(list[q], c, j);  // changes nothing in a lane that does not want it
+        }
+    }
+    int found[RPL];
+    float kth[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const bool live = q * T + tid < n;  // a row from the count on walked the columns from the origin: it holds nothing
+        found[q] = live ? neighbours_found(list[q], k) : 0;
+        kth[q] = neighbours_kth(list[q], k);
+    }
+    __syncthreads();  // every lane is done with the columns
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            nearest[r] = list[q].index[0];
+    }
+    __syncthreads();
+    int listed = 0, complete = 0, mutual = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        listed += found[q] >= 1 ? 1 : 0;
+        complete += found[q] == k ? 1 : 0;
+        mutual += r < n && neighbours_mutual(nearest, r) ? 1 : 0;
+    }
+    // Integers: the order of the additions does not matter.
+    if (listed)
+        atomicAdd(&tally[1], listed);
+    if (complete)
+        atomicAdd(&tally[2], complete);
+    if (mutual)
+        atomicAdd(&tally[3], mutual);
+    __syncthreads();  // every lane is done with the nearest indices
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n)
+            term[r] = make_double2(neighbours_term(found[q] >= 1, list[q].r2[0]), neighbours_term(found[q] == k, kth[q]));
+    }
+    __syncthreads();
+    // The lists, k words per row, and the body records; slot by slot under t < k: a list indexed by the slot would live in
+    // scratch memory.  A live row's slots from `found` on hold the empty values already.
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < max_bodies) {
+            const bool live = r < n;
+            if (index) {
+                const size_t at = (base + r) * (size_t)k;
+#pragma unroll
+                for (int t = 0; t < kNeighboursMax; ++t) {
+                    if (t < k) {
+                        index[at + t] = live ? list[q].index[t] : kNeighboursNoIndex;
+                        r2[at + t] = live ? list[q].r2[t] : neighbours_no_r2();
+                    }
+                }
+            }
+            if (bodies)
+                bodies[base + r] = live ? BatchNeighbourBody{found[q], list[q].within} : neighbours_empty_body();
+        }
+    }
+    // The two sums, by one thread in ascending i: the same bits in any slot, batch and capacity.
+    if (tid == 0) {
+        double nearest_sum = 0.0, kth_sum = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double2 t = term[i];
+            nearest_sum += t.x;
+            kth_sum += t.y;
+        }
+        systems[blockIdx.x] = BatchNeighbourSystem{n, tally[0], tally[1], tally[2], tally[3], 0, neighbours_mean(nearest_sum, tally[1]),
+                                                   neighbours_mean(kth_sum, tally[2])};
+    }
+}
+
+// One launch over all systems.  16 bytes of dynamic LDS per body, 64 KiB at 4096 bodies beside the tallies.  sources, radius2,
+// bodies and the two list arrays may be NULL.
+hipError_t launch_batch_neighbours(const float4 *pos, const int *counts, const unsigned char *sources, const float *radius2,
+                                   int n_systems, int max_bodies, int k, BatchNeighbourBody *bodies, int *index, float *r2,
+                                   BatchNeighbourSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_neighbours_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, counts, sources,
+                                      radius2, max_bodies, k, bodies, index, r2, systems);
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -1672,6 +1843,13 @@ struct BatchAnalysis {
     DeviceArray<BatchSpanEdge> span_edges;      // [n_systems][max_bodies]
     DeviceArray<BatchSpanBody> span_bodies;     // [n_systems][max_bodies]
     DeviceArray<unsigned char> span_subset;     // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<BatchNeighbourSystem> neighbours_systems;  // [n_systems]
+    DeviceArray<BatchNeighbourBody> neighbours_bodies;     // [n_systems][max_bodies]
+    DeviceArray<int> neighbours_index;                     // [n_systems][max_bodies][k] of the largest k that asked for lists
+    DeviceArray<float> neighbours_r2;                      // the same
+    DeviceArray<unsigned char> neighbours_sources;         // [n_systems][max_bodies], the device copy of `sources`
+    DeviceArray<float> neighbours_radius2;                 // [n_systems]
+    std::vector<float> neighbours_radius2_host;            // the last call's b[s] b[s]
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -1945,6 +2123,55 @@ int nbody_batch_span(nbody_batch *b, const float *d_pos, const unsigned char *su
     BATCH_TRY(b, copy_out(b, systems_out, a->span_systems, B));
     BATCH_TRY(b, copy_out(b, edges_out, a->span_edges, slots));
     BATCH_TRY(b, copy_out(b, bodies_out, a->span_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_neighbours(nbody_batch *b, const float *d_pos, int k, const float *radii, const unsigned char *sources,
+                           nbody_batch_neighbour_system *systems_out, nbody_batch_neighbour_body *bodies_out, int *index_out,
+                           float *r2_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_neighbours: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_neighbours: NULL argument");
+    if (k < 1 || k > NBODY_BATCH_NEIGHBOURS_MAX)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_neighbours: k must be 1 ... 8");
+    if (!index_out != !r2_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_neighbours: index_out and r2_out must be given both or neither");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, words = index_out ? slots * (size_t)k : 0;
+    for (size_t s = 0; radii && s < B; ++s) {
+        if (!(radii[s] >= 0.f))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_neighbours: the radius of system " + std::to_string(s) + " must be >= 0");
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    if (radii) {
+        a->neighbours_radius2_host.assign(radii, radii + B);
+        for (float &r : a->neighbours_radius2_host)
+            r = r * r;  // b2: one fp32 product
+    }
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->neighbours_systems.ensure(B));
+    BATCH_TRY(b, a->neighbours_radius2.ensure(radii ? B : 0));
+    BATCH_TRY(b, a->neighbours_sources.ensure(sources ? slots : 0));
+    BATCH_TRY(b, a->neighbours_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->neighbours_index.ensure(words));
+    BATCH_TRY(b, a->neighbours_r2.ensure(words));
+    if (radii)
+        BATCH_TRY(b, hipMemcpyAsync(a->neighbours_radius2.ptr, a->neighbours_radius2_host.data(), sizeof(float) * B,
+                                    hipMemcpyHostToDevice, b->stream));
+    if (sources)
+        BATCH_TRY(b, hipMemcpyAsync(a->neighbours_sources.ptr, sources, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_neighbours(reinterpret_cast<const float4 *>(d_pos), b->counts_dev.ptr,
+                                         sources ? a->neighbours_sources.ptr : nullptr, radii ? a->neighbours_radius2.ptr : nullptr,
+                                         (int)b->n_systems, (int)b->max_bodies, k, bodies_out ? a->neighbours_bodies.ptr : nullptr,
+                                         index_out ? a->neighbours_index.ptr : nullptr, index_out ? a->neighbours_r2.ptr : nullptr,
+                                         a->neighbours_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->neighbours_systems, B));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->neighbours_bodies, slots));
+    BATCH_TRY(b, copy_out(b, index_out, a->neighbours_index, words));
+    BATCH_TRY(b, copy_out(b, r2_out, a->neighbours_r2, words));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

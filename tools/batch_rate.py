@@ -101,7 +101,15 @@ the kernel, its launch and the wait for it), the same with separations, the whol
 subsets of 20 random bodies per system, against groups() without its records at one mean spacing and pairs() on the same
 state -- all synchronous calls, wall clock, alternated, medians and spreads -- and the rounds run.  A round is one n x n walk of
 about a dozen fp32 and integer operations per pair; the separations take one more walk with an fp32 square root and an fp64
-add per pair.  The kernel's time alone comes from a traced run of this mode."""
+add per pair.  The kernel's time alone comes from a traced run of this mode.
+
+--neighbours: instead, the nearest-neighbour lists (BatchedSystem.neighbours).  For n x B = 1024 x 1024 and 4096 x 256 (or
+--cases), one line per case on Plummer spheres: neighbours() without the lists and the per-body records (40 bytes per system come
+back: the kernel, its launch and the wait for it) at k = 1, 6 and 8, the same at k = 6 with a radius of one mean spacing and with
+the first 8 bodies of every system as the only sources, and the whole call at k = 6 with the lists and the records, against
+structure(k=6) without its records and pairs() on the same state -- all synchronous calls, wall clock, alternated, medians and
+spreads.  The kernel always keeps eight (r2, index) pairs per row, so k changes only what is stored; a column costs a row about
+6 + 2 + 8 x 5 vector operations against 6 + 8 x 2 in the first of structure()'s three walks."""
 import argparse
 import json
 import os
@@ -153,6 +161,8 @@ ap.add_argument("--groups", action="store_true", help="groups() at 0.2 and 1.0 m
                 "per-body records against pairs() on the same Plummer spheres, wall clock, and the sweeps run")
 ap.add_argument("--span", action="store_true", help="spanning_tree() with and without the separations, the records and subsets "
                 "of 20 bodies against groups() and pairs() on the same Plummer spheres, wall clock, and the rounds run")
+ap.add_argument("--neighbours", action="store_true", help="neighbours() at k = 1, 6 and 8, with a radius, with 8 sources and with "
+                "the lists against structure(k=6) and pairs() on the same Plummer spheres, wall clock")
 args = ap.parse_args()
 
 
@@ -1003,6 +1013,65 @@ def span_lines():
         print(json.dumps(line), flush=True)
 
 
+def neighbours_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        spacing = float(np.float32((4.0 / 3.0 * np.pi * 1.3048 ** 3 / (n / 2.0)) ** (1.0 / 3.0)))   # as in --groups
+        massive = np.zeros((B, n), np.uint8)
+        massive[:, :8] = 1
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"pairs": batch.pairs,
+                     "structure_lean_k6": lambda: batch.structure(k=6, bodies=False),
+                     "neighbours_lean_k1": lambda: batch.neighbours(k=1, lists=False, bodies=False),
+                     "neighbours_lean_k6": lambda: batch.neighbours(k=6, lists=False, bodies=False),
+                     "neighbours_lean_k8": lambda: batch.neighbours(k=8, lists=False, bodies=False),
+                     "neighbours_lean_k6_radius": lambda: batch.neighbours(k=6, radius=spacing, lists=False, bodies=False),
+                     "neighbours_lean_k6_sources_8": lambda: batch.neighbours(k=6, sources=massive, lists=False, bodies=False),
+                     "neighbours_k6": lambda: batch.neighbours(k=6, radius=spacing)}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        res = found["neighbours_k6"]
+        line.update({"lean_k6_over_structure_lean": round(med["neighbours_lean_k6"] / med["structure_lean_k6"], 3),
+                     "lean_k6_over_pairs": round(med["neighbours_lean_k6"] / med["pairs"], 3),
+                     "lists_ms": round(med["neighbours_k6"] - med["neighbours_lean_k6_radius"], 3),
+                     "pair_walks_per_s": float(f"{B * n * n / (med['neighbours_lean_k6'] * 1e-3):.4g}"),
+                     "mutual_fraction": round(float(res.mutual.sum()) / float(res.bodies.sum()), 4),
+                     "mean_within": round(float(res.within.mean()), 3),
+                     "median_mean_nearest": round(float(np.median(res.mean_nearest)), 5),
+                     "median_mean_kth": round(float(np.median(res.mean_kth)), 5),
+                     "list_megabytes": round(B * n * 6 * 8 / 1e6, 1), "body_megabytes": round(B * n * 8 / 1e6, 1),
+                     "system_kilobytes": round(B * 40 / 1e3, 1)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.neighbours:
+    neighbours_lines()
+    sys.exit(0)
 if args.span:
     span_lines()
     sys.exit(0)
