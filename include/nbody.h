@@ -551,6 +551,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_span.h"
 /* neighbours: every body's k nearest sources by index and squared distance, and how many lie within a radius */
 #include "nbody_batch_neighbours.h"
+/* correlation: per system the ordered pairs (row, source) in each of up to 32 bins of separation, for xi(r), C(r) and DD / DR / RR */
+#include "nbody_batch_correlation.h"
 
 #ifdef __cplusplus
 }

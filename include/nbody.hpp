@@ -655,6 +655,35 @@ public:
               "nbody_batch_neighbours");
         return s;
     }
+    // Pair-separation counts (nbody_batch_correlation.h): for every system the ordered pairs (row, source) in each bin of
+    // separation, from the positions in the caller's buffer.  edges: bins + 1 ascending values >= 0 (host), one set for all
+    // systems, or numSystems sets, one per system; bins is 1 ... 32.  rows, sources: empty for all bodies, or numSystems x
+    // maxBodies bytes (host), non-zero where a body is a row or a source.  Per system the rows, the sources, those that are
+    // both, the pairs examined and those below the first edge, above the last and unmeasured.  counts, where given, is resized
+    // to numSystems x bins and takes the bins; nullptr skips that copy.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_correlation_system> correlation(const float *dPositions, int bins, const std::vector<float> &edges,
+                                                            const std::vector<unsigned char> &rows = {},
+                                                            const std::vector<unsigned char> &sources = {},
+                                                            std::vector<unsigned int> *counts = nullptr)
+    {
+        if (bins < 1 || bins > NBODY_BATCH_CORRELATION_MAX_BINS)
+            throw std::invalid_argument("nbody::Batch::correlation: bins must be 1 ... 32");
+        const size_t set = (size_t)bins + 1;
+        if (edges.size() != set && edges.size() != (size_t)systems_ * set)
+            throw std::invalid_argument("nbody::Batch::correlation: bins + 1 edges, or as many per system");
+        if (!rows.empty() && rows.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::correlation: one row byte per slot, or none");
+        if (!sources.empty() && sources.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::correlation: one source byte per slot, or none");
+        std::vector<nbody_batch_correlation_system> s((size_t)systems_);
+        if (counts)
+            counts->resize((size_t)systems_ * (size_t)bins);
+        const int perSystem = edges.size() == set ? 0 : 1;
+        check(nbody_batch_correlation(b_, dPositions, bins, edges.data(), perSystem, rows.empty() ? nullptr : rows.data(),
+                                      sources.empty() ? nullptr : sources.data(), s.data(), counts ? counts->data() : nullptr),
+              "nbody_batch_correlation");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

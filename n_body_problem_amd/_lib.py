@@ -432,6 +432,22 @@ _NEIGHBOURS_PROTOTYPES = {
 }
 
 
+BATCH_CORRELATION_MAX_BINS = 32
+
+
+class BatchCorrelationSystem(ctypes.Structure):
+    """``nbody_batch_correlation_system`` of include/nbody_batch_correlation.h."""
+    _fields_ = [("rows", c_int), ("sources", c_int), ("both", c_int), ("bins", c_int), ("pairs", ctypes.c_longlong),
+                ("below", ctypes.c_longlong), ("above", ctypes.c_longlong), ("unmeasured", ctypes.c_longlong)]
+
+
+#: the entry point of include/nbody_batch_correlation.h (pair-separation counts of batched ensembles), which nbody.h includes
+_CORRELATION_PROTOTYPES = {
+    "nbody_batch_correlation": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_float), c_int, POINTER(ctypes.c_ubyte),
+                                        POINTER(ctypes.c_ubyte), POINTER(BatchCorrelationSystem), POINTER(ctypes.c_uint)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -461,7 +477,7 @@ def load() -> ctypes.CDLL:
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
-                list(_NEIGHBOURS_PROTOTYPES.items()):
+                list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -552,6 +568,11 @@ def span_names():
 def neighbours_names():
     """The entry point of nbody_batch_neighbours.h."""
     return list(_NEIGHBOURS_PROTOTYPES)
+
+
+def correlation_names():
+    """The entry point of nbody_batch_correlation.h."""
+    return list(_CORRELATION_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -89,6 +89,10 @@ NEIGHBOUR_SYSTEM_DTYPE = np.dtype([("bodies", np.int32), ("sources", np.int32), 
 NEIGHBOUR_BODY_DTYPE = np.dtype([("found", np.int32), ("within", np.int32)])
 assert NEIGHBOUR_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchNeighbourSystem) == 40
 assert NEIGHBOUR_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchNeighbourBody) == 8
+#: the record of :meth:`BatchedSystem.correlation`: numpy's view of ``nbody_batch_correlation_system``
+CORRELATION_SYSTEM_DTYPE = np.dtype([("rows", np.int32), ("sources", np.int32), ("both", np.int32), ("bins", np.int32),
+                                     ("pairs", np.int64), ("below", np.int64), ("above", np.int64), ("unmeasured", np.int64)])
+assert CORRELATION_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchCorrelationSystem) == 48
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -739,6 +743,56 @@ class BatchedSystem:
             r2.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if lists else None), self._h)
         return NeighbourResult(systems, body, index, r2, k)
 
+    def correlation(self, edges, rows=None, sources=None, counts: bool = True) -> "CorrelationResult":
+        """How many pairs lie at which separation (``include/nbody_batch_correlation.h`` states the rules): for every system
+        the number of ordered pairs (row, source) in each bin of separation, counted on the device from the current state
+        (waits for the queued work).  ``edges`` holds the ``bins + 1`` (2 ... 33) ascending bin edges, ``>= 0``: one set
+        ``(bins + 1,)`` for all systems or ``(B, bins + 1)``, one per system.  Bin ``t`` holds the pairs with
+        ``edges[t] < r <= edges[t + 1]``, compared as fp32 squares, which is :meth:`neighbours`' ``within`` and :meth:`groups`'
+        link.  ``rows`` and ``sources``, ``(B, max_bodies)`` bool or uint8 arrays (numpy or torch), select who is counted
+        around whom (all bodies, without them); a body is never paired with itself.  With the same mask on both sides every
+        unordered pair is counted twice.  Two different masks give a cross-count: planetesimals around planets, the stars of
+        one cluster around those of another.  ``counts=False`` skips the bins on their way to the host: ``counts`` of the
+        result is ``None``, the per-system words (``pairs``, ``below``, ``above``, ``unmeasured``) the same bits.  Changes
+        nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if hasattr(edges, "detach"):  # a torch tensor
+            edges = edges.detach().cpu().numpy()
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32))
+        if e.ndim == 1:
+            per_system = 0
+        elif e.ndim == 2 and e.shape[0] == B:
+            per_system = 1
+        else:
+            raise ValueError(f"edges must have shape (bins + 1,) or ({B}, bins + 1), got {tuple(e.shape)}")
+        bins = e.shape[-1] - 1
+        if not 1 <= bins <= _lib.BATCH_CORRELATION_MAX_BINS:
+            raise ValueError(f"bins must be 1 ... {_lib.BATCH_CORRELATION_MAX_BINS}, not {bins}")
+
+        def mask(name, m):
+            if m is None:
+                return None
+            if hasattr(m, "detach"):
+                m = m.detach().cpu().numpy()
+            m = np.ascontiguousarray(np.asarray(m))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError(f"{name} must be bool or uint8, not {m.dtype}")
+            if m.shape != (B, n):
+                raise ValueError(f"{name} must have shape ({B}, {n}), got {tuple(m.shape)}")
+            return m.view(np.uint8)
+
+        row, src = mask("rows", rows), mask("sources", sources)
+        systems = np.zeros(B, dtype=CORRELATION_SYSTEM_DTYPE)
+        out = np.zeros((B, bins), dtype=np.uint32) if counts else None
+        ubyte = ctypes.POINTER(ctypes.c_ubyte)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_correlation(
+            self._h, _ptr(self.positions), bins, e.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), per_system,
+            row.ctypes.data_as(ubyte) if row is not None else None, src.ctypes.data_as(ubyte) if src is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchCorrelationSystem)),
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)) if counts else None), self._h)
+        return CorrelationResult(systems, out.astype(np.int64) if counts else None, e)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1166,6 +1220,94 @@ class NeighbourResult:
                 f"mutual={self.mutual.tolist()}, mean_nearest={self.mean_nearest.tolist()})")
 
 
+class CorrelationResult:
+    """What :meth:`BatchedSystem.correlation` counted.  ``edges`` are the bin edges as given (float32, ``(bins + 1,)`` or
+    ``(B, bins + 1)``); ``counts`` is ``(B, bins)`` int64, the ordered pairs (row, source) with
+    ``edges[t] < r <= edges[t + 1]``, or ``None`` without ``counts``.  Per system (``(B,)`` arrays): ``rows`` and ``sources``
+    (int32: the selected bodies below the count), ``both`` (those that are a row and a source), ``pairs`` (int64: the pairs
+    examined, ``rows * sources - both``), ``below`` (within the first edge; with a first edge of 0 the coincident pairs),
+    ``above`` (beyond the last edge) and ``unmeasured`` (a NaN or infinite coordinate), so that
+    ``below + counts.sum(axis=1) + above + unmeasured == pairs``.  ``auto`` (bool) tells where rows and sources are the same
+    bodies: there every unordered pair was counted twice, every count is even and ``unordered`` is ``counts // 2`` (-1
+    elsewhere).  ``systems`` is the records themselves, ``bins`` the number of bins."""
+
+    def __init__(self, systems, counts, edges):
+        self.systems, self.counts, self.edges = systems, counts, edges
+        for name in ("rows", "sources", "both", "pairs", "below", "above", "unmeasured"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.bins = int(edges.shape[-1]) - 1
+        self.auto = (self.rows == self.both) & (self.sources == self.both)
+
+    def _need_counts(self):
+        if self.counts is None:
+            raise ValueError("this needs the bins: call correlation(counts=True)")
+
+    def _edges(self) -> np.ndarray:
+        """``(B, bins + 1)`` float64."""
+        return np.broadcast_to(self.edges.astype(np.float64), (len(self.systems), self.bins + 1))
+
+    @property
+    def unordered(self) -> np.ndarray:
+        """``(B, bins)`` int64: the unordered pairs per bin where ``auto``, -1 in the systems where not."""
+        self._need_counts()
+        return np.where(self.auto[:, None], self.counts // 2, -1)
+
+    def cumulative(self) -> np.ndarray:
+        """``(B, bins)`` int64: the ordered pairs within the upper edge of every bin, ``below + cumsum(counts)``: what
+        ``neighbours(radius=edge).within`` sums to over the rows.  Divided by ``pairs`` it is the correlation integral."""
+        self._need_counts()
+        return self.below[:, None] + np.cumsum(self.counts, axis=1)
+
+    def shell_volumes(self) -> np.ndarray:
+        """``(B, bins)`` float64: ``4 pi / 3 (hi^3 - lo^3)`` of every bin."""
+        e = self._edges()
+        return 4.0 / 3.0 * np.pi * (e[:, 1:] ** 3 - e[:, :-1] ** 3)
+
+    def density(self) -> np.ndarray:
+        """``(B, bins)`` float64: the ordered counts per row and shell volume -- the mean number density of sources around a
+        row at that separation.  NaN in a system without rows."""
+        self._need_counts()
+        rows = np.where(self.rows > 0, self.rows, 1).astype(np.float64)[:, None]
+        return np.where(self.rows[:, None] > 0, self.counts / rows / self.shell_volumes(), np.nan)
+
+    def xi(self, mean_density) -> np.ndarray:
+        """``(B, bins)`` float64: the two-point correlation function against a mean source density (a scalar or ``B`` values):
+        ``density() / mean_density - 1``."""
+        mean = np.asarray(mean_density, dtype=np.float64)
+        return self.density() / (mean[:, None] if mean.ndim == 1 else mean) - 1.0
+
+    def correlation_dimension(self, lo: int = 0, hi=None) -> np.ndarray:
+        """``(B,)`` float64: the slope of ``log cumulative()`` against the log of the bins' upper edges over the bins
+        ``lo ... hi`` (both included; ``hi`` defaults to the last), by least squares: the correlation dimension D2 where the
+        correlation integral is a power law.  NaN where a cumulative count in the range is 0."""
+        hi = self.bins - 1 if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi < self.bins:
+            raise ValueError(f"need 0 <= lo < hi < {self.bins}, got {lo} and {hi}")
+        c = self.cumulative()[:, lo:hi + 1].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            y = np.where(c > 0, np.log(np.where(c > 0, c, 1.0)), np.nan)
+            x = np.log(self._edges()[:, lo + 1:hi + 2])
+            x = x - x.mean(axis=1, keepdims=True)
+            return (x * (y - y.mean(axis=1, keepdims=True))).sum(axis=1) / (x * x).sum(axis=1)
+
+    @staticmethod
+    def landy_szalay(dd, dr, rr, n_d, n_r) -> np.ndarray:
+        """The Landy-Szalay estimator ``(DD - 2 DR + RR) / RR`` of xi from three ordered counts as :meth:`correlation` gives
+        them -- ``dd`` data around data, ``dr`` data around randoms (or randoms around data), ``rr`` randoms around randoms --
+        each normalised by its ordered pairs: ``n_d (n_d - 1)``, ``n_d n_r`` and ``n_r (n_r - 1)``.  NaN where ``rr`` is 0."""
+        dd, dr, rr = (np.asarray(a, dtype=np.float64) for a in (dd, dr, rr))
+        n_d, n_r = np.asarray(n_d, dtype=np.float64), np.asarray(n_r, dtype=np.float64)
+        n_d, n_r = (n[:, None] if n.ndim == 1 else n for n in (n_d, n_r))
+        DD, DR, RR = dd / (n_d * (n_d - 1.0)), dr / (n_d * n_r), rr / (n_r * (n_r - 1.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(RR > 0, (DD - 2.0 * DR + RR) / np.where(RR > 0, RR, 1.0), np.nan)
+
+    def __repr__(self):
+        return (f"CorrelationResult(bins={self.bins}, pairs={self.pairs.tolist()}, below={self.below.tolist()}, "
+                f"above={self.above.tolist()}, unmeasured={self.unmeasured.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -1240,4 +1382,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

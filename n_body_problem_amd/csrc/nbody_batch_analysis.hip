@@ -1,9 +1,10 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
-// structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, energy and momentum
-// (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_neighbours.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, energy and
+// momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_correlation.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
+#include "nbody_batch_correlation_math.h"
 #include "nbody_batch_gravity_math.h"
 #include "nbody_batch_groups_math.h"
 #include "nbody_batch_handle.h"
@@ -1745,6 +1746,166 @@ hipError_t launch_batch_neighbours(const float4 *pos, const int *counts, const u
     });
 }
 
+// ---- correlation (include/nbody_batch_correlation.h): per system the ordered pairs (row, source) in each of up to 32 bins of
+// separation, and those below the first edge, above the last and unmeasured.  A sibling of batch_neighbours_kernel, whose
+// count within a radius this is at bins + 1 radii at once: one workgroup per system with batch_shape's workgroup, the columns
+// broadcast from LDS, RPL rows per lane at r = q * T + lane.  It reads the positions and writes only the handle's records.
+
+static_assert(sizeof(BatchCorrelationSystem) == sizeof(nbody_batch_correlation_system) && sizeof(nbody_batch_correlation_system) == 48 &&
+                  offsetof(BatchCorrelationSystem, rows) == offsetof(nbody_batch_correlation_system, rows) &&
+                  offsetof(BatchCorrelationSystem, sources) == offsetof(nbody_batch_correlation_system, sources) &&
+                  offsetof(BatchCorrelationSystem, both) == offsetof(nbody_batch_correlation_system, both) &&
+                  offsetof(BatchCorrelationSystem, bins) == offsetof(nbody_batch_correlation_system, bins) &&
+                  offsetof(BatchCorrelationSystem, pairs) == offsetof(nbody_batch_correlation_system, pairs) &&
+                  offsetof(BatchCorrelationSystem, below) == offsetof(nbody_batch_correlation_system, below) &&
+                  offsetof(BatchCorrelationSystem, above) == offsetof(nbody_batch_correlation_system, above) &&
+                  offsetof(BatchCorrelationSystem, unmeasured) == offsetof(nbody_batch_correlation_system, unmeasured) &&
+                  offsetof(nbody_batch_correlation_system, pairs) == 16 && offsetof(nbody_batch_correlation_system, unmeasured) == 40,
+              "nbody_batch_correlation_math.h mirrors the system record of nbody_batch_correlation.h");
+static_assert(kCorrelationMaxBins == NBODY_BATCH_CORRELATION_MAX_BINS, "nbody_batch_correlation_math.h mirrors the limit of nbody_batch_correlation.h");
+
+// The two loops, the same integers.  0: counters the wave shares -- per column and edge one v_cmp against a wave-uniform e2[t],
+// whose lane mask is popcounted and added into a scalar register: no vector register per counter, whatever the rows per lane.
+// 1: a counter per lane and edge, BINS + 2 more vector registers, summed over the wave once at the end; the compiler makes a
+// compare, a select and half an add3 of each edge and pair, 2.6 vector instructions.
+// Measured on an MI355X (profiles/batch_rate_correlation.txt; lean calls at 32 bins, ms): loop 0 2.68 at 1024 x 1024 and 10.40
+// at 4096 x 256, loop 1 3.04 and 11.70.  Loop 0 is bound by the scalar unit, which the four SIMDs of a compute unit share: its
+// first form, which AND-ed every edge's mask with the mask of the lanes that examine the pair (three scalar instructions per
+// edge and pair), took 3.68 and 14.47 and lost to loop 1; hiding a pair that is not examined behind a NaN (one select per
+// pair) leaves two scalar instructions per edge and pair, and wins.  So: loop 0.
+#ifndef NBODY_BATCH_CORRELATION_LANE_COUNTERS
+#define NBODY_BATCH_CORRELATION_LANE_COUNTERS 0
+#endif
+
+constexpr int kCorrelationTallies = 3;  // rows, sources, both
+
+#if NBODY_BATCH_CORRELATION_LANE_COUNTERS
+using CorrelationAdd = CorrelationAddOne;
+// The wave's sum of its lanes' counters, in lane 0.
+__device__ inline unsigned int correlation_wave_total(unsigned int word)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        word += __shfl_down(word, off, 64);
+    return word;
+}
+#else
+// The counter of a wave takes the number of its lanes whose flag is set.  A pair that is not examined shows a NaN, one select
+// per pair, so that the flag is a compare alone, whose result is a lane mask already: the builtin takes it as that (__ballot
+// would make a word per lane of it and compare again), and the count and the addition are scalar instructions.
+struct CorrelationAdd {
+    __device__ float seen(bool examined, float r2) const { return examined ? r2 : __builtin_nanf(""); }
+    __device__ void operator()(unsigned int &word, bool, bool flag) const
+    {
+        word += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(flag));
+    }
+};
+__device__ inline unsigned int correlation_wave_total(unsigned int word) { return word; }
+#endif
+
+// LDS: img[j] = {x, y, z, source flag} of body j as four words, one ds_read_b128 per column (64 KiB at 4096 bodies; with the
+// totals above the default limit, which is raised before the launch).  edges2 holds BINS + 1 squared edges per system
+// (edge_stride = BINS + 1) or one set for all (edge_stride = 0), the edges from `bins` on copies of edge `bins`: their
+// counters equal within[bins] and are not read.  BINS is a template argument and every loop over the edges is unrolled, so
+// that no edge index ever becomes a register index.  rows, sources and counts_out may be NULL.
+template <int RPL, int BINS>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_correlation_kernel(
+    const float4 *__restrict__ pos, const int *__restrict__ counts, const unsigned char *__restrict__ rows,
+    const unsigned char *__restrict__ sources, const float *__restrict__ edges2, int edge_stride, int max_bodies, int bins,
+    unsigned int *__restrict__ counts_out, BatchCorrelationSystem *__restrict__ systems)
+{
+    constexpr int EDGES = BINS + 1;
+    extern __shared__ int4 img[];
+    __shared__ unsigned int total[EDGES + 1];  // within[0 ... BINS], measured
+    __shared__ int tally[kCorrelationTallies];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float *mine2 = edges2 + (size_t)blockIdx.x * (size_t)edge_stride;
+    float e2[EDGES];  // the same in every lane
+#pragma unroll
+    for (int t = 0; t < EDGES; ++t)
+        e2[t] = mine2[t];
+    if (tid < EDGES + 1)
+        total[tid] = 0;
+    if (tid < kCorrelationTallies)
+        tally[tid] = 0;
+    __syncthreads();
+    float4 x[RPL];  // {x, y, z, the mass word}
+    bool row[RPL];
+    int n_rows = 0, n_sources = 0, n_both = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        row[q] = false;
+        if (r < n) {
+            x[q] = pos[base + r];
+            const bool source = !sources || sources[base + r] != 0;
+            row[q] = !rows || rows[base + r] != 0;
+            n_rows += row[q] ? 1 : 0;
+            n_sources += source ? 1 : 0;
+            n_both += row[q] && source ? 1 : 0;
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z), source ? 1 : 0);
+        }
+    }
+    // Integers: the order of the additions does not matter.
+    if (n_rows)
+        atomicAdd(&tally[0], n_rows);
+    if (n_sources)
+        atomicAdd(&tally[1], n_sources);
+    if (n_both)
+        atomicAdd(&tally[2], n_both);
+    __syncthreads();  // the image is in place
+    CorrelationCounters<EDGES> c;
+    correlation_clear(c);
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[j];  // a wave-uniform address: one broadcast LDS read
+        if (__builtin_amdgcn_readfirstlane(pj.w) == 0)
+            continue;  // no source: the flag is the same in every lane, so the branch is a scalar one
+        const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            correlation_step(c, correlation_examined(row[q], true, q * T + tid, j), x[q].x, x[q].y, x[q].z, xj, yj, zj, e2, CorrelationAdd{});
+    }
+    // Every wave adds its counters into the totals; t is a constant in every copy of the body.
+#pragma unroll
+    for (int t = 0; t < EDGES; ++t) {
+        const unsigned int w = correlation_wave_total(c.within[t]);
+        if ((tid & 63) == 0 && w)
+            atomicAdd(&total[t], w);
+    }
+    const unsigned int m = correlation_wave_total(c.measured);
+    if ((tid & 63) == 0 && m)
+        atomicAdd(&total[EDGES], m);
+    __syncthreads();
+    // One lane per word: the bins by differences of their two edges, and the record.
+    if (counts_out && tid < bins)
+        counts_out[(size_t)blockIdx.x * (size_t)bins + tid] = correlation_bin(total[tid], total[tid + 1]);
+    if (tid == 0)
+        systems[blockIdx.x] = correlation_record(tally[0], tally[1], tally[2], bins, total, total[EDGES]);
+}
+
+// One launch over all systems.  16 bytes of dynamic LDS per body, 64 KiB at 4096 bodies beside the totals.  The call runs the
+// instantiation of correlation_padded_bins(bins), for which edges2 is laid out.  rows, sources and counts_out may be NULL.
+hipError_t launch_batch_correlation(const float4 *pos, const int *counts, const unsigned char *rows, const unsigned char *sources,
+                                    const float *edges2, int edge_stride, int n_systems, int max_bodies, int bins,
+                                    unsigned int *counts_out, BatchCorrelationSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        const auto launch = [&](auto padded) {
+            return launch_analysis_kernel(batch_correlation_kernel<rpl(), padded()>, n_systems, sh.threads, lds, stream, pos, counts,
+                                          rows, sources, edges2, edge_stride, max_bodies, bins, counts_out, systems);
+        };
+        switch (correlation_padded_bins(bins)) {
+        case 8: return launch(std::integral_constant<int, 8>{});
+        case 16: return launch(std::integral_constant<int, 16>{});
+        default: return launch(std::integral_constant<int, kCorrelationMaxBins>{});
+        }
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -1850,6 +2011,12 @@ struct BatchAnalysis {
     DeviceArray<unsigned char> neighbours_sources;         // [n_systems][max_bodies], the device copy of `sources`
     DeviceArray<float> neighbours_radius2;                 // [n_systems]
     std::vector<float> neighbours_radius2_host;            // the last call's b[s] b[s]
+    DeviceArray<BatchCorrelationSystem> correlation_systems;  // [n_systems]
+    DeviceArray<unsigned int> correlation_counts;             // [n_systems][bins] of the largest call that asked for counts
+    DeviceArray<unsigned char> correlation_rows;              // [n_systems][max_bodies], the device copy of `rows`
+    DeviceArray<unsigned char> correlation_sources;           // [n_systems][max_bodies], the device copy of `sources`
+    DeviceArray<float> correlation_edges2;                    // one set or [n_systems] sets of padded bins + 1 squared edges
+    std::vector<float> correlation_edges2_host;               // the last call's: the copy's source until the stream is idle
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -2172,6 +2339,59 @@ int nbody_batch_neighbours(nbody_batch *b, const float *d_pos, int k, const floa
     BATCH_TRY(b, copy_out(b, bodies_out, a->neighbours_bodies, slots));
     BATCH_TRY(b, copy_out(b, index_out, a->neighbours_index, words));
     BATCH_TRY(b, copy_out(b, r2_out, a->neighbours_r2, words));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_correlation(nbody_batch *b, const float *d_pos, int bins, const float *edges, int per_system,
+                            const unsigned char *rows, const unsigned char *sources, nbody_batch_correlation_system *systems_out,
+                            unsigned int *counts_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_correlation: batch is NULL");
+    if (!d_pos || !edges || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_correlation: NULL argument");
+    if (bins < 1 || bins > NBODY_BATCH_CORRELATION_MAX_BINS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_correlation: bins must be 1 ... 32");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, sets = per_system ? B : 1;
+    const size_t given = (size_t)bins + 1, padded = (size_t)correlation_padded_bins(bins) + 1;
+    for (size_t s = 0; s < sets; ++s) {
+        const float *e = edges + s * given;
+        const std::string which = per_system ? " of system " + std::to_string(s) : std::string(" of all systems");
+        for (size_t t = 0; t < given; ++t) {
+            if (!correlation_edge_valid(e[t]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_correlation: edge " + std::to_string(t) + which + " must be finite and >= 0");
+            if (t > 0 && !(e[t] > e[t - 1]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_correlation: edge " + std::to_string(t) + which +
+                                                       " is not above edge " + std::to_string(t - 1) + ": the edges must be strictly ascending");
+        }
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->correlation_edges2_host.resize(sets * padded);
+    for (size_t s = 0; s < sets; ++s)
+        for (size_t t = 0; t < padded; ++t)  // e2: one fp32 product; from `bins` on copies of the last edge
+            a->correlation_edges2_host[s * padded + t] = correlation_edge2(edges[s * given + (t < given ? t : given - 1)]);
+    const size_t words = counts_out ? B * (size_t)bins : 0;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->correlation_systems.ensure(B));
+    BATCH_TRY(b, a->correlation_edges2.ensure(sets * padded));
+    BATCH_TRY(b, a->correlation_rows.ensure(rows ? slots : 0));
+    BATCH_TRY(b, a->correlation_sources.ensure(sources ? slots : 0));
+    BATCH_TRY(b, a->correlation_counts.ensure(words));
+    BATCH_TRY(b, hipMemcpyAsync(a->correlation_edges2.ptr, a->correlation_edges2_host.data(), sizeof(float) * sets * padded,
+                                hipMemcpyHostToDevice, b->stream));
+    if (rows)
+        BATCH_TRY(b, hipMemcpyAsync(a->correlation_rows.ptr, rows, slots, hipMemcpyHostToDevice, b->stream));
+    if (sources)
+        BATCH_TRY(b, hipMemcpyAsync(a->correlation_sources.ptr, sources, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_correlation(reinterpret_cast<const float4 *>(d_pos), b->counts_dev.ptr,
+                                          rows ? a->correlation_rows.ptr : nullptr, sources ? a->correlation_sources.ptr : nullptr,
+                                          a->correlation_edges2.ptr, per_system ? (int)padded : 0, (int)b->n_systems,
+                                          (int)b->max_bodies, bins, counts_out ? a->correlation_counts.ptr : nullptr,
+                                          a->correlation_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->correlation_systems, B));
+    BATCH_TRY(b, copy_out(b, counts_out, a->correlation_counts, words));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

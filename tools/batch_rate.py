@@ -109,7 +109,16 @@ back: the kernel, its launch and the wait for it) at k = 1, 6 and 8, the same at
 the first 8 bodies of every system as the only sources, and the whole call at k = 6 with the lists and the records, against
 structure(k=6) without its records and pairs() on the same state -- all synchronous calls, wall clock, alternated, medians and
 spreads.  The kernel always keeps eight (r2, index) pairs per row, so k changes only what is stored; a column costs a row about
-6 + 2 + 8 x 5 vector operations against 6 + 8 x 2 in the first of structure()'s three walks."""
+6 + 2 + 8 x 5 vector operations against 6 + 8 x 2 in the first of structure()'s three walks.
+
+--correlation: instead, the pair-separation counts (BatchedSystem.correlation).  For n x B = 1024 x 1024 and 4096 x 256 (or
+--cases), one line per case on Plummer spheres: correlation() without the bins (48 bytes per system come back: the kernel, its
+launch and the wait for it) at 8, 16 and 32 bins between 0.02 and 5 length units, logarithmically spaced, the same at 32 bins
+with the first 8 bodies of every system as the only sources, and the whole call at 32 bins with the bins, against pairs() and
+neighbours(k=6) without its lists and records on the same state -- all synchronous calls, wall clock, alternated, medians and
+spreads.  The kernel has two loops behind NBODY_BATCH_CORRELATION_LANE_COUNTERS: the line names the library it timed
+(NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both.  By instruction count a column costs a row
+about 7 + bins vector operations."""
 import argparse
 import json
 import os
@@ -163,6 +172,8 @@ ap.add_argument("--span", action="store_true", help="spanning_tree() with and wi
                 "of 20 bodies against groups() and pairs() on the same Plummer spheres, wall clock, and the rounds run")
 ap.add_argument("--neighbours", action="store_true", help="neighbours() at k = 1, 6 and 8, with a radius, with 8 sources and with "
                 "the lists against structure(k=6) and pairs() on the same Plummer spheres, wall clock")
+ap.add_argument("--correlation", action="store_true", help="correlation() at 8, 16 and 32 bins, with 8 sources and with the bins "
+                "against pairs() and neighbours(k=6) on the same Plummer spheres, wall clock")
 args = ap.parse_args()
 
 
@@ -1069,6 +1080,62 @@ def neighbours_lines():
         print(json.dumps(line), flush=True)
 
 
+def correlation_lines():
+    import time
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        edges = {bins: np.geomspace(0.02, 5.0, bins + 1).astype(np.float32) for bins in (8, 16, 32)}
+        massive = np.zeros((B, n), np.uint8)
+        massive[:, :8] = 1
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            calls = {"pairs": batch.pairs,
+                     "neighbours_lean_k6": lambda: batch.neighbours(k=6, lists=False, bodies=False),
+                     "correlation_lean_8": lambda: batch.correlation(edges[8], counts=False),
+                     "correlation_lean_16": lambda: batch.correlation(edges[16], counts=False),
+                     "correlation_lean_32": lambda: batch.correlation(edges[32], counts=False),
+                     "correlation_lean_32_sources_8": lambda: batch.correlation(edges[32], sources=massive, counts=False),
+                     "correlation_32": lambda: batch.correlation(edges[32])}
+            for fn in calls.values():                   # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):               # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree")}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        res = found["correlation_32"]
+        for bins in (8, 16, 32):
+            line[f"lean_{bins}_over_neighbours_lean"] = round(med[f"correlation_lean_{bins}"] / med["neighbours_lean_k6"], 3)
+        line.update({"pair_walks_per_s": float(f"{B * n * n / (med['correlation_lean_32'] * 1e-3):.4g}"),
+                     "counted_fraction": round(float(res.counts.sum()) / float(res.pairs.sum()), 4),
+                     "below_fraction": round(float(res.below.sum()) / float(res.pairs.sum()), 6),
+                     "above_fraction": round(float(res.above.sum()) / float(res.pairs.sum()), 6),
+                     "fullest_bin_fraction": round(float(res.counts.sum(axis=0).max()) / float(res.pairs.sum()), 4),
+                     "count_kilobytes": round(B * 32 * 4 / 1e3, 1), "system_kilobytes": round(B * 48 / 1e3, 1)})
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+            line[name + "_repeats"] = [round(x, 3) for x in times[name]]
+        print(json.dumps(line), flush=True)
+
+
+if args.correlation:
+    correlation_lines()
+    sys.exit(0)
 if args.neighbours:
     neighbours_lines()
     sys.exit(0)
