@@ -553,6 +553,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_neighbours.h"
 /* correlation: per system the ordered pairs (row, source) in each of up to 32 bins of separation, for xi(r), C(r) and DD / DR / RR */
 #include "nbody_batch_correlation.h"
+/* contacts: per system every pair of bodies within a radius, or within the sum of its two radii, as a list (i, j, r2) with per-body and per-system records */
+#include "nbody_batch_contacts.h"
 
 #ifdef __cplusplus
 }

@@ -684,6 +684,40 @@ public:
               "nbody_batch_correlation");
         return s;
     }
+    // Contact lists (nbody_batch_contacts.h): for every system every unordered pair of bodies within a radius of each other, or
+    // within the sum of their two radii, from the positions in the caller's buffer.  threshold: numSystems values (host), one
+    // radius per system, or numSystems x maxBodies values, one radius per slot.  subset: empty for all bodies, or numSystems x
+    // maxBodies bytes (host), non-zero where a body takes part.  capacity: the list entries kept per system; 0 only counts.
+    // Per system the bodies taking part, those with a contact, the largest degree, the contacts (exact whatever the capacity),
+    // those stored and the closest.  list, where given, is resized to numSystems x capacity and takes the entries (i, j, r2),
+    // i < j, ascending in i and then in j, {-1, -1, +inf} from `stored` on; it must be given iff capacity > 0.  bodies, where
+    // given, is resized to numSystems x maxBodies and takes the per-body records.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_contact_system> contacts(const float *dPositions, const std::vector<float> &threshold,
+                                                     long long capacity = 0, std::vector<nbody_batch_contact> *list = nullptr,
+                                                     const std::vector<unsigned char> &subset = {},
+                                                     std::vector<nbody_batch_contact_body> *bodies = nullptr)
+    {
+        const size_t slots = (size_t)systems_ * (size_t)maxBodies_;
+        const bool perBody = threshold.size() == slots && threshold.size() != (size_t)systems_;
+        if (threshold.size() != (size_t)systems_ && !perBody)
+            throw std::invalid_argument("nbody::Batch::contacts: one radius per system, or one per slot");
+        if (!subset.empty() && subset.size() != slots)
+            throw std::invalid_argument("nbody::Batch::contacts: one subset byte per slot, or none");
+        if (capacity < 0 || (capacity > 0) != (list != nullptr))
+            throw std::invalid_argument("nbody::Batch::contacts: a list iff capacity > 0");
+        if (capacity > NBODY_BATCH_CONTACTS_MAX_ENTRIES / (long long)systems_)
+            throw std::invalid_argument("nbody::Batch::contacts: numSystems x capacity must not exceed 2^28");
+        std::vector<nbody_batch_contact_system> s((size_t)systems_);
+        if (list)
+            list->resize((size_t)systems_ * (size_t)capacity);
+        if (bodies)
+            bodies->resize(slots);
+        check(nbody_batch_contacts(b_, dPositions, perBody ? nullptr : threshold.data(), perBody ? threshold.data() : nullptr,
+                                   subset.empty() ? nullptr : subset.data(), capacity, s.data(), bodies ? bodies->data() : nullptr,
+                                   list ? list->data() : nullptr),
+              "nbody_batch_contacts");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -448,6 +448,34 @@ _CORRELATION_PROTOTYPES = {
 }
 
 
+BATCH_CONTACTS_MAX_ENTRIES = 1 << 28
+
+
+class BatchContactSystem(ctypes.Structure):
+    """``nbody_batch_contact_system`` of include/nbody_batch_contacts.h."""
+    _fields_ = [("bodies", c_int), ("touching", c_int), ("max_degree", c_int), ("reserved", c_int), ("pairs", ctypes.c_longlong),
+                ("stored", ctypes.c_longlong), ("closest_i", c_int), ("closest_j", c_int), ("closest_r2", c_float),
+                ("reserved2", c_int)]
+
+
+class BatchContactBody(ctypes.Structure):
+    """``nbody_batch_contact_body`` of include/nbody_batch_contacts.h."""
+    _fields_ = [("degree", c_int), ("upper", c_int), ("first", c_int), ("nearest", c_int)]
+
+
+class BatchContact(ctypes.Structure):
+    """``nbody_batch_contact`` of include/nbody_batch_contacts.h."""
+    _fields_ = [("i", c_int), ("j", c_int), ("r2", c_float)]
+
+
+#: the entry point of include/nbody_batch_contacts.h (contact lists of batched ensembles), which nbody.h includes
+_CONTACTS_PROTOTYPES = {
+    "nbody_batch_contacts": (c_int, [c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_ubyte),
+                                     ctypes.c_longlong, POINTER(BatchContactSystem), POINTER(BatchContactBody),
+                                     POINTER(BatchContact)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -477,7 +505,8 @@ def load() -> ctypes.CDLL:
                 list(_ACCRETE_PROTOTYPES.items()) + list(_FIELD_PROTOTYPES.items()) + list(_PAIRS_PROTOTYPES.items()) + \
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
-                list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()):
+                list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
+                list(_CONTACTS_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -573,6 +602,11 @@ def neighbours_names():
 def correlation_names():
     """The entry point of nbody_batch_correlation.h."""
     return list(_CORRELATION_PROTOTYPES)
+
+
+def contacts_names():
+    """The entry point of nbody_batch_contacts.h."""
+    return list(_CONTACTS_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -93,6 +93,15 @@ assert NEIGHBOUR_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchNeighbourBody) =
 CORRELATION_SYSTEM_DTYPE = np.dtype([("rows", np.int32), ("sources", np.int32), ("both", np.int32), ("bins", np.int32),
                                      ("pairs", np.int64), ("below", np.int64), ("above", np.int64), ("unmeasured", np.int64)])
 assert CORRELATION_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchCorrelationSystem) == 48
+#: the records of :meth:`BatchedSystem.contacts`: numpy's views of ``nbody_batch_contact_system``, ``_body`` and ``nbody_batch_contact``
+CONTACT_SYSTEM_DTYPE = np.dtype([("bodies", np.int32), ("touching", np.int32), ("max_degree", np.int32), ("reserved", np.int32),
+                                 ("pairs", np.int64), ("stored", np.int64), ("closest_i", np.int32), ("closest_j", np.int32),
+                                 ("closest_r2", np.float32), ("reserved2", np.int32)])
+CONTACT_BODY_DTYPE = np.dtype([("degree", np.int32), ("upper", np.int32), ("first", np.int32), ("nearest", np.int32)])
+CONTACT_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("r2", np.float32)])
+assert CONTACT_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContactSystem) == 48
+assert CONTACT_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContactBody) == 16
+assert CONTACT_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContact) == 12
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -793,6 +802,82 @@ class BatchedSystem:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)) if counts else None), self._h)
         return CorrelationResult(systems, out.astype(np.int64) if counts else None, e)
 
+    def contacts(self, radius=None, *, radii=None, subset=None, capacity=None, lists: bool = True,
+                 bodies: bool = True) -> "ContactsResult":
+        """Which pairs are within a distance of each other (``include/nbody_batch_contacts.h`` states the rules): for every
+        system every unordered pair of bodies that is a contact, listed on the device from the current state (waits for the
+        queued work) as ``(i, j, r2)`` with ``i < j``, ascending in ``i`` and then in ``j``.  Exactly one threshold: ``radius``,
+        a scalar or ``(B,)``, makes a contact of every pair with ``r <= radius`` (compared as fp32 squares, which is
+        :meth:`neighbours`' ``within``, :meth:`correlation`'s edge and :meth:`groups`' link); ``radii``, ``(B, max_bodies)``
+        float32, of every pair with ``r <= R_i + R_j``, :meth:`set_radii`'s own rule at no softening -- ``radii=b.radii()``
+        asks which bodies overlap now.  ``subset``, a ``(B, max_bodies)`` bool or uint8 array (numpy or torch), selects the
+        bodies that take part (all, without it).  ``capacity`` is the number of list entries kept per system: a system with
+        more contacts is ``truncated`` to the first ``capacity`` of them, its ``pairs`` exact all the same.  ``capacity=None``
+        makes one counting call and then one with room for the fullest system.  ``lists=False`` only counts (one call at
+        capacity 0: ``i``, ``j``, ``r2`` are ``None`` and ``stored`` is 0); ``bodies=False`` skips the per-body records on their
+        way to the host.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if (radius is None) == (radii is None):
+            raise ValueError("exactly one of radius and radii must be given")
+        rad = rr = None
+        if radius is not None:
+            if hasattr(radius, "detach"):  # a torch tensor
+                radius = radius.detach().cpu().numpy()
+            rad = np.asarray(radius, dtype=np.float32)
+            if rad.ndim == 0:
+                rad = np.full(B, rad, dtype=np.float32)
+            if rad.shape != (B,):
+                raise ValueError(f"radius must be a scalar or have shape ({B},), got {tuple(rad.shape)}")
+            rad = np.ascontiguousarray(rad)
+        else:
+            if hasattr(radii, "detach"):
+                radii = radii.detach().cpu().numpy()
+            rr = np.ascontiguousarray(np.asarray(radii, dtype=np.float32))
+            if rr.shape != (B, n):
+                raise ValueError(f"radii must have shape ({B}, {n}), got {tuple(rr.shape)}")
+        sub = None
+        if subset is not None:
+            if hasattr(subset, "detach"):
+                subset = subset.detach().cpu().numpy()
+            sub = np.ascontiguousarray(np.asarray(subset))
+            if sub.dtype != np.bool_ and sub.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {sub.dtype}")
+            if sub.shape != (B, n):
+                raise ValueError(f"subset must have shape ({B}, {n}), got {tuple(sub.shape)}")
+            sub = sub.view(np.uint8)
+        if capacity is not None:
+            if int(capacity) != capacity or capacity < 0:
+                raise ValueError(f"capacity must be an integer >= 0, not {capacity!r}")
+            if B * int(capacity) > _lib.BATCH_CONTACTS_MAX_ENTRIES:
+                raise ValueError(f"{B} systems x capacity {capacity} exceed 2^28 list entries")
+        fp, ubyte = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)
+
+        def call(cap, want_bodies):
+            systems = np.zeros(B, dtype=CONTACT_SYSTEM_DTYPE)
+            body = np.zeros((B, n), dtype=CONTACT_BODY_DTYPE) if want_bodies else None
+            entries = np.zeros((B, cap), dtype=CONTACT_DTYPE) if cap > 0 else None
+            self._use_current_stream()
+            _check(self._lib, self._lib.nbody_batch_contacts(
+                self._h, _ptr(self.positions), rad.ctypes.data_as(fp) if rad is not None else None,
+                rr.ctypes.data_as(fp) if rr is not None else None, sub.ctypes.data_as(ubyte) if sub is not None else None,
+                cap, systems.ctypes.data_as(ctypes.POINTER(_lib.BatchContactSystem)),
+                body.ctypes.data_as(ctypes.POINTER(_lib.BatchContactBody)) if want_bodies else None,
+                entries.ctypes.data_as(ctypes.POINTER(_lib.BatchContact)) if cap > 0 else None), self._h)
+            return systems, body, entries
+
+        if not lists:
+            systems, body, _ = call(0, bodies)
+            return ContactsResult(systems, body, None)
+        if capacity is None:
+            systems, body, _ = call(0, bodies)
+            capacity = int(systems["pairs"].max()) if B else 0
+            if capacity == 0:
+                return ContactsResult(systems, body, np.zeros((B, 0), dtype=CONTACT_DTYPE))
+            if B * capacity > _lib.BATCH_CONTACTS_MAX_ENTRIES:
+                raise ValueError(f"{B} systems x {capacity} contacts in the fullest exceed 2^28 list entries: pass a capacity")
+        systems, body, entries = call(int(capacity), bodies)
+        return ContactsResult(systems, body, entries if entries is not None else np.zeros((B, 0), dtype=CONTACT_DTYPE))
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1308,6 +1393,56 @@ class CorrelationResult:
                 f"above={self.above.tolist()}, unmeasured={self.unmeasured.tolist()})")
 
 
+class ContactsResult:
+    """What :meth:`BatchedSystem.contacts` listed.  Per system (``(B,)`` arrays): ``pairs`` (int64: the contacts, exact
+    whatever the capacity), ``stored`` (int64: those in the list, ``min(pairs, capacity)``), ``truncated`` (bool:
+    ``stored < pairs``), ``bodies`` (int32: the bodies taking part), ``touching`` (those with a contact), ``max_degree``,
+    ``closest`` (``(B, 2)`` int32: the contact of smallest separation, ``i < j``, -1 without one) and ``closest_distance``
+    (float64, ``inf`` without one).  Per body (``(B, max_bodies)`` int32, ``None`` without ``bodies``): ``degree`` (its
+    contacts), ``upper`` (those of higher index), ``first`` (where its entries start in the list: the exclusive sum of
+    ``upper``) and ``nearest`` (the partner of smallest separation, ties to the lower index, -1 without one).  The list
+    (``(B, capacity)``, ``None`` without ``lists``): ``i``, ``j`` (int32, -1 from ``stored`` on), ``r2`` (float32, ``inf`` from
+    ``stored`` on) and ``distance`` (float64).  ``systems``, ``body_records`` and ``entries`` are the records themselves."""
+
+    def __init__(self, systems, bodies, entries):
+        self.systems, self.body_records, self.entries = systems, bodies, entries
+        for name in ("pairs", "stored", "bodies", "touching", "max_degree"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.truncated = self.stored < self.pairs
+        self.closest = np.stack([systems["closest_i"], systems["closest_j"]], axis=1)
+        self.closest_r2 = np.ascontiguousarray(systems["closest_r2"])
+        self.closest_distance = np.sqrt(self.closest_r2.astype(np.float64))
+        for name in ("degree", "upper", "first", "nearest"):
+            setattr(self, name, None if bodies is None else np.ascontiguousarray(bodies[name]))
+        for name in ("i", "j", "r2"):
+            setattr(self, name, None if entries is None else np.ascontiguousarray(entries[name]))
+        self.distance = None if entries is None else np.sqrt(self.r2.astype(np.float64))
+        self.capacity = 0 if entries is None else int(entries.shape[1])
+
+    def _need_list(self):
+        if self.entries is None:
+            raise ValueError("this needs the list: call contacts(lists=True)")
+
+    def pairs_of(self, s: int) -> np.ndarray:
+        """``(stored[s], 2)`` int32: the listed contacts of system ``s`` as rows ``(i, j)``, ``i < j``, in the list's order."""
+        self._need_list()
+        m = int(self.stored[s])
+        return np.stack([self.i[s, :m], self.j[s, :m]], axis=1)
+
+    def partners_of(self, s: int, i: int) -> np.ndarray:
+        """int32, ascending: every body in contact with body ``i`` of system ``s``, from the list, in both directions.  Raises
+        where the system is truncated: the list would not hold them all."""
+        self._need_list()
+        if self.truncated[s]:
+            raise ValueError(f"system {s} is truncated ({int(self.stored[s])} of {int(self.pairs[s])} contacts): call again with more capacity")
+        p = self.pairs_of(s)
+        return np.sort(np.concatenate([p[p[:, 0] == i, 1], p[p[:, 1] == i, 0]]))
+
+    def __repr__(self):
+        return (f"ContactsResult(pairs={self.pairs.tolist()}, stored={self.stored.tolist()}, touching={self.touching.tolist()}, "
+                f"max_degree={self.max_degree.tolist()}, closest={self.closest.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -1382,4 +1517,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

@@ -1,9 +1,10 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
-// structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, energy and
-// momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_correlation.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
+// lists, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_contacts.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
+#include "nbody_batch_contacts_math.h"
 #include "nbody_batch_correlation_math.h"
 #include "nbody_batch_gravity_math.h"
 #include "nbody_batch_groups_math.h"
@@ -12,6 +13,7 @@
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_neighbours_math.h"
 #include "nbody_batch_pairs_elements.h"
+#include "nbody_batch_radii_check.h"
 #include "nbody_batch_span_math.h"
 #include "nbody_batch_structure_math.h"
 #include "nbody_kernels.h"
@@ -1906,6 +1908,213 @@ hipError_t launch_batch_correlation(const float4 *pos, const int *counts, const 
     });
 }
 
+// ---- contacts (include/nbody_batch_contacts.h): per system every unordered pair of bodies within a radius, or within the sum
+// of its two bodies' radii, as a list (i, j, r2) ascending in i and then in j, with per body its contacts and their place in
+// the list and per system their number and the closest.  A sibling of batch_correlation_kernel: one workgroup per system with
+// batch_shape's workgroup, the columns broadcast from LDS, RPL rows per lane at r = q * T + lane.  It reads the positions and
+// writes only the handle's records.  The first result here of variable length: the kernel counts, places and fills in one
+// launch, and no choice in it depends on the schedule -- the counts are integers, the places a prefix sum in ascending row
+// index, and every entry has one place that only its row writes.
+
+static_assert(sizeof(BatchContactSystem) == sizeof(nbody_batch_contact_system) && sizeof(nbody_batch_contact_system) == 48 &&
+                  offsetof(BatchContactSystem, bodies) == offsetof(nbody_batch_contact_system, bodies) &&
+                  offsetof(BatchContactSystem, touching) == offsetof(nbody_batch_contact_system, touching) &&
+                  offsetof(BatchContactSystem, max_degree) == offsetof(nbody_batch_contact_system, max_degree) &&
+                  offsetof(BatchContactSystem, reserved) == offsetof(nbody_batch_contact_system, reserved) &&
+                  offsetof(BatchContactSystem, pairs) == offsetof(nbody_batch_contact_system, pairs) &&
+                  offsetof(BatchContactSystem, stored) == offsetof(nbody_batch_contact_system, stored) &&
+                  offsetof(BatchContactSystem, closest_i) == offsetof(nbody_batch_contact_system, closest_i) &&
+                  offsetof(BatchContactSystem, closest_j) == offsetof(nbody_batch_contact_system, closest_j) &&
+                  offsetof(BatchContactSystem, closest_r2) == offsetof(nbody_batch_contact_system, closest_r2) &&
+                  offsetof(BatchContactSystem, reserved2) == offsetof(nbody_batch_contact_system, reserved2) &&
+                  offsetof(nbody_batch_contact_system, pairs) == 16 && offsetof(nbody_batch_contact_system, reserved2) == 44,
+              "nbody_batch_contacts_math.h mirrors the system record of nbody_batch_contacts.h");
+static_assert(sizeof(BatchContactBody) == sizeof(nbody_batch_contact_body) && sizeof(nbody_batch_contact_body) == 16 &&
+                  offsetof(BatchContactBody, degree) == offsetof(nbody_batch_contact_body, degree) &&
+                  offsetof(BatchContactBody, upper) == offsetof(nbody_batch_contact_body, upper) &&
+                  offsetof(BatchContactBody, first) == offsetof(nbody_batch_contact_body, first) &&
+                  offsetof(BatchContactBody, nearest) == offsetof(nbody_batch_contact_body, nearest),
+              "nbody_batch_contacts_math.h mirrors the body record of nbody_batch_contacts.h");
+static_assert(sizeof(BatchContact) == sizeof(nbody_batch_contact) && sizeof(nbody_batch_contact) == 12 &&
+                  offsetof(BatchContact, i) == offsetof(nbody_batch_contact, i) && offsetof(BatchContact, j) == offsetof(nbody_batch_contact, j) &&
+                  offsetof(BatchContact, r2) == offsetof(nbody_batch_contact, r2),
+              "nbody_batch_contacts_math.h mirrors the list entry of nbody_batch_contacts.h");
+static_assert(kContactsMaxEntries == NBODY_BATCH_CONTACTS_MAX_ENTRIES, "nbody_batch_contacts_math.h mirrors the limit of nbody_batch_contacts.h");
+
+// The fill, the same entries either way.  0: a wave none of whose rows has an entry to write below the capacity skips the
+// second walk -- one ballot, so the branch is a scalar one.  1: every wave repeats the walk.
+// Measured on an MI355X (profiles/batch_rate_contacts.txt; the listing call without the body records at 1024 x 1024, 256 x 4096
+// and 4096 x 256, ms): with few contacts (0.2 mean spacings) fill 0 0.97, 0.41 and 3.12, fill 1 0.96, 0.42 and 3.09; with many
+// (1.0 spacings, a list of 24 to 30 MB whose copy to the host is most of the call) fill 0 6.54, 7.03 and 8.18 -- 6.81, 7.11 and
+// 8.40 when run again -- and fill 1 6.84, 7.43 and 8.81.  The same bytes.  The difference is inside the spread of the repeats:
+// the second walk starts above the wave's first row and is short beside the first.  So: fill 0, which never does more work.
+#ifndef NBODY_BATCH_CONTACTS_FILL_ALWAYS
+#define NBODY_BATCH_CONTACTS_FILL_ALWAYS 0
+#endif
+
+constexpr int kContactTallies = 3;   // bodies, touching, max_degree
+constexpr int kContactUnits = 64;    // rows per lane x waves, at most: 4 x 16
+
+// The inclusive sum of `word` over the lanes of a wave up to the lane's own: lane l holds word[0] + ... + word[l].
+__device__ inline int contacts_wave_scan(int word, int lane)
+{
+    for (int off = 1; off < kContactsWave; off <<= 1) {
+        const int below = __shfl_up(word, off, kContactsWave);
+        word += lane >= off ? below : 0;
+    }
+    return word;
+}
+
+// LDS: img[j] = {x, y, z, w} of body j as four words, one ds_read_b128 per column (64 KiB at 4096 bodies; with the totals
+// above the default limit, which is raised before the launch).  RADII: w is the body's radius, a NaN where the body does not
+// take part, which is within no threshold; else w is the take-part flag, and a column without it is skipped on the scalar
+// unit.  The sums of `upper` over the 64 rows of every unit (a wave's rows of one q) are the only other LDS: the places inside
+// a unit come from shuffles.  radius2 is b2 per system (!RADII), radii one radius per slot (RADII); subset and bodies may be
+// NULL; list is NULL iff capacity == 0.
+template <int RPL, bool RADII>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_contacts_kernel(
+    const float4 *__restrict__ pos, const int *__restrict__ counts, const unsigned char *__restrict__ subset,
+    const float *__restrict__ radius2, const float *__restrict__ radii, int max_bodies, long long capacity,
+    BatchContactBody *__restrict__ bodies, BatchContact *__restrict__ list, BatchContactSystem *__restrict__ systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int totals[kContactUnits];
+    __shared__ int tally[kContactTallies];
+    __shared__ SpanKey closest;
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & (kContactsWave - 1), wave = tid / kContactsWave, waves = T / kContactsWave;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float b2 = RADII ? 0.f : radius2[blockIdx.x];
+    if (tid < kContactUnits)
+        totals[tid] = 0;
+    if (tid < kContactTallies)
+        tally[tid] = 0;
+    if (tid == 0)
+        closest = kSpanNoKey;
+    __syncthreads();
+    float4 x[RPL];  // {x, y, z, the mass word}
+    float rad[RPL];
+    bool take[RPL];
+    int taking = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        rad[q] = contacts_no_radius();
+        take[q] = false;
+        if (r < n) {
+            x[q] = pos[base + r];
+            take[q] = !subset || subset[base + r] != 0;
+            if (RADII)
+                rad[q] = take[q] ? radii[base + r] : contacts_no_radius();
+            taking += take[q] ? 1 : 0;
+            img[r] = make_int4(__float_as_int(x[q].x), __float_as_int(x[q].y), __float_as_int(x[q].z),
+                               RADII ? __float_as_int(rad[q]) : (take[q] ? 1 : 0));
+        }
+    }
+    if (taking)
+        atomicAdd(&tally[0], taking);  // integers: the order of the additions does not matter
+    __syncthreads();                   // the image is in place
+    // Count: every row walks every column.
+    ContactRow row[RPL];
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[j];  // a wave-uniform address: one broadcast LDS read
+        if (!RADII && __builtin_amdgcn_readfirstlane(pj.w) == 0)
+            continue;  // takes no part: the flag is the same in every lane, so the branch is a scalar one
+        const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z), wj = __int_as_float(pj.w);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            contacts_step(row[q], contacts_examined(take[q], true, r, j), r, j, groups_r2(x[q].x, x[q].y, x[q].z, xj, yj, zj),
+                          RADII ? contacts_radii_t2(rad[q], wj) : b2);
+        }
+    }
+    int touching = 0, max_degree = 0;
+    SpanKey key = kSpanNoKey;
+    int within[RPL];  // the inclusive sum of upper over the lower lanes of the row's unit, and the row
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        touching += row[q].degree >= 1 ? 1 : 0;
+        max_degree = row[q].degree > max_degree ? row[q].degree : max_degree;
+        const SpanKey mine = contacts_row_key(row[q], q * T + tid);
+        key = mine < key ? mine : key;
+        within[q] = contacts_wave_scan(row[q].upper, lane);
+        if (lane == kContactsWave - 1)
+            totals[contacts_unit(q, waves, wave)] = within[q];
+    }
+    // Integers again: a sum, a maximum and a minimum, in any order.
+    if (touching)
+        atomicAdd(&tally[1], touching);
+    if (max_degree)
+        atomicMax(&tally[2], max_degree);
+    if (key != kSpanNoKey)
+        atomicMin(&closest, key);
+    __syncthreads();
+    // Place: the units in ascending order hold the rows in ascending order, so a row starts at the sum of the units below its
+    // own and of the lower rows of its own.  A slot from the count on, or a body that takes no part, has no entry and takes
+    // the running sum like any other row.
+    int first[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        first[q] = contacts_units_below(totals, contacts_unit(q, waves, wave)) + within[q] - row[q].upper;
+    const long long pairs = (long long)contacts_units_below(totals, RPL * waves);
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (bodies && r < max_bodies)
+            bodies[base + r] = contacts_body(row[q], first[q]);
+    }
+    if (tid == 0)
+        systems[blockIdx.x] = contacts_system(tally[0], tally[1], tally[2], pairs, capacity, closest);
+    if (capacity == 0)
+        return;  // the same in every lane; no barrier follows
+    // Fill: a row walks the columns above it again and writes its entries from `first` on while they are below the capacity.
+    // No row of this wave is below its first lane's row of q = 0, so no column up to that one is above any of them.
+    BatchContact *mine = list + (size_t)blockIdx.x * (size_t)capacity;
+    bool fills = false;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        fills = fills || contacts_row_fills(first[q], row[q].upper, capacity);
+    if (NBODY_BATCH_CONTACTS_FILL_ALWAYS || __ballot(fills) != 0) {
+        int t[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            t[q] = 0;
+        for (int j = wave * kContactsWave + 1; j < n; ++j) {
+            const int4 pj = img[j];
+            if (!RADII && __builtin_amdgcn_readfirstlane(pj.w) == 0)
+                continue;
+            const float xj = __int_as_float(pj.x), yj = __int_as_float(pj.y), zj = __int_as_float(pj.z), wj = __int_as_float(pj.w);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                contacts_fill(mine, capacity, first[q], t[q], contacts_examined(take[q], true, r, j), r, j,
+                              groups_r2(x[q].x, x[q].y, x[q].z, xj, yj, zj), RADII ? contacts_radii_t2(rad[q], wj) : b2);
+            }
+        }
+    }
+    // The pads, from `stored` on.
+    for (long long k = contacts_stored(pairs, capacity) + tid; k < capacity; k += T)
+        mine[k] = contacts_pad();
+}
+
+// One launch over all systems.  16 bytes of dynamic LDS per body, 64 KiB at 4096 bodies beside the totals.  Exactly one of
+// radius2 and radii is given; subset and bodies may be NULL; list is NULL iff capacity == 0.
+hipError_t launch_batch_contacts(const float4 *pos, const int *counts, const unsigned char *subset, const float *radius2,
+                                 const float *radii, int n_systems, int max_bodies, long long capacity, BatchContactBody *bodies,
+                                 BatchContact *list, BatchContactSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        const auto launch = [&](auto mode) {
+            return launch_analysis_kernel(batch_contacts_kernel<rpl(), mode()>, n_systems, sh.threads, lds, stream, pos, counts, subset,
+                                          radius2, radii, max_bodies, capacity, bodies, list, systems);
+        };
+        return radii ? launch(std::true_type{}) : launch(std::false_type{});
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -2017,6 +2226,13 @@ struct BatchAnalysis {
     DeviceArray<unsigned char> correlation_sources;           // [n_systems][max_bodies], the device copy of `sources`
     DeviceArray<float> correlation_edges2;                    // one set or [n_systems] sets of padded bins + 1 squared edges
     std::vector<float> correlation_edges2_host;               // the last call's: the copy's source until the stream is idle
+    DeviceArray<BatchContactSystem> contacts_systems;  // [n_systems]
+    DeviceArray<BatchContactBody> contacts_bodies;     // [n_systems][max_bodies]
+    DeviceArray<BatchContact> contacts_list;           // [n_systems][capacity] of the largest call so far
+    DeviceArray<unsigned char> contacts_subset;        // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<float> contacts_radius2;               // [n_systems]
+    std::vector<float> contacts_radius2_host;          // the last call's b[s] b[s]
+    DeviceArray<float> contacts_radii;                 // [n_systems][max_bodies], the device copy of `radii`
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -2392,6 +2608,64 @@ int nbody_batch_correlation(nbody_batch *b, const float *d_pos, int bins, const 
                                           a->correlation_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->correlation_systems, B));
     BATCH_TRY(b, copy_out(b, counts_out, a->correlation_counts, words));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_contacts(nbody_batch *b, const float *d_pos, const float *radius, const float *radii, const unsigned char *subset,
+                         long long capacity, nbody_batch_contact_system *systems_out, nbody_batch_contact_body *bodies_out,
+                         nbody_batch_contact *list_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_contacts: batch is NULL");
+    if (!d_pos || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: NULL argument");
+    if (!radius == !radii)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: exactly one of radius and radii must be given");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    for (size_t s = 0; radius && s < B; ++s) {
+        if (!correlation_edge_valid(radius[s]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: the radius of system " + std::to_string(s) + " must be finite and >= 0");
+    }
+    std::string refused;
+    if (radii && !batch_radii_ok(radii, b->counts.data(), b->n_systems, b->max_bodies, &refused))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: " + refused);
+    if (capacity < 0)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: capacity must be >= 0");
+    if ((capacity > 0) != (list_out != nullptr))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: list_out must be given iff capacity > 0");
+    if (capacity > kContactsMaxEntries / (long long)B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_contacts: n_systems x capacity must not exceed 2^28");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    if (radius) {
+        a->contacts_radius2_host.resize(B);
+        for (size_t s = 0; s < B; ++s)
+            a->contacts_radius2_host[s] = contacts_radius_t2(radius[s]);  // b2: one fp32 product
+    }
+    const size_t entries = B * (size_t)capacity;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->contacts_systems.ensure(B));
+    BATCH_TRY(b, a->contacts_radius2.ensure(radius ? B : 0));
+    BATCH_TRY(b, a->contacts_radii.ensure(radii ? slots : 0));
+    BATCH_TRY(b, a->contacts_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->contacts_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->contacts_list.ensure(entries));
+    if (radius)
+        BATCH_TRY(b, hipMemcpyAsync(a->contacts_radius2.ptr, a->contacts_radius2_host.data(), sizeof(float) * B, hipMemcpyHostToDevice,
+                                    b->stream));
+    if (radii)
+        BATCH_TRY(b, hipMemcpyAsync(a->contacts_radii.ptr, radii, sizeof(float) * slots, hipMemcpyHostToDevice, b->stream));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->contacts_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_contacts(reinterpret_cast<const float4 *>(d_pos), b->counts_dev.ptr,
+                                       subset ? a->contacts_subset.ptr : nullptr, radius ? a->contacts_radius2.ptr : nullptr,
+                                       radii ? a->contacts_radii.ptr : nullptr, (int)b->n_systems, (int)b->max_bodies, capacity,
+                                       bodies_out ? a->contacts_bodies.ptr : nullptr, capacity > 0 ? a->contacts_list.ptr : nullptr,
+                                       a->contacts_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->contacts_systems, B));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->contacts_bodies, slots));
+    BATCH_TRY(b, copy_out(b, list_out, a->contacts_list, entries));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

@@ -118,7 +118,16 @@ with the first 8 bodies of every system as the only sources, and the whole call 
 neighbours(k=6) without its lists and records on the same state -- all synchronous calls, wall clock, alternated, medians and
 spreads.  The kernel has two loops behind NBODY_BATCH_CORRELATION_LANE_COUNTERS: the line names the library it timed
 (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both.  By instruction count a column costs a row
-about 7 + bins vector operations."""
+about 7 + bins vector operations.
+
+--contacts: instead, the contact lists (BatchedSystem.contacts).  For n x B = 1024 x 1024 and 256 x 4096 (or --cases), one
+line per case on Plummer spheres, at radii of 0.2 and 1.0 mean interparticle spacings within the half-mass radius (few contacts
+and many): the counting call (capacity 0, without the per-body records: 48 bytes per system come back), the listing call with
+room for the fullest system without and with the per-body records, and the same listing call under per-body radii of half the
+radius, against neighbours(k=1, radius, lists=False) without its records -- the nearest existing work, the yardstick -- and
+pairs() on the same state: all synchronous calls, wall clock, alternated, medians and spreads.  The kernel has two fills behind
+NBODY_BATCH_CONTACTS_FILL_ALWAYS: the line names the library it timed (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run
+per build gives both, and the line carries a checksum of the list so that the two can be seen to agree."""
 import argparse
 import json
 import os
@@ -172,6 +181,8 @@ ap.add_argument("--span", action="store_true", help="spanning_tree() with and wi
                 "of 20 bodies against groups() and pairs() on the same Plummer spheres, wall clock, and the rounds run")
 ap.add_argument("--neighbours", action="store_true", help="neighbours() at k = 1, 6 and 8, with a radius, with 8 sources and with "
                 "the lists against structure(k=6) and pairs() on the same Plummer spheres, wall clock")
+ap.add_argument("--contacts", action="store_true", help="contacts() at 0.2 and 1.0 mean spacings, counting and listing, with radii, "
+                "against neighbours(k=1, radius, lists=False) and pairs() on the same Plummer spheres, wall clock")
 ap.add_argument("--correlation", action="store_true", help="correlation() at 8, 16 and 32 bins, with 8 sources and with the bins "
                 "against pairs() and neighbours(k=6) on the same Plummer spheres, wall clock")
 args = ap.parse_args()
@@ -1133,6 +1144,61 @@ def correlation_lines():
         print(json.dumps(line), flush=True)
 
 
+def contacts_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "256x4096"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        spacing = float(np.float32((4.0 / 3.0 * np.pi * 1.3048 ** 3 / (n / 2.0)) ** (1.0 / 3.0)))   # as in --groups
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"), "mean_spacing": round(spacing, 5)}
+            for f in (0.2, 1.0):
+                b = float(np.float32(f * spacing))
+                half = np.full((B, n), 0.5 * b, np.float32)
+                room = int(batch.contacts(b, lists=False, bodies=False).pairs.max())
+                calls = {"pairs": batch.pairs,
+                         "neighbours_lean_k1_radius": lambda: batch.neighbours(k=1, radius=b, lists=False, bodies=False),
+                         "contacts_count": lambda: batch.contacts(b, lists=False, bodies=False),
+                         "contacts_list_lean": lambda: batch.contacts(b, capacity=room, bodies=False),
+                         "contacts_list": lambda: batch.contacts(b, capacity=room),
+                         "contacts_list_lean_radii": lambda: batch.contacts(radii=half, capacity=room, bodies=False)}
+                for fn in calls.values():                           # the first calls allocate the records and set the kernels' LDS limits
+                    wall(fn)
+                times = {name: [] for name in calls}
+                found = {}
+                for _ in range(args.repeats):                       # alternated
+                    for name, fn in calls.items():
+                        t, out = wall(fn)
+                        times[name].append(t)
+                        found[name] = out
+                med = {name: statistics.median(ts) for name, ts in times.items()}
+                res, tag = found["contacts_list"], f"b{f}"
+                line[tag] = {"radius": round(b, 5), "capacity": room, "pairs_per_system": round(float(res.pairs.mean()), 1),
+                             "max_degree": int(res.max_degree.max()), "list_megabytes": round(B * room * 12 / 1e6, 2),
+                             "list_crc32": zlib.crc32(res.entries.tobytes()),
+                             "radii_same_list": bool(found["contacts_list_lean_radii"].entries.tobytes() == res.entries.tobytes())}
+                for name in calls:
+                    line[tag][name + "_ms"] = round(med[name], 3)
+                for name in ("contacts_count", "contacts_list_lean", "contacts_list"):
+                    line[tag][name + "_over_neighbours"] = round(med[name] / med["neighbours_lean_k1_radius"], 3)
+                for name in calls:
+                    line[tag][name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+        print(json.dumps(line), flush=True)
+
+
+if args.contacts:
+    contacts_lines()
+    sys.exit(0)
 if args.correlation:
     correlation_lines()
     sys.exit(0)
