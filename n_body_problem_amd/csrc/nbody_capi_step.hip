@@ -18,14 +18,16 @@ static void free_sym_tiles(nbody_ctx *c)
     c->step_graph.reset();
 }
 
-// Small and mid-size pair-once systems (every row, the tiles in one part, nothing summed yet, up to 320 splits of single tiles):
-// ONE finishing kernel forms the column sums, the row sums and their combination and ends in the update / the half kick.
-static bool sym_fused_finish(const nbody_ctx *c)
+// The kernel that finishes nbody_update, nbody_kdk_prepare or nbody_kdk_kick: finish_choice (nbody_launch_choice.h) on the
+// context's state.
+static FinishChoice finish_of(const nbody_ctx *c, FinishOp op)
 {
-    constexpr int fused_max_splits = 320;
-    return c->force_mode == NBODY_FORCE_SYMMETRIC && c->row_lo == 0 && c->row_count == c->n_total && c->pending &&
-           !c->sym_reduced && !c->sym_rows_summed && c->pending->g1 - c->pending->g0 == c->group_count &&
-           c->pending->row_off == 0 && c->pending->col_off == 0 && c->n_splits <= fused_max_splits && c->strip_len == 1;
+    const bool pair_once = c->force_mode == NBODY_FORCE_SYMMETRIC;
+    const bool whole = c->row_lo == 0 && c->row_count == c->n_total;
+    const bool one_part_unsummed = pair_once && c->pending && !c->sym_reduced && !c->sym_rows_summed &&
+                                   c->pending->g1 - c->pending->g0 == c->group_count && c->pending->row_off == 0 &&
+                                   c->pending->col_off == 0;
+    return finish_choice(op, pair_once, whole, one_part_unsummed, c->n_splits, c->strip_len, c->row_count);
 }
 
 // Partial sums consumed or forgotten: the next force call starts a new step (and recomputes the equal-mass flags).
@@ -626,16 +628,16 @@ int nbody_update(nbody_ctx *c, float *d_pos, float *d_vel, float dt)
     {
         TimedLaunch t(c, &c->ev_update, &c->update_ms, &c->update_launches);
         // Small and mid-size systems (every row, the tiles in one part, nothing summed yet): one finishing kernel instead of
-        // column sums + row sums + update (up to 320 splits: -4 % per step at N = 32 768, nothing from 131 072 on,
-        // profiles/r03_ab_fused_finish.txt; the bits are the same either way).
-        if (sym_fused_finish(c)) {
+        // column sums + row sums + update (finish_choice; the bits are the same either way).
+        const FinishChoice k = finish_of(c, FinishOp::update);
+        if (k.fused()) {
             int rc = all_splits_done(c, "nbody_update");
             if (rc != NBODY_OK)
                 return rc;
             HIP_TRY(c, launch_sym_finish_update(reinterpret_cast<const float3 *>(c->partials.ptr), c->col_partials.ptr,
                                                 reinterpret_cast<float4 *>(d_pos), reinterpret_cast<float4 *>(d_vel), (int)c->n_total,
                                                 (int)c->split_len, c->n_splits, c->group_splits, dt, c->stream));
-        } else if (c->force_mode == NBODY_FORCE_SYMMETRIC) {  // the combination of the group sums rides in the update kernel
+        } else if (k.family == FinishFamily::update_sym_kernel) {  // the combination of the group sums rides in the update kernel
             int rc = all_splits_done(c, "nbody_update");
             if (rc == NBODY_OK)
                 rc = sym_group_sums(c, "nbody_update");
@@ -695,7 +697,7 @@ int nbody_kdk_prepare(nbody_ctx *c)
         c->acc_valid = true;
         return NBODY_OK;
     }
-    if (sym_fused_finish(c)) {  // one kernel instead of column sums + row sums + combination + copy (the same bits)
+    if (finish_of(c, FinishOp::prepare).fused()) {  // one kernel instead of column sums + row sums + combination + copy (the same bits)
         int rc = all_splits_done(c, "nbody_kdk_prepare");
         if (rc == NBODY_OK)
             rc = ensure_acc(c);
@@ -758,7 +760,7 @@ int nbody_kdk_kick(nbody_ctx *c, float *d_vel, float dt)
     HIP_TRY(c, hipSetDevice(c->device));
     {
         TimedLaunch t(c, &c->ev_update, &c->update_ms, &c->update_launches);
-        if (sym_fused_finish(c)) {
+        if (finish_of(c, FinishOp::kick).fused()) {
             rc = all_splits_done(c, "nbody_kdk_kick");
             if (rc != NBODY_OK)
                 return rc;

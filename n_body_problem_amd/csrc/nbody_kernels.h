@@ -95,7 +95,8 @@ hipError_t launch_sym_finish_kick(const float3 *row_partials, const float3 *col_
 // k: force_choice() of the context and of a.split_len, a.eps2 and a.eps_pp (eps2 == 0 selects the zero-distance-guarded variant).
 hipError_t launch_forces(const ForceArgs &a, const ForceChoice &k, hipStream_t stream);
 
-// Sum the partials of n_splits splits in ascending order and kick-drift rows of this context.
+// Sum the partials of n_splits splits in ascending order and kick-drift rows of this context.  Threads per workgroup, here and
+// in launch_update_sym: update_threads(row_count), as finish_choice() reports them.
 hipError_t launch_update(float4 *pos_all, float4 *vel_rows, const float4 *partials, int row_lo, int row_count,
                          int n_splits, float dt, hipStream_t stream);
 

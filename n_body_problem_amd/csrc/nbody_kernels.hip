@@ -827,8 +827,8 @@ hipError_t launch_update(float4 *pos_all, float4 *vel_rows, const float4 *partia
 {
     if (row_count <= 0)
         return hipSuccess;
-    // few rows: one wave per workgroup, so that every CU gets some (20 225 rows: 317 workgroups instead of 80)
-    if (row_count < 256 * kTile)
+    // few rows: one wave per workgroup (update_threads, nbody_launch_choice.h)
+    if (update_threads(row_count) == 64)
         hipLaunchKernelGGL(update_kernel<64>, dim3((row_count + 63) / 64), dim3(64), 0, stream, pos_all, vel_rows, partials,
                            row_lo, row_count, n_splits, dt);
     else
@@ -874,7 +874,7 @@ hipError_t launch_update_sym(float4 *pos_all, float4 *vel_rows, const float4 *ro
 {
     if (row_count <= 0)
         return hipSuccess;
-    if (row_count < 256 * kTile)
+    if (update_threads(row_count) == 64)
         hipLaunchKernelGGL(update_sym_kernel<64>, dim3((row_count + 63) / 64), dim3(64), 0, stream, pos_all, vel_rows, rowsum,
                            colparts, row_lo, row_count, n_total, n_groups, dt);
     else
@@ -1051,7 +1051,8 @@ __global__ __launch_bounds__(kTile) void energy_kernel(const float4 *pos_all, co
                 ei2[k] = __builtin_fmaf(eps_pp[gi[k]], eps_pp[gi[k]], eps2);
         }
     }
-    // the tiles that hold this workgroup's rows (row_lo is a multiple of the tile: a split boundary)
+    // the tiles that hold this workgroup's rows (row_lo is a multiple of 64, a split boundary, not of the tile: up to five
+    // tiles can overlap a workgroup's 1024 rows)
     const int self_lo = row_lo + row0, self_hi = self_lo + kTile * kEnergyRows;
     for (int j0 = 0; j0 < n_total; j0 += kTile) {
         __syncthreads();

@@ -1,5 +1,5 @@
-// nbody_launch_choice.h -- which force kernel a configuration runs and with what launch shape, the split-length rules and the
-// automatic graph-replay rule: pure functions of their arguments.  Plain C++17 without HIP, like nbody_sym_plan.h (which tiles, in
+// nbody_launch_choice.h -- which force kernel a configuration runs and with what launch shape, which kernel finishes the step,
+// the split-length rules and the automatic graph-replay rule: pure functions of their arguments.  Plain C++17 without HIP, like nbody_sym_plan.h (which tiles, in
 // which order): the launchers (nbody_kernels.hip, nbody_symmetric.hip) look the chosen kernel up in their tables, the C ABI
 // (nbody_capi_step.hip) reads what its sequencing needs, and a CPU test (tests/test_launch_choice_cpu.py) checks every choice without
 // a GPU.  Internal; the public surface is include/nbody.h.
@@ -225,6 +225,59 @@ inline ForceChoice force_choice(int setting, int split_len, int64_t row_count, i
     case -4: return kernel(F::force_kernel, 4, !eps, eps_pp, kTile * 4, kTile);
     default: return k;
     }
+}
+
+// ---- the finish: partial sums into velocities and positions ------------------------------------------------------------------
+
+// What a step runs behind its force pass.  update_kernel<BLOCK> and update_sym_kernel<BLOCK> (nbody_kernels.hip: the kick-drift
+// from the one-sided partial sums / from the pair-once group sums, which sym_group_sums has completed in front),
+// sym_finish_update_kernel<MODE> (nbody_symmetric.hip: column sums, row sums, combination and MODE 0 the kick-drift, 1 the
+// closing half kick, 2 the acceleration alone, in one launch), kdk_kick_kernel<MODE> (0 the acceleration alone, 1 with the
+// closing half kick) -- in the pair-once mode behind sym_combine_kernel (`combine`), which hands it one "split".
+enum class FinishOp { update, prepare, kick };  // nbody_update, nbody_kdk_prepare, nbody_kdk_kick
+enum class FinishFamily { none, update_kernel, update_sym_kernel, sym_finish_update_kernel, kdk_kick_kernel };
+
+struct FinishChoice {
+    FinishFamily family = FinishFamily::none;
+    int targ = 0;          // BLOCK of the update kernels, MODE of the others
+    int threads = 0;       // per workgroup
+    bool combine = false;  // sym_combine_kernel in front (after whatever group sums are missing)
+    bool fused() const { return family == FinishFamily::sym_finish_update_kernel; }
+};
+
+constexpr int kFusedFinishMaxSplits = 320;
+
+// few rows: one wave per workgroup, so that every CU gets some (20 225 rows: 317 workgroups instead of 80)
+inline int update_threads(int64_t row_count) { return row_count < 256 * (int64_t)kTile ? 64 : kTile; }
+
+// pair_once: the force mode; whole: the context owns every row; one_part_unsummed: the last force call left its tiles in ONE
+// summation part that holds every group of the context, at the start of both partial-sum arrays, and neither nbody_sym_reduce
+// nor nbody_sym_rowsum has run since; strip_len: sym_strip_len() (pair-once mode).
+// Small and mid-size pair-once systems (every row, the tiles in one part, nothing summed yet, up to 320 splits of single tiles):
+// ONE finishing kernel forms the column sums, the row sums and their combination and ends in the update / the half kick (up to
+// 320 splits: -4 % per step at N = 32 768, nothing from 131 072 on, profiles/r03_ab_fused_finish.txt; the bits are the same
+// either way).
+inline FinishChoice finish_choice(FinishOp op, bool pair_once, bool whole, bool one_part_unsummed, int n_splits, int strip_len,
+                                  int64_t row_count)
+{
+    using F = FinishFamily;
+    FinishChoice k;
+    if (pair_once && whole && one_part_unsummed && n_splits <= kFusedFinishMaxSplits && strip_len == 1) {
+        k.family = F::sym_finish_update_kernel;
+        k.targ = op == FinishOp::update ? 0 : op == FinishOp::kick ? 1 : 2;
+        k.threads = 256;
+        return k;
+    }
+    if (op == FinishOp::update) {  // pair-once: the combination of the group sums rides in the update kernel
+        k.family = pair_once ? F::update_sym_kernel : F::update_kernel;
+        k.targ = k.threads = update_threads(row_count);
+        return k;
+    }
+    k.family = F::kdk_kick_kernel;
+    k.targ = op == FinishOp::kick ? 1 : 0;
+    k.threads = kTile;
+    k.combine = pair_once;
+    return k;
 }
 
 // ---- graph replay --------------------------------------------------------------------------------------------------------

@@ -2,7 +2,10 @@
 tests/launch_choice_driver.cpp (g++) over the whole domain and compared, entry for entry, with tests/golden/launch_choice.json.
 That table was recorded from the dispatch code the header replaced (see tests/golden/README.md): a change to it must be
 deliberate.  The anchors are the kernel names the profiles in the tree recorded on hardware; the properties are the conditions
-the kernels put on their launch shape."""
+the kernels put on their launch shape.  The finish choice (which kernel turns the partial sums into velocities and positions)
+is compared over its whole domain with the rule its call sites held before the header did; tests/test_finish_bits_cpu.py ties
+the GPU cases of the finish tests to it."""
+import itertools
 import json
 import os
 import random
@@ -180,3 +183,22 @@ def test_every_choice_has_a_table_entry(golden):
     for name in sorted(names):
         kernel, args = re.fullmatch(r"(\w+)<(.*)>", name).groups()
         assert f"ROW({kernel}, {args})" in tables, name
+
+
+def finish_rule(op, pair_once, whole, one_part_unsummed, n_splits, strip_len, row_count):
+    """The decisions nbody_update, nbody_kdk_prepare, nbody_kdk_kick and the update launchers made, each at its own place."""
+    if pair_once and whole and one_part_unsummed and n_splits <= 320 and strip_len == 1:      # one finishing kernel
+        return f"sym_finish_update_kernel<{dict(update=0, kick=1, prepare=2)[op]}>|256|0"
+    if op == "update":
+        block = 64 if row_count < 256 * 256 else 256
+        return f"{'update_sym_kernel' if pair_once else 'update_kernel'}<{block}>|{block}|0"
+    return f"kdk_kick_kernel<{1 if op == 'kick' else 0}>|256|{int(bool(pair_once))}"
+
+
+def test_the_finish_choice_is_the_rule_its_call_sites_held(driver):
+    domain = list(itertools.product(("update", "prepare", "kick"), (0, 1), (0, 1), (0, 1), (1, 20, 319, 320, 321, 4096), (1, 2, 4, 8),
+                                    (1, 64, 1000, 65535, 65536, 65537, 1 << 20)))
+    lines = driver(["choice " + " ".join(str(v) for v in d) for d in domain]).splitlines()
+    assert len(lines) == len(domain)
+    assert {d: (got, finish_rule(*d)) for d, got in zip(domain, lines) if got != finish_rule(*d)} == {}
+    assert len(set(lines)) == 11          # two block sizes of two update kernels, three modes fused, two kicks with and without the combination
