@@ -555,6 +555,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_correlation.h"
 /* contacts: per system every pair of bodies within a radius, or within the sum of its two radii, as a list (i, j, r2) with per-body and per-system records */
 #include "nbody_batch_contacts.h"
+/* approaches: per system every pair of bodies that comes within a radius, or within the sum of its two radii, on straight lines before a horizon, as a list (i, j, r2, rv, v2, phase) */
+#include "nbody_batch_approaches.h"
 
 #ifdef __cplusplus
 }

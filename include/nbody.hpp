@@ -718,6 +718,42 @@ public:
               "nbody_batch_contacts");
         return s;
     }
+    // Approach lists (nbody_batch_approaches.h): for every system every unordered pair of bodies that comes within a radius, or
+    // within the sum of its two radii, before a horizon, with both bodies moved on straight lines at the velocities in the
+    // caller's buffer.  horizon: numSystems values (host), finite and >= 0.  threshold, subset, capacity, list and bodies: as in
+    // contacts().  Per system the bodies taking part, those with an approach, the largest degree, the approaches (exact whatever
+    // the capacity), those stored, and the pairs within reach now, passing before the horizon and still closing at it.  list
+    // takes the entries (i, j, r2, rv, v2, phase), i < j, ascending in i and then in j, {-1, -1, +inf, 0, 0, -1} from `stored`
+    // on.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_approach_system> approaches(const float *dPositions, const float *dVelocities, const std::vector<float> &horizon,
+                                                        const std::vector<float> &threshold, long long capacity = 0,
+                                                        std::vector<nbody_batch_approach> *list = nullptr,
+                                                        const std::vector<unsigned char> &subset = {},
+                                                        std::vector<nbody_batch_approach_body> *bodies = nullptr)
+    {
+        const size_t slots = (size_t)systems_ * (size_t)maxBodies_;
+        const bool perBody = threshold.size() == slots && threshold.size() != (size_t)systems_;
+        if (horizon.size() != (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::approaches: one horizon per system");
+        if (threshold.size() != (size_t)systems_ && !perBody)
+            throw std::invalid_argument("nbody::Batch::approaches: one radius per system, or one per slot");
+        if (!subset.empty() && subset.size() != slots)
+            throw std::invalid_argument("nbody::Batch::approaches: one subset byte per slot, or none");
+        if (capacity < 0 || (capacity > 0) != (list != nullptr))
+            throw std::invalid_argument("nbody::Batch::approaches: a list iff capacity > 0");
+        if (capacity > NBODY_BATCH_APPROACHES_MAX_ENTRIES / (long long)systems_)
+            throw std::invalid_argument("nbody::Batch::approaches: numSystems x capacity must not exceed 2^27");
+        std::vector<nbody_batch_approach_system> s((size_t)systems_);
+        if (list)
+            list->resize((size_t)systems_ * (size_t)capacity);
+        if (bodies)
+            bodies->resize(slots);
+        check(nbody_batch_approaches(b_, dPositions, dVelocities, horizon.data(), perBody ? nullptr : threshold.data(),
+                                     perBody ? threshold.data() : nullptr, subset.empty() ? nullptr : subset.data(), capacity,
+                                     s.data(), bodies ? bodies->data() : nullptr, list ? list->data() : nullptr),
+              "nbody_batch_approaches");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -476,6 +476,34 @@ _CONTACTS_PROTOTYPES = {
 }
 
 
+BATCH_APPROACHES_MAX_ENTRIES = 1 << 27
+BATCH_APPROACH_NOW, BATCH_APPROACH_PASSAGE, BATCH_APPROACH_END = 0, 1, 2
+
+
+class BatchApproachSystem(ctypes.Structure):
+    """``nbody_batch_approach_system`` of include/nbody_batch_approaches.h."""
+    _fields_ = [("bodies", c_int), ("approaching", c_int), ("max_degree", c_int), ("reserved", c_int), ("pairs", ctypes.c_longlong),
+                ("stored", ctypes.c_longlong), ("now", c_int), ("passing", c_int), ("ending", c_int), ("reserved2", c_int)]
+
+
+class BatchApproachBody(ctypes.Structure):
+    """``nbody_batch_approach_body`` of include/nbody_batch_approaches.h."""
+    _fields_ = [("degree", c_int), ("upper", c_int), ("first", c_int), ("now", c_int)]
+
+
+class BatchApproach(ctypes.Structure):
+    """``nbody_batch_approach`` of include/nbody_batch_approaches.h."""
+    _fields_ = [("i", c_int), ("j", c_int), ("r2", c_float), ("rv", c_float), ("v2", c_float), ("phase", c_int)]
+
+
+#: the entry point of include/nbody_batch_approaches.h (approach lists of batched ensembles), which nbody.h includes
+_APPROACHES_PROTOTYPES = {
+    "nbody_batch_approaches": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                       POINTER(ctypes.c_ubyte), ctypes.c_longlong, POINTER(BatchApproachSystem),
+                                       POINTER(BatchApproachBody), POINTER(BatchApproach)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -506,7 +534,7 @@ def load() -> ctypes.CDLL:
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
-                list(_CONTACTS_PROTOTYPES.items()):
+                list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -607,6 +635,11 @@ def correlation_names():
 def contacts_names():
     """The entry point of nbody_batch_contacts.h."""
     return list(_CONTACTS_PROTOTYPES)
+
+
+def approaches_names():
+    """The entry point of nbody_batch_approaches.h."""
+    return list(_APPROACHES_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -102,6 +102,16 @@ CONTACT_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("r2", np.float32)])
 assert CONTACT_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContactSystem) == 48
 assert CONTACT_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContactBody) == 16
 assert CONTACT_DTYPE.itemsize == ctypes.sizeof(_lib.BatchContact) == 12
+#: the records of :meth:`BatchedSystem.approaches`: numpy's views of ``nbody_batch_approach_system``, ``_body`` and ``nbody_batch_approach``
+APPROACH_SYSTEM_DTYPE = np.dtype([("bodies", np.int32), ("approaching", np.int32), ("max_degree", np.int32), ("reserved", np.int32),
+                                  ("pairs", np.int64), ("stored", np.int64), ("now", np.int32), ("passing", np.int32),
+                                  ("ending", np.int32), ("reserved2", np.int32)])
+APPROACH_BODY_DTYPE = np.dtype([("degree", np.int32), ("upper", np.int32), ("first", np.int32), ("now", np.int32)])
+APPROACH_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("r2", np.float32), ("rv", np.float32), ("v2", np.float32),
+                           ("phase", np.int32)])
+assert APPROACH_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproachSystem) == 48
+assert APPROACH_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproachBody) == 16
+assert APPROACH_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproach) == 24
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -878,6 +888,87 @@ class BatchedSystem:
         systems, body, entries = call(int(capacity), bodies)
         return ContactsResult(systems, body, entries if entries is not None else np.zeros((B, 0), dtype=CONTACT_DTYPE))
 
+    def approaches(self, horizon, radius=None, *, radii=None, subset=None, capacity=None, lists: bool = True,
+                   bodies: bool = True) -> "ApproachesResult":
+        """Which pairs will come within a distance of each other (``include/nbody_batch_approaches.h`` states the rules): for
+        every system every unordered pair of bodies whose separation, with both bodies moved on straight lines at their current
+        velocities, is within the threshold at some time in ``[0, horizon]``, listed on the device from the current state
+        (waits for the queued work) as ``(i, j, r2, rv, v2, phase)`` with ``i < j``, ascending in ``i`` and then in ``j``.
+        ``horizon`` is a scalar or ``(B,)``, finite and ``>= 0``.  The thresholds, ``subset``, ``capacity``, ``lists`` and
+        ``bodies`` are :meth:`contacts`' own: exactly one of ``radius`` (a scalar or ``(B,)``) and ``radii``
+        (``(B, max_bodies)`` float32, a pair within ``R_i + R_j``); ``capacity=None`` makes one counting call and then one with
+        room for the fullest system; ``lists=False`` only counts.  ``phase`` is 0 for a pair within reach now (a
+        :meth:`contacts` pair), 1 for one whose closest passage falls before the horizon and within reach, 2 for one still
+        closing at the horizon and within reach there.  With a horizon of 0, or with all velocities equal, the approaches are
+        the contacts.  The device computes no time and no distance: the result derives ``time`` and ``miss_distance`` in float64
+        from the entries' words.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if (radius is None) == (radii is None):
+            raise ValueError("exactly one of radius and radii must be given")
+
+        def per_system(value, name):
+            if hasattr(value, "detach"):  # a torch tensor
+                value = value.detach().cpu().numpy()
+            out = np.asarray(value, dtype=np.float32)
+            if out.ndim == 0:
+                out = np.full(B, out, dtype=np.float32)
+            if out.shape != (B,):
+                raise ValueError(f"{name} must be a scalar or have shape ({B},), got {tuple(out.shape)}")
+            return np.ascontiguousarray(out)
+        hor = per_system(horizon, "horizon")
+        rad = rr = None
+        if radius is not None:
+            rad = per_system(radius, "radius")
+        else:
+            if hasattr(radii, "detach"):
+                radii = radii.detach().cpu().numpy()
+            rr = np.ascontiguousarray(np.asarray(radii, dtype=np.float32))
+            if rr.shape != (B, n):
+                raise ValueError(f"radii must have shape ({B}, {n}), got {tuple(rr.shape)}")
+        sub = None
+        if subset is not None:
+            if hasattr(subset, "detach"):
+                subset = subset.detach().cpu().numpy()
+            sub = np.ascontiguousarray(np.asarray(subset))
+            if sub.dtype != np.bool_ and sub.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {sub.dtype}")
+            if sub.shape != (B, n):
+                raise ValueError(f"subset must have shape ({B}, {n}), got {tuple(sub.shape)}")
+            sub = sub.view(np.uint8)
+        if capacity is not None:
+            if int(capacity) != capacity or capacity < 0:
+                raise ValueError(f"capacity must be an integer >= 0, not {capacity!r}")
+            if B * int(capacity) > _lib.BATCH_APPROACHES_MAX_ENTRIES:
+                raise ValueError(f"{B} systems x capacity {capacity} exceed 2^27 list entries")
+        fp, ubyte = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)
+
+        def call(cap, want_bodies):
+            systems = np.zeros(B, dtype=APPROACH_SYSTEM_DTYPE)
+            body = np.zeros((B, n), dtype=APPROACH_BODY_DTYPE) if want_bodies else None
+            entries = np.zeros((B, cap), dtype=APPROACH_DTYPE) if cap > 0 else None
+            self._use_current_stream()
+            _check(self._lib, self._lib.nbody_batch_approaches(
+                self._h, _ptr(self.positions), _ptr(self.velocities), hor.ctypes.data_as(fp),
+                rad.ctypes.data_as(fp) if rad is not None else None, rr.ctypes.data_as(fp) if rr is not None else None,
+                sub.ctypes.data_as(ubyte) if sub is not None else None, cap,
+                systems.ctypes.data_as(ctypes.POINTER(_lib.BatchApproachSystem)),
+                body.ctypes.data_as(ctypes.POINTER(_lib.BatchApproachBody)) if want_bodies else None,
+                entries.ctypes.data_as(ctypes.POINTER(_lib.BatchApproach)) if cap > 0 else None), self._h)
+            return systems, body, entries
+
+        if not lists:
+            systems, body, _ = call(0, bodies)
+            return ApproachesResult(systems, body, None, hor)
+        if capacity is None:
+            systems, body, _ = call(0, bodies)
+            capacity = int(systems["pairs"].max()) if B else 0
+            if capacity == 0:
+                return ApproachesResult(systems, body, np.zeros((B, 0), dtype=APPROACH_DTYPE), hor)
+            if B * capacity > _lib.BATCH_APPROACHES_MAX_ENTRIES:
+                raise ValueError(f"{B} systems x {capacity} approaches in the fullest exceed 2^27 list entries: pass a capacity")
+        systems, body, entries = call(int(capacity), bodies)
+        return ApproachesResult(systems, body, entries if entries is not None else np.zeros((B, 0), dtype=APPROACH_DTYPE), hor)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1443,6 +1534,75 @@ class ContactsResult:
                 f"max_degree={self.max_degree.tolist()}, closest={self.closest.tolist()})")
 
 
+class ApproachesResult:
+    """What :meth:`BatchedSystem.approaches` listed.  Per system (``(B,)`` arrays): ``pairs`` (int64: the approaches, exact
+    whatever the capacity), ``stored`` (int64: those in the list, ``min(pairs, capacity)``), ``truncated`` (bool:
+    ``stored < pairs``), ``bodies`` (int32: the bodies taking part), ``approaching`` (those with an approach), ``max_degree``,
+    ``now_pairs``, ``passing`` and ``ending`` (int32: the pairs of phase 0, 1 and 2, which add up to ``pairs``) and ``horizon``
+    (float64: the call's).  Per body (``(B, max_bodies)`` int32, ``None`` without ``bodies``): ``degree`` (its approaches),
+    ``upper`` (those of higher index), ``first`` (where its entries start in the list: the exclusive sum of ``upper``) and
+    ``now`` (those of phase 0: its :meth:`BatchedSystem.contacts` degree).  The list (``(B, capacity)``, ``None`` without
+    ``lists``): ``i``, ``j`` (int32, -1 from ``stored`` on), ``r2``, ``rv``, ``v2`` (float32: the separation squared, ``d . w``
+    and the relative speed squared, from ``i`` to ``j``), ``phase`` (int32: 0 now, 1 passage, 2 end, -1 from ``stored`` on) and,
+    derived here in float64 from those words, ``time`` (0, ``-rv / v2`` and the horizon by phase) and ``miss_distance``
+    (``sqrt(r2)``, ``sqrt(max(0, r2 - rv^2 / v2))`` and ``sqrt(r2 + 2 rv H + v2 H^2)``), both ``inf`` from ``stored`` on.
+    ``systems``, ``body_records`` and ``entries`` are the records themselves."""
+
+    def __init__(self, systems, bodies, entries, horizon):
+        self.systems, self.body_records, self.entries = systems, bodies, entries
+        self.horizon = np.asarray(horizon, dtype=np.float64)
+        for name in ("pairs", "stored", "bodies", "approaching", "max_degree", "passing", "ending"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.now_pairs = np.ascontiguousarray(systems["now"])
+        self.truncated = self.stored < self.pairs
+        for name in ("degree", "upper", "first", "now"):
+            setattr(self, name, None if bodies is None else np.ascontiguousarray(bodies[name]))
+        for name in ("i", "j", "r2", "rv", "v2", "phase"):
+            setattr(self, name, None if entries is None else np.ascontiguousarray(entries[name]))
+        self.capacity = 0 if entries is None else int(entries.shape[1])
+        self.time = self.miss_distance = None
+        if entries is not None:
+            r2, rv, v2 = (getattr(self, name).astype(np.float64) for name in ("r2", "rv", "v2"))
+            H = np.broadcast_to(self.horizon[:, None], r2.shape)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                passage = -rv / v2
+                time = np.select([self.phase == 0, self.phase == 1, self.phase == 2], [0.0, passage, H], np.inf)
+                miss2 = np.select([self.phase == 0, self.phase == 1, self.phase == 2],
+                                  [r2, r2 - rv * rv / v2, r2 + 2.0 * rv * H + v2 * H * H], np.inf)
+            self.time, self.miss_distance = time, np.sqrt(np.maximum(miss2, 0.0))
+
+    def _need_list(self):
+        if self.entries is None:
+            raise ValueError("this needs the list: call approaches(lists=True)")
+
+    def pairs_of(self, s: int) -> np.ndarray:
+        """``(stored[s], 2)`` int32: the listed approaches of system ``s`` as rows ``(i, j)``, ``i < j``, in the list's order."""
+        self._need_list()
+        m = int(self.stored[s])
+        return np.stack([self.i[s, :m], self.j[s, :m]], axis=1)
+
+    def partners_of(self, s: int, i: int) -> np.ndarray:
+        """int32, ascending: every body that approaches body ``i`` of system ``s``, from the list, in both directions.  Raises
+        where the system is truncated: the list would not hold them all."""
+        self._need_list()
+        if self.truncated[s]:
+            raise ValueError(f"system {s} is truncated ({int(self.stored[s])} of {int(self.pairs[s])} approaches): call again with more capacity")
+        p = self.pairs_of(s)
+        return np.sort(np.concatenate([p[p[:, 0] == i, 1], p[p[:, 1] == i, 0]]))
+
+    def soonest(self, s: int):
+        """``(entries, time, miss_distance)`` of system ``s``'s listed approaches ordered by ``time``, ties in the list's order:
+        the records, and the two float64 arrays that go with them.  The first is the next encounter."""
+        self._need_list()
+        m = int(self.stored[s])
+        order = np.argsort(self.time[s, :m], kind="stable")
+        return self.entries[s, :m][order], self.time[s, :m][order], self.miss_distance[s, :m][order]
+
+    def __repr__(self):
+        return (f"ApproachesResult(pairs={self.pairs.tolist()}, stored={self.stored.tolist()}, now={self.now_pairs.tolist()}, "
+                f"passing={self.passing.tolist()}, ending={self.ending.tolist()}, approaching={self.approaching.tolist()})")
+
+
 def interactions_per_step(counts, massive=None) -> int:
     """Ordered body-body interactions one step of these systems evaluates (``sum n_s^2``, the one-sided convention); with
     ``massive`` (:meth:`BatchedSystem.set_massive_counts`) ``sum n_s * min(m_s, n_s)``: every body against the massive ones."""
@@ -1517,4 +1677,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "ApproachesResult", "APPROACH_SYSTEM_DTYPE", "APPROACH_BODY_DTYPE", "APPROACH_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]

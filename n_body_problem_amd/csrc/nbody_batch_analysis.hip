@@ -1,9 +1,10 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
 // structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
-// lists, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_contacts.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// lists, approach lists, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_approaches.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
+#include "nbody_batch_approaches_math.h"
 #include "nbody_batch_contacts_math.h"
 #include "nbody_batch_correlation_math.h"
 #include "nbody_batch_gravity_math.h"
@@ -2115,6 +2116,239 @@ hipError_t launch_batch_contacts(const float4 *pos, const int *counts, const uns
     });
 }
 
+// ---- approaches (include/nbody_batch_approaches.h): per system every unordered pair of bodies that comes within a radius, or
+// within the sum of its two bodies' radii, on straight lines at the current velocities before a horizon, as a list
+// (i, j, r2, rv, v2, phase) ascending in i and then in j, with per body its approaches and their place in the list and per
+// system their number by phase.  batch_contacts_kernel's sibling, with its count, place and fill in one launch and its units,
+// over the position-plus-velocity image of batch_pairs_kernel.  It reads the state and writes only the handle's records; no
+// choice in it depends on the schedule, and it computes no time and no distance.
+
+static_assert(sizeof(BatchApproachSystem) == sizeof(nbody_batch_approach_system) && sizeof(nbody_batch_approach_system) == 48 &&
+                  offsetof(BatchApproachSystem, bodies) == offsetof(nbody_batch_approach_system, bodies) &&
+                  offsetof(BatchApproachSystem, approaching) == offsetof(nbody_batch_approach_system, approaching) &&
+                  offsetof(BatchApproachSystem, max_degree) == offsetof(nbody_batch_approach_system, max_degree) &&
+                  offsetof(BatchApproachSystem, reserved) == offsetof(nbody_batch_approach_system, reserved) &&
+                  offsetof(BatchApproachSystem, pairs) == offsetof(nbody_batch_approach_system, pairs) &&
+                  offsetof(BatchApproachSystem, stored) == offsetof(nbody_batch_approach_system, stored) &&
+                  offsetof(BatchApproachSystem, now) == offsetof(nbody_batch_approach_system, now) &&
+                  offsetof(BatchApproachSystem, passing) == offsetof(nbody_batch_approach_system, passing) &&
+                  offsetof(BatchApproachSystem, ending) == offsetof(nbody_batch_approach_system, ending) &&
+                  offsetof(BatchApproachSystem, reserved2) == offsetof(nbody_batch_approach_system, reserved2) &&
+                  offsetof(nbody_batch_approach_system, pairs) == 16 && offsetof(nbody_batch_approach_system, reserved2) == 44,
+              "nbody_batch_approaches_math.h mirrors the system record of nbody_batch_approaches.h");
+static_assert(sizeof(BatchApproachBody) == sizeof(nbody_batch_approach_body) && sizeof(nbody_batch_approach_body) == 16 &&
+                  offsetof(BatchApproachBody, degree) == offsetof(nbody_batch_approach_body, degree) &&
+                  offsetof(BatchApproachBody, upper) == offsetof(nbody_batch_approach_body, upper) &&
+                  offsetof(BatchApproachBody, first) == offsetof(nbody_batch_approach_body, first) &&
+                  offsetof(BatchApproachBody, now) == offsetof(nbody_batch_approach_body, now),
+              "nbody_batch_approaches_math.h mirrors the body record of nbody_batch_approaches.h");
+static_assert(sizeof(BatchApproach) == sizeof(nbody_batch_approach) && sizeof(nbody_batch_approach) == 24 &&
+                  offsetof(BatchApproach, i) == offsetof(nbody_batch_approach, i) && offsetof(BatchApproach, j) == offsetof(nbody_batch_approach, j) &&
+                  offsetof(BatchApproach, r2) == offsetof(nbody_batch_approach, r2) && offsetof(BatchApproach, rv) == offsetof(nbody_batch_approach, rv) &&
+                  offsetof(BatchApproach, v2) == offsetof(nbody_batch_approach, v2) &&
+                  offsetof(BatchApproach, phase) == offsetof(nbody_batch_approach, phase),
+              "nbody_batch_approaches_math.h mirrors the list entry of nbody_batch_approaches.h");
+static_assert(kApproachesMaxEntries == NBODY_BATCH_APPROACHES_MAX_ENTRIES, "nbody_batch_approaches_math.h mirrors the limit of nbody_batch_approaches.h");
+static_assert(kApproachNow == NBODY_BATCH_APPROACH_NOW && kApproachPassage == NBODY_BATCH_APPROACH_PASSAGE && kApproachEnd == NBODY_BATCH_APPROACH_END,
+              "nbody_batch_approaches_math.h mirrors the phases of nbody_batch_approaches.h");
+
+// The separation at the horizon (m2, six fused operations), the same phases either way.  0: it is computed for a column only
+// where a ballot finds a lane whose pair is decided at the horizon -- a scalar branch.  1: every lane computes it for every pair.
+// Measured on an MI355X (profiles/batch_rate_approaches.txt; Plummer spheres at 0.2 mean spacings and a horizon of one
+// crossing, the counting call and the listing call without the body records at 1024 x 1024, 4096 x 256 and 256 x 4096, ms):
+// behind the ballot 1.87, 7.17 and 0.55 counting and 3.97, 13.30 and 1.63 listing; in every lane 1.48, 5.62 and 0.45 counting
+// and 3.23, 10.27 and 1.46 listing.  The same bytes (the list's checksum agrees).  Half of all pairs are closing, and a
+// distant closing pair has its closest point beyond a short horizon, so nearly every column finds such a lane in its wave: the
+// branch saves nothing and adds its compare and its wait.  So: every lane, which lost in no case.
+#ifndef NBODY_BATCH_APPROACHES_END_ALWAYS
+#define NBODY_BATCH_APPROACHES_END_ALWAYS 1
+#endif
+// The fill's second walk, as NBODY_BATCH_CONTACTS_FILL_ALWAYS: 0 skips it in a wave with nothing to write.
+#ifndef NBODY_BATCH_APPROACHES_FILL_ALWAYS
+#define NBODY_BATCH_APPROACHES_FILL_ALWAYS 0
+#endif
+
+constexpr int kApproachTallies = 3 + kApproachPhases;  // bodies, approaching, max_degree, then the pairs of each phase
+
+// The phases of the RPL pairs of one column: words[q] and phase[q] of row q against pj.
+template <int RPL>
+__device__ inline void approaches_column(const ApproachPoint (&mine)[RPL], const float (&t2)[RPL], const ApproachPoint &pj, float h,
+                                         ApproachWords (&words)[RPL], int (&phase)[RPL])
+{
+    bool ends = false;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        words[q] = approaches_words(mine[q], pj);
+        ends = ends || approaches_ends(words[q], t2[q], h);
+    }
+    const bool reach = NBODY_BATCH_APPROACHES_END_ALWAYS || __ballot(ends) != 0;  // the same in every lane of the wave
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        phase[q] = approaches_phase(words[q], t2[q], h, reach ? approaches_m2(mine[q], pj, h) : __builtin_inff());
+}
+
+// LDS: img[2 j] = {x, y, z, radius} and img[2 j + 1] = {vx, vy, vz, take} of body j, two ds_read_b128 per column (128 KiB at
+// 4096 bodies, batch_pairs_kernel's image, under the limit raised before the launch).  The radius is 0 in radius mode and in
+// radii mode a NaN where the body takes no part, which is within no threshold; the take-part flag replaces the velocity's unused
+// fourth word, and a column without it is skipped on the scalar unit.  The sums of `upper` over the 64 rows of every unit are
+// the only other LDS.  radius2 is b2 per system (!RADII), radii one radius per slot (RADII), horizon H per system; subset and
+// bodies may be NULL; list is NULL iff capacity == 0.
+template <int RPL, bool RADII>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RPL == 1 ? 8 : 4))) void batch_approaches_kernel(
+    const float4 *__restrict__ pos, const float4 *__restrict__ vel, const int *__restrict__ counts,
+    const unsigned char *__restrict__ subset, const float *__restrict__ radius2, const float *__restrict__ radii,
+    const float *__restrict__ horizon, int max_bodies, long long capacity, BatchApproachBody *__restrict__ bodies,
+    BatchApproach *__restrict__ list, BatchApproachSystem *__restrict__ systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ int totals[kContactUnits];
+    __shared__ int tally[kApproachTallies];
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & (kContactsWave - 1), wave = tid / kContactsWave, waves = T / kContactsWave;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float b2 = RADII ? 0.f : radius2[blockIdx.x];
+    const float h = horizon[blockIdx.x];
+    if (tid < kContactUnits)
+        totals[tid] = 0;
+    if (tid < kApproachTallies)
+        tally[tid] = 0;
+    __syncthreads();
+    ApproachPoint x[RPL];
+    float rad[RPL];
+    bool take[RPL];
+    int taking = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        x[q] = ApproachPoint{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        rad[q] = contacts_no_radius();
+        take[q] = false;
+        if (r < n) {
+            const float4 p = pos[base + r], v = vel[base + r];
+            x[q] = ApproachPoint{p.x, p.y, p.z, v.x, v.y, v.z};
+            take[q] = !subset || subset[base + r] != 0;
+            if (RADII)
+                rad[q] = take[q] ? radii[base + r] : contacts_no_radius();
+            taking += take[q] ? 1 : 0;
+            img[2 * r] = make_int4(__float_as_int(p.x), __float_as_int(p.y), __float_as_int(p.z), RADII ? __float_as_int(rad[q]) : 0);
+            img[2 * r + 1] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), take[q] ? 1 : 0);
+        }
+    }
+    if (taking)
+        atomicAdd(&tally[0], taking);  // integers: the order of the additions does not matter
+    __syncthreads();                   // the image is in place
+    // Count: every row walks every column.
+    ApproachRow row[RPL];
+    int phases[kApproachPhases] = {0, 0, 0};
+    float t2[RPL];
+    ApproachWords words[RPL];
+    int phase[RPL];
+    for (int j = 0; j < n; ++j) {
+        const int4 pj = img[2 * j], vj = img[2 * j + 1];  // wave-uniform addresses: broadcast LDS reads
+        if (__builtin_amdgcn_readfirstlane(vj.w) == 0)
+            continue;  // takes no part: the flag is the same in every lane, so the branch is a scalar one
+        const ApproachPoint column{__int_as_float(pj.x), __int_as_float(pj.y), __int_as_float(pj.z),
+                                   __int_as_float(vj.x), __int_as_float(vj.y), __int_as_float(vj.z)};
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            t2[q] = RADII ? contacts_radii_t2(rad[q], __int_as_float(pj.w)) : b2;
+        approaches_column<RPL>(x, t2, column, h, words, phase);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = q * T + tid;
+            approaches_step(row[q], phases, contacts_examined(take[q], true, r, j), r, j, phase[q]);
+        }
+    }
+    int approaching = 0, max_degree = 0;
+    int within[RPL];  // the inclusive sum of upper over the lower lanes of the row's unit, and the row
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        approaching += row[q].degree >= 1 ? 1 : 0;
+        max_degree = row[q].degree > max_degree ? row[q].degree : max_degree;
+        within[q] = contacts_wave_scan(row[q].upper, lane);
+        if (lane == kContactsWave - 1)
+            totals[contacts_unit(q, waves, wave)] = within[q];
+    }
+    // Integers again: sums and a maximum, in any order.
+    if (approaching)
+        atomicAdd(&tally[1], approaching);
+    if (max_degree)
+        atomicMax(&tally[2], max_degree);
+#pragma unroll
+    for (int k = 0; k < kApproachPhases; ++k)
+        if (phases[k])
+            atomicAdd(&tally[3 + k], phases[k]);
+    __syncthreads();
+    // Place, as batch_contacts_kernel does: the units in ascending order hold the rows in ascending order.
+    int first[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        first[q] = contacts_units_below(totals, contacts_unit(q, waves, wave)) + within[q] - row[q].upper;
+    const long long pairs = (long long)contacts_units_below(totals, RPL * waves);
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (bodies && r < max_bodies)
+            bodies[base + r] = approaches_body(row[q], first[q]);
+    }
+    if (tid == 0)
+        systems[blockIdx.x] = approaches_system(tally[0], tally[1], tally[2], pairs, capacity, tally[3 + kApproachNow],
+                                                tally[3 + kApproachPassage], tally[3 + kApproachEnd]);
+    if (capacity == 0)
+        return;  // the same in every lane; no barrier follows
+    // Fill: a row walks the columns above it again and writes its entries from `first` on while they are below the capacity.
+    // No row of this wave is below its first lane's row of q = 0, so no column up to that one is above any of them.
+    BatchApproach *mine = list + (size_t)blockIdx.x * (size_t)capacity;
+    bool fills = false;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        fills = fills || approaches_row_fills(first[q], row[q].upper, capacity);
+    if (NBODY_BATCH_APPROACHES_FILL_ALWAYS || __ballot(fills) != 0) {
+        int t[RPL];
+#pragma unroll
+        for (int q = 0; q < RPL; ++q)
+            t[q] = 0;
+        for (int j = wave * kContactsWave + 1; j < n; ++j) {
+            const int4 pj = img[2 * j], vj = img[2 * j + 1];
+            if (__builtin_amdgcn_readfirstlane(vj.w) == 0)
+                continue;
+            const ApproachPoint column{__int_as_float(pj.x), __int_as_float(pj.y), __int_as_float(pj.z),
+                                       __int_as_float(vj.x), __int_as_float(vj.y), __int_as_float(vj.z)};
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                t2[q] = RADII ? contacts_radii_t2(rad[q], __int_as_float(pj.w)) : b2;
+            approaches_column<RPL>(x, t2, column, h, words, phase);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                const int r = q * T + tid;
+                approaches_fill(mine, capacity, first[q], t[q], contacts_examined(take[q], true, r, j), r, j, words[q], phase[q]);
+            }
+        }
+    }
+    // The pads, from `stored` on.
+    for (long long k = contacts_stored(pairs, capacity) + tid; k < capacity; k += T)
+        mine[k] = approaches_pad();
+}
+
+// One launch over all systems.  32 bytes of dynamic LDS per body, 128 KiB at 4096 bodies beside the totals: the figure
+// launch_batch_pairs runs at.  Exactly one of radius2 and radii is given; subset and bodies may be NULL; list is NULL iff
+// capacity == 0.
+hipError_t launch_batch_approaches(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *subset,
+                                   const float *radius2, const float *radii, const float *horizon, int n_systems, int max_bodies,
+                                   long long capacity, BatchApproachBody *bodies, BatchApproach *list, BatchApproachSystem *systems,
+                                   hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = 2 * kBatchBytesPerBody * (size_t)max_bodies;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        const auto launch = [&](auto mode) {
+            return launch_analysis_kernel(batch_approaches_kernel<rpl(), mode()>, n_systems, sh.threads, lds, stream, pos, vel, counts,
+                                          subset, radius2, radii, horizon, max_bodies, capacity, bodies, list, systems);
+        };
+        return radii ? launch(std::true_type{}) : launch(std::false_type{});
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -2233,6 +2467,14 @@ struct BatchAnalysis {
     DeviceArray<float> contacts_radius2;               // [n_systems]
     std::vector<float> contacts_radius2_host;          // the last call's b[s] b[s]
     DeviceArray<float> contacts_radii;                 // [n_systems][max_bodies], the device copy of `radii`
+    DeviceArray<BatchApproachSystem> approaches_systems;  // [n_systems]
+    DeviceArray<BatchApproachBody> approaches_bodies;     // [n_systems][max_bodies]
+    DeviceArray<BatchApproach> approaches_list;           // [n_systems][capacity] of the largest call so far
+    DeviceArray<unsigned char> approaches_subset;         // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<float> approaches_radius2;                // [n_systems]
+    std::vector<float> approaches_radius2_host;           // the last call's b[s] b[s]
+    DeviceArray<float> approaches_radii;                  // [n_systems][max_bodies], the device copy of `radii`
+    DeviceArray<float> approaches_horizon;                // [n_systems], the device copy of `horizon`
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -2666,6 +2908,70 @@ int nbody_batch_contacts(nbody_batch *b, const float *d_pos, const float *radius
     BATCH_TRY(b, copy_out(b, systems_out, a->contacts_systems, B));
     BATCH_TRY(b, copy_out(b, bodies_out, a->contacts_bodies, slots));
     BATCH_TRY(b, copy_out(b, list_out, a->contacts_list, entries));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_approaches(nbody_batch *b, const float *d_pos, const float *d_vel, const float *horizon, const float *radius,
+                           const float *radii, const unsigned char *subset, long long capacity, nbody_batch_approach_system *systems_out,
+                           nbody_batch_approach_body *bodies_out, nbody_batch_approach *list_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_approaches: batch is NULL");
+    if (!d_pos || !d_vel || !horizon || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: NULL argument");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies;
+    for (size_t s = 0; s < B; ++s) {
+        if (!approaches_horizon_valid(horizon[s]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: the horizon of system " + std::to_string(s) + " must be finite and >= 0");
+    }
+    if (!radius == !radii)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: exactly one of radius and radii must be given");
+    for (size_t s = 0; radius && s < B; ++s) {
+        if (!correlation_edge_valid(radius[s]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: the radius of system " + std::to_string(s) + " must be finite and >= 0");
+    }
+    std::string refused;
+    if (radii && !batch_radii_ok(radii, b->counts.data(), b->n_systems, b->max_bodies, &refused))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: " + refused);
+    if (capacity < 0)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: capacity must be >= 0");
+    if ((capacity > 0) != (list_out != nullptr))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: list_out must be given iff capacity > 0");
+    if (capacity > kApproachesMaxEntries / (long long)B)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_approaches: n_systems x capacity must not exceed 2^27");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    if (radius) {
+        a->approaches_radius2_host.resize(B);
+        for (size_t s = 0; s < B; ++s)
+            a->approaches_radius2_host[s] = contacts_radius_t2(radius[s]);  // b2: one fp32 product
+    }
+    const size_t entries = B * (size_t)capacity;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->approaches_systems.ensure(B));
+    BATCH_TRY(b, a->approaches_horizon.ensure(B));
+    BATCH_TRY(b, a->approaches_radius2.ensure(radius ? B : 0));
+    BATCH_TRY(b, a->approaches_radii.ensure(radii ? slots : 0));
+    BATCH_TRY(b, a->approaches_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->approaches_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->approaches_list.ensure(entries));
+    BATCH_TRY(b, hipMemcpyAsync(a->approaches_horizon.ptr, horizon, sizeof(float) * B, hipMemcpyHostToDevice, b->stream));
+    if (radius)
+        BATCH_TRY(b, hipMemcpyAsync(a->approaches_radius2.ptr, a->approaches_radius2_host.data(), sizeof(float) * B, hipMemcpyHostToDevice,
+                                    b->stream));
+    if (radii)
+        BATCH_TRY(b, hipMemcpyAsync(a->approaches_radii.ptr, radii, sizeof(float) * slots, hipMemcpyHostToDevice, b->stream));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->approaches_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_approaches(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                         subset ? a->approaches_subset.ptr : nullptr, radius ? a->approaches_radius2.ptr : nullptr,
+                                         radii ? a->approaches_radii.ptr : nullptr, a->approaches_horizon.ptr, (int)b->n_systems,
+                                         (int)b->max_bodies, capacity, bodies_out ? a->approaches_bodies.ptr : nullptr,
+                                         capacity > 0 ? a->approaches_list.ptr : nullptr, a->approaches_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->approaches_systems, B));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->approaches_bodies, slots));
+    BATCH_TRY(b, copy_out(b, list_out, a->approaches_list, entries));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

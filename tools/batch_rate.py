@@ -127,7 +127,17 @@ room for the fullest system without and with the per-body records, and the same 
 radius, against neighbours(k=1, radius, lists=False) without its records -- the nearest existing work, the yardstick -- and
 pairs() on the same state: all synchronous calls, wall clock, alternated, medians and spreads.  The kernel has two fills behind
 NBODY_BATCH_CONTACTS_FILL_ALWAYS: the line names the library it timed (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run
-per build gives both, and the line carries a checksum of the list so that the two can be seen to agree."""
+per build gives both, and the line carries a checksum of the list so that the two can be seen to agree.
+
+--approaches: instead, the approach lists (BatchedSystem.approaches).  For n x B = 1024 x 1024, 4096 x 256 and 256 x 4096 (or
+--cases), one line per case on Plummer spheres at a radius of 0.2 mean interparticle spacings within the half-mass radius: the
+counting call (capacity 0, without the per-body records) and the listing call with room for the fullest system, at a horizon
+of one crossing of that radius at the velocity dispersion (H = radius / rms speed) and at H = 0, next to the same two calls of
+contacts() at the same radius in the same run: all synchronous calls, wall clock, alternated, medians and spreads, and the ratio
+of every approaches() call to its contacts() call.  The H = 0 list is asserted to be contacts()' list.  The kernel computes the
+separation at the horizon two ways behind NBODY_BATCH_APPROACHES_END_ALWAYS: the line names the library it timed
+(NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both, and carries a checksum of the list so that the
+two can be seen to agree.  By instruction count a pair costs about three r2 chains plus the compares, against one in contacts()."""
 import argparse
 import json
 import os
@@ -183,6 +193,8 @@ ap.add_argument("--neighbours", action="store_true", help="neighbours() at k = 1
                 "the lists against structure(k=6) and pairs() on the same Plummer spheres, wall clock")
 ap.add_argument("--contacts", action="store_true", help="contacts() at 0.2 and 1.0 mean spacings, counting and listing, with radii, "
                 "against neighbours(k=1, radius, lists=False) and pairs() on the same Plummer spheres, wall clock")
+ap.add_argument("--approaches", action="store_true", help="approaches() at 0.2 mean spacings, counting and listing, at a horizon of "
+                "one crossing and at 0, against contacts() at the same radius on the same Plummer spheres, wall clock")
 ap.add_argument("--correlation", action="store_true", help="correlation() at 8, 16 and 32 bins, with 8 sources and with the bins "
                 "against pairs() and neighbours(k=6) on the same Plummer spheres, wall clock")
 args = ap.parse_args()
@@ -1196,6 +1208,66 @@ def contacts_lines():
         print(json.dumps(line), flush=True)
 
 
+def approaches_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        spacing = float(np.float32((4.0 / 3.0 * np.pi * 1.3048 ** 3 / (n / 2.0)) ** (1.0 / 3.0)))   # as in --contacts
+        b = float(np.float32(0.2 * spacing))
+        speed = float(np.sqrt((V[..., :3].astype(np.float64) ** 2).sum(axis=-1).mean()))             # the rms speed
+        H = float(np.float32(b / speed))
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            room = int(batch.approaches(H, b, lists=False, bodies=False).pairs.max())
+            room0 = int(batch.contacts(b, lists=False, bodies=False).pairs.max())
+            calls = {"contacts_count": lambda: batch.contacts(b, lists=False, bodies=False),
+                     "contacts_list_lean": lambda: batch.contacts(b, capacity=room0, bodies=False),
+                     "approaches_count": lambda: batch.approaches(H, b, lists=False, bodies=False),
+                     "approaches_list_lean": lambda: batch.approaches(H, b, capacity=room, bodies=False),
+                     "approaches_count_h0": lambda: batch.approaches(0.0, b, lists=False, bodies=False),
+                     "approaches_list_lean_h0": lambda: batch.approaches(0.0, b, capacity=room0, bodies=False)}
+            for fn in calls.values():                               # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):                           # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        res, still, touching = found["approaches_list_lean"], found["approaches_list_lean_h0"], found["contacts_list_lean"]
+        for name in ("i", "j", "r2"):                               # the H = 0 list is contacts()' list
+            assert getattr(still, name).tobytes() == getattr(touching, name).tobytes(), name
+        assert np.array_equal(still.pairs, touching.pairs) and not still.passing.any() and not still.ending.any()
+        line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"), "mean_spacing": round(spacing, 5),
+                "radius": round(b, 5), "rms_speed": round(speed, 5), "horizon": round(H, 5), "capacity": room, "capacity_h0": room0,
+                "pairs_per_system": round(float(res.pairs.mean()), 1), "now_per_system": round(float(res.now_pairs.mean()), 1),
+                "passing_per_system": round(float(res.passing.mean()), 1), "ending_per_system": round(float(res.ending.mean()), 1),
+                "list_megabytes": round(B * room * 24 / 1e6, 2), "list_crc32": zlib.crc32(res.entries.tobytes()), "h0_is_contacts": True}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for name in ("count", "list_lean"):
+            line[f"approaches_{name}_over_contacts"] = round(med[f"approaches_{name}"] / med[f"contacts_{name}"], 3)
+            line[f"approaches_{name}_h0_over_contacts"] = round(med[f"approaches_{name}_h0"] / med[f"contacts_{name}"], 3)
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+        print(json.dumps(line), flush=True)
+
+
+if args.approaches:
+    approaches_lines()
+    sys.exit(0)
 if args.contacts:
     contacts_lines()
     sys.exit(0)
