@@ -557,6 +557,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_contacts.h"
 /* approaches: per system every pair of bodies that comes within a radius, or within the sum of its two radii, on straight lines before a horizon, as a list (i, j, r2, rv, v2, phase) */
 #include "nbody_batch_approaches.h"
+/* radial profiles: per system the bodies in up to 32 shells about a centre and per shell the count and 23 fp64 sums (weight, radius, radial and tangential velocities, angular momentum, mean velocity, shape and velocity tensors), each in ascending body index */
+#include "nbody_batch_radial.h"
 
 #ifdef __cplusplus
 }

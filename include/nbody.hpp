@@ -754,6 +754,43 @@ public:
               "nbody_batch_approaches");
         return s;
     }
+    // Radial profiles (nbody_batch_radial.h): for every system the bodies in up to 32 shells about a centre.  edges: shells + 1
+    // ascending values >= 0 for all systems, or numSystems sets of them (told apart by the size: pass `shells`).  centre and
+    // velocity: empty for zeros, or numSystems x 3 values.  weight: NBODY_BATCH_WEIGHT_MASS or _NUMBER.  projected: -1, or the
+    // axis the radius leaves out.  subset: empty, or one byte per slot.  Returns the per-system records; records takes the
+    // shells of every system (shell t of system s at s * shells + t) and bodies the per-body records.  Every sum runs over the
+    // shell's members in ascending body index.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_radial_system> radialProfile(const float *dPositions, const float *dVelocities, int shells,
+                                                         const std::vector<double> &edges,
+                                                         std::vector<nbody_batch_radial_shell> *records = nullptr,
+                                                         const std::vector<double> &centre = {}, const std::vector<double> &velocity = {},
+                                                         int weight = NBODY_BATCH_WEIGHT_MASS, int projected = -1,
+                                                         const std::vector<unsigned char> &subset = {},
+                                                         std::vector<nbody_batch_radial_body> *bodies = nullptr)
+    {
+        const size_t slots = (size_t)systems_ * (size_t)maxBodies_;
+        if (shells < 1 || shells > NBODY_BATCH_RADIAL_MAX_SHELLS)
+            throw std::invalid_argument("nbody::Batch::radialProfile: shells must be 1 ... 32");
+        const size_t given = (size_t)shells + 1;
+        const bool perSystem = edges.size() == given * (size_t)systems_ && systems_ != 1;
+        if (edges.size() != given && !perSystem)
+            throw std::invalid_argument("nbody::Batch::radialProfile: shells + 1 edges, or as many per system");
+        if ((!centre.empty() && centre.size() != 3 * (size_t)systems_) || (!velocity.empty() && velocity.size() != 3 * (size_t)systems_))
+            throw std::invalid_argument("nbody::Batch::radialProfile: three values per system for centre and velocity, or none");
+        if (!subset.empty() && subset.size() != slots)
+            throw std::invalid_argument("nbody::Batch::radialProfile: one subset byte per slot, or none");
+        std::vector<nbody_batch_radial_system> s((size_t)systems_);
+        if (records)
+            records->resize((size_t)systems_ * (size_t)shells);
+        if (bodies)
+            bodies->resize(slots);
+        check(nbody_batch_radial_profile(b_, dPositions, dVelocities, shells, edges.data(), perSystem ? 1 : 0,
+                                         centre.empty() ? nullptr : centre.data(), velocity.empty() ? nullptr : velocity.data(), weight,
+                                         projected, subset.empty() ? nullptr : subset.data(), s.data(),
+                                         records ? records->data() : nullptr, bodies ? bodies->data() : nullptr),
+              "nbody_batch_radial_profile");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

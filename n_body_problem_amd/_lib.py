@@ -504,6 +504,35 @@ _APPROACHES_PROTOTYPES = {
 }
 
 
+BATCH_RADIAL_MAX_SHELLS = 32
+BATCH_RADIAL_BELOW, BATCH_RADIAL_UNMEASURED, BATCH_RADIAL_NOT_TAKING = -1, -2, -3
+
+
+class BatchRadialShell(ctypes.Structure):
+    """``nbody_batch_radial_shell`` of include/nbody_batch_radial.h."""
+    _fields_ = [("count", ctypes.c_longlong), ("weight", c_double), ("radius", c_double), ("vr1", c_double), ("vr2", c_double),
+                ("vt2", c_double), ("L", c_double * 3), ("U", c_double * 3), ("M", c_double * 6), ("V", c_double * 6)]
+
+
+class BatchRadialSystem(ctypes.Structure):
+    """``nbody_batch_radial_system`` of include/nbody_batch_radial.h."""
+    _fields_ = [("selected", c_int), ("below", c_int), ("above", c_int), ("unmeasured", c_int), ("shells", c_int), ("projected", c_int),
+                ("total_weight", c_double), ("centre", c_double * 3), ("velocity", c_double * 3)]
+
+
+class BatchRadialBody(ctypes.Structure):
+    """``nbody_batch_radial_body`` of include/nbody_batch_radial.h."""
+    _fields_ = [("shell", c_int), ("reserved", c_int), ("radius", c_double), ("radial_velocity", c_double)]
+
+
+#: the entry point of include/nbody_batch_radial.h (radial profiles of batched ensembles), which nbody.h includes
+_RADIAL_PROTOTYPES = {
+    "nbody_batch_radial_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), c_int, POINTER(c_double),
+                                           POINTER(c_double), c_int, c_int, POINTER(ctypes.c_ubyte), POINTER(BatchRadialSystem),
+                                           POINTER(BatchRadialShell), POINTER(BatchRadialBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -534,7 +563,7 @@ def load() -> ctypes.CDLL:
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
-                list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()):
+                list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -640,6 +669,11 @@ def contacts_names():
 def approaches_names():
     """The entry point of nbody_batch_approaches.h."""
     return list(_APPROACHES_PROTOTYPES)
+
+
+def radial_names():
+    """The entry point of nbody_batch_radial.h."""
+    return list(_RADIAL_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

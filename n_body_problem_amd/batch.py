@@ -112,6 +112,17 @@ APPROACH_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("r2", np.float32),
 assert APPROACH_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproachSystem) == 48
 assert APPROACH_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproachBody) == 16
 assert APPROACH_DTYPE.itemsize == ctypes.sizeof(_lib.BatchApproach) == 24
+#: the records of :meth:`BatchedSystem.radial_profile`: numpy's views of ``nbody_batch_radial_system``, ``_shell`` and ``_body``
+RADIAL_SYSTEM_DTYPE = np.dtype([("selected", np.int32), ("below", np.int32), ("above", np.int32), ("unmeasured", np.int32),
+                                ("shells", np.int32), ("projected", np.int32), ("total_weight", np.float64),
+                                ("centre", np.float64, 3), ("velocity", np.float64, 3)])
+RADIAL_SHELL_DTYPE = np.dtype([("count", np.int64), ("weight", np.float64), ("radius", np.float64), ("vr1", np.float64),
+                               ("vr2", np.float64), ("vt2", np.float64), ("L", np.float64, 3), ("U", np.float64, 3),
+                               ("M", np.float64, 6), ("V", np.float64, 6)])
+RADIAL_BODY_DTYPE = np.dtype([("shell", np.int32), ("reserved", np.int32), ("radius", np.float64), ("radial_velocity", np.float64)])
+assert RADIAL_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialSystem) == 80
+assert RADIAL_SHELL_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialShell) == 192
+assert RADIAL_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialBody) == 24
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -969,6 +980,84 @@ class BatchedSystem:
         systems, body, entries = call(int(capacity), bodies)
         return ApproachesResult(systems, body, entries if entries is not None else np.zeros((B, 0), dtype=APPROACH_DTYPE), hor)
 
+    def radial_profile(self, edges, *, centre=None, velocity=None, weight: str = "mass", subset=None, projected=None,
+                       shells: bool = True, bodies: bool = False) -> "RadialProfileResult":
+        """How every system is built as a function of radius (``include/nbody_batch_radial.h`` states the rules): the bodies
+        binned on the device into up to 32 shells about a centre, from the current state (waits for the queued work), and per
+        shell the count and the 23 float64 sums that density, mean radial velocity, velocity dispersions, anisotropy,
+        rotation and shape are made of.  ``edges`` holds the ``shells + 1`` (2 ... 33) ascending float64 edges, ``>= 0``: one
+        set ``(shells + 1,)`` for all systems or ``(B, shells + 1)``, one per system.  Shell ``t`` holds the bodies with
+        ``edges[t] < r <= edges[t + 1]``, compared as float64 squares.  ``centre`` and ``velocity`` give the frame: ``None``
+        (zeros), ``(3,)``, ``(B, 3)``, for ``centre`` also a :class:`StructureResult` (its ``centre``) or ``"density"``, which
+        calls ``structure(weight=weight, bodies=False)`` first and takes its density centre.  ``weight``: ``"mass"`` or
+        ``"number"``.  ``subset``, a ``(B, max_bodies)`` bool or uint8 array (numpy or torch), selects who takes part (all
+        bodies below the count, without it), whatever the massive counts.  ``projected``: ``None`` for spherical shells, or the
+        axis 0, 1 or 2 that the radius and the radial velocity leave out: annuli in the plane of the other two.  Every sum
+        runs over the shell's members in ascending body index, so a system's records are the same bits in any slot, batch and
+        capacity.  ``shells=False`` skips the 192 bytes per shell on their way to the host and ``bodies=True`` adds the 24
+        bytes per body (``body_shell``, ``body_radius``, ``body_radial_velocity``); the remaining records are the same bits
+        either way.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+        if projected is not None and projected not in (0, 1, 2):
+            raise ValueError(f"projected must be None, 0, 1 or 2, not {projected!r}")
+        if hasattr(edges, "detach"):  # a torch tensor
+            edges = edges.detach().cpu().numpy()
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
+        if e.ndim == 1:
+            per_system = 0
+        elif e.ndim == 2 and e.shape[0] == B:
+            per_system = 1
+        else:
+            raise ValueError(f"edges must have shape (shells + 1,) or ({B}, shells + 1), got {tuple(e.shape)}")
+        count = e.shape[-1] - 1
+        if not 1 <= count <= _lib.BATCH_RADIAL_MAX_SHELLS:
+            raise ValueError(f"shells must be 1 ... {_lib.BATCH_RADIAL_MAX_SHELLS}, not {count}")
+
+        def frame(name, value):
+            if value is None:
+                return None
+            if hasattr(value, "detach"):
+                value = value.detach().cpu().numpy()
+            v = np.asarray(value, dtype=np.float64)
+            if v.shape == (3,):
+                v = np.broadcast_to(v, (B, 3))
+            if v.shape != (B, 3):
+                raise ValueError(f"{name} must have shape (3,) or ({B}, 3), got {tuple(v.shape)}")
+            return np.ascontiguousarray(v)
+
+        if isinstance(centre, str):
+            if centre != "density":
+                raise ValueError(f"centre must be an array, a StructureResult or 'density', not {centre!r}")
+            centre = self.structure(weight=weight, bodies=False).centre
+        elif isinstance(centre, StructureResult):
+            centre = centre.centre
+        c, v0 = frame("centre", centre), frame("velocity", velocity)
+        mask = None
+        if subset is not None:
+            mask = subset.detach().cpu().numpy() if hasattr(subset, "detach") else subset
+            mask = np.ascontiguousarray(np.asarray(mask))
+            if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {mask.dtype}")
+            if mask.shape != (B, n):
+                raise ValueError(f"subset must have shape ({B}, {n}), got {tuple(mask.shape)}")
+            mask = mask.view(np.uint8)
+        systems = np.zeros(B, dtype=RADIAL_SYSTEM_DTYPE)
+        rec = np.zeros((B, count), dtype=RADIAL_SHELL_DTYPE) if shells else None
+        body = np.zeros((B, n), dtype=RADIAL_BODY_DTYPE) if bodies else None
+        dbl = ctypes.POINTER(ctypes.c_double)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_radial_profile(
+            self._h, _ptr(self.positions), _ptr(self.velocities), count, e.ctypes.data_as(dbl), per_system,
+            c.ctypes.data_as(dbl) if c is not None else None, v0.ctypes.data_as(dbl) if v0 is not None else None,
+            WEIGHTS[weight], -1 if projected is None else int(projected),
+            mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if mask is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchRadialSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchRadialShell)) if shells else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchRadialBody)) if bodies else None), self._h)
+        return RadialProfileResult(systems, rec, body, e, weight)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1601,6 +1690,146 @@ class ApproachesResult:
     def __repr__(self):
         return (f"ApproachesResult(pairs={self.pairs.tolist()}, stored={self.stored.tolist()}, now={self.now_pairs.tolist()}, "
                 f"passing={self.passing.tolist()}, ending={self.ending.tolist()}, approaching={self.approaching.tolist()})")
+
+
+class RadialProfileResult:
+    """What :meth:`BatchedSystem.radial_profile` found.  ``edges`` as given (float64, ``(shells + 1,)`` or ``(B, shells + 1)``),
+    ``shells`` their number less one, ``weight`` as given and ``projected`` (``None``, or the axis left out).  Per system
+    (``(B,)`` arrays): ``selected`` (int32: the bodies taking part), ``below`` (within the first edge), ``above`` (beyond the
+    last) and ``unmeasured`` (a NaN or infinite coordinate or velocity), so that ``below + count.sum(axis=1) + above +
+    unmeasured == selected``; ``total_weight`` (float64: the weight of all measured bodies taking part, ``below`` and ``above``
+    included); ``centre`` and ``velocity`` ``(B, 3)``, the frame as used.  Per shell, ``None`` without ``shells``: ``count``
+    ``(B, shells)`` int64, and the float64 sums over the shell's members in ascending body index ``weight_sum`` (w), ``radius``
+    (w r), ``vr1`` (w vr), ``vr2`` (w vr vr), ``vt2`` (w vt2), all ``(B, shells)``; ``L`` (w d x u) and ``U`` (w u), ``(B,
+    shells, 3)``; ``M`` (w d_a d_b) and ``V`` (w u_a u_b), ``(B, shells, 6)`` in the order xx, yy, zz, xy, xz, yz.  Per body,
+    ``(B, max_bodies)`` or ``None`` without ``bodies``: ``body_shell`` (int32: the shell, -1 below, ``shells`` above, -2
+    unmeasured, -3 not taking part), ``body_radius`` and ``body_radial_velocity`` (float64).  ``systems``, ``shell_records`` and
+    ``body_records`` are the records themselves.  The derived values below are computed on the host in float64; one that
+    divides by a shell's weight is NaN where the shell is empty (or weighs nothing)."""
+
+    def __init__(self, systems, shells, bodies, edges, weight):
+        self.systems, self.shell_records, self.body_records, self.edges, self.weight = systems, shells, bodies, edges, weight
+        for name in ("selected", "below", "above", "unmeasured", "total_weight", "centre", "velocity"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.shells = int(edges.shape[-1]) - 1
+        p = int(systems["projected"][0]) if len(systems) else -1
+        self.projected = None if p < 0 else p
+        self.count = self.weight_sum = self.radius = self.vr1 = self.vr2 = self.vt2 = self.L = self.U = self.M = self.V = None
+        if shells is not None:
+            self.count = np.ascontiguousarray(shells["count"])
+            self.weight_sum = np.ascontiguousarray(shells["weight"])
+            for name in ("radius", "vr1", "vr2", "vt2", "L", "U", "M", "V"):
+                setattr(self, name, np.ascontiguousarray(shells[name]))
+        self.body_shell = self.body_radius = self.body_radial_velocity = None
+        if bodies is not None:
+            self.body_shell, self.body_radius, self.body_radial_velocity = (
+                np.ascontiguousarray(bodies[name]) for name in ("shell", "radius", "radial_velocity"))
+
+    def _need_shells(self):
+        if self.count is None:
+            raise ValueError("this needs the shell records: call radial_profile(shells=True)")
+
+    def _edges(self) -> np.ndarray:
+        """``(B, shells + 1)`` float64."""
+        return np.broadcast_to(self.edges, (len(self.systems), self.shells + 1))
+
+    def _per_weight(self, total) -> np.ndarray:
+        """``total / weight_sum`` with the weight broadcast over trailing axes, NaN where the weight is not > 0."""
+        self._need_shells()
+        w = self.weight_sum.reshape(self.weight_sum.shape + (1,) * (total.ndim - 2))
+        ok = w > 0.0
+        return np.where(ok, total / np.where(ok, w, 1.0), np.nan)
+
+    @staticmethod
+    def _tensor(t6) -> np.ndarray:
+        """``(..., 6)`` in the order xx, yy, zz, xy, xz, yz as symmetric ``(..., 3, 3)``."""
+        return t6[..., [0, 3, 4, 3, 1, 5, 4, 5, 2]].reshape(t6.shape[:-1] + (3, 3))
+
+    def mean_radius(self) -> np.ndarray:
+        """``(B, shells)``: the weighted mean radius of every shell's members."""
+        return self._per_weight(self.radius)
+
+    def volume(self) -> np.ndarray:
+        """``(B, shells)``: ``4 pi / 3 (hi^3 - lo^3)`` of every shell; in projected mode the area ``pi (hi^2 - lo^2)`` of the
+        annulus."""
+        e = self._edges()
+        if self.projected is not None:
+            return np.pi * (e[:, 1:] ** 2 - e[:, :-1] ** 2)
+        return 4.0 / 3.0 * np.pi * (e[:, 1:] ** 3 - e[:, :-1] ** 3)
+
+    def density(self) -> np.ndarray:
+        """``(B, shells)``: the weight per volume (per area, projected); 0 in an empty shell."""
+        self._need_shells()
+        return self.weight_sum / self.volume()
+
+    def number_density(self) -> np.ndarray:
+        """``(B, shells)``: the members per volume (per area, projected); 0 in an empty shell."""
+        self._need_shells()
+        return self.count / self.volume()
+
+    def cumulative_weight(self) -> np.ndarray:
+        """``(B, shells)``: the weight between the first edge and the outer edge of every shell.  The bodies within the first
+        edge (``below``) are not in it: ``total_weight`` is the weight of all measured bodies, those and ``above`` included."""
+        self._need_shells()
+        return np.cumsum(self.weight_sum, axis=1)
+
+    def radial_velocity(self) -> np.ndarray:
+        """``(B, shells)``: the weighted mean radial velocity."""
+        return self._per_weight(self.vr1)
+
+    def sigma_r(self) -> np.ndarray:
+        """``(B, shells)``: the radial velocity dispersion, ``sqrt(<vr^2> - <vr>^2)``."""
+        return np.sqrt(np.maximum(self._per_weight(self.vr2) - self.radial_velocity() ** 2, 0.0))
+
+    def sigma_t(self, rotation: bool = False) -> np.ndarray:
+        """``(B, shells)``: the tangential velocity dispersion per tangential direction, ``sqrt(<vt^2> / 2)``.  With
+        ``rotation`` the mean rotation is taken off first: ``sqrt((<vt^2> - v_rot^2) / 2)`` with the streaming speed ``v_rot =
+        |L| / (sum of w r)``, the shell's angular momentum over its weighted radius."""
+        vt2 = self._per_weight(self.vt2)
+        if rotation:
+            ok = self.radius > 0.0
+            v_rot = np.where(ok, np.linalg.norm(self.L, axis=2) / np.where(ok, self.radius, 1.0), np.nan)
+            vt2 = np.maximum(vt2 - v_rot ** 2, 0.0)
+        return np.sqrt(vt2 / 2.0)
+
+    def anisotropy(self) -> np.ndarray:
+        """``(B, shells)``: Binney's ``beta = 1 - <vt^2> / (2 <vr^2>)``: 0 isotropic, 1 radial, negative tangential.  NaN where
+        ``<vr^2>`` is 0.  Spherical shells only."""
+        if self.projected is not None:
+            raise ValueError("the anisotropy needs spherical shells: radial_profile(projected=None)")
+        vr2, vt2 = self._per_weight(self.vr2), self._per_weight(self.vt2)
+        ok = vr2 > 0.0
+        return np.where(ok, 1.0 - vt2 / (2.0 * np.where(ok, vr2, 1.0)), np.nan)
+
+    def specific_angular_momentum(self) -> np.ndarray:
+        """``(B, shells, 3)``: ``L / W``, the weighted mean of ``d x u``."""
+        return self._per_weight(self.L)
+
+    def dispersion_tensor(self) -> np.ndarray:
+        """``(B, shells, 3, 3)``: ``V / W - (U / W)(U / W)^T``, the velocity dispersion tensor about the shell's mean velocity."""
+        mean = self._per_weight(self.U)
+        return self._tensor(self._per_weight(self.V)) - mean[..., :, None] * mean[..., None, :]
+
+    def axis_ratios(self) -> np.ndarray:
+        """``(B, shells, 2)``: ``b / a`` and ``c / a`` of every shell, the square roots of the ratios of the eigenvalues
+        (``numpy.linalg.eigvalsh``) of the shape tensor ``M / W`` to its largest.  NaN where the shell is empty."""
+        m = self._tensor(self._per_weight(self.M))
+        ok = np.isfinite(m).all(axis=(2, 3))
+        lam = np.linalg.eigvalsh(np.where(ok[..., None, None], m, np.eye(3)))  # ascending
+        top = lam[..., 2]
+        good = ok & (top > 0.0)
+        ratio = np.maximum(lam[..., 1::-1], 0.0) / np.where(good, top, 1.0)[..., None]
+        return np.where(good[..., None], np.sqrt(ratio), np.nan)
+
+    def circular_velocity(self) -> np.ndarray:
+        """``(B, shells)``: ``sqrt(cumulative_weight() / outer edge)``, the circular speed at every shell's outer edge from the
+        weight between the first edge and it (``below`` is not in it), with G = 1."""
+        return np.sqrt(self.cumulative_weight() / self._edges()[:, 1:])
+
+    def __repr__(self):
+        return (f"RadialProfileResult(shells={self.shells}, weight={self.weight!r}, projected={self.projected}, "
+                f"selected={self.selected.tolist()}, below={self.below.tolist()}, above={self.above.tolist()}, "
+                f"unmeasured={self.unmeasured.tolist()})")
 
 
 def interactions_per_step(counts, massive=None) -> int:

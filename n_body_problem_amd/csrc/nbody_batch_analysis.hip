@@ -1,6 +1,6 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
 // structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
-// lists, approach lists, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_approaches.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// lists, approach lists, radial profiles, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_radial.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
@@ -14,6 +14,7 @@
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_neighbours_math.h"
 #include "nbody_batch_pairs_elements.h"
+#include "nbody_batch_radial_math.h"
 #include "nbody_batch_radii_check.h"
 #include "nbody_batch_span_math.h"
 #include "nbody_batch_structure_math.h"
@@ -2349,6 +2350,162 @@ hipError_t launch_batch_approaches(const float4 *pos, const float4 *vel, const i
     });
 }
 
+// ---- radial profiles (include/nbody_batch_radial.h): per system the bodies in up to 32 shells about a centre and per shell
+// the count and 23 fp64 sums, each over the shell's members in ascending body index.  A sibling of the other analysis kernels:
+// one workgroup per system with batch_shape's workgroup over the position-plus-velocity image of batch_pairs_kernel.  It reads
+// the state and writes only the handle's records.  The arithmetic is nbody_batch_radial_math.h's, which the CPU driver runs too.
+
+static_assert(sizeof(BatchRadialShell) == sizeof(nbody_batch_radial_shell) && sizeof(nbody_batch_radial_shell) == 192 &&
+                  offsetof(BatchRadialShell, count) == offsetof(nbody_batch_radial_shell, count) &&
+                  offsetof(BatchRadialShell, weight) == offsetof(nbody_batch_radial_shell, weight) &&
+                  offsetof(BatchRadialShell, radius) == offsetof(nbody_batch_radial_shell, radius) &&
+                  offsetof(BatchRadialShell, vr1) == offsetof(nbody_batch_radial_shell, vr1) &&
+                  offsetof(BatchRadialShell, vr2) == offsetof(nbody_batch_radial_shell, vr2) &&
+                  offsetof(BatchRadialShell, vt2) == offsetof(nbody_batch_radial_shell, vt2) &&
+                  offsetof(BatchRadialShell, L) == offsetof(nbody_batch_radial_shell, L) &&
+                  offsetof(BatchRadialShell, U) == offsetof(nbody_batch_radial_shell, U) &&
+                  offsetof(BatchRadialShell, M) == offsetof(nbody_batch_radial_shell, M) &&
+                  offsetof(BatchRadialShell, V) == offsetof(nbody_batch_radial_shell, V) && offsetof(nbody_batch_radial_shell, L) == 48 &&
+                  offsetof(nbody_batch_radial_shell, V) == 144,
+              "nbody_batch_radial_math.h mirrors the shell record of nbody_batch_radial.h");
+static_assert(sizeof(BatchRadialSystem) == sizeof(nbody_batch_radial_system) && sizeof(nbody_batch_radial_system) == 80 &&
+                  offsetof(BatchRadialSystem, selected) == offsetof(nbody_batch_radial_system, selected) &&
+                  offsetof(BatchRadialSystem, below) == offsetof(nbody_batch_radial_system, below) &&
+                  offsetof(BatchRadialSystem, above) == offsetof(nbody_batch_radial_system, above) &&
+                  offsetof(BatchRadialSystem, unmeasured) == offsetof(nbody_batch_radial_system, unmeasured) &&
+                  offsetof(BatchRadialSystem, shells) == offsetof(nbody_batch_radial_system, shells) &&
+                  offsetof(BatchRadialSystem, projected) == offsetof(nbody_batch_radial_system, projected) &&
+                  offsetof(BatchRadialSystem, total_weight) == offsetof(nbody_batch_radial_system, total_weight) &&
+                  offsetof(BatchRadialSystem, centre) == offsetof(nbody_batch_radial_system, centre) &&
+                  offsetof(BatchRadialSystem, velocity) == offsetof(nbody_batch_radial_system, velocity) &&
+                  offsetof(nbody_batch_radial_system, total_weight) == 24 && offsetof(nbody_batch_radial_system, velocity) == 56,
+              "nbody_batch_radial_math.h mirrors the system record of nbody_batch_radial.h");
+static_assert(sizeof(BatchRadialBody) == sizeof(nbody_batch_radial_body) && sizeof(nbody_batch_radial_body) == 24 &&
+                  offsetof(BatchRadialBody, shell) == offsetof(nbody_batch_radial_body, shell) &&
+                  offsetof(BatchRadialBody, reserved) == offsetof(nbody_batch_radial_body, reserved) &&
+                  offsetof(BatchRadialBody, radius) == offsetof(nbody_batch_radial_body, radius) &&
+                  offsetof(BatchRadialBody, radial_velocity) == offsetof(nbody_batch_radial_body, radial_velocity),
+              "nbody_batch_radial_math.h mirrors the body record of nbody_batch_radial.h");
+static_assert(kRadialMaxShells == NBODY_BATCH_RADIAL_MAX_SHELLS && kRadialBelow == NBODY_BATCH_RADIAL_BELOW &&
+                  kRadialUnmeasured == NBODY_BATCH_RADIAL_UNMEASURED && kRadialNotTaking == NBODY_BATCH_RADIAL_NOT_TAKING,
+              "nbody_batch_radial_math.h mirrors the limit and the shell words of nbody_batch_radial.h");
+
+// The ascending walk (phase 2), the same bytes either way (the shell records' checksum agrees).  1: one walker per (shell, term
+// group), 6 x 32 walkers in three waves, each wave running two groups' code (one wave's lanes go round three times where the
+// workgroup is one wave).  0: one walker per shell adding all 23 terms, 32 lanes of one wave.  Measured on an MI355X
+// (profiles/batch_rate_radial.txt; Plummer spheres, the call with the shell records alone at 1024 x 1024, 4096 x 256 and
+// 256 x 4096, medians of 31, ms): split 2.31, 3.10 and 6.85 at 32 shells and 1.48, 3.19 and 2.00 at 8; whole 2.13, 2.66 and 6.97
+// at 32 shells and 1.59, 2.24 and 1.86 at 8.  The whole walk wins where the walk is long (4096 bodies: by 14 % and 30 %) and is
+// within the run-to-run scatter of the split elsewhere: every wave of the split forms the words of every body again, and the
+// square root and the division once more, and a wave with members in most shells gains no idle lanes from the split.  So:
+// whole, which no case lost beyond the scatter.
+#ifndef NBODY_BATCH_RADIAL_SPLIT_WALK
+#define NBODY_BATCH_RADIAL_SPLIT_WALK 0
+#endif
+
+constexpr int kRadialTallies = 4;  // selected, below, above, unmeasured
+
+// The image of a system as the walk reads it: wave-uniform addresses, broadcast LDS reads.
+struct RadialImage {
+    const int4 *img;
+    const signed char *shells;
+    __host__ __device__ int shell(int j) const { return shells[j]; }
+    __host__ __device__ RadialPoint point(int j) const
+    {
+        const int4 p = img[2 * j], v = img[2 * j + 1];
+        return RadialPoint{__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), __int_as_float(p.w),
+                           __int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z)};
+    }
+};
+
+// LDS: img[2 j] = {x, y, z, m} and img[2 j + 1] = {vx, vy, vz, 0} of body j (128 KiB at 4096 bodies, batch_pairs_kernel's
+// image, under the limit raised before the launch), then one byte per body, its shell word (-3 ... 32).  The squared edges and
+// the frame of the system are in LDS too: every read of them is a broadcast.  edges2: the squared edges, those of system s at
+// s * edges_stride (0: one set for all); frames: centre[3], velocity[3] per system.  subset, bodies and shells_out may be NULL.
+// No waves_per_eu: the walker of a whole shell holds 24 fp64 words beside those of the body, which 64 registers do not hold.
+template <int RPL, bool SPLIT>
+__global__ __launch_bounds__(1024) void batch_radial_kernel(const float4 *__restrict__ pos, const float4 *__restrict__ vel,
+                                                            const int *__restrict__ counts, const unsigned char *__restrict__ subset,
+                                                            const double *__restrict__ edges2, int edges_stride,
+                                                            const double *__restrict__ frames, int max_bodies, int shells, int projected,
+                                                            int weight, BatchRadialBody *__restrict__ bodies,
+                                                            BatchRadialShell *__restrict__ shells_out, BatchRadialSystem *__restrict__ systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ double e2[kRadialMaxShells + 1];
+    __shared__ double frame[kRadialFrameWords];
+    __shared__ int tally[kRadialTallies];
+    signed char *shell_of = reinterpret_cast<signed char *>(img + 2 * (size_t)max_bodies);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    if (tid <= shells)  // shells + 1 <= 33 edges, and no workgroup is below 64 lanes
+        e2[tid] = edges2[(size_t)blockIdx.x * (size_t)edges_stride + tid];
+    if (tid < kRadialFrameWords)
+        frame[tid] = frames[(size_t)blockIdx.x * kRadialFrameWords + tid];
+    if (tid < kRadialTallies)
+        tally[tid] = 0;
+    __syncthreads();
+    // Phase 1: every row decides its shell on squares and writes its shell byte and its body record.
+    int selected = 0, below = 0, above = 0, unmeasured = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        BatchRadialBody record = radial_body_absent();
+        if (r < n) {
+            const float4 p = pos[base + r], v = vel[base + r];
+            img[2 * r] = make_int4(__float_as_int(p.x), __float_as_int(p.y), __float_as_int(p.z), __float_as_int(p.w));
+            img[2 * r + 1] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), 0);
+            int sh = kRadialNotTaking;
+            if (!subset || subset[base + r] != 0) {
+                const RadialWords b = radial_words(RadialPoint{p.x, p.y, p.z, p.w, v.x, v.y, v.z}, frame, projected);
+                sh = radial_shell(b, e2, shells);
+                selected += 1;
+                below += sh == kRadialBelow ? 1 : 0;
+                above += sh == shells ? 1 : 0;
+                unmeasured += sh == kRadialUnmeasured ? 1 : 0;
+                if (bodies)
+                    record = radial_body(sh, b);
+            }
+            shell_of[r] = (signed char)sh;
+        }
+        if (bodies && r < max_bodies)
+            bodies[base + r] = record;
+    }
+    // Integers: the order of the additions does not matter.
+    if (selected)
+        atomicAdd(&tally[0], selected);
+    if (below)
+        atomicAdd(&tally[1], below);
+    if (above)
+        atomicAdd(&tally[2], above);
+    if (unmeasured)
+        atomicAdd(&tally[3], unmeasured);
+    __syncthreads();  // the image, the shell bytes and the tallies are in place
+    // Phase 2: the walkers, each through j = 0 ... n - 1.  Walker 0 is lane 0's first, and it alone adds total_weight.
+    const RadialImage image{img, shell_of};
+    double total = 0.0;
+    for (int w = tid; w < radial_walkers(SPLIT); w += T)
+        radial_walker(SPLIT, w, image, n, shells, frame, projected, weight,
+                      shells_out ? shells_out + (size_t)blockIdx.x * (size_t)shells : nullptr, &total);
+    if (tid == 0)
+        systems[blockIdx.x] = radial_system(tally[0], tally[1], tally[2], tally[3], shells, projected, total, frame);
+}
+
+// One launch over all systems.  32 bytes of dynamic LDS per body for the image and one for the shell byte, rounded up to 16.
+hipError_t launch_batch_radial(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *subset, const double *edges2,
+                               int edges_stride, const double *frames, int n_systems, int max_bodies, int shells, int projected, int weight,
+                               BatchRadialBody *bodies, BatchRadialShell *shells_out, BatchRadialSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = 2 * kBatchBytesPerBody * (size_t)max_bodies + ((size_t)max_bodies + 15) / 16 * 16;
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_radial_kernel<rpl(), NBODY_BATCH_RADIAL_SPLIT_WALK != 0>, n_systems, sh.threads, lds, stream, pos,
+                                      vel, counts, subset, edges2, edges_stride, frames, max_bodies, shells, projected, weight, bodies,
+                                      shells_out, systems);
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -2475,6 +2632,14 @@ struct BatchAnalysis {
     std::vector<float> approaches_radius2_host;           // the last call's b[s] b[s]
     DeviceArray<float> approaches_radii;                  // [n_systems][max_bodies], the device copy of `radii`
     DeviceArray<float> approaches_horizon;                // [n_systems], the device copy of `horizon`
+    DeviceArray<BatchRadialSystem> radial_systems;  // [n_systems]
+    DeviceArray<BatchRadialShell> radial_shells;    // [n_systems][shells] of the largest call that asked for shells
+    DeviceArray<BatchRadialBody> radial_bodies;     // [n_systems][max_bodies]
+    DeviceArray<unsigned char> radial_subset;       // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<double> radial_edges2;              // one set or [n_systems] sets of shells + 1 squared edges
+    std::vector<double> radial_edges2_host;         // the last call's: the copy's source until the stream is idle
+    DeviceArray<double> radial_frames;              // [n_systems][6]: centre, velocity
+    std::vector<double> radial_frames_host;         // the last call's
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -2972,6 +3137,77 @@ int nbody_batch_approaches(nbody_batch *b, const float *d_pos, const float *d_ve
     BATCH_TRY(b, copy_out(b, systems_out, a->approaches_systems, B));
     BATCH_TRY(b, copy_out(b, bodies_out, a->approaches_bodies, slots));
     BATCH_TRY(b, copy_out(b, list_out, a->approaches_list, entries));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_radial_profile(nbody_batch *b, const float *d_pos, const float *d_vel, int shells, const double *edges, int per_system,
+                               const double *centre, const double *velocity, int weight, int projected, const unsigned char *subset,
+                               nbody_batch_radial_system *systems_out, nbody_batch_radial_shell *shells_out,
+                               nbody_batch_radial_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_radial_profile: batch is NULL");
+    if (!d_pos || !d_vel || !edges || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: NULL argument");
+    if (shells < 1 || shells > NBODY_BATCH_RADIAL_MAX_SHELLS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: shells must be 1 ... 32");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (projected < kRadialSpherical || projected > 2)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: projected must be -1 ... 2");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, sets = per_system ? B : 1;
+    const size_t given = (size_t)shells + 1;
+    for (size_t s = 0; s < sets; ++s) {
+        const double *e = edges + s * given;
+        const std::string which = per_system ? " of system " + std::to_string(s) : std::string(" of all systems");
+        for (size_t t = 0; t < given; ++t) {
+            if (!radial_edge_valid(e[t]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: edge " + std::to_string(t) + which + " must be finite and >= 0");
+            if (t > 0 && !(e[t] > e[t - 1]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: edge " + std::to_string(t) + which +
+                                                       " is not above edge " + std::to_string(t - 1) + ": the edges must be strictly ascending");
+        }
+    }
+    for (size_t k = 0; k < 3 * B; ++k) {
+        if (centre && !radial_finite(centre[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: the centre of system " + std::to_string(k / 3) + " must be finite");
+        if (velocity && !radial_finite(velocity[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_radial_profile: the velocity of system " + std::to_string(k / 3) + " must be finite");
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->radial_edges2_host.resize(sets * given);
+    for (size_t k = 0; k < sets * given; ++k)
+        a->radial_edges2_host[k] = radial_edge2(edges[k]);  // e2: one fp64 product
+    a->radial_frames_host.resize(B * kRadialFrameWords);
+    for (size_t s = 0; s < B; ++s)
+        for (size_t c = 0; c < 3; ++c) {
+            a->radial_frames_host[s * kRadialFrameWords + c] = centre ? centre[3 * s + c] : 0.0;
+            a->radial_frames_host[s * kRadialFrameWords + 3 + c] = velocity ? velocity[3 * s + c] : 0.0;
+        }
+    const size_t records = shells_out ? B * (size_t)shells : 0;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->radial_systems.ensure(B));
+    BATCH_TRY(b, a->radial_edges2.ensure(sets * given));
+    BATCH_TRY(b, a->radial_frames.ensure(B * kRadialFrameWords));
+    BATCH_TRY(b, a->radial_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->radial_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->radial_shells.ensure(records));
+    BATCH_TRY(b, hipMemcpyAsync(a->radial_edges2.ptr, a->radial_edges2_host.data(), sizeof(double) * sets * given, hipMemcpyHostToDevice,
+                                b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(a->radial_frames.ptr, a->radial_frames_host.data(), sizeof(double) * B * kRadialFrameWords,
+                                hipMemcpyHostToDevice, b->stream));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->radial_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_radial(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                     subset ? a->radial_subset.ptr : nullptr, a->radial_edges2.ptr, per_system ? (int)given : 0,
+                                     a->radial_frames.ptr, (int)b->n_systems, (int)b->max_bodies, shells, projected, weight,
+                                     bodies_out ? a->radial_bodies.ptr : nullptr, shells_out ? a->radial_shells.ptr : nullptr,
+                                     a->radial_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->radial_systems, B));
+    BATCH_TRY(b, copy_out(b, shells_out, a->radial_shells, records));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->radial_bodies, slots));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

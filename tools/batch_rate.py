@@ -137,7 +137,16 @@ contacts() at the same radius in the same run: all synchronous calls, wall clock
 of every approaches() call to its contacts() call.  The H = 0 list is asserted to be contacts()' list.  The kernel computes the
 separation at the horizon two ways behind NBODY_BATCH_APPROACHES_END_ALWAYS: the line names the library it timed
 (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both, and carries a checksum of the list so that the
-two can be seen to agree.  By instruction count a pair costs about three r2 chains plus the compares, against one in contacts()."""
+two can be seen to agree.  By instruction count a pair costs about three r2 chains plus the compares, against one in contacts().
+
+--radial: instead, the radial profiles (BatchedSystem.radial_profile).  For n x B = 1024 x 1024, 4096 x 256 and 256 x 4096 (or
+--cases), one line per case on Plummer spheres about the origin with logarithmic edges from 0.05 to 10: the call with the shell
+records alone (32 and 8 shells), with the per-body records too, and with the per-system words alone, against
+structure(bodies=False) and against what the call replaces -- positions.cpu() plus velocities.cpu() plus a numpy binning of one
+quantity (the mass per shell) -- in the same run: all synchronous calls, wall clock, alternated after a warm-up of every call,
+medians and spreads.  The kernel walks the shells two ways behind NBODY_BATCH_RADIAL_SPLIT_WALK: the line names the library it
+timed (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both, and carries a checksum of the shell records
+so that the two can be seen to agree."""
 import argparse
 import json
 import os
@@ -197,6 +206,8 @@ ap.add_argument("--approaches", action="store_true", help="approaches() at 0.2 m
                 "one crossing and at 0, against contacts() at the same radius on the same Plummer spheres, wall clock")
 ap.add_argument("--correlation", action="store_true", help="correlation() at 8, 16 and 32 bins, with 8 sources and with the bins "
                 "against pairs() and neighbours(k=6) on the same Plummer spheres, wall clock")
+ap.add_argument("--radial", action="store_true", help="radial_profile() at 32 and 8 logarithmic shells, with and without the shell "
+                "and body records, against structure(bodies=False) and the download plus a numpy binning, wall clock")
 args = ap.parse_args()
 
 
@@ -1265,6 +1276,71 @@ def approaches_lines():
         print(json.dumps(line), flush=True)
 
 
+def radial_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        edges = {32: np.geomspace(0.05, 10.0, 33), 8: np.geomspace(0.05, 10.0, 9)}
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            def download_and_bin():
+                """What the call replaces: both arrays to the host, then the mass per shell of every system in numpy."""
+                p, v = batch.positions.cpu().numpy(), batch.velocities.cpu().numpy()
+                x = p[..., :3].astype(np.float64)
+                r = np.sqrt((x[..., 0] * x[..., 0] + x[..., 1] * x[..., 1]) + x[..., 2] * x[..., 2])
+                shell = np.searchsorted(edges[32], r, side="left")                  # 0 below, 1 ... 32 the shells, 33 above
+                flat = (np.arange(B)[:, None] * 34 + shell).ravel()
+                return np.bincount(flat, weights=p[..., 3].astype(np.float64).ravel(), minlength=B * 34).reshape(B, 34), v
+
+            calls = {"radial32": lambda: batch.radial_profile(edges[32]),
+                     "radial32_bodies": lambda: batch.radial_profile(edges[32], bodies=True),
+                     "radial32_systems_only": lambda: batch.radial_profile(edges[32], shells=False),
+                     "radial8": lambda: batch.radial_profile(edges[8]),
+                     "radial8_bodies": lambda: batch.radial_profile(edges[8], bodies=True),
+                     "structure_lean": lambda: batch.structure(bodies=False),
+                     "download_and_bin": download_and_bin}
+            for fn in calls.values():                               # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):                           # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        res, binned = found["radial32"], found["download_and_bin"][0]
+        assert np.array_equal(res.count.sum(axis=1) + res.below + res.above + res.unmeasured, res.selected)
+        assert np.allclose(res.weight_sum, binned[:, 1:33], rtol=1e-9, atol=1e-12)                 # the same profile, summed in another order
+        assert found["radial32_bodies"].shell_records.tobytes() == res.shell_records.tobytes()
+        line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"),
+                "members_per_system": round(float(res.count.sum(axis=1).mean()), 1),
+                "shells_megabytes": round(B * 32 * 192 / 1e6, 3), "bodies_megabytes": round(B * n * 24 / 1e6, 2),
+                "download_megabytes": round(2 * B * n * 16 / 1e6, 2), "shells_crc32": zlib.crc32(res.shell_records.tobytes()),
+                "shells8_crc32": zlib.crc32(found["radial8"].shell_records.tobytes())}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for name in ("radial32", "radial32_bodies", "radial8"):
+            line[name + "_over_structure"] = round(med[name] / med["structure_lean"], 3)
+            line[name + "_over_download_and_bin"] = round(med[name] / med["download_and_bin"], 3)
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+        print(json.dumps(line), flush=True)
+
+
+if args.radial:
+    radial_lines()
+    sys.exit(0)
 if args.approaches:
     approaches_lines()
     sys.exit(0)
