@@ -559,6 +559,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_approaches.h"
 /* radial profiles: per system the bodies in up to 32 shells about a centre and per shell the count and 23 fp64 sums (weight, radius, radial and tangential velocities, angular momentum, mean velocity, shape and velocity tensors), each in ascending body index */
 #include "nbody_batch_radial.h"
+/* surface maps: per system the bodies in a grid of up to 64 x 64 cells in a plane of the caller's choice and per cell the count and seven fp64 sums (weight, the line-of-sight velocity and its square, the two velocities in the plane, the depth and its square), each in ascending body index */
+#include "nbody_batch_surface.h"
 
 #ifdef __cplusplus
 }

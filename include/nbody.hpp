@@ -791,6 +791,47 @@ public:
               "nbody_batch_radial_profile");
         return s;
     }
+    // Surface maps (nbody_batch_surface.h): for every system the bodies in a grid of columns x rows cells (1 ... 64 each) in the
+    // plane of a view.  edgesA: columns + 1 ascending values for all systems, or numSystems sets of them; edgesB likewise with
+    // rows + 1 (both shared or both per system, told apart by edgesA's size).  centre and velocity: empty for zeros, or
+    // numSystems x 3 values.  axes: empty for the identity (A = x, B = y, Q = z), or numSystems x 9 values, the rows A, B and Q
+    // of every system.  weight: NBODY_BATCH_WEIGHT_MASS or _NUMBER.  subset: empty, or one byte per slot.  Returns the
+    // per-system records; cells takes the cells of every system (cell (i, j) of system s at (s * rows + j) * columns + i) and
+    // bodies the per-body records.  Every sum runs over the cell's members in ascending body index.  Changes nothing the
+    // handle keeps.
+    std::vector<nbody_batch_surface_system> surfaceMap(const float *dPositions, const float *dVelocities, int columns, int rows,
+                                                       const std::vector<double> &edgesA, const std::vector<double> &edgesB,
+                                                       std::vector<nbody_batch_surface_cell> *cells = nullptr,
+                                                       const std::vector<double> &centre = {}, const std::vector<double> &velocity = {},
+                                                       const std::vector<double> &axes = {}, int weight = NBODY_BATCH_WEIGHT_MASS,
+                                                       const std::vector<unsigned char> &subset = {},
+                                                       std::vector<nbody_batch_surface_body> *bodies = nullptr)
+    {
+        const size_t slots = (size_t)systems_ * (size_t)maxBodies_;
+        if (columns < 1 || columns > NBODY_BATCH_SURFACE_MAX_SIDE || rows < 1 || rows > NBODY_BATCH_SURFACE_MAX_SIDE)
+            throw std::invalid_argument("nbody::Batch::surfaceMap: columns and rows must be 1 ... 64");
+        const size_t givenA = (size_t)columns + 1, givenB = (size_t)rows + 1;
+        const bool perSystem = edgesA.size() == givenA * (size_t)systems_ && systems_ != 1;
+        if (edgesA.size() != givenA * (perSystem ? (size_t)systems_ : 1) || edgesB.size() != givenB * (perSystem ? (size_t)systems_ : 1))
+            throw std::invalid_argument("nbody::Batch::surfaceMap: columns + 1 and rows + 1 edges, or as many per system of both");
+        if ((!centre.empty() && centre.size() != 3 * (size_t)systems_) || (!velocity.empty() && velocity.size() != 3 * (size_t)systems_))
+            throw std::invalid_argument("nbody::Batch::surfaceMap: three values per system for centre and velocity, or none");
+        if (!axes.empty() && axes.size() != 9 * (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::surfaceMap: nine values per system for axes, or none");
+        if (!subset.empty() && subset.size() != slots)
+            throw std::invalid_argument("nbody::Batch::surfaceMap: one subset byte per slot, or none");
+        std::vector<nbody_batch_surface_system> s((size_t)systems_);
+        if (cells)
+            cells->resize((size_t)systems_ * (size_t)columns * (size_t)rows);
+        if (bodies)
+            bodies->resize(slots);
+        check(nbody_batch_surface_map(b_, dPositions, dVelocities, columns, rows, edgesA.data(), edgesB.data(), perSystem ? 1 : 0,
+                                      centre.empty() ? nullptr : centre.data(), velocity.empty() ? nullptr : velocity.data(),
+                                      axes.empty() ? nullptr : axes.data(), weight, subset.empty() ? nullptr : subset.data(), s.data(),
+                                      cells ? cells->data() : nullptr, bodies ? bodies->data() : nullptr),
+              "nbody_batch_surface_map");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

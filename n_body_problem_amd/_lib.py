@@ -533,6 +533,35 @@ _RADIAL_PROTOTYPES = {
 }
 
 
+BATCH_SURFACE_MAX_SIDE = 64
+BATCH_SURFACE_OUTSIDE, BATCH_SURFACE_UNMEASURED, BATCH_SURFACE_NOT_TAKING = -1, -2, -3
+
+
+class BatchSurfaceCell(ctypes.Structure):
+    """``nbody_batch_surface_cell`` of include/nbody_batch_surface.h."""
+    _fields_ = [("count", ctypes.c_longlong), ("weight", c_double), ("v1", c_double), ("v2", c_double), ("pa", c_double),
+                ("pb", c_double), ("z1", c_double), ("z2", c_double)]
+
+
+class BatchSurfaceSystem(ctypes.Structure):
+    """``nbody_batch_surface_system`` of include/nbody_batch_surface.h."""
+    _fields_ = [("selected", c_int), ("outside", c_int), ("unmeasured", c_int), ("columns", c_int), ("rows", c_int), ("occupied", c_int),
+                ("peak", c_int), ("peak_count", c_int), ("total_weight", c_double), ("centre", c_double * 3), ("velocity", c_double * 3)]
+
+
+class BatchSurfaceBody(ctypes.Structure):
+    """``nbody_batch_surface_body`` of include/nbody_batch_surface.h."""
+    _fields_ = [("cell", c_int), ("reserved", c_int), ("a", c_double), ("b", c_double)]
+
+
+#: the entry point of include/nbody_batch_surface.h (surface maps of batched ensembles), which nbody.h includes
+_SURFACE_PROTOTYPES = {
+    "nbody_batch_surface_map": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), c_int,
+                                        POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int, POINTER(ctypes.c_ubyte),
+                                        POINTER(BatchSurfaceSystem), POINTER(BatchSurfaceCell), POINTER(BatchSurfaceBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -563,7 +592,8 @@ def load() -> ctypes.CDLL:
                 list(_STRUCTURE_PROTOTYPES.items()) + list(_MEMBERS_PROTOTYPES.items()) + list(_HIERARCHY_PROTOTYPES.items()) + \
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
-                list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()):
+                list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()) + \
+                list(_SURFACE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -674,6 +704,11 @@ def approaches_names():
 def radial_names():
     """The entry point of nbody_batch_radial.h."""
     return list(_RADIAL_PROTOTYPES)
+
+
+def surface_names():
+    """The entry point of nbody_batch_surface.h."""
+    return list(_SURFACE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

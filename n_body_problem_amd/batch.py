@@ -123,6 +123,16 @@ RADIAL_BODY_DTYPE = np.dtype([("shell", np.int32), ("reserved", np.int32), ("rad
 assert RADIAL_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialSystem) == 80
 assert RADIAL_SHELL_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialShell) == 192
 assert RADIAL_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchRadialBody) == 24
+#: the records of :meth:`BatchedSystem.surface_map`: numpy's views of ``nbody_batch_surface_system``, ``_cell`` and ``_body``
+SURFACE_SYSTEM_DTYPE = np.dtype([("selected", np.int32), ("outside", np.int32), ("unmeasured", np.int32), ("columns", np.int32),
+                                 ("rows", np.int32), ("occupied", np.int32), ("peak", np.int32), ("peak_count", np.int32),
+                                 ("total_weight", np.float64), ("centre", np.float64, 3), ("velocity", np.float64, 3)])
+SURFACE_CELL_DTYPE = np.dtype([("count", np.int64), ("weight", np.float64), ("v1", np.float64), ("v2", np.float64),
+                               ("pa", np.float64), ("pb", np.float64), ("z1", np.float64), ("z2", np.float64)])
+SURFACE_BODY_DTYPE = np.dtype([("cell", np.int32), ("reserved", np.int32), ("a", np.float64), ("b", np.float64)])
+assert SURFACE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceSystem) == 88
+assert SURFACE_CELL_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceCell) == 64
+assert SURFACE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceBody) == 24
 #: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -1058,6 +1068,99 @@ class BatchedSystem:
             body.ctypes.data_as(ctypes.POINTER(_lib.BatchRadialBody)) if bodies else None), self._h)
         return RadialProfileResult(systems, rec, body, e, weight)
 
+    def surface_map(self, edges_a, edges_b=None, *, centre=None, velocity=None, axes=None, projected: int = 2, weight: str = "mass",
+                    subset=None, cells: bool = True, bodies: bool = False) -> "SurfaceMapResult":
+        """What every system looks like from a direction (``include/nbody_batch_surface.h`` states the rules): the bodies
+        binned on the device into a grid of ``columns x rows`` cells (1 ... 64 each) in the plane of a view, from the current
+        state (waits for the queued work), and per cell the count and the seven float64 sums that the surface density, the
+        line-of-sight velocity and its dispersion, the velocity in the plane and the depth are made of.  ``edges_a`` holds the
+        ``columns + 1`` ascending float64 edges of the map's first axis and ``edges_b`` the ``rows + 1`` of its second
+        (``None``: ``edges_a`` again): each ``(bins + 1,)`` for all systems or ``(B, bins + 1)``, one set per system
+        (:meth:`SurfaceMapResult.grid` makes evenly spaced ones).  Cell ``(j, i)`` holds the bodies with ``edges_a[i] <= a <
+        edges_a[i + 1]`` and ``edges_b[j] <= b < edges_b[j + 1]``: half-open on the right, the last edge included.
+        ``centre``, ``velocity``, ``weight`` and ``subset`` are :meth:`radial_profile`'s: the frame (``None``, ``(3,)``, ``(B,
+        3)``, for ``centre`` also a :class:`StructureResult` or ``"density"``), ``"mass"`` or ``"number"``, and a ``(B,
+        max_bodies)`` bool or uint8 mask (numpy or torch).  The view is three float64 row vectors per system, ``A`` (the first
+        axis), ``B`` (the second) and ``Q`` (the line of sight), as ``axes`` of shape ``(3, 3)`` or ``(B, 3, 3)``
+        (:meth:`SurfaceMapResult.view` builds an orthonormal triple for a direction; only finiteness is checked).  Without
+        ``axes``, ``projected = p`` takes the unit vectors of the two axes that are not ``p``, in ascending order, and ``p``
+        itself as ``Q``.  Every sum runs over the cell's members in ascending body index, so a system's records are the same
+        bits in any slot, batch and capacity.  ``cells=False`` skips the 64 bytes per cell on their way to the host and
+        ``bodies=True`` adds the 24 bytes per body (``body_cell``, ``body_a``, ``body_b``); the remaining records are the same
+        bits either way.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+
+        def host(value):
+            return value.detach().cpu().numpy() if hasattr(value, "detach") else value
+
+        def edge_set(name, value):
+            e = np.asarray(host(value), dtype=np.float64)
+            if not (e.ndim == 1 or (e.ndim == 2 and e.shape[0] == B)):
+                raise ValueError(f"{name} must have shape (bins + 1,) or ({B}, bins + 1), got {tuple(e.shape)}")
+            if not 1 <= e.shape[-1] - 1 <= _lib.BATCH_SURFACE_MAX_SIDE:
+                raise ValueError(f"columns and rows must be 1 ... {_lib.BATCH_SURFACE_MAX_SIDE}, not {e.shape[-1] - 1}")
+            return e
+
+        ea = edge_set("edges_a", edges_a)
+        eb = ea if edges_b is None else edge_set("edges_b", edges_b)
+        per_system = int(ea.ndim == 2 or eb.ndim == 2)
+        if per_system:
+            ea, eb = (np.broadcast_to(e, (B, e.shape[-1])) for e in (ea, eb))
+        ea, eb = np.ascontiguousarray(ea), np.ascontiguousarray(eb)
+        columns, rows = ea.shape[-1] - 1, eb.shape[-1] - 1
+
+        def frame(name, value):
+            if value is None:
+                return None
+            v = np.asarray(host(value), dtype=np.float64)
+            if v.shape == (3,):
+                v = np.broadcast_to(v, (B, 3))
+            if v.shape != (B, 3):
+                raise ValueError(f"{name} must have shape (3,) or ({B}, 3), got {tuple(v.shape)}")
+            return np.ascontiguousarray(v)
+
+        if isinstance(centre, str):
+            if centre != "density":
+                raise ValueError(f"centre must be an array, a StructureResult or 'density', not {centre!r}")
+            centre = self.structure(weight=weight, bodies=False).centre
+        elif isinstance(centre, StructureResult):
+            centre = centre.centre
+        c, v0 = frame("centre", centre), frame("velocity", velocity)
+        if axes is None:
+            if projected not in (0, 1, 2):
+                raise ValueError(f"projected must be 0, 1 or 2, not {projected!r}")
+            kept = [k for k in range(3) if k != projected]
+            view = np.eye(3)[[kept[0], kept[1], projected]]
+        else:
+            view = np.asarray(host(axes), dtype=np.float64)
+            if view.shape != (3, 3) and view.shape != (B, 3, 3):
+                raise ValueError(f"axes must have shape (3, 3) or ({B}, 3, 3), got {tuple(view.shape)}")
+        view = np.ascontiguousarray(np.broadcast_to(view, (B, 3, 3)))
+        mask = None
+        if subset is not None:
+            mask = np.ascontiguousarray(np.asarray(host(subset)))
+            if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {mask.dtype}")
+            if mask.shape != (B, n):
+                raise ValueError(f"subset must have shape ({B}, {n}), got {tuple(mask.shape)}")
+            mask = mask.view(np.uint8)
+        systems = np.zeros(B, dtype=SURFACE_SYSTEM_DTYPE)
+        rec = np.zeros((B, rows, columns), dtype=SURFACE_CELL_DTYPE) if cells else None
+        body = np.zeros((B, n), dtype=SURFACE_BODY_DTYPE) if bodies else None
+        dbl = ctypes.POINTER(ctypes.c_double)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_surface_map(
+            self._h, _ptr(self.positions), _ptr(self.velocities), columns, rows, ea.ctypes.data_as(dbl), eb.ctypes.data_as(dbl),
+            per_system, c.ctypes.data_as(dbl) if c is not None else None, v0.ctypes.data_as(dbl) if v0 is not None else None,
+            view.ctypes.data_as(dbl), WEIGHTS[weight],
+            mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if mask is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchSurfaceSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchSurfaceCell)) if cells else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchSurfaceBody)) if bodies else None), self._h)
+        return SurfaceMapResult(systems, rec, body, ea, eb, view, weight)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -1830,6 +1933,138 @@ class RadialProfileResult:
         return (f"RadialProfileResult(shells={self.shells}, weight={self.weight!r}, projected={self.projected}, "
                 f"selected={self.selected.tolist()}, below={self.below.tolist()}, above={self.above.tolist()}, "
                 f"unmeasured={self.unmeasured.tolist()})")
+
+
+class SurfaceMapResult:
+    """What :meth:`BatchedSystem.surface_map` found.  ``edges_a`` and ``edges_b`` as used (float64, ``(bins + 1,)`` or ``(B,
+    bins + 1)``), ``columns`` and ``rows`` their numbers less one, ``axes`` ``(B, 3, 3)`` the rows ``A``, ``B`` and ``Q`` of
+    every system and ``weight`` as given.  Per system (``(B,)`` arrays): ``selected`` (int32: the bodies taking part),
+    ``outside`` (beyond the grid) and ``unmeasured`` (a word that is not finite), so that ``outside + count.sum(axis=(1, 2)) +
+    unmeasured == selected``; ``occupied`` (the cells with a member), ``peak`` (the cell ``j * columns + i`` with the most
+    members, ties to the lower index, -1 if there is none) and ``peak_count``; ``total_weight`` (float64: the weight of all
+    measured bodies taking part, ``outside`` included); ``centre`` and ``velocity`` ``(B, 3)``, the frame as used.  Per cell,
+    ``(B, rows, columns)`` or ``None`` without ``cells``: ``count`` (int64) and the float64 sums over the cell's members in
+    ascending body index ``weight_sum`` (w), ``v1`` (w uq), ``v2`` (w uq uq), ``pa`` (w ua), ``pb`` (w ub), ``z1`` (w q) and
+    ``z2`` (w q q), with ``uq`` the velocity along the line of sight, ``ua`` and ``ub`` those in the plane and ``q`` the depth.
+    Per body, ``(B, max_bodies)`` or ``None`` without ``bodies``: ``body_cell`` (int32: the cell, -1 outside, -2 unmeasured, -3
+    not taking part), ``body_a`` and ``body_b`` (float64: the rotated coordinates).  ``systems``, ``cell_records`` and
+    ``body_records`` are the records themselves.  The derived values below are computed on the host in float64; the moments
+    are NaN where a cell is empty (or weighs nothing)."""
+
+    def __init__(self, systems, cells, bodies, edges_a, edges_b, axes, weight):
+        self.systems, self.cell_records, self.body_records = systems, cells, bodies
+        self.edges_a, self.edges_b, self.axes, self.weight = edges_a, edges_b, axes, weight
+        for name in ("selected", "outside", "unmeasured", "occupied", "peak", "peak_count", "total_weight", "centre", "velocity"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.columns, self.rows = int(edges_a.shape[-1]) - 1, int(edges_b.shape[-1]) - 1
+        self.count = self.weight_sum = self.v1 = self.v2 = self.pa = self.pb = self.z1 = self.z2 = None
+        if cells is not None:
+            self.count = np.ascontiguousarray(cells["count"])
+            self.weight_sum = np.ascontiguousarray(cells["weight"])
+            for name in ("v1", "v2", "pa", "pb", "z1", "z2"):
+                setattr(self, name, np.ascontiguousarray(cells[name]))
+        self.body_cell = self.body_a = self.body_b = None
+        if bodies is not None:
+            self.body_cell, self.body_a, self.body_b = (np.ascontiguousarray(bodies[name]) for name in ("cell", "a", "b"))
+
+    @staticmethod
+    def grid(extent, bins) -> np.ndarray:
+        """``bins + 1`` evenly spaced float64 edges (``numpy.linspace``): ``extent`` is ``(lo, hi)``, or one number for ``(-extent,
+        extent)``.  With ``(B, 2)`` extents, ``(B, bins + 1)``: one set per system."""
+        e = np.asarray(extent, dtype=np.float64)
+        if e.ndim == 0:
+            e = np.array([-float(e), float(e)])
+        if e.shape[-1] != 2 or int(bins) < 1:
+            raise ValueError(f"extent must be a number, (lo, hi) or (B, 2) and bins >= 1, got {extent!r} and {bins!r}")
+        return np.ascontiguousarray(np.linspace(e[..., 0], e[..., 1], int(bins) + 1, axis=-1))
+
+    @staticmethod
+    def view(direction, up=(0.0, 0.0, 1.0)) -> np.ndarray:
+        """The right-handed orthonormal triple ``(A, B, Q)`` of an observer who looks along ``direction``: ``Q = direction /
+        |direction|`` (the line of sight, pointing away from the observer), ``A = up x Q`` normalised (the map's first axis,
+        to the right of an observer whose head points along ``up``), ``B = Q x A``, so that ``A x B = Q``.  Where ``up`` is
+        parallel to the direction the coordinate axis least aligned with it stands in.  ``direction`` ``(3,)`` gives ``(3, 3)``
+        and ``(B, 3)`` gives ``(B, 3, 3)``: one view per system."""
+        d = np.asarray(direction, dtype=np.float64)
+        if d.shape[-1:] != (3,) or d.ndim > 2:
+            raise ValueError(f"direction must have shape (3,) or (B, 3), got {tuple(d.shape)}")
+        norm = np.linalg.norm(d, axis=-1, keepdims=True)
+        if not np.all(np.isfinite(d)) or not np.all(norm > 0.0):
+            raise ValueError("direction must be finite and not zero")
+        q = d / norm
+        u = np.broadcast_to(np.asarray(up, dtype=np.float64), q.shape)
+        a = np.cross(u, q)
+        flat = np.linalg.norm(a, axis=-1) < 1.0e-12 * np.linalg.norm(u, axis=-1)
+        if np.any(flat):
+            spare = np.eye(3)[np.argmin(np.abs(q), axis=-1)]
+            a = np.where(flat[..., None], np.cross(spare, q), a)
+        a = a / np.linalg.norm(a, axis=-1, keepdims=True)
+        return np.ascontiguousarray(np.stack([a, np.cross(q, a), q], axis=-2))
+
+    def _need_cells(self):
+        if self.count is None:
+            raise ValueError("this needs the cell records: call surface_map(cells=True)")
+
+    def area(self) -> np.ndarray:
+        """``(B, rows, columns)``: the area of every cell."""
+        B = len(self.systems)
+        wa = np.diff(np.broadcast_to(self.edges_a, (B, self.columns + 1)), axis=1)
+        wb = np.diff(np.broadcast_to(self.edges_b, (B, self.rows + 1)), axis=1)
+        return wb[:, :, None] * wa[:, None, :]
+
+    def _per_weight(self, total) -> np.ndarray:
+        """``total / weight_sum``, NaN where the weight is not > 0."""
+        self._need_cells()
+        ok = self.weight_sum > 0.0
+        return np.where(ok, total / np.where(ok, self.weight_sum, 1.0), np.nan)
+
+    def surface_density(self) -> np.ndarray:
+        """``(B, rows, columns)``: the weight per area; 0 in an empty cell."""
+        self._need_cells()
+        return self.weight_sum / self.area()
+
+    def number_density(self) -> np.ndarray:
+        """``(B, rows, columns)``: the members per area; 0 in an empty cell."""
+        self._need_cells()
+        return self.count / self.area()
+
+    def mean_velocity(self) -> np.ndarray:
+        """``(B, rows, columns)``: ``v1 / weight``, the weighted mean velocity along the line of sight (the first moment)."""
+        return self._per_weight(self.v1)
+
+    def dispersion(self) -> np.ndarray:
+        """``(B, rows, columns)``: ``sqrt(max(v2 / weight - mean^2, 0))``, the line-of-sight velocity dispersion (the second
+        moment)."""
+        return np.sqrt(np.maximum(self._per_weight(self.v2) - self.mean_velocity() ** 2, 0.0))
+
+    def plane_velocity(self):
+        """Two ``(B, rows, columns)`` arrays: ``(pa / weight, pb / weight)``, the weighted mean velocity in the plane of the
+        map, along its first and second axis."""
+        return self._per_weight(self.pa), self._per_weight(self.pb)
+
+    def mean_depth(self) -> np.ndarray:
+        """``(B, rows, columns)``: ``z1 / weight``, the weighted mean of ``q``, the coordinate along the line of sight."""
+        return self._per_weight(self.z1)
+
+    def depth_dispersion(self) -> np.ndarray:
+        """``(B, rows, columns)``: ``sqrt(max(z2 / weight - mean_depth^2, 0))``, the spread of ``q`` in every cell."""
+        return np.sqrt(np.maximum(self._per_weight(self.z2) - self.mean_depth() ** 2, 0.0))
+
+    def image(self, s: int = 0, quantity: str = "surface_density"):
+        """System ``s``'s map ready for ``matplotlib``: ``(array, extent)`` with the ``(rows, columns)`` array of ``quantity``
+        (the name of one of the single-valued helpers above, or ``"count"``) and ``extent = (a_lo, a_hi, b_lo, b_hi)``, for
+        ``imshow(array, extent=extent, origin="lower")``: row ``j`` of the array is the ``j``-th interval of the second axis."""
+        self._need_cells()
+        if quantity not in ("count", "surface_density", "number_density", "mean_velocity", "dispersion", "mean_depth", "depth_dispersion"):
+            raise ValueError(f"quantity must be count or a single-valued helper of SurfaceMapResult, not {quantity!r}")
+        values = self.count if quantity == "count" else getattr(self, quantity)()
+        B = len(self.systems)
+        ea, eb = np.broadcast_to(self.edges_a, (B, self.columns + 1))[s], np.broadcast_to(self.edges_b, (B, self.rows + 1))[s]
+        return np.array(values[s]), (float(ea[0]), float(ea[-1]), float(eb[0]), float(eb[-1]))
+
+    def __repr__(self):
+        return (f"SurfaceMapResult(columns={self.columns}, rows={self.rows}, weight={self.weight!r}, selected={self.selected.tolist()}, "
+                f"outside={self.outside.tolist()}, unmeasured={self.unmeasured.tolist()}, occupied={self.occupied.tolist()})")
 
 
 def interactions_per_step(counts, massive=None) -> int:

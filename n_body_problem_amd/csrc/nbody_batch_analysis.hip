@@ -1,6 +1,6 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
 // structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
-// lists, approach lists, radial profiles, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_radial.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// lists, approach lists, radial profiles, surface maps, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_surface.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
@@ -18,6 +18,7 @@
 #include "nbody_batch_radii_check.h"
 #include "nbody_batch_span_math.h"
 #include "nbody_batch_structure_math.h"
+#include "nbody_batch_surface_math.h"
 #include "nbody_kernels.h"
 
 #include <cmath>
@@ -2506,6 +2507,230 @@ hipError_t launch_batch_radial(const float4 *pos, const float4 *vel, const int *
     });
 }
 
+// ---- surface maps (include/nbody_batch_surface.h): per system the bodies in a grid of up to 64 x 64 cells in a plane of the
+// caller's choice and per cell the count and seven fp64 sums, each over the cell's members in ascending body index.  A sibling
+// of batch_radial_kernel over the same position-plus-velocity image; where that kernel gives each of at most 32 shells a lane
+// that walks every body, this one sorts the bodies by cell first, stably and inside the workgroup, so that the lane of a cell
+// walks its own members alone.  It reads the state and writes only the handle's records.  The arithmetic is
+// nbody_batch_surface_math.h's, which the CPU driver runs too.
+
+static_assert(sizeof(BatchSurfaceCell) == sizeof(nbody_batch_surface_cell) && sizeof(nbody_batch_surface_cell) == 64 &&
+                  offsetof(BatchSurfaceCell, count) == offsetof(nbody_batch_surface_cell, count) &&
+                  offsetof(BatchSurfaceCell, weight) == offsetof(nbody_batch_surface_cell, weight) &&
+                  offsetof(BatchSurfaceCell, v1) == offsetof(nbody_batch_surface_cell, v1) &&
+                  offsetof(BatchSurfaceCell, v2) == offsetof(nbody_batch_surface_cell, v2) &&
+                  offsetof(BatchSurfaceCell, pa) == offsetof(nbody_batch_surface_cell, pa) &&
+                  offsetof(BatchSurfaceCell, pb) == offsetof(nbody_batch_surface_cell, pb) &&
+                  offsetof(BatchSurfaceCell, z1) == offsetof(nbody_batch_surface_cell, z1) &&
+                  offsetof(BatchSurfaceCell, z2) == offsetof(nbody_batch_surface_cell, z2) && offsetof(nbody_batch_surface_cell, z2) == 56,
+              "nbody_batch_surface_math.h mirrors the cell record of nbody_batch_surface.h");
+static_assert(sizeof(BatchSurfaceSystem) == sizeof(nbody_batch_surface_system) && sizeof(nbody_batch_surface_system) == 88 &&
+                  offsetof(BatchSurfaceSystem, selected) == offsetof(nbody_batch_surface_system, selected) &&
+                  offsetof(BatchSurfaceSystem, outside) == offsetof(nbody_batch_surface_system, outside) &&
+                  offsetof(BatchSurfaceSystem, unmeasured) == offsetof(nbody_batch_surface_system, unmeasured) &&
+                  offsetof(BatchSurfaceSystem, columns) == offsetof(nbody_batch_surface_system, columns) &&
+                  offsetof(BatchSurfaceSystem, rows) == offsetof(nbody_batch_surface_system, rows) &&
+                  offsetof(BatchSurfaceSystem, occupied) == offsetof(nbody_batch_surface_system, occupied) &&
+                  offsetof(BatchSurfaceSystem, peak) == offsetof(nbody_batch_surface_system, peak) &&
+                  offsetof(BatchSurfaceSystem, peak_count) == offsetof(nbody_batch_surface_system, peak_count) &&
+                  offsetof(BatchSurfaceSystem, total_weight) == offsetof(nbody_batch_surface_system, total_weight) &&
+                  offsetof(BatchSurfaceSystem, centre) == offsetof(nbody_batch_surface_system, centre) &&
+                  offsetof(BatchSurfaceSystem, velocity) == offsetof(nbody_batch_surface_system, velocity) &&
+                  offsetof(nbody_batch_surface_system, total_weight) == 32 && offsetof(nbody_batch_surface_system, velocity) == 64,
+              "nbody_batch_surface_math.h mirrors the system record of nbody_batch_surface.h");
+static_assert(sizeof(BatchSurfaceBody) == sizeof(nbody_batch_surface_body) && sizeof(nbody_batch_surface_body) == 24 &&
+                  offsetof(BatchSurfaceBody, cell) == offsetof(nbody_batch_surface_body, cell) &&
+                  offsetof(BatchSurfaceBody, reserved) == offsetof(nbody_batch_surface_body, reserved) &&
+                  offsetof(BatchSurfaceBody, a) == offsetof(nbody_batch_surface_body, a) &&
+                  offsetof(BatchSurfaceBody, b) == offsetof(nbody_batch_surface_body, b),
+              "nbody_batch_surface_math.h mirrors the body record of nbody_batch_surface.h");
+static_assert(kSurfaceMaxSide == NBODY_BATCH_SURFACE_MAX_SIDE && kSurfaceOutside == NBODY_BATCH_SURFACE_OUTSIDE &&
+                  kSurfaceUnmeasured == NBODY_BATCH_SURFACE_UNMEASURED && kSurfaceNotTaking == NBODY_BATCH_SURFACE_NOT_TAKING &&
+                  NBODY_BATCH_MAX_BODIES <= 4096,
+              "nbody_batch_surface_math.h mirrors the limit and the cell words of nbody_batch_surface.h; surface_key holds a body index in 12 bits");
+
+constexpr int kSurfaceTallies = 5;  // selected, outside, unmeasured; then occupied and the peak key
+
+// The image of a system as the walks read it.
+struct SurfaceImage {
+    const int4 *img;
+    const unsigned short *words, *places, *starts;
+    __host__ __device__ int word(int j) const { return words[j]; }
+    __host__ __device__ int order(int k) const { return places[k]; }
+    __host__ __device__ int start(int c) const { return starts[c]; }
+    __host__ __device__ SurfacePoint point(int j) const
+    {
+        const int4 p = img[2 * j], v = img[2 * j + 1];
+        return SurfacePoint{__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), __int_as_float(p.w),
+                            __int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z)};
+    }
+};
+
+// The words of max_bodies rounded up to the eight that one 16-byte LDS read holds.
+__host__ __device__ inline int surface_padded(int max_bodies) { return (max_bodies + 7) / 8 * 8; }
+
+// LDS: batch_radial_kernel's image, img[2 j] = {x, y, z, m} and img[2 j + 1] = {vx, vy, vz, 0} (128 KiB at 4096 bodies), then
+// three arrays of 16-bit words: the cell word of every body (surface_word: the cell, or a sentinel above 4095), order[] (the
+// members sorted by (cell, index)) and the start of every cell in order[].  The edges of both axes, the frame and the view are
+// in static LDS.
+//   Phase 1, decide: every row forms its six words, decides its cell and writes its cell word and its body record.  Two
+//     neighbouring lanes write the two halves of one dword; the stores are ds_write_b16, which leave the other half alone.
+//   Phase 2, sort: the rank walk.  Row i's place is the number of bodies whose (word, index) is below its own (surface_key).
+//     The cell words are read eight at a time at a wave-uniform address -- one ds_read_b128 broadcast per eight columns, no
+//     bank conflict whatever the 16-bit packing -- and each costs every row a compare and an add.  No atomics, no scan, no
+//     ordering between waves.  The starts of the cells fall out of order[] where the cell word changes.
+//   Phase 3, walk: one lane per cell, striding over columns x rows, adds its members' seven terms through order[] from its
+//     start; these reads are gathers (the lanes of a wave are at different places).  occupied and peak are integer
+//     reductions through LDS atomics.  Lane 0 also walks j = 0 ... n - 1 for total_weight.
+// Only this sort is built: the alternative of a histogram, a scan and a placement by ballots was not, so nothing compares them.
+// No waves_per_eu, as for batch_radial_kernel: the rows' keys and ranks and the walker's eight fp64 words are held at once.
+template <int RPL>
+__global__ __launch_bounds__(1024) void batch_surface_kernel(const float4 *__restrict__ pos, const float4 *__restrict__ vel,
+                                                             const int *__restrict__ counts, const unsigned char *__restrict__ subset,
+                                                             const double *__restrict__ edges_a, int stride_a,
+                                                             const double *__restrict__ edges_b, int stride_b,
+                                                             const double *__restrict__ frames, int max_bodies, int columns, int rows,
+                                                             int weight, BatchSurfaceBody *__restrict__ bodies,
+                                                             BatchSurfaceCell *__restrict__ cells_out, BatchSurfaceSystem *__restrict__ systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ double ea[kSurfaceMaxSide + 1], eb[kSurfaceMaxSide + 1];
+    __shared__ double frame[kSurfaceFrameWords];
+    __shared__ unsigned tally[kSurfaceTallies];
+    const int padded = surface_padded(max_bodies), cells = columns * rows;
+    unsigned short *cell_of = reinterpret_cast<unsigned short *>(img + 2 * (size_t)max_bodies);
+    unsigned short *order = cell_of + padded;
+    unsigned short *starts = order + padded;
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    for (int t = tid; t <= columns; t += T)
+        ea[t] = edges_a[(size_t)blockIdx.x * (size_t)stride_a + t];
+    for (int t = tid; t <= rows; t += T)
+        eb[t] = edges_b[(size_t)blockIdx.x * (size_t)stride_b + t];
+    if (tid < kSurfaceFrameWords)
+        frame[tid] = frames[(size_t)blockIdx.x * kSurfaceFrameWords + tid];
+    if (tid < kSurfaceTallies)
+        tally[tid] = 0;
+    for (int c = tid; c < cells; c += T)
+        starts[c] = (unsigned short)kSurfaceNoStart;
+    __syncthreads();
+    // Phase 1: every row decides its cell and writes its cell word and its body record.
+    unsigned key[RPL];
+    int selected = 0, outside = 0, unmeasured = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        BatchSurfaceBody record = surface_body_absent();
+        int word = kSurfaceWordNotTaking;
+        if (r < n) {
+            const float4 p = pos[base + r], v = vel[base + r];
+            img[2 * r] = make_int4(__float_as_int(p.x), __float_as_int(p.y), __float_as_int(p.z), __float_as_int(p.w));
+            img[2 * r + 1] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), 0);
+            if (!subset || subset[base + r] != 0) {
+                const SurfaceWords b = surface_words(SurfacePoint{p.x, p.y, p.z, p.w, v.x, v.y, v.z}, frame);
+                const int cell = surface_cell(b, ea, columns, eb, rows);
+                word = surface_word(cell);
+                selected += 1;
+                outside += cell == kSurfaceOutside ? 1 : 0;
+                unmeasured += cell == kSurfaceUnmeasured ? 1 : 0;
+                if (bodies)
+                    record = surface_body(cell, b);
+            }
+        }
+        if (r < padded)
+            cell_of[r] = (unsigned short)word;  // the words from n on are sentinels: the rank walk reads them in eights
+        key[q] = surface_key(word, r);
+        if (bodies && r < max_bodies)
+            bodies[base + r] = record;
+    }
+    // Integers: the order of the additions does not matter.
+    if (selected)
+        atomicAdd(&tally[0], (unsigned)selected);
+    if (outside)
+        atomicAdd(&tally[1], (unsigned)outside);
+    if (unmeasured)
+        atomicAdd(&tally[2], (unsigned)unmeasured);
+    __syncthreads();  // the image, the cell words and the tallies are in place
+    const int m = (int)(tally[0] - tally[1] - tally[2]);  // the members of all cells: the places of order[]
+    // Phase 2: the rank walk, eight columns per broadcast read.
+    int rank[RPL];
+#pragma unroll
+    for (int q = 0; q < RPL; ++q)
+        rank[q] = 0;
+    const uint4 *eights = reinterpret_cast<const uint4 *>(cell_of);
+    for (int g = 0; g < (n + 7) / 8; ++g) {
+        const uint4 w = eights[g];
+        const unsigned two[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int j = 8 * g + 2 * h, lo = (int)(two[h] & 0xFFFFu), hi = (int)(two[h] >> 16);
+#pragma unroll
+            for (int q = 0; q < RPL; ++q)
+                rank[q] += surface_rank_step(key[q], lo, j) + surface_rank_step(key[q], hi, j + 1);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = q * T + tid;
+        if (r < n && surface_word_inside((int)(key[q] >> 12)) && rank[q] < m)
+            order[rank[q]] = (unsigned short)r;
+    }
+    __syncthreads();  // order[] is in place
+    for (int k = tid; k < m; k += T) {
+        const int here = cell_of[order[k]], before = k > 0 ? cell_of[order[k - 1]] : here;
+        if (surface_is_start(k, here, before) && here < cells)
+            starts[here] = (unsigned short)k;
+    }
+    __syncthreads();  // the starts are in place
+    // Phase 3: the walkers, one per cell; lane 0 also adds total_weight.
+    const SurfaceImage image{img, cell_of, order, starts};
+    int occupied = 0;
+    unsigned peak = 0;
+    for (int c = tid; c < cells; c += T) {
+        const BatchSurfaceCell cell = surface_walk(image, m, c, frame, weight, cells_out != nullptr);
+        if (cells_out)
+            cells_out[(size_t)blockIdx.x * (size_t)cells + c] = cell;
+        occupied += cell.count > 0 ? 1 : 0;
+        const unsigned mine = surface_peak_key(cell.count, c);
+        peak = mine > peak ? mine : peak;
+    }
+    if (occupied) {
+        atomicAdd(&tally[3], (unsigned)occupied);
+        atomicMax(&tally[4], peak);
+    }
+    double total = 0.0;
+    if (tid == 0)
+        total = surface_walk_total(image, n, weight);
+    __syncthreads();  // occupied and the peak are in place
+    if (tid == 0)
+        systems[blockIdx.x] = surface_system((int)tally[0], (int)tally[1], (int)tally[2], columns, rows, (int)tally[3], tally[4], total, frame);
+}
+
+// The dynamic LDS of one workgroup: 32 bytes per body for the image and three arrays of 16-bit words, the cell words and
+// order[] over the padded capacity and the starts over the cells, each a multiple of 16 bytes.  At 4096 bodies and 64 x 64
+// cells 131072 + 8192 + 8192 + 8192 = 155648 bytes; with the 1216 bytes of static LDS (two sets of 65 edges, 15 words of frame
+// and view, the tallies; the compiler's figure, padding included) 156864 bytes, 153.2 KiB of the 160 KiB of a gfx950 workgroup.
+inline size_t surface_lds_bytes(int max_bodies, int cells)
+{
+    return 2 * kBatchBytesPerBody * (size_t)max_bodies + 2 * sizeof(unsigned short) * (size_t)surface_padded(max_bodies) +
+           (sizeof(unsigned short) * (size_t)cells + 15) / 16 * 16;
+}
+
+// One launch over all systems.
+hipError_t launch_batch_surface(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *subset, const double *edges_a,
+                                int stride_a, const double *edges_b, int stride_b, const double *frames, int n_systems, int max_bodies,
+                                int columns, int rows, int weight, BatchSurfaceBody *bodies, BatchSurfaceCell *cells_out,
+                                BatchSurfaceSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = surface_lds_bytes(max_bodies, columns * rows);
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_surface_kernel<rpl()>, n_systems, sh.threads, lds, stream, pos, vel, counts, subset, edges_a,
+                                      stride_a, edges_b, stride_b, frames, max_bodies, columns, rows, weight, bodies, cells_out, systems);
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -2640,6 +2865,14 @@ struct BatchAnalysis {
     std::vector<double> radial_edges2_host;         // the last call's: the copy's source until the stream is idle
     DeviceArray<double> radial_frames;              // [n_systems][6]: centre, velocity
     std::vector<double> radial_frames_host;         // the last call's
+    DeviceArray<BatchSurfaceSystem> surface_systems;  // [n_systems]
+    DeviceArray<BatchSurfaceCell> surface_cells;      // [n_systems][rows][columns] of the largest call that asked for cells
+    DeviceArray<BatchSurfaceBody> surface_bodies;     // [n_systems][max_bodies]
+    DeviceArray<unsigned char> surface_subset;        // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<double> surface_edges;                // the sets of columns + 1 edges, then the sets of rows + 1
+    std::vector<double> surface_edges_host;           // the last call's: the copy's source until the stream is idle
+    DeviceArray<double> surface_frames;               // [n_systems][15]: centre, velocity, A, B, Q
+    std::vector<double> surface_frames_host;          // the last call's
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -3208,6 +3441,86 @@ int nbody_batch_radial_profile(nbody_batch *b, const float *d_pos, const float *
     BATCH_TRY(b, copy_out(b, systems_out, a->radial_systems, B));
     BATCH_TRY(b, copy_out(b, shells_out, a->radial_shells, records));
     BATCH_TRY(b, copy_out(b, bodies_out, a->radial_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_surface_map(nbody_batch *b, const float *d_pos, const float *d_vel, int columns, int rows, const double *edges_a,
+                            const double *edges_b, int per_system, const double *centre, const double *velocity, const double *axes,
+                            int weight, const unsigned char *subset, nbody_batch_surface_system *systems_out,
+                            nbody_batch_surface_cell *cells_out, nbody_batch_surface_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_surface_map: batch is NULL");
+    if (!d_pos || !d_vel || !edges_a || !edges_b || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: NULL argument");
+    if (columns < 1 || columns > NBODY_BATCH_SURFACE_MAX_SIDE || rows < 1 || rows > NBODY_BATCH_SURFACE_MAX_SIDE)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: columns and rows must be 1 ... 64");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, sets = per_system ? B : 1;
+    const size_t given_a = (size_t)columns + 1, given_b = (size_t)rows + 1;
+    for (int axis = 0; axis < 2; ++axis) {
+        const size_t given = axis ? given_b : given_a;
+        for (size_t s = 0; s < sets; ++s) {
+            const double *e = (axis ? edges_b : edges_a) + s * given;
+            const std::string which = std::string(axis ? " of axis b" : " of axis a") +
+                                      (per_system ? " of system " + std::to_string(s) : std::string(" of all systems"));
+            for (size_t t = 0; t < given; ++t) {
+                if (!surface_finite(e[t]))
+                    return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: edge " + std::to_string(t) + which + " must be finite");
+                if (t > 0 && !(e[t] > e[t - 1]))
+                    return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: edge " + std::to_string(t) + which + " is not above edge " +
+                                                           std::to_string(t - 1) + ": the edges must be strictly ascending");
+            }
+        }
+    }
+    for (size_t k = 0; k < 3 * B; ++k) {
+        if (centre && !surface_finite(centre[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: the centre of system " + std::to_string(k / 3) + " must be finite");
+        if (velocity && !surface_finite(velocity[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: the velocity of system " + std::to_string(k / 3) + " must be finite");
+    }
+    for (size_t k = 0; axes && k < 9 * B; ++k)
+        if (!surface_finite(axes[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_surface_map: the axes of system " + std::to_string(k / 9) + " must be finite");
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->surface_edges_host.assign(edges_a, edges_a + sets * given_a);
+    a->surface_edges_host.insert(a->surface_edges_host.end(), edges_b, edges_b + sets * given_b);
+    a->surface_frames_host.resize(B * kSurfaceFrameWords);
+    for (size_t s = 0; s < B; ++s) {
+        double *f = a->surface_frames_host.data() + s * kSurfaceFrameWords;
+        for (size_t c = 0; c < 3; ++c) {
+            f[c] = centre ? centre[3 * s + c] : 0.0;
+            f[3 + c] = velocity ? velocity[3 * s + c] : 0.0;
+        }
+        for (size_t k = 0; k < 9; ++k)
+            f[kSurfaceViewAt + k] = axes ? axes[9 * s + k] : surface_identity((int)k);
+    }
+    const size_t edge_words = sets * (given_a + given_b), records = cells_out ? B * (size_t)columns * (size_t)rows : 0;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->surface_systems.ensure(B));
+    BATCH_TRY(b, a->surface_edges.ensure(edge_words));
+    BATCH_TRY(b, a->surface_frames.ensure(B * kSurfaceFrameWords));
+    BATCH_TRY(b, a->surface_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->surface_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->surface_cells.ensure(records));
+    BATCH_TRY(b, hipMemcpyAsync(a->surface_edges.ptr, a->surface_edges_host.data(), sizeof(double) * edge_words, hipMemcpyHostToDevice,
+                                b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(a->surface_frames.ptr, a->surface_frames_host.data(), sizeof(double) * B * kSurfaceFrameWords,
+                                hipMemcpyHostToDevice, b->stream));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->surface_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_surface(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                      subset ? a->surface_subset.ptr : nullptr, a->surface_edges.ptr, per_system ? (int)given_a : 0,
+                                      a->surface_edges.ptr + sets * given_a, per_system ? (int)given_b : 0, a->surface_frames.ptr,
+                                      (int)b->n_systems, (int)b->max_bodies, columns, rows, weight,
+                                      bodies_out ? a->surface_bodies.ptr : nullptr, cells_out ? a->surface_cells.ptr : nullptr,
+                                      a->surface_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->surface_systems, B));
+    BATCH_TRY(b, copy_out(b, cells_out, a->surface_cells, records));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->surface_bodies, slots));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

@@ -146,7 +146,14 @@ structure(bodies=False) and against what the call replaces -- positions.cpu() pl
 quantity (the mass per shell) -- in the same run: all synchronous calls, wall clock, alternated after a warm-up of every call,
 medians and spreads.  The kernel walks the shells two ways behind NBODY_BATCH_RADIAL_SPLIT_WALK: the line names the library it
 timed (NBODY_AMD_LIBRARY, tools/build_variant.sh), so one run per build gives both, and carries a checksum of the shell records
-so that the two can be seen to agree."""
+so that the two can be seen to agree.
+
+--surface: instead, the surface maps (BatchedSystem.surface_map).  For n x B = 1024 x 1024, 4096 x 256 and 256 x 4096 (or
+--cases), one line per case on Plummer spheres seen along z on a grid from -2 to 2 on both axes: the call at 16 x 16, 32 x 32 and
+64 x 64 cells with the cell records and without them (the per-system words alone: the kernel, its launch and the wait for it),
+against what the call replaces -- positions.cpu() plus velocities.cpu() plus one numpy.histogram2d per system at 64 x 64 --
+against radial_profile() at 32 shells and against pairs() in the same run: all synchronous calls, wall clock, alternated after a
+warm-up of every call, medians and spreads.  The counts of the 64 x 64 map are asserted to be numpy's before a line is printed."""
 import argparse
 import json
 import os
@@ -208,6 +215,8 @@ ap.add_argument("--correlation", action="store_true", help="correlation() at 8, 
                 "against pairs() and neighbours(k=6) on the same Plummer spheres, wall clock")
 ap.add_argument("--radial", action="store_true", help="radial_profile() at 32 and 8 logarithmic shells, with and without the shell "
                 "and body records, against structure(bodies=False) and the download plus a numpy binning, wall clock")
+ap.add_argument("--surface", action="store_true", help="surface_map() at 16 x 16, 32 x 32 and 64 x 64 cells, with and without the cell "
+                "records, against the download plus one numpy.histogram2d per system, radial_profile() and pairs(), wall clock")
 args = ap.parse_args()
 
 
@@ -1338,6 +1347,77 @@ def radial_lines():
         print(json.dumps(line), flush=True)
 
 
+def surface_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        edges = {side: nb.SurfaceMapResult.grid(2.0, side) for side in (16, 32, 64)}
+        shells = np.geomspace(0.05, 10.0, 33)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            def download_and_bin():
+                """What the call replaces: both arrays to the host, then the mass per cell of every system, one numpy.histogram2d each."""
+                p, v = batch.positions.cpu().numpy(), batch.velocities.cpu().numpy()
+                maps = np.empty((B, 64, 64))
+                for s in range(B):
+                    maps[s] = np.histogram2d(p[s, :, 0], p[s, :, 1], bins=(edges[64], edges[64]), weights=p[s, :, 3])[0].T
+                return maps, v
+
+            calls = {}
+            for side in (16, 32, 64):
+                calls[f"surface{side}"] = lambda side=side: batch.surface_map(edges[side])
+                calls[f"surface{side}_systems_only"] = lambda side=side: batch.surface_map(edges[side], cells=False)
+            calls["surface64_bodies"] = lambda: batch.surface_map(edges[64], bodies=True)
+            calls["radial32"] = lambda: batch.radial_profile(shells)
+            calls["pairs"] = batch.pairs
+            calls["download_and_bin"] = download_and_bin
+            for fn in calls.values():                               # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(args.repeats):                           # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        res, binned = found["surface64"], found["download_and_bin"][0]
+        assert np.array_equal(res.count.sum(axis=(1, 2)) + res.outside + res.unmeasured, res.selected)
+        p = P.astype(np.float64)
+        assert not (p[..., 0] == 2.0).any() and not (p[..., 1] == 2.0).any()                       # nobody on numpy's closed last edge
+        assert np.allclose(res.weight_sum, binned, rtol=1e-6, atol=1e-9)                            # numpy bins in fp32 weights, another order
+        assert found["surface64_bodies"].cell_records.tobytes() == res.cell_records.tobytes()
+        assert found["surface64_systems_only"].systems.tobytes() == res.systems.tobytes()
+        line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"),
+                "members_per_system": round(float(res.count.sum(axis=(1, 2)).mean()), 1),
+                "occupied_per_system": round(float(res.occupied.mean()), 1), "peak_count_per_system": round(float(res.peak_count.mean()), 1),
+                "cells64_megabytes": round(B * 4096 * 64 / 1e6, 2), "bodies_megabytes": round(B * n * 24 / 1e6, 2),
+                "download_megabytes": round(2 * B * n * 16 / 1e6, 2), "cells64_crc32": zlib.crc32(res.cell_records.tobytes()),
+                "cells16_crc32": zlib.crc32(found["surface16"].cell_records.tobytes())}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for name in ("surface16", "surface32", "surface64", "surface64_systems_only", "surface64_bodies"):
+            line[name + "_over_download_and_bin"] = round(med[name] / med["download_and_bin"], 4)
+            line[name + "_over_radial32"] = round(med[name] / med["radial32"], 3)
+            line[name + "_over_pairs"] = round(med[name] / med["pairs"], 3)
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+        print(json.dumps(line), flush=True)
+
+
+if args.surface:
+    surface_lines()
+    sys.exit(0)
 if args.radial:
     radial_lines()
     sys.exit(0)
