@@ -561,6 +561,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_radial.h"
 /* surface maps: per system the bodies in a grid of up to 64 x 64 cells in a plane of the caller's choice and per cell the count and seven fp64 sums (weight, the line-of-sight velocity and its square, the two velocities in the plane, the depth and its square), each in ascending body index */
 #include "nbody_batch_surface.h"
+/* shapes: per system and each of up to 8 apertures the ellipsoid the iterated moment tensor converges to -- axis ratios, axes, members and the sums inside it -- every sum over blocks of 64 bodies in ascending index and then over the blocks */
+#include "nbody_batch_shape.h"
 
 #ifdef __cplusplus
 }

@@ -832,6 +832,47 @@ public:
               "nbody_batch_surface_map");
         return s;
     }
+    // Shapes (nbody_batch_shape.h): for every system and each of `apertures` (1 ... 8) apertures the ellipsoid the iterated
+    // moment tensor converges to.  radii: `apertures` values > 0 for all systems, or numSystems sets of them; inner: empty for
+    // zeros, or like radii (ellipsoidal shells).  centre and velocity: empty for zeros, or numSystems x 3 values.  weight:
+    // NBODY_BATCH_WEIGHT_MASS or _NUMBER.  reduced: the tensor's addends are divided by the squared elliptical radius.  subset:
+    // empty, or one byte per slot.  Returns the per-system records; records takes the apertures of every system (aperture a of
+    // system s at s * apertures + a) and bodies the per-body membership bits.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_shape_system> shape(const float *dPositions, const float *dVelocities, const std::vector<double> &radii,
+                                                std::vector<nbody_batch_shape_aperture> *records)
+    {
+        return shape(dPositions, dVelocities, (int)radii.size(), radii, records);
+    }
+    std::vector<nbody_batch_shape_system> shape(const float *dPositions, const float *dVelocities, int apertures,
+                                                const std::vector<double> &radii, std::vector<nbody_batch_shape_aperture> *records,
+                                                const std::vector<double> &inner = {}, const std::vector<double> &centre = {},
+                                                const std::vector<double> &velocity = {}, int weight = NBODY_BATCH_WEIGHT_MASS,
+                                                bool reduced = true, double tol = 1e-3, int maxIterations = NBODY_BATCH_SHAPE_MAX_ITERATIONS,
+                                                int minMembers = 10, const std::vector<unsigned char> &subset = {},
+                                                std::vector<nbody_batch_shape_body> *bodies = nullptr)
+    {
+        const size_t slots = (size_t)systems_ * (size_t)maxBodies_;
+        if (apertures < 1 || apertures > NBODY_BATCH_SHAPE_MAX_APERTURES)
+            throw std::invalid_argument("nbody::Batch::shape: apertures must be 1 ... 8");
+        const bool perSystem = radii.size() == (size_t)apertures * (size_t)systems_ && systems_ != 1;
+        if (radii.size() != (size_t)apertures * (perSystem ? (size_t)systems_ : 1) || (!inner.empty() && inner.size() != radii.size()))
+            throw std::invalid_argument("nbody::Batch::shape: `apertures` radii, or as many per system, and as many inner radii or none");
+        if ((!centre.empty() && centre.size() != 3 * (size_t)systems_) || (!velocity.empty() && velocity.size() != 3 * (size_t)systems_))
+            throw std::invalid_argument("nbody::Batch::shape: three values per system for centre and velocity, or none");
+        if (!subset.empty() && subset.size() != slots)
+            throw std::invalid_argument("nbody::Batch::shape: one subset byte per slot, or none");
+        std::vector<nbody_batch_shape_system> s((size_t)systems_);
+        if (records)
+            records->resize((size_t)systems_ * (size_t)apertures);
+        if (bodies)
+            bodies->resize(slots);
+        check(nbody_batch_shape(b_, dPositions, dVelocities, apertures, radii.data(), inner.empty() ? nullptr : inner.data(),
+                                perSystem ? 1 : 0, centre.empty() ? nullptr : centre.data(), velocity.empty() ? nullptr : velocity.data(),
+                                weight, reduced ? 1 : 0, tol, maxIterations, minMembers, subset.empty() ? nullptr : subset.data(), s.data(),
+                                records ? records->data() : nullptr, bodies ? bodies->data() : nullptr),
+              "nbody_batch_shape");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

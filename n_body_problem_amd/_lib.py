@@ -562,6 +562,37 @@ _SURFACE_PROTOTYPES = {
 }
 
 
+BATCH_SHAPE_MAX_APERTURES = 8
+BATCH_SHAPE_MAX_ITERATIONS = 64
+BATCH_SHAPE_CONVERGED, BATCH_SHAPE_MAX, BATCH_SHAPE_FEW, BATCH_SHAPE_DEGENERATE = 0, 1, 2, 3
+
+
+class BatchShapeAperture(ctypes.Structure):
+    """``nbody_batch_shape_aperture`` of include/nbody_batch_shape.h."""
+    _fields_ = [("status", c_int), ("iterations", c_int), ("count", ctypes.c_longlong), ("radius", c_double), ("inner", c_double),
+                ("q", c_double), ("s", c_double), ("change", c_double), ("eigenvalues", c_double * 3), ("axes", c_double * 9),
+                ("weight", c_double), ("D", c_double * 3), ("M", c_double * 6), ("L", c_double * 3)]
+
+
+class BatchShapeSystem(ctypes.Structure):
+    """``nbody_batch_shape_system`` of include/nbody_batch_shape.h."""
+    _fields_ = [("selected", c_int), ("unmeasured", c_int), ("apertures", c_int), ("reduced", c_int), ("converged", c_int),
+                ("reserved", c_int), ("total_weight", c_double), ("centre", c_double * 3), ("velocity", c_double * 3)]
+
+
+class BatchShapeBody(ctypes.Structure):
+    """``nbody_batch_shape_body`` of include/nbody_batch_shape.h."""
+    _fields_ = [("inside", ctypes.c_uint), ("reserved", c_int)]
+
+
+#: the entry point of include/nbody_batch_shape.h (shapes of batched ensembles), which nbody.h includes
+_SHAPE_PROTOTYPES = {
+    "nbody_batch_shape": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double),
+                                  POINTER(c_double), c_int, c_int, c_double, c_int, c_int, POINTER(ctypes.c_ubyte),
+                                  POINTER(BatchShapeSystem), POINTER(BatchShapeAperture), POINTER(BatchShapeBody)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -593,7 +624,7 @@ def load() -> ctypes.CDLL:
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
                 list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()) + \
-                list(_SURFACE_PROTOTYPES.items()):
+                list(_SURFACE_PROTOTYPES.items()) + list(_SHAPE_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -709,6 +740,11 @@ def radial_names():
 def surface_names():
     """The entry point of nbody_batch_surface.h."""
     return list(_SURFACE_PROTOTYPES)
+
+
+def shape_names():
+    """The entry point of nbody_batch_shape.h."""
+    return list(_SHAPE_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -133,7 +133,19 @@ SURFACE_BODY_DTYPE = np.dtype([("cell", np.int32), ("reserved", np.int32), ("a",
 assert SURFACE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceSystem) == 88
 assert SURFACE_CELL_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceCell) == 64
 assert SURFACE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchSurfaceBody) == 24
-#: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1
+#: the weight of a body in :meth:`BatchedSystem.structure` and :meth:`BatchedSystem.groups`: its mass word, or 1#: the records of :meth:`BatchedSystem.shape`: numpy's views of ``nbody_batch_shape_system``, ``_aperture`` and ``_body``
+SHAPE_SYSTEM_DTYPE = np.dtype([("selected", np.int32), ("unmeasured", np.int32), ("apertures", np.int32), ("reduced", np.int32),
+                               ("converged", np.int32), ("reserved", np.int32), ("total_weight", np.float64),
+                               ("centre", np.float64, 3), ("velocity", np.float64, 3)])
+SHAPE_APERTURE_DTYPE = np.dtype([("status", np.int32), ("iterations", np.int32), ("count", np.int64), ("radius", np.float64),
+                                 ("inner", np.float64), ("q", np.float64), ("s", np.float64), ("change", np.float64),
+                                 ("eigenvalues", np.float64, 3), ("axes", np.float64, 9), ("weight", np.float64),
+                                 ("D", np.float64, 3), ("M", np.float64, 6), ("L", np.float64, 3)])
+SHAPE_BODY_DTYPE = np.dtype([("inside", np.uint32), ("reserved", np.int32)])
+assert SHAPE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeSystem) == 80
+assert SHAPE_APERTURE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeAperture) == 256
+assert SHAPE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeBody) == 8
+
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
 
@@ -1161,6 +1173,92 @@ class BatchedSystem:
             body.ctypes.data_as(ctypes.POINTER(_lib.BatchSurfaceBody)) if bodies else None), self._h)
         return SurfaceMapResult(systems, rec, body, ea, eb, view, weight)
 
+    def shape(self, radii, *, inner=None, centre=None, velocity=None, weight: str = "mass", subset=None, reduced: bool = True,
+              tol: float = 1e-3, max_iterations: int = 64, min_members: int = 10, apertures: bool = True,
+              bodies: bool = False) -> "ShapeResult":
+        """How every system is shaped and oriented (``include/nbody_batch_shape.h`` states the rules): for each of up to 8
+        apertures the ellipsoid that the iterated moment tensor converges to, found on the device from the current state
+        (waits for the queued work).  ``radii`` holds the major semi-axes, ``> 0``: ``(apertures,)`` for all systems or ``(B,
+        apertures)``; ``inner``, of the same shape, makes ellipsoidal shells ``inner < r_ell <= radius`` (``None``: full
+        ellipsoids).  Each aperture starts as the sphere of its radius; a pass takes the bodies inside the current ellipsoid,
+        diagonalises their moment tensor -- the reduced one, every body's term divided by its squared elliptical radius, or
+        with ``reduced=False`` the plain one -- and deforms the ellipsoid to the axis ratios found, keeping the major axis at
+        the radius, until ``q`` (middle over major) and ``s`` (minor over major) change by at most ``tol`` of themselves
+        (status 0) or ``max_iterations`` (1 ... 64) passes are made (status 1).  A pass with fewer than ``min_members`` (>= 4)
+        members ends the aperture with status 2 and a tensor without three positive eigenvalues with status 3, both with the
+        state of the pass before.  ``centre``, ``velocity``, ``weight`` and ``subset`` are :meth:`radial_profile`'s: the frame
+        (``None``, ``(3,)``, ``(B, 3)``, for ``centre`` also a :class:`StructureResult` or ``"density"``), ``"mass"`` or
+        ``"number"``, and a ``(B, max_bodies)`` bool or uint8 mask (numpy or torch).  Every sum runs over blocks of 64 bodies in
+        ascending index and then over the blocks, so a system's records are the same bits in any slot, batch and capacity.
+        ``apertures=False`` skips the 256 bytes per aperture on their way to the host and ``bodies=True`` adds the 8 bytes per
+        body (``inside``: bit ``a`` set for a member of aperture ``a``'s final ellipsoid); the remaining records are the same
+        bits either way.  Changes nothing: an :meth:`evolve` after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+
+        def host(value):
+            return value.detach().cpu().numpy() if hasattr(value, "detach") else value
+
+        R = np.atleast_1d(np.asarray(host(radii), dtype=np.float64))
+        if not (R.ndim == 1 or (R.ndim == 2 and R.shape[0] == B)):
+            raise ValueError(f"radii must have shape (apertures,) or ({B}, apertures), got {tuple(R.shape)}")
+        count = R.shape[-1]
+        if not 1 <= count <= _lib.BATCH_SHAPE_MAX_APERTURES:
+            raise ValueError(f"apertures must be 1 ... {_lib.BATCH_SHAPE_MAX_APERTURES}, not {count}")
+        Rin = None
+        if inner is not None:
+            Rin = np.atleast_1d(np.asarray(host(inner), dtype=np.float64))
+            if Rin.shape[-1] != count or not (Rin.ndim == 1 or (Rin.ndim == 2 and Rin.shape[0] == B)):
+                raise ValueError(f"inner must have shape ({count},) or ({B}, {count}), got {tuple(Rin.shape)}")
+        per_system = int(R.ndim == 2 or (Rin is not None and Rin.ndim == 2))
+        if per_system:
+            R = np.broadcast_to(R, (B, count))
+            Rin = None if Rin is None else np.broadcast_to(Rin, (B, count))
+        R = np.ascontiguousarray(R)
+        Rin = None if Rin is None else np.ascontiguousarray(Rin)
+
+        def frame(name, value):
+            if value is None:
+                return None
+            v = np.asarray(host(value), dtype=np.float64)
+            if v.shape == (3,):
+                v = np.broadcast_to(v, (B, 3))
+            if v.shape != (B, 3):
+                raise ValueError(f"{name} must have shape (3,) or ({B}, 3), got {tuple(v.shape)}")
+            return np.ascontiguousarray(v)
+
+        if isinstance(centre, str):
+            if centre != "density":
+                raise ValueError(f"centre must be an array, a StructureResult or 'density', not {centre!r}")
+            centre = self.structure(weight=weight, bodies=False).centre
+        elif isinstance(centre, StructureResult):
+            centre = centre.centre
+        c, v0 = frame("centre", centre), frame("velocity", velocity)
+        mask = None
+        if subset is not None:
+            mask = np.ascontiguousarray(np.asarray(host(subset)))
+            if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+                raise ValueError(f"subset must be bool or uint8, not {mask.dtype}")
+            if mask.shape != (B, n):
+                raise ValueError(f"subset must have shape ({B}, {n}), got {tuple(mask.shape)}")
+            mask = mask.view(np.uint8)
+        systems = np.zeros(B, dtype=SHAPE_SYSTEM_DTYPE)
+        rec = np.zeros((B, count), dtype=SHAPE_APERTURE_DTYPE) if apertures else None
+        body = np.zeros((B, n), dtype=SHAPE_BODY_DTYPE) if bodies else None
+        dbl = ctypes.POINTER(ctypes.c_double)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_shape(
+            self._h, _ptr(self.positions), _ptr(self.velocities), count, R.ctypes.data_as(dbl),
+            Rin.ctypes.data_as(dbl) if Rin is not None else None, per_system,
+            c.ctypes.data_as(dbl) if c is not None else None, v0.ctypes.data_as(dbl) if v0 is not None else None,
+            WEIGHTS[weight], 1 if reduced else 0, float(tol), int(max_iterations), int(min_members),
+            mask.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if mask is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchShapeSystem)),
+            rec.ctypes.data_as(ctypes.POINTER(_lib.BatchShapeAperture)) if apertures else None,
+            body.ctypes.data_as(ctypes.POINTER(_lib.BatchShapeBody)) if bodies else None), self._h)
+        return ShapeResult(systems, rec, body, weight)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -2065,6 +2163,96 @@ class SurfaceMapResult:
     def __repr__(self):
         return (f"SurfaceMapResult(columns={self.columns}, rows={self.rows}, weight={self.weight!r}, selected={self.selected.tolist()}, "
                 f"outside={self.outside.tolist()}, unmeasured={self.unmeasured.tolist()}, occupied={self.occupied.tolist()})")
+
+
+class ShapeResult:
+    """What :meth:`BatchedSystem.shape` found.  ``weight_kind`` as given.  Per system (``(B,)`` arrays): ``selected`` (int32: the
+    bodies taking part), ``unmeasured`` (a word that is not finite), ``converged`` (the apertures with status 0),
+    ``total_weight`` (float64: the weight of all measured bodies taking part); ``centre`` and ``velocity`` ``(B, 3)``, the frame
+    as used; ``reduced`` (bool) the tensor used.  Per aperture, ``(B, apertures)`` or ``None`` without ``apertures``: ``status``
+    (int32: 0 converged, 1 the iteration limit, 2 too few members, 3 degenerate), ``iterations`` (the passes made), ``count``
+    (int64: the members of the final ellipsoid), ``radius`` and ``inner`` as given, ``q`` and ``s`` (middle and minor over
+    major), ``change`` (the last relative change of the two), ``eigenvalues`` ``(B, apertures, 3)`` descending, ``axes`` ``(B,
+    apertures, 3, 3)`` with the major, middle and minor axis as rows (right-handed), and the float64 sums over the members:
+    ``weight`` (w), ``D`` ``(..., 3)`` (w d), ``M`` ``(..., 6)`` (w d_a d_b: xx, yy, zz, xy, xz, yz, not reduced) and ``L``
+    ``(..., 3)`` (w d x u).  Per body, ``(B, max_bodies)`` or ``None`` without ``bodies``: ``inside`` (uint32: bit ``a`` set for a
+    member of aperture ``a``).  ``systems``, ``aperture_records`` and ``body_records`` are the records themselves.  The derived
+    values below are computed on the host in float64."""
+
+    def __init__(self, systems, apertures, bodies, weight):
+        self.systems, self.aperture_records, self.body_records, self.weight_kind = systems, apertures, bodies, weight
+        for name in ("selected", "unmeasured", "converged", "total_weight", "centre", "velocity"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.reduced = bool(systems["reduced"][0]) if len(systems) else True
+        self.apertures = int(systems["apertures"][0]) if len(systems) else 0
+        names = ("status", "iterations", "count", "radius", "inner", "q", "s", "change", "eigenvalues", "weight", "D", "M", "L")
+        for name in names + ("axes",):
+            setattr(self, name, None)
+        if apertures is not None:
+            for name in names:
+                setattr(self, name, np.ascontiguousarray(apertures[name]))
+            self.axes = np.ascontiguousarray(apertures["axes"]).reshape(apertures.shape + (3, 3))
+        self.inside = None if bodies is None else np.ascontiguousarray(bodies["inside"])
+
+    def _need_apertures(self):
+        if self.q is None:
+            raise ValueError("this needs the aperture records: call shape(apertures=True)")
+
+    def triaxiality(self) -> np.ndarray:
+        """``(B, apertures)``: ``T = (1 - q^2) / (1 - s^2)``: 0 oblate, 1 prolate.  NaN where ``s == 1``."""
+        self._need_apertures()
+        den = 1.0 - self.s * self.s
+        return np.where(den != 0.0, (1.0 - self.q * self.q) / np.where(den != 0.0, den, 1.0), np.nan)
+
+    def ellipticity(self) -> np.ndarray:
+        """``(B, apertures)``: ``1 - s``, the flattening of the minor against the major axis."""
+        self._need_apertures()
+        return 1.0 - self.s
+
+    def offset(self) -> np.ndarray:
+        """``(B, apertures, 3)``: ``D / weight``, the members' centre relative to the frame's.  NaN where the weight is not
+        ``> 0``."""
+        self._need_apertures()
+        ok = self.weight > 0.0
+        return np.where(ok[..., None], self.D / np.where(ok, self.weight, 1.0)[..., None], np.nan)
+
+    def spin_axis(self) -> np.ndarray:
+        """``(B, apertures, 3)``: ``L / |L|``, the direction of the members' angular momentum.  NaN where ``L == 0``."""
+        self._need_apertures()
+        norm = np.linalg.norm(self.L, axis=-1)
+        ok = norm > 0.0
+        return np.where(ok[..., None], self.L / np.where(ok, norm, 1.0)[..., None], np.nan)
+
+    def misalignment(self) -> np.ndarray:
+        """``(B, apertures)``: the angle in radians, 0 ... pi, between ``L`` and the minor axis ``e3``.  NaN where ``L == 0``."""
+        cosine = np.einsum("...k,...k->...", self.spin_axis(), self.axes[..., 2, :])
+        return np.arccos(np.clip(cosine, -1.0, 1.0))
+
+    def view(self, a: int = 0, kind: str = "face_on") -> np.ndarray:
+        """``(B, 3, 3)``: a right-handed view of every system for :meth:`BatchedSystem.surface_map`'s ``axes``, from aperture
+        ``a``'s axes.  ``"face_on"``: the map's axes are the major and the middle axis and the line of sight is the minor one,
+        ``(e1, e2, e3)``.  ``"edge_on"``: the major axis across, the minor axis up and the line of sight against the middle
+        one, ``(e1, e3, -e2)``."""
+        self._need_apertures()
+        e = self.axes[:, a]
+        if kind == "face_on":
+            return np.ascontiguousarray(e)
+        if kind == "edge_on":
+            return np.ascontiguousarray(np.stack([e[:, 0], e[:, 2], -e[:, 1]], axis=1))
+        raise ValueError(f"kind must be 'face_on' or 'edge_on', not {kind!r}")
+
+    def members_mask(self, a: int = 0) -> np.ndarray:
+        """``(B, max_bodies)`` bool: the members of aperture ``a``'s final ellipsoid, for :meth:`BatchedSystem.members`'
+        ``initial`` and the ``subset`` arguments."""
+        if self.inside is None:
+            raise ValueError("this needs the per-body records: call shape(bodies=True)")
+        if not 0 <= int(a) < max(self.apertures, 1):
+            raise ValueError(f"a must be 0 ... {self.apertures - 1}, not {a!r}")
+        return np.ascontiguousarray((self.inside >> np.uint32(int(a))) & np.uint32(1)).astype(np.bool_)
+
+    def __repr__(self):
+        return (f"ShapeResult(apertures={self.apertures}, reduced={self.reduced}, weight={self.weight_kind!r}, "
+                f"selected={self.selected.tolist()}, converged={self.converged.tolist()})")
 
 
 def interactions_per_step(counts, massive=None) -> int:

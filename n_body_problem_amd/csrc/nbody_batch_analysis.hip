@@ -16,6 +16,7 @@
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radial_math.h"
 #include "nbody_batch_radii_check.h"
+#include "nbody_batch_shape_math.h"
 #include "nbody_batch_span_math.h"
 #include "nbody_batch_structure_math.h"
 #include "nbody_batch_surface_math.h"
@@ -2731,6 +2732,237 @@ hipError_t launch_batch_surface(const float4 *pos, const float4 *vel, const int 
     });
 }
 
+// ---- shapes (include/nbody_batch_shape.h): per system and each of up to 8 apertures the ellipsoid that the iterated moment
+// tensor converges to, and what lies inside it.  A sibling of batch_radial_kernel over the same position-plus-velocity image.
+// It reads the state and writes only the handle's records.  The arithmetic is nbody_batch_shape_math.h's, which the CPU driver
+// runs too.
+
+static_assert(sizeof(BatchShapeAperture) == sizeof(nbody_batch_shape_aperture) && sizeof(nbody_batch_shape_aperture) == 256 &&
+                  offsetof(BatchShapeAperture, status) == offsetof(nbody_batch_shape_aperture, status) &&
+                  offsetof(BatchShapeAperture, iterations) == offsetof(nbody_batch_shape_aperture, iterations) &&
+                  offsetof(BatchShapeAperture, count) == offsetof(nbody_batch_shape_aperture, count) &&
+                  offsetof(BatchShapeAperture, radius) == offsetof(nbody_batch_shape_aperture, radius) &&
+                  offsetof(BatchShapeAperture, inner) == offsetof(nbody_batch_shape_aperture, inner) &&
+                  offsetof(BatchShapeAperture, q) == offsetof(nbody_batch_shape_aperture, q) &&
+                  offsetof(BatchShapeAperture, s) == offsetof(nbody_batch_shape_aperture, s) &&
+                  offsetof(BatchShapeAperture, change) == offsetof(nbody_batch_shape_aperture, change) &&
+                  offsetof(BatchShapeAperture, eigenvalues) == offsetof(nbody_batch_shape_aperture, eigenvalues) &&
+                  offsetof(BatchShapeAperture, axes) == offsetof(nbody_batch_shape_aperture, axes) &&
+                  offsetof(BatchShapeAperture, weight) == offsetof(nbody_batch_shape_aperture, weight) &&
+                  offsetof(BatchShapeAperture, D) == offsetof(nbody_batch_shape_aperture, D) &&
+                  offsetof(BatchShapeAperture, M) == offsetof(nbody_batch_shape_aperture, M) &&
+                  offsetof(BatchShapeAperture, L) == offsetof(nbody_batch_shape_aperture, L) && offsetof(nbody_batch_shape_aperture, axes) == 80 &&
+                  offsetof(nbody_batch_shape_aperture, L) == 232,
+              "nbody_batch_shape_math.h mirrors the aperture record of nbody_batch_shape.h");
+static_assert(sizeof(BatchShapeSystem) == sizeof(nbody_batch_shape_system) && sizeof(nbody_batch_shape_system) == 80 &&
+                  offsetof(BatchShapeSystem, selected) == offsetof(nbody_batch_shape_system, selected) &&
+                  offsetof(BatchShapeSystem, unmeasured) == offsetof(nbody_batch_shape_system, unmeasured) &&
+                  offsetof(BatchShapeSystem, apertures) == offsetof(nbody_batch_shape_system, apertures) &&
+                  offsetof(BatchShapeSystem, reduced) == offsetof(nbody_batch_shape_system, reduced) &&
+                  offsetof(BatchShapeSystem, converged) == offsetof(nbody_batch_shape_system, converged) &&
+                  offsetof(BatchShapeSystem, reserved) == offsetof(nbody_batch_shape_system, reserved) &&
+                  offsetof(BatchShapeSystem, total_weight) == offsetof(nbody_batch_shape_system, total_weight) &&
+                  offsetof(BatchShapeSystem, centre) == offsetof(nbody_batch_shape_system, centre) &&
+                  offsetof(BatchShapeSystem, velocity) == offsetof(nbody_batch_shape_system, velocity) &&
+                  offsetof(nbody_batch_shape_system, total_weight) == 24 && offsetof(nbody_batch_shape_system, velocity) == 56,
+              "nbody_batch_shape_math.h mirrors the system record of nbody_batch_shape.h");
+static_assert(sizeof(BatchShapeBody) == sizeof(nbody_batch_shape_body) && sizeof(nbody_batch_shape_body) == 8 &&
+                  offsetof(BatchShapeBody, inside) == offsetof(nbody_batch_shape_body, inside) &&
+                  offsetof(BatchShapeBody, reserved) == offsetof(nbody_batch_shape_body, reserved),
+              "nbody_batch_shape_math.h mirrors the body record of nbody_batch_shape.h");
+static_assert(kShapeMaxApertures == NBODY_BATCH_SHAPE_MAX_APERTURES && kShapeMaxIterations == NBODY_BATCH_SHAPE_MAX_ITERATIONS &&
+                  kShapeConverged == NBODY_BATCH_SHAPE_CONVERGED && kShapeMax == NBODY_BATCH_SHAPE_MAX && kShapeFew == NBODY_BATCH_SHAPE_FEW &&
+                  kShapeDegenerate == NBODY_BATCH_SHAPE_DEGENERATE && kShapeBlock == 64,
+              "nbody_batch_shape_math.h mirrors the limits and the status words of nbody_batch_shape.h; a block is a wave's width");
+
+constexpr int kShapeTallies = 3;  // selected, unmeasured, converged
+
+// The image of a system as a lane reads it: lane k at body 64 k + j, which shape_image_slot spreads over the banks.
+struct ShapeImage {
+    const int4 *img;
+    __device__ ShapePoint point(int i) const
+    {
+        const int at = shape_image_slot(i);
+        const int4 p = img[at], v = img[at + 1];
+        return ShapePoint{__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), __int_as_float(p.w),
+                          __int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z)};
+    }
+};
+
+// The partial that lane k of the wave holds, in every lane.
+template <int N>
+__device__ inline ShapePartial<N> shape_partial_of_lane(const ShapePartial<N> &mine, int k)
+{
+    ShapePartial<N> p;
+#pragma unroll
+    for (int c = 0; c < N; ++c)
+        p.v[c] = __shfl(mine.v[c], k, 64);
+    p.count = __shfl(mine.count, k, 64);
+    return p;
+}
+
+// A word that every lane of the wave holds alike, told to the compiler: it then lives in scalar registers, which the walk's
+// fp64 operations read as they read vector ones.  The state, the frame and the aperture are such words, 19 doubles that would
+// otherwise cost every lane 38 registers beside its sums.
+__device__ inline double shape_uniform(double v)
+{
+    const long long bits = __double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)bits), hi = __builtin_amdgcn_readfirstlane((unsigned)(bits >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ inline void shape_uniform(ShapeState &st)
+{
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+        st.e[c] = shape_uniform(st.e[c]);
+    st.w2 = shape_uniform(st.w2);
+    st.w3 = shape_uniform(st.w3);
+}
+
+// One wave per aperture: the waves of the workgroup take the apertures in turn, wave w the apertures w, w + waves, ...  In
+// every pass lane k walks block k (bodies 64 k ... 64 k + 63) through LDS: the level-1 partial.  Then every lane of the wave
+// adds the partials of lanes 0 ... blocks - 1 in that order, read by shuffles -- the level-2 sum -- and runs the Jacobi
+// iteration and the update on what are the same words in all 64 lanes: the new state is in registers everywhere and nothing
+// is published through LDS, and the loop's exit is the same in every lane.  The other mapping, all waves of the workgroup
+// splitting the blocks of one aperture, was not built: nothing compares them.
+// LDS: the image at 32 B per body, img[slot] = {x, y, z, m} and img[slot + 1] = {vx, vy, vz, 0} with slot = 2 i + i / 64
+// (shape_image_slot: 2 KiB apart the 64 lanes' reads would all fall on one 16-byte bank group; half a body per block puts 16
+// consecutive lanes on 16 groups), x = NaN for a body that is a member of nothing, then one membership byte per body at
+// i + 4 (i / 64), one bit per aperture.  At 4096 bodies: 16 * (2 * 4096 + 64) + 4352 = 136448 bytes dynamic and 320 bytes
+// static (the apertures, the frame and three tallies, as the compiler reports them), 136768 bytes in all, under the limit
+// launch_analysis_kernel raises.  The compiler reports 132 VGPRs, 106 SGPRs and no scratch for each of the three
+// instantiations; the workgroup is kept at eight waves (shape_threads) because at sixteen, with 128 registers, it spilled.
+// aps: radius, inner, out2, in2 per aperture, those of system s at s * aps_stride (0: one set for all); frames: centre[3],
+// velocity[3] per system.  subset, bodies and apertures_out may be NULL.
+template <int RPL>
+__global__ __launch_bounds__(kShapeMaxThreads) void batch_shape_kernel(const float4 *__restrict__ pos, const float4 *__restrict__ vel,
+                                                           const int *__restrict__ counts, const unsigned char *__restrict__ subset,
+                                                           const double *__restrict__ aps, int aps_stride, const double *__restrict__ frames,
+                                                           int max_bodies, int apertures, int weight, int reduced, double tol,
+                                                           int max_iterations, int min_members, BatchShapeBody *__restrict__ bodies,
+                                                           BatchShapeAperture *__restrict__ apertures_out,
+                                                           BatchShapeSystem *__restrict__ systems)
+{
+    extern __shared__ int4 img[];
+    __shared__ double ap[kShapeMaxApertures * kShapeApertureWords];
+    __shared__ double frame[kShapeFrameWords];
+    __shared__ int tally[kShapeTallies];
+    unsigned *inside = reinterpret_cast<unsigned *>(img + shape_image_slots(max_bodies));
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    if (tid < apertures * kShapeApertureWords)  // at most 32 words, and no workgroup is below 64 lanes
+        ap[tid] = aps[(size_t)blockIdx.x * (size_t)aps_stride + tid];
+    if (tid < kShapeFrameWords)
+        frame[tid] = frames[(size_t)blockIdx.x * kShapeFrameWords + tid];
+    if (tid < kShapeTallies)
+        tally[tid] = 0;
+    for (int w = tid; w < shape_inside_bytes(max_bodies) / 4; w += T)
+        inside[w] = 0u;
+    // Phase 1: every row decides whether it can be a member of anything and writes its words to the image.
+    int selected = 0, unmeasured = 0;
+    const int rows = shape_rows(RPL, T, max_bodies);  // RPL, or 2 RPL where the workgroup was kept at eight waves
+    for (int q0 = 0; q0 < rows; q0 += RPL)
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = (q0 + q) * T + tid;
+        if (r < n) {
+            const float4 p = pos[base + r], v = vel[base + r];
+            const ShapePoint given{p.x, p.y, p.z, p.w, v.x, v.y, v.z};
+            const bool takes = !subset || subset[base + r] != 0, measured = shape_measured(given);
+            selected += takes ? 1 : 0;
+            unmeasured += takes && !measured ? 1 : 0;
+            const ShapePoint held = shape_image_point(given, takes && measured);
+            const int at = shape_image_slot(r);
+            img[at] = make_int4(__float_as_int(held.x), __float_as_int(held.y), __float_as_int(held.z), __float_as_int(held.m));
+            img[at + 1] = make_int4(__float_as_int(held.vx), __float_as_int(held.vy), __float_as_int(held.vz), 0);
+        }
+    }
+    __syncthreads();  // the tallies are zeroed
+    // Integers: the order of the additions does not matter.
+    if (selected)
+        atomicAdd(&tally[0], selected);
+    if (unmeasured)
+        atomicAdd(&tally[1], unmeasured);
+    __syncthreads();  // the image, the zeroed membership bytes, the apertures, the frame and the tallies are in place
+    const ShapeImage image{img};
+    const int lane = tid & 63, wave = tid >> 6, waves = T >> 6;
+    const int blocks = shape_blocks(n), first = lane * kShapeBlock, last = shape_block_end(lane, n);
+    double total_weight = 0.0;
+    if (wave == 0) {
+        ShapePartial<1> part{};
+        for (int i = first; i < last; ++i)
+            shape_total_step(part, image.point(i), weight);
+        total_weight = shape_level2<1>([&](int k) { return shape_partial_of_lane(part, k); }, blocks).v[0];
+    }
+    double centred[kShapeFrameWords];
+#pragma unroll
+    for (int c = 0; c < kShapeFrameWords; ++c)
+        centred[c] = shape_uniform(frame[c]);
+    for (int a = wave; a < apertures; a += waves) {
+        const double radius = ap[kShapeApertureWords * a], inner = ap[kShapeApertureWords * a + 1];
+        const double out2 = shape_uniform(ap[kShapeApertureWords * a + 2]), in2 = shape_uniform(ap[kShapeApertureWords * a + 3]);
+        ShapeProgress g = shape_start();
+        // Every lane holds the same g: the loop is left by the whole wave at once, at most after max_iterations <= 64 passes.
+        for (int pass = 0; pass < kShapeMaxIterations && !g.done; ++pass) {
+            ShapePartial<kShapePassWords> part{};
+            for (int i = first; i < last; ++i)
+                shape_pass_step(part, image.point(i), centred, g.state, in2, out2, weight, reduced != 0);
+            const ShapePartial<kShapePassWords> sum =
+                shape_level2<kShapePassWords>([&](int k) { return shape_partial_of_lane(part, k); }, blocks);
+            shape_update(g, sum, tol, max_iterations, min_members);
+            shape_uniform(g.state);
+        }
+        ShapePartial<kShapeFinalWords> part{};
+        for (int i = first; i < last; ++i)
+            if (shape_final_step(part, image.point(i), centred, g.state, in2, out2, weight)) {
+                const int at = shape_inside_at(i);
+                atomicOr(&inside[at >> 2], 1u << (8 * (at & 3) + a));
+            }
+        const ShapePartial<kShapeFinalWords> sum =
+            shape_level2<kShapeFinalWords>([&](int k) { return shape_partial_of_lane(part, k); }, blocks);
+        if (lane == 0) {
+            if (apertures_out)
+                apertures_out[(size_t)blockIdx.x * (size_t)apertures + a] = shape_record(g, radius, inner, sum);
+            if (g.status == kShapeConverged)
+                atomicAdd(&tally[2], 1);
+        }
+    }
+    __syncthreads();  // every aperture's membership bits and the count of the converged are in
+    if (bodies) {
+        for (int q = 0; q < rows; ++q) {
+            const int r = q * T + tid;
+            if (r < max_bodies) {
+                const int at = shape_inside_at(r);
+                bodies[base + r] = shape_body(r < n ? (inside[at >> 2] >> (8 * (at & 3))) & 0xFFu : 0u);
+            }
+        }
+    }
+    if (tid == 0)
+        systems[blockIdx.x] = shape_system(tally[0], tally[1], apertures, reduced != 0 ? 1 : 0, tally[2], total_weight, frame);
+}
+
+// The dynamic LDS of one launch: the shifted image and the membership bytes.
+inline size_t shape_lds_bytes(int max_bodies)
+{
+    return sizeof(int4) * (size_t)shape_image_slots(max_bodies) + (size_t)shape_inside_bytes(max_bodies);
+}
+
+// One launch over all systems.
+hipError_t launch_batch_shape(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *subset, const double *aps,
+                              int aps_stride, const double *frames, int n_systems, int max_bodies, int apertures, int weight, int reduced,
+                              double tol, int max_iterations, int min_members, BatchShapeBody *bodies, BatchShapeAperture *apertures_out,
+                              BatchShapeSystem *systems, hipStream_t stream)
+{
+    const BatchShape sh = batch_shape(max_bodies);
+    const size_t lds = shape_lds_bytes(max_bodies);
+    return with_rpl(sh.rpl, [&](auto rpl) {
+        return launch_analysis_kernel(batch_shape_kernel<rpl()>, n_systems, shape_threads(sh.threads), lds, stream, pos, vel, counts, subset, aps, aps_stride,
+                                      frames, max_bodies, apertures, weight, reduced, tol, max_iterations, min_members, bodies, apertures_out,
+                                      systems);
+    });
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -2873,6 +3105,14 @@ struct BatchAnalysis {
     std::vector<double> surface_edges_host;           // the last call's: the copy's source until the stream is idle
     DeviceArray<double> surface_frames;               // [n_systems][15]: centre, velocity, A, B, Q
     std::vector<double> surface_frames_host;          // the last call's
+    DeviceArray<BatchShapeSystem> shape_systems;      // [n_systems]
+    DeviceArray<BatchShapeAperture> shape_apertures;  // [n_systems][apertures] of the largest call that asked for them
+    DeviceArray<BatchShapeBody> shape_bodies;         // [n_systems][max_bodies]
+    DeviceArray<unsigned char> shape_subset;          // [n_systems][max_bodies], the device copy of `subset`
+    DeviceArray<double> shape_aps;                    // one set or [n_systems] sets of apertures x {radius, inner, out2, in2}
+    std::vector<double> shape_aps_host;               // the last call's: the copy's source until the stream is idle
+    DeviceArray<double> shape_frames;                 // [n_systems][6]: centre, velocity
+    std::vector<double> shape_frames_host;            // the last call's
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -3521,6 +3761,85 @@ int nbody_batch_surface_map(nbody_batch *b, const float *d_pos, const float *d_v
     BATCH_TRY(b, copy_out(b, systems_out, a->surface_systems, B));
     BATCH_TRY(b, copy_out(b, cells_out, a->surface_cells, records));
     BATCH_TRY(b, copy_out(b, bodies_out, a->surface_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_shape(nbody_batch *b, const float *d_pos, const float *d_vel, int apertures, const double *radii, const double *inner,
+                      int per_system, const double *centre, const double *velocity, int weight, int reduced, double tol, int max_iterations,
+                      int min_members, const unsigned char *subset, nbody_batch_shape_system *systems_out,
+                      nbody_batch_shape_aperture *apertures_out, nbody_batch_shape_body *bodies_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_shape: batch is NULL");
+    if (!d_pos || !d_vel || !radii || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: NULL argument");
+    if (apertures < 1 || apertures > NBODY_BATCH_SHAPE_MAX_APERTURES)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: apertures must be 1 ... 8");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    if (!shape_finite(tol) || tol < 0.0)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: tol must be finite and >= 0");
+    if (max_iterations < 1 || max_iterations > NBODY_BATCH_SHAPE_MAX_ITERATIONS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: max_iterations must be 1 ... 64");
+    if (min_members < kShapeLeastMembers)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: min_members must be >= 4");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, sets = per_system ? B : 1;
+    const size_t given = (size_t)apertures;
+    for (size_t s = 0; s < sets; ++s)
+        for (size_t t = 0; t < given; ++t) {
+            const std::string which = " of aperture " + std::to_string(t) +
+                                      (per_system ? " of system " + std::to_string(s) : std::string(" of all systems"));
+            const double R = radii[s * given + t];
+            if (!shape_finite(R) || !(R > 0.0))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: the radius" + which + " must be finite and > 0");
+            if (inner && (!shape_finite(inner[s * given + t]) || !(inner[s * given + t] >= 0.0) || !(inner[s * given + t] < R)))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: the inner radius" + which + " must be finite, >= 0 and below its radius");
+        }
+    for (size_t k = 0; k < 3 * B; ++k) {
+        if (centre && !shape_finite(centre[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: the centre of system " + std::to_string(k / 3) + " must be finite");
+        if (velocity && !shape_finite(velocity[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_shape: the velocity of system " + std::to_string(k / 3) + " must be finite");
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->shape_aps_host.resize(sets * given * kShapeApertureWords);
+    for (size_t k = 0; k < sets * given; ++k) {
+        double *w = a->shape_aps_host.data() + k * kShapeApertureWords;
+        w[0] = radii[k];
+        w[1] = inner ? inner[k] : 0.0;
+        w[2] = shape_square(w[0]);  // out2 and in2: one fp64 product each
+        w[3] = shape_square(w[1]);
+    }
+    a->shape_frames_host.resize(B * kShapeFrameWords);
+    for (size_t s = 0; s < B; ++s)
+        for (size_t c = 0; c < 3; ++c) {
+            a->shape_frames_host[s * kShapeFrameWords + c] = centre ? centre[3 * s + c] : 0.0;
+            a->shape_frames_host[s * kShapeFrameWords + 3 + c] = velocity ? velocity[3 * s + c] : 0.0;
+        }
+    const size_t records = apertures_out ? B * given : 0, ap_words = sets * given * kShapeApertureWords;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->shape_systems.ensure(B));
+    BATCH_TRY(b, a->shape_aps.ensure(ap_words));
+    BATCH_TRY(b, a->shape_frames.ensure(B * kShapeFrameWords));
+    BATCH_TRY(b, a->shape_subset.ensure(subset ? slots : 0));
+    BATCH_TRY(b, a->shape_bodies.ensure(bodies_out ? slots : 0));
+    BATCH_TRY(b, a->shape_apertures.ensure(records));
+    BATCH_TRY(b, hipMemcpyAsync(a->shape_aps.ptr, a->shape_aps_host.data(), sizeof(double) * ap_words, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(a->shape_frames.ptr, a->shape_frames_host.data(), sizeof(double) * B * kShapeFrameWords,
+                                hipMemcpyHostToDevice, b->stream));
+    if (subset)
+        BATCH_TRY(b, hipMemcpyAsync(a->shape_subset.ptr, subset, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_shape(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                    subset ? a->shape_subset.ptr : nullptr, a->shape_aps.ptr,
+                                    per_system ? (int)(given * kShapeApertureWords) : 0, a->shape_frames.ptr, (int)b->n_systems,
+                                    (int)b->max_bodies, apertures, weight, reduced != 0 ? 1 : 0, tol, max_iterations, min_members,
+                                    bodies_out ? a->shape_bodies.ptr : nullptr, apertures_out ? a->shape_apertures.ptr : nullptr,
+                                    a->shape_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->shape_systems, B));
+    BATCH_TRY(b, copy_out(b, apertures_out, a->shape_apertures, records));
+    BATCH_TRY(b, copy_out(b, bodies_out, a->shape_bodies, slots));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

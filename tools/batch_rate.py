@@ -153,7 +153,16 @@ so that the two can be seen to agree.
 64 x 64 cells with the cell records and without them (the per-system words alone: the kernel, its launch and the wait for it),
 against what the call replaces -- positions.cpu() plus velocities.cpu() plus one numpy.histogram2d per system at 64 x 64 --
 against radial_profile() at 32 shells and against pairs() in the same run: all synchronous calls, wall clock, alternated after a
-warm-up of every call, medians and spreads.  The counts of the 64 x 64 map are asserted to be numpy's before a line is printed."""
+warm-up of every call, medians and spreads.  The counts of the 64 x 64 map are asserted to be numpy's before a line is printed.
+
+--shape: instead, the shapes (BatchedSystem.shape).  For n x B = 1024 x 1024, 4096 x 256 and 256 x 4096 (or --cases), one line
+per case on Plummer spheres flattened to 1 : 0.7 : 0.4 about the origin, four apertures of 0.5, 1, 2 and 4, the reduced tensor:
+the call with the aperture records, with the per-body masks too and with the per-system words alone, against radial_profile() at
+32 shells and against what the call replaces in the same run -- positions.cpu() plus velocities.cpu(), measured on the whole
+batch, plus the same iteration in numpy (einsum and numpy.linalg.eigh), measured on the first --subset systems and extrapolated
+to B, which the line says: all synchronous calls, wall clock, alternated after a warm-up of every call, medians of at least 15
+and spreads.  The line gives the passes of the slowest system, which sets the launch's time, and the converged q and s of the
+timed systems are asserted to be numpy's to 1e-2 (another order of summation, another eigensolver) before a line is printed."""
 import argparse
 import json
 import os
@@ -217,6 +226,8 @@ ap.add_argument("--radial", action="store_true", help="radial_profile() at 32 an
                 "and body records, against structure(bodies=False) and the download plus a numpy binning, wall clock")
 ap.add_argument("--surface", action="store_true", help="surface_map() at 16 x 16, 32 x 32 and 64 x 64 cells, with and without the cell "
                 "records, against the download plus one numpy.histogram2d per system, radial_profile() and pairs(), wall clock")
+ap.add_argument("--shape", action="store_true", help="shape() at four apertures, reduced, with and without the aperture and body "
+                "records, against the download plus the iteration in numpy (timed on --subset systems) and radial_profile(), wall clock")
 args = ap.parse_args()
 
 
@@ -1415,6 +1426,105 @@ def surface_lines():
         print(json.dumps(line), flush=True)
 
 
+def host_shape(x, w, radius, tol=1e-3, max_iterations=64, min_members=10):
+    """The iteration of include/nbody_batch_shape.h for one system and one aperture as numpy would be asked to do it on the
+    host: the reduced tensor by einsum, numpy.linalg.eigh, no pinned order.  Returns q, s and the passes made."""
+    axes, w2, w3, q0, s0 = np.eye(3), 1.0, 1.0, 1.0, 1.0
+    out2 = radius * radius
+    for k in range(1, max_iterations + 1):
+        y = x @ axes.T
+        r2e = y[:, 0] ** 2 + w2 * y[:, 1] ** 2 + w3 * y[:, 2] ** 2
+        inside = (r2e > 0.0) & (r2e <= out2)
+        if inside.sum() < min_members:
+            break
+        xi = x[inside]
+        values, vectors = np.linalg.eigh(np.einsum("i,ia,ib->ab", w[inside] / r2e[inside], xi, xi))
+        if not values[0] > 0.0:
+            break
+        q, s = np.sqrt(values[1] / values[2]), np.sqrt(values[0] / values[2])
+        axes, w2, w3 = vectors[:, ::-1].T, values[2] / values[1], values[2] / values[0]
+        done = abs(q - q0) <= tol * q0 and abs(s - s0) <= tol * s0
+        q0, s0 = q, s
+        if done:
+            break
+    return q0, s0, k
+
+
+def shape_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    repeats = max(args.repeats, 15)
+    radii = np.array([0.5, 1.0, 2.0, 4.0])
+    shells = np.geomspace(0.05, 10.0, 33)
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        P[:, :, :3] *= np.array([1.0, 0.7, 0.4], dtype=np.float32)   # Plummer spheres flattened to 1 : 0.7 : 0.4
+        few = min(args.subset, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            def download():
+                return batch.positions.cpu().numpy(), batch.velocities.cpu().numpy()
+
+            def host_iteration():
+                """The host's part of what the call replaces, on the first `few` systems only: four apertures each."""
+                return [[host_shape(P[s, :, :3].astype(np.float64), P[s, :, 3].astype(np.float64), R) for R in radii] for s in range(few)]
+
+            calls = {"shape4": lambda: batch.shape(radii),
+                     "shape4_bodies": lambda: batch.shape(radii, bodies=True),
+                     "shape4_systems_only": lambda: batch.shape(radii, apertures=False),
+                     "radial32": lambda: batch.radial_profile(shells),
+                     "download": download,
+                     "host_iteration_subset": host_iteration}
+            for fn in calls.values():                               # the first calls allocate the records and set the kernels' LDS limits
+                wall(fn)
+            times = {name: [] for name in calls}
+            found = {}
+            for _ in range(repeats):                                # alternated
+                for name, fn in calls.items():
+                    t, out = wall(fn)
+                    times[name].append(t)
+                    found[name] = out
+            med = {name: statistics.median(ts) for name, ts in times.items()}
+        res, host = found["shape4"], found["host_iteration_subset"]
+        assert found["shape4_bodies"].aperture_records.tobytes() == res.aperture_records.tobytes()
+        assert found["shape4_systems_only"].systems.tobytes() == res.systems.tobytes()
+        for s in range(few):                                        # the same shapes, summed in another order
+            for a in range(len(radii)):
+                if res.status[s, a] == 0:
+                    assert abs(res.q[s, a] - host[s][a][0]) < 1e-2 and abs(res.s[s, a] - host[s][a][1]) < 1e-2, (s, a)
+        # measured: the download of the whole batch and the host iteration of `few` systems; the product with B is extrapolated
+        replaced = med["download"] + med["host_iteration_subset"] * B / few
+        line = {"n": n, "B": B, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"), "apertures": len(radii), "repeats": repeats,
+                "status_counts": np.bincount(res.status.ravel(), minlength=4).tolist(),
+                "passes_mean": round(float(res.iterations.mean()), 2), "passes_of_the_slowest_system": int(res.iterations.max()),
+                "q_mean": round(float(res.q[res.status == 0].mean()), 4), "s_mean": round(float(res.s[res.status == 0].mean()), 4),
+                "apertures_megabytes": round(B * len(radii) * 256 / 1e6, 3), "bodies_megabytes": round(B * n * 8 / 1e6, 2),
+                "download_megabytes": round(2 * B * n * 16 / 1e6, 2), "apertures_crc32": zlib.crc32(res.aperture_records.tobytes()),
+                "host_systems_timed": few, "host_iteration_ms_per_system": round(med["host_iteration_subset"] / few, 3),
+                "replaced_ms_extrapolated_to_B": round(replaced, 2)}
+        for name in calls:
+            line[name + "_ms"] = round(med[name], 3)
+        for name in ("shape4", "shape4_bodies", "shape4_systems_only"):
+            line[name + "_over_replaced"] = round(med[name] / replaced, 5)
+            line[name + "_over_download"] = round(med[name] / med["download"], 4)
+            line[name + "_over_radial32"] = round(med[name] / med["radial32"], 3)
+        for name in calls:
+            line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+        print(json.dumps(line), flush=True)
+
+
+if args.shape:
+    shape_lines()
+    sys.exit(0)
 if args.surface:
     surface_lines()
     sys.exit(0)
