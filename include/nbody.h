@@ -563,6 +563,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_surface.h"
 /* shapes: per system and each of up to 8 apertures the ellipsoid the iterated moment tensor converges to -- axis ratios, axes, members and the sums inside it -- every sum over blocks of 64 bodies in ascending index and then over the blocks */
 #include "nbody_batch_shape.h"
+/* pair velocities: per system and each of up to 32 bins of separation the count and nine fp64 sums over the ordered pairs (row, source) of the bin -- separation, radial velocity and its square, tangential and whole relative velocity -- every sum over the columns in ascending index, then over blocks of 64 rows, then over the blocks */
+#include "nbody_batch_pair_velocities.h"
 
 #ifdef __cplusplus
 }

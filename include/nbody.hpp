@@ -873,6 +873,41 @@ public:
               "nbody_batch_shape");
         return s;
     }
+    // Pair velocity statistics (nbody_batch_pair_velocities.h): for every system and each bin of separation the count and
+    // nine fp64 sums over the ordered pairs (row, source) of the bin, in a pinned order.  edges: bins + 1 ascending values
+    // >= 0 (host), one set for all systems, or numSystems sets (bins taken from `bins`, or from the one set where bins is 0);
+    // bins is 1 ... 32.  weight: NBODY_BATCH_WEIGHT_NUMBER or _MASS (the product of the two mass words).  rows, sources: empty
+    // for all bodies, or numSystems x maxBodies bytes (host).  Returns the per-system records; records, where given, is
+    // resized to numSystems x bins and takes the bins (bin t of system s at s * bins + t); nullptr skips that copy.  Changes
+    // nothing the handle keeps.
+    std::vector<nbody_batch_pair_velocities_system> pairVelocities(const float *dPositions, const float *dVelocities,
+                                                                   const std::vector<float> &edges,
+                                                                   std::vector<nbody_batch_pair_velocities_bin> *records,
+                                                                   int weight = NBODY_BATCH_WEIGHT_NUMBER, int bins = 0,
+                                                                   const std::vector<unsigned char> &rows = {},
+                                                                   const std::vector<unsigned char> &sources = {})
+    {
+        if (bins == 0)
+            bins = (int)edges.size() - 1;
+        if (bins < 1 || bins > NBODY_BATCH_PAIR_VELOCITIES_MAX_BINS)
+            throw std::invalid_argument("nbody::Batch::pairVelocities: bins must be 1 ... 32");
+        const size_t set = (size_t)bins + 1;
+        if (edges.size() != set && edges.size() != (size_t)systems_ * set)
+            throw std::invalid_argument("nbody::Batch::pairVelocities: bins + 1 edges, or as many per system");
+        if (!rows.empty() && rows.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::pairVelocities: one row byte per slot, or none");
+        if (!sources.empty() && sources.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::pairVelocities: one source byte per slot, or none");
+        std::vector<nbody_batch_pair_velocities_system> s((size_t)systems_);
+        if (records)
+            records->resize((size_t)systems_ * (size_t)bins);
+        const int perSystem = edges.size() == set ? 0 : 1;
+        check(nbody_batch_pair_velocities(b_, dPositions, dVelocities, bins, edges.data(), perSystem, rows.empty() ? nullptr : rows.data(),
+                                          sources.empty() ? nullptr : sources.data(), weight, s.data(),
+                                          records ? records->data() : nullptr),
+              "nbody_batch_pair_velocities");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

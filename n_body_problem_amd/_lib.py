@@ -593,6 +593,31 @@ _SHAPE_PROTOTYPES = {
 }
 
 
+BATCH_PAIR_VELOCITIES_MAX_BINS = 32
+
+
+class BatchPairVelocitiesBin(ctypes.Structure):
+    """``nbody_batch_pair_velocities_bin`` of include/nbody_batch_pair_velocities.h."""
+    _fields_ = [("count", ctypes.c_longlong), ("approaching", ctypes.c_longlong), ("receding", ctypes.c_longlong),
+                ("weight", c_double), ("r1", c_double), ("r2", c_double), ("rv", c_double), ("vr1", c_double), ("vr2", c_double),
+                ("vt2", c_double), ("v1", c_double), ("v2", c_double)]
+
+
+class BatchPairVelocitiesSystem(ctypes.Structure):
+    """``nbody_batch_pair_velocities_system`` of include/nbody_batch_pair_velocities.h."""
+    _fields_ = [("rows", c_int), ("sources", c_int), ("both", c_int), ("bins", c_int), ("weight", c_int), ("reserved", c_int),
+                ("pairs", ctypes.c_longlong), ("below", ctypes.c_longlong), ("above", ctypes.c_longlong),
+                ("unmeasured", ctypes.c_longlong)]
+
+
+#: the entry point of include/nbody_batch_pair_velocities.h (pair velocity statistics of batched ensembles), which nbody.h includes
+_PAIR_VELOCITIES_PROTOTYPES = {
+    "nbody_batch_pair_velocities": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_float), c_int, POINTER(ctypes.c_ubyte),
+                                            POINTER(ctypes.c_ubyte), c_int, POINTER(BatchPairVelocitiesSystem),
+                                            POINTER(BatchPairVelocitiesBin)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -624,7 +649,8 @@ def load() -> ctypes.CDLL:
                 list(_GRAVITY_PROTOTYPES.items()) + list(_GROUPS_PROTOTYPES.items()) + list(_SPAN_PROTOTYPES.items()) + \
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
                 list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()) + \
-                list(_SURFACE_PROTOTYPES.items()) + list(_SHAPE_PROTOTYPES.items()):
+                list(_SURFACE_PROTOTYPES.items()) + list(_SHAPE_PROTOTYPES.items()) + \
+                list(_PAIR_VELOCITIES_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -745,6 +771,11 @@ def surface_names():
 def shape_names():
     """The entry point of nbody_batch_shape.h."""
     return list(_SHAPE_PROTOTYPES)
+
+
+def pair_velocities_names():
+    """The entry point of nbody_batch_pair_velocities.h."""
+    return list(_PAIR_VELOCITIES_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -145,6 +145,14 @@ SHAPE_BODY_DTYPE = np.dtype([("inside", np.uint32), ("reserved", np.int32)])
 assert SHAPE_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeSystem) == 80
 assert SHAPE_APERTURE_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeAperture) == 256
 assert SHAPE_BODY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchShapeBody) == 8
+#: the records of :meth:`BatchedSystem.pair_velocities`: numpy's views of ``nbody_batch_pair_velocities_system`` and ``_bin``
+PAIR_VELOCITIES_SYSTEM_DTYPE = np.dtype([("rows", np.int32), ("sources", np.int32), ("both", np.int32), ("bins", np.int32),
+                                         ("weight", np.int32), ("reserved", np.int32), ("pairs", np.int64), ("below", np.int64),
+                                         ("above", np.int64), ("unmeasured", np.int64)])
+PAIR_VELOCITIES_BIN_DTYPE = np.dtype([("count", np.int64), ("approaching", np.int64), ("receding", np.int64)] +
+                                     [(name, np.float64) for name in ("weight", "r1", "r2", "rv", "vr1", "vr2", "vt2", "v1", "v2")])
+assert PAIR_VELOCITIES_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairVelocitiesSystem) == 56
+assert PAIR_VELOCITIES_BIN_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairVelocitiesBin) == 96
 
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -1259,6 +1267,57 @@ class BatchedSystem:
             body.ctypes.data_as(ctypes.POINTER(_lib.BatchShapeBody)) if bodies else None), self._h)
         return ShapeResult(systems, rec, body, weight)
 
+    def pair_velocities(self, edges, rows=None, sources=None, weight: str = "number", bins: bool = True) -> "PairVelocityResult":
+        """How pairs move at which separation (``include/nbody_batch_pair_velocities.h`` states the rules): for every system
+        and each bin of separation the number of ordered pairs (row, source), how many approach and recede, and the fp64 sums
+        of separation, radial velocity and its square, tangential and whole relative velocity over them, summed on the device
+        from the current state in a pinned order (waits for the queued work).  ``edges``, ``rows`` and ``sources`` are
+        :meth:`correlation`'s: ``(bins + 1,)`` or ``(B, bins + 1)`` ascending edges ``>= 0`` (1 ... 32 bins) and
+        ``(B, max_bodies)`` bool or uint8 masks (numpy or torch); the bin of a pair is decided by :meth:`correlation`'s code, so
+        on finite velocities the counts are :meth:`correlation`'s.  ``weight``: ``"number"`` (every pair weighs 1) or
+        ``"mass"`` (the product of the two mass words).  ``bins=False`` skips the bin records on their way to the host:
+        ``bin_records`` of the result is ``None``, the per-system words the same bits.  Changes nothing: an :meth:`evolve`
+        after it is bit for bit the :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(WEIGHTS)}, not {weight!r}")
+        if hasattr(edges, "detach"):  # a torch tensor
+            edges = edges.detach().cpu().numpy()
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32))
+        if e.ndim == 1:
+            per_system = 0
+        elif e.ndim == 2 and e.shape[0] == B:
+            per_system = 1
+        else:
+            raise ValueError(f"edges must have shape (bins + 1,) or ({B}, bins + 1), got {tuple(e.shape)}")
+        nbins = e.shape[-1] - 1
+        if not 1 <= nbins <= _lib.BATCH_PAIR_VELOCITIES_MAX_BINS:
+            raise ValueError(f"bins must be 1 ... {_lib.BATCH_PAIR_VELOCITIES_MAX_BINS}, not {nbins}")
+
+        def mask(name, m):
+            if m is None:
+                return None
+            if hasattr(m, "detach"):
+                m = m.detach().cpu().numpy()
+            m = np.ascontiguousarray(np.asarray(m))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError(f"{name} must be bool or uint8, not {m.dtype}")
+            if m.shape != (B, n):
+                raise ValueError(f"{name} must have shape ({B}, {n}), got {tuple(m.shape)}")
+            return m.view(np.uint8)
+
+        row, src = mask("rows", rows), mask("sources", sources)
+        systems = np.zeros(B, dtype=PAIR_VELOCITIES_SYSTEM_DTYPE)
+        out = np.zeros((B, nbins), dtype=PAIR_VELOCITIES_BIN_DTYPE) if bins else None
+        ubyte = ctypes.POINTER(ctypes.c_ubyte)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_pair_velocities(
+            self._h, _ptr(self.positions), _ptr(self.velocities), nbins, e.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), per_system,
+            row.ctypes.data_as(ubyte) if row is not None else None, src.ctypes.data_as(ubyte) if src is not None else None,
+            WEIGHTS[weight], systems.ctypes.data_as(ctypes.POINTER(_lib.BatchPairVelocitiesSystem)),
+            out.ctypes.data_as(ctypes.POINTER(_lib.BatchPairVelocitiesBin)) if bins else None), self._h)
+        return PairVelocityResult(systems, out, e, weight)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -2270,6 +2329,92 @@ NODE_FIELDS = ("child", "parent", "level", "leaves", "slot", "mass", "energy", "
                "separation", "perturbation", "mutual_inclination", "h")
 
 
+class PairVelocityResult:
+    """What :meth:`BatchedSystem.pair_velocities` summed.  ``edges`` are the bin edges as given (float32, ``(bins + 1,)`` or
+    ``(B, bins + 1)``); ``bin_records`` is ``(B, bins)`` of ``PAIR_VELOCITIES_BIN_DTYPE`` (``None`` without ``bins``), and each
+    of its words a ``(B, bins)`` array of that name: ``count``, ``approaching``, ``receding`` (int64) and the sums ``weight``,
+    ``r1``, ``r2``, ``rv``, ``vr1``, ``vr2``, ``vt2``, ``v1``, ``v2`` (float64) over the ordered pairs (row, source) with
+    ``edges[t] < r <= edges[t + 1]``.  Per system (``(B,)`` arrays): ``rows``, ``sources``, ``both``, ``pairs``, ``below``,
+    ``above`` and ``unmeasured`` as in :class:`CorrelationResult` (a pair with a NaN or infinite velocity word is unmeasured
+    too).  ``auto`` (bool) tells where rows and sources are the same bodies.  ``systems`` is the records themselves, ``bins``
+    the number of bins, ``weight`` the weight's name.  The derived quantities are NaN where a bin is empty."""
+
+    WORDS = ("count", "approaching", "receding", "weight", "r1", "r2", "rv", "vr1", "vr2", "vt2", "v1", "v2")
+
+    def __init__(self, systems, bin_records, edges, weight="number"):
+        self.systems, self.bin_records, self.edges, self.weight_name = systems, bin_records, edges, weight
+        for name in ("rows", "sources", "both", "pairs", "below", "above", "unmeasured"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.bins = int(edges.shape[-1]) - 1
+        self.auto = (self.rows == self.both) & (self.sources == self.both)
+        for name in self.WORDS:
+            setattr(self, name, None if bin_records is None else np.ascontiguousarray(bin_records[name]))
+
+    def _need_bins(self):
+        if self.bin_records is None:
+            raise ValueError("this needs the bins: call pair_velocities(bins=True)")
+
+    def _per_weight(self, total) -> np.ndarray:
+        self._need_bins()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.count > 0, total / np.where(self.count > 0, self.weight, 1.0), np.nan)
+
+    def mean_separation(self) -> np.ndarray:
+        """``(B, bins)``: the weighted mean separation of the pairs of every bin, ``r1 / weight``."""
+        return self._per_weight(self.r1)
+
+    def mean_radial_velocity(self) -> np.ndarray:
+        """``(B, bins)``: the mean pairwise radial velocity v12(r), ``vr1 / weight``; negative where pairs approach."""
+        return self._per_weight(self.vr1)
+
+    def sigma_radial(self) -> np.ndarray:
+        """``(B, bins)``: the pairwise dispersion along the separation, ``sqrt(max(vr2 / weight - v12^2, 0))``."""
+        return np.sqrt(np.maximum(self._per_weight(self.vr2) - self.mean_radial_velocity() ** 2, 0.0))
+
+    def sigma_tangential(self) -> np.ndarray:
+        """``(B, bins)``: the pairwise dispersion across the separation per component, ``sqrt(vt2 / (2 weight))``."""
+        return np.sqrt(self._per_weight(self.vt2) / 2.0)
+
+    def anisotropy(self) -> np.ndarray:
+        """``(B, bins)``: ``1 - sigma_tangential^2 / sigma_radial^2``; NaN where the radial dispersion is 0."""
+        st, sr = self.sigma_tangential(), self.sigma_radial()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(sr > 0, 1.0 - st * st / np.where(sr > 0, sr * sr, 1.0), np.nan)
+
+    def structure_function(self, order: int = 2) -> np.ndarray:
+        """``(B, bins)``: the velocity structure function of order 1 (``v1 / weight``, the mean relative speed) or 2
+        (``v2 / weight``, its mean square)."""
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, not {order}")
+        return self._per_weight(self.v1 if order == 1 else self.v2)
+
+    def approaching_fraction(self) -> np.ndarray:
+        """``(B, bins)``: the fraction of the pairs of every bin that approach, ``approaching / count``."""
+        self._need_bins()
+        return np.where(self.count > 0, self.approaching / np.where(self.count > 0, self.count, 1), np.nan)
+
+    def expansion_rate(self) -> np.ndarray:
+        """``(B, bins)``: the least-squares expansion rate ``sum(d.w) / sum(d.d)`` of the pairs of every bin, ``rv / r2``."""
+        self._need_bins()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.count > 0, self.rv / np.where(self.count > 0, self.r2, 1.0), np.nan)
+
+    def unordered(self) -> np.ndarray:
+        """``(B, bins)`` of ``PAIR_VELOCITIES_BIN_DTYPE``: the records over unordered pairs where ``auto`` -- every pair was
+        summed twice there, as (i, j) and (j, i) with the same terms, so counts and sums are halved -- and the records as
+        they are in the systems where rows and sources differ."""
+        self._need_bins()
+        out = self.bin_records.copy()
+        for name in self.WORDS:
+            half = out[name] // 2 if out[name].dtype == np.int64 else out[name] / 2.0
+            out[name] = np.where(self.auto[:, None], half, out[name])
+        return out
+
+    def __repr__(self):
+        return (f"PairVelocityResult(bins={self.bins}, weight={self.weight_name!r}, pairs={self.pairs.tolist()}, "
+                f"below={self.below.tolist()}, above={self.above.tolist()}, unmeasured={self.unmeasured.tolist()})")
+
+
 class HierarchyResult:
     """What :meth:`BatchedSystem.hierarchy` found.  Per system (``(B,)`` int32 arrays): ``nodes`` (made), ``roots`` (live at the
     end, leaves only), ``levels`` (evaluated), ``singles``, ``binaries``, ``triples``, ``higher`` (roots with 1, 2, 3 and >= 4
@@ -2329,4 +2474,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "ApproachesResult", "APPROACH_SYSTEM_DTYPE", "APPROACH_BODY_DTYPE", "APPROACH_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "ApproachesResult", "APPROACH_SYSTEM_DTYPE", "APPROACH_BODY_DTYPE", "APPROACH_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step", "PairVelocityResult", "PAIR_VELOCITIES_SYSTEM_DTYPE", "PAIR_VELOCITIES_BIN_DTYPE"]

@@ -1,6 +1,6 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
 // structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
-// lists, approach lists, radial profiles, surface maps, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_surface.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// lists, approach lists, radial profiles, surface maps, shapes, pair velocity statistics, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_surface.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
@@ -13,6 +13,7 @@
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
 #include "nbody_batch_neighbours_math.h"
+#include "nbody_batch_pair_velocities_math.h"
 #include "nbody_batch_pairs_elements.h"
 #include "nbody_batch_radial_math.h"
 #include "nbody_batch_radii_check.h"
@@ -2963,6 +2964,256 @@ hipError_t launch_batch_shape(const float4 *pos, const float4 *vel, const int *c
     });
 }
 
+// ---- pair velocities (include/nbody_batch_pair_velocities.h): per system and bin of separation the fp64 sums over the ordered
+// pairs (row, source) of the bin, in the header's pinned order.  A sibling of batch_correlation_kernel, whose bin decision it
+// runs: one workgroup per system with batch_shape's workgroup, the columns broadcast from LDS, rows at r = q * T + lane, so
+// that a block of 64 rows is one wave at one q and its tree is six shuffles per term.  It reads the state and writes only the
+// handle's records.
+
+static_assert(sizeof(BatchPairVelocitiesBin) == sizeof(nbody_batch_pair_velocities_bin) && sizeof(nbody_batch_pair_velocities_bin) == 96 &&
+                  offsetof(BatchPairVelocitiesBin, count) == offsetof(nbody_batch_pair_velocities_bin, count) &&
+                  offsetof(BatchPairVelocitiesBin, approaching) == offsetof(nbody_batch_pair_velocities_bin, approaching) &&
+                  offsetof(BatchPairVelocitiesBin, receding) == offsetof(nbody_batch_pair_velocities_bin, receding) &&
+                  offsetof(BatchPairVelocitiesBin, weight) == offsetof(nbody_batch_pair_velocities_bin, weight) &&
+                  offsetof(BatchPairVelocitiesBin, r1) == offsetof(nbody_batch_pair_velocities_bin, r1) &&
+                  offsetof(BatchPairVelocitiesBin, r2) == offsetof(nbody_batch_pair_velocities_bin, r2) &&
+                  offsetof(BatchPairVelocitiesBin, rv) == offsetof(nbody_batch_pair_velocities_bin, rv) &&
+                  offsetof(BatchPairVelocitiesBin, vr1) == offsetof(nbody_batch_pair_velocities_bin, vr1) &&
+                  offsetof(BatchPairVelocitiesBin, vr2) == offsetof(nbody_batch_pair_velocities_bin, vr2) &&
+                  offsetof(BatchPairVelocitiesBin, vt2) == offsetof(nbody_batch_pair_velocities_bin, vt2) &&
+                  offsetof(BatchPairVelocitiesBin, v1) == offsetof(nbody_batch_pair_velocities_bin, v1) &&
+                  offsetof(BatchPairVelocitiesBin, v2) == offsetof(nbody_batch_pair_velocities_bin, v2) &&
+                  offsetof(nbody_batch_pair_velocities_bin, weight) == 24 && offsetof(nbody_batch_pair_velocities_bin, v2) == 88,
+              "nbody_batch_pair_velocities_math.h mirrors the bin record of nbody_batch_pair_velocities.h");
+static_assert(sizeof(BatchPairVelocitiesSystem) == sizeof(nbody_batch_pair_velocities_system) && sizeof(nbody_batch_pair_velocities_system) == 56 &&
+                  offsetof(BatchPairVelocitiesSystem, rows) == offsetof(nbody_batch_pair_velocities_system, rows) &&
+                  offsetof(BatchPairVelocitiesSystem, sources) == offsetof(nbody_batch_pair_velocities_system, sources) &&
+                  offsetof(BatchPairVelocitiesSystem, both) == offsetof(nbody_batch_pair_velocities_system, both) &&
+                  offsetof(BatchPairVelocitiesSystem, bins) == offsetof(nbody_batch_pair_velocities_system, bins) &&
+                  offsetof(BatchPairVelocitiesSystem, weight) == offsetof(nbody_batch_pair_velocities_system, weight) &&
+                  offsetof(BatchPairVelocitiesSystem, reserved) == offsetof(nbody_batch_pair_velocities_system, reserved) &&
+                  offsetof(BatchPairVelocitiesSystem, pairs) == offsetof(nbody_batch_pair_velocities_system, pairs) &&
+                  offsetof(BatchPairVelocitiesSystem, below) == offsetof(nbody_batch_pair_velocities_system, below) &&
+                  offsetof(BatchPairVelocitiesSystem, above) == offsetof(nbody_batch_pair_velocities_system, above) &&
+                  offsetof(BatchPairVelocitiesSystem, unmeasured) == offsetof(nbody_batch_pair_velocities_system, unmeasured) &&
+                  offsetof(nbody_batch_pair_velocities_system, pairs) == 24 && offsetof(nbody_batch_pair_velocities_system, unmeasured) == 48,
+              "nbody_batch_pair_velocities_math.h mirrors the system record of nbody_batch_pair_velocities.h");
+static_assert(kPairVelocitiesMaxBins == NBODY_BATCH_PAIR_VELOCITIES_MAX_BINS, "nbody_batch_pair_velocities_math.h mirrors the limit of nbody_batch_pair_velocities.h");
+
+// 1: a column none of whose 64 pairs falls into a bin of the pass is left on the scalar unit before any fp64 word is formed.
+// 0: every column reaches the masked add.  The same bytes either way.
+#ifndef NBODY_BATCH_PAIR_VELOCITIES_SKIP
+#define NBODY_BATCH_PAIR_VELOCITIES_SKIP 1
+#endif
+
+constexpr int kPairVelocitiesTallies = 3;  // rows, sources, both
+
+// The wave's sum of its lanes' integers, in lane 0: integers, any order.
+__device__ inline unsigned int pair_velocities_wave_total(unsigned int word)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        word += __shfl_down(word, off, 64);
+    return word;
+}
+
+__device__ inline PairVelocityPoint pair_velocities_point(const int4 &p, const int4 &v)
+{
+    return PairVelocityPoint{__int_as_float(p.x), __int_as_float(p.y), __int_as_float(p.z), __int_as_float(v.w),
+                             __int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z)};
+}
+
+// The workgroup: batch_shape's, held to NBODY_BATCH_PAIR_VELOCITIES_MAX_THREADS lanes.  At 256 -- four waves, one per SIMD -- a
+// lane may use all 512 registers and holds the sums of G = 8 bins; its rows follow one another, so fewer lanes cost no pass.
+// At batch_shape's own 1024 lanes a lane has 128 registers, which hold G = 2 (DESIGN.md 3.6 has both measured).
+#ifndef NBODY_BATCH_PAIR_VELOCITIES_MAX_THREADS
+#define NBODY_BATCH_PAIR_VELOCITIES_MAX_THREADS 256
+#endif
+constexpr int kPairVelocitiesMaxThreads = NBODY_BATCH_PAIR_VELOCITIES_MAX_THREADS;
+inline int pair_velocities_threads(int threads) { return threads < kPairVelocitiesMaxThreads ? threads : kPairVelocitiesMaxThreads; }
+
+// LDS: img[2 j] = {x, y, z, flags} and img[2 j + 1] = {vx, vy, vz, mass word} of body j, batch_approaches_kernel's image with
+// the flags (source, row, measurable velocity) in the free word, two broadcast ds_read_b128 per column, 128 KiB at 4096 bodies;
+// behind it the partials of one round, G x 9 doubles per wave (2.25 KiB at four waves and G = 8).  A lane holds the sums of one
+// row at a time -- G x 9 doubles.  A round is the T rows from q0 on: wave w walks block q0 / 64 + w, lane l its row
+// r = q0 + 64 w + l over all columns; six shuffles per sum make the block's partial; the partials of the round go through LDS
+// and the lane of each sum adds them to its total in ascending block order; then the next round.  Every pass walks all rounds
+// again.  The order of the header is that of body indices, so neither G nor the workgroup's shape nor the number of rounds
+// shows in a record.  The fp32 r2 chain and the bin decision come first; the fp64 terms are formed under the mask of the lanes
+// whose pair is a member of one of the pass's bins.
+// edges2 holds pair_velocities_padded_edges(bins, G) squared edges per system (edge_stride that many) or one set for all
+// (edge_stride = 0).  rows, sources and bins_out may be NULL.
+// The compiler's figures for the instantiation built are in DESIGN.md 3.6: no scratch.
+template <int G>
+__global__ __launch_bounds__(kPairVelocitiesMaxThreads) void batch_pair_velocities_kernel(
+    const float4 *__restrict__ pos, const float4 *__restrict__ vel, const int *__restrict__ counts, const unsigned char *__restrict__ rows,
+    const unsigned char *__restrict__ sources, const float *__restrict__ edges2, int edge_stride, int max_bodies, int bins, int weight,
+    BatchPairVelocitiesBin *__restrict__ bins_out, BatchPairVelocitiesSystem *__restrict__ systems)
+{
+    constexpr int SUMS = G * kPairVelocitiesTerms;                                          // the sums of one pass
+    constexpr int SLOTS = (SUMS + kPairVelocitiesBlock - 1) / kPairVelocitiesBlock;        // of them per lane, in the smallest workgroup
+    extern __shared__ int4 img[];
+    __shared__ unsigned int totals[3 * G + 3];  // count, approaching, receding of the pass's bins; the system's three counters
+    __shared__ int tally[kPairVelocitiesTallies];
+    double *partials = reinterpret_cast<double *>(img + 2 * (size_t)max_bodies);  // [wave][G][9]
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & (kPairVelocitiesBlock - 1), wave = tid / kPairVelocitiesBlock;
+    const int waves = T / kPairVelocitiesBlock;
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    const float *mine2 = edges2 + (size_t)blockIdx.x * (size_t)edge_stride;
+    if (tid < 3 * G + 3)
+        totals[tid] = 0;
+    if (tid < kPairVelocitiesTallies)
+        tally[tid] = 0;
+    __syncthreads();
+    int n_rows = 0, n_sources = 0, n_both = 0;
+    for (int r = tid; r < n; r += T) {
+        const float4 p = pos[base + r], v = vel[base + r];
+        const bool source = !sources || sources[base + r] != 0, row = !rows || rows[base + r] != 0;
+        const PairVelocityPoint given{p.x, p.y, p.z, p.w, v.x, v.y, v.z};
+        n_rows += row ? 1 : 0;
+        n_sources += source ? 1 : 0;
+        n_both += row && source ? 1 : 0;
+        img[2 * r] = make_int4(__float_as_int(p.x), __float_as_int(p.y), __float_as_int(p.z),
+                               pair_velocities_flags(row, source, pair_velocities_body_measured(given)));
+        img[2 * r + 1] = make_int4(__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), __float_as_int(p.w));
+    }
+    // Integers: the order of the additions does not matter.
+    if (n_rows)
+        atomicAdd(&tally[0], n_rows);
+    if (n_sources)
+        atomicAdd(&tally[1], n_sources);
+    if (n_both)
+        atomicAdd(&tally[2], n_both);
+    __syncthreads();  // the image is in place
+    const int passes = pair_velocities_passes(bins, G), blocks = pair_velocities_blocks(n);
+    const float first = mine2[0], last = mine2[bins];
+    PairVelocitySystemCounts seen;
+    pair_velocities_clear(seen);
+    for (int pass = 0; pass < passes; ++pass) {
+        float e2[G + 1];  // the same in every lane
+#pragma unroll
+        for (int t = 0; t <= G; ++t)
+            e2[t] = mine2[pass * G + t];
+        PairVelocityCounts<G> c;
+        pair_velocities_clear(c);
+        double total[SLOTS];  // of sum tid + i T, in the lanes that have one
+#pragma unroll
+        for (int i = 0; i < SLOTS; ++i)
+            total[i] = 0.0;
+        for (int q0 = 0; q0 < n; q0 += T) {  // a round: the same for every lane of the workgroup
+            const int r0 = q0 + wave * kPairVelocitiesBlock, r = r0 + lane;
+            if (r0 < n) {  // the wave's block holds a row: the same in every lane of the wave
+                PairVelocityPoint mine{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                int flags = 0;
+                if (r < n) {
+                    const int4 p = img[2 * r], v = img[2 * r + 1];
+                    mine = pair_velocities_point(p, v);
+                    flags = p.w;
+                }
+                const bool row = (flags & kPairVelocitiesRow) != 0, row_measured = (flags & kPairVelocitiesMeasured) != 0;
+                PairVelocitySums<G> a;
+                pair_velocities_clear(a);
+#pragma unroll 1
+                for (int j = 0; j < n; ++j) {
+                    const int4 pj = img[2 * j], vj = img[2 * j + 1];  // wave-uniform addresses: broadcast LDS reads
+                    const int fj = __builtin_amdgcn_readfirstlane(pj.w);
+                    if ((fj & kPairVelocitiesSource) == 0)
+                        continue;  // no source: the flag is the same in every lane, so the branch is a scalar one
+                    const PairVelocityPoint column = pair_velocities_point(pj, vj);
+                    const float r2 = pair_velocities_r2(correlation_examined(row, true, r, j),
+                                                        row_measured && (fj & kPairVelocitiesMeasured) != 0, mine, column);
+                    if (pass == 0)
+                        pair_velocities_system_step(seen, r2, first, last);
+                    const int bin = pair_velocities_bin<G>(r2, e2);
+                    const bool member = pair_velocities_member<G>(bin);
+                    if (NBODY_BATCH_PAIR_VELOCITIES_SKIP && __builtin_amdgcn_ballot_w64(member) == 0)
+                        continue;  // the same in every lane of the wave
+                    if (member)
+                        pair_velocities_add<G>(a, c, bin, mine, column, weight);
+                }
+                // The block's partial of every sum: the halving tree over the 64 row sums, the result in lane 0.
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+#pragma unroll
+                    for (int k = 0; k < kPairVelocitiesTerms; ++k)
+                        for (int off = kPairVelocitiesBlock / 2; off > 0; off >>= 1)
+                            a.w[g][k] = pair_velocities_tree_step(a.w[g][k], __shfl_down(a.w[g][k], off, kPairVelocitiesBlock));
+                if (lane == 0) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+#pragma unroll
+                        for (int k = 0; k < kPairVelocitiesTerms; ++k)
+                            partials[wave * SUMS + g * kPairVelocitiesTerms + k] = a.w[g][k];
+                }
+            }
+            __syncthreads();  // the partials of the round are in
+            const int left = blocks - q0 / kPairVelocitiesBlock;  // the round's blocks that hold a row, in ascending order
+#pragma unroll
+            for (int i = 0; i < SLOTS; ++i)
+                if (tid + i * T < SUMS)
+                    total[i] = pair_velocities_total(total[i], partials + tid + i * T, SUMS, left < waves ? left : waves);
+            __syncthreads();  // read before the next round writes
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const unsigned int count = pair_velocities_wave_total(c.count[g]), approaching = pair_velocities_wave_total(c.approaching[g]),
+                               receding = pair_velocities_wave_total(c.receding[g]);
+            if (lane == 0 && count) {
+                atomicAdd(&totals[g], count);
+                atomicAdd(&totals[G + g], approaching);
+                atomicAdd(&totals[2 * G + g], receding);
+            }
+        }
+        if (pass == 0) {
+            const unsigned int within_first = pair_velocities_wave_total(seen.within_first),
+                               within_last = pair_velocities_wave_total(seen.within_last), measured = pair_velocities_wave_total(seen.measured);
+            if (lane == 0) {
+                atomicAdd(&totals[3 * G], within_first);
+                atomicAdd(&totals[3 * G + 1], within_last);
+                atomicAdd(&totals[3 * G + 2], measured);
+            }
+        }
+        __syncthreads();  // the integers of the pass are in
+        // One lane per word of the pass's records: a sum from its total, an integer from the workgroup's.
+        if (bins_out) {
+            BatchPairVelocitiesBin *out = bins_out + (size_t)blockIdx.x * (size_t)bins + (size_t)pass * G;
+#pragma unroll
+            for (int i = 0; i < SLOTS; ++i) {
+                const int sum = tid + i * T, g = sum / kPairVelocitiesTerms;
+                if (sum < SUMS && pass * G + g < bins)
+                    pair_velocities_store(out + g, kPairVelocitiesIntegers + sum % kPairVelocitiesTerms, total[i]);
+            }
+            if (tid < kPairVelocitiesIntegers * G && pass * G + tid % G < bins)
+                pair_velocities_store(out + tid % G, tid / G, totals[tid]);
+        }
+        __syncthreads();  // the integers are read
+        if (tid < 3 * G)
+            totals[tid] = 0;
+        __syncthreads();  // cleared before the next pass adds
+    }
+    if (tid == 0)
+        systems[blockIdx.x] = pair_velocities_system(tally[0], tally[1], tally[2], bins, weight,
+                                                     PairVelocitySystemCounts{totals[3 * G], totals[3 * G + 1], totals[3 * G + 2]});
+}
+
+// The dynamic LDS of one launch: the image, and the partials of one round, one set per wave.
+inline size_t pair_velocities_lds_bytes(int max_bodies, int threads, int g)
+{
+    return 2 * sizeof(int4) * (size_t)max_bodies + sizeof(double) * (size_t)(threads / kPairVelocitiesBlock) * (size_t)(g * kPairVelocitiesTerms);
+}
+
+// One launch over all systems, G = kPairVelocitiesPassBins, for which edges2 is laid out.
+hipError_t launch_batch_pair_velocities(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *rows,
+                                        const unsigned char *sources, const float *edges2, int edge_stride, int n_systems, int max_bodies,
+                                        int bins, int weight, BatchPairVelocitiesBin *bins_out, BatchPairVelocitiesSystem *systems,
+                                        hipStream_t stream)
+{
+    const int threads = pair_velocities_threads(batch_shape(max_bodies).threads);
+    return launch_analysis_kernel(batch_pair_velocities_kernel<kPairVelocitiesPassBins>, n_systems, threads,
+                                  pair_velocities_lds_bytes(max_bodies, threads, kPairVelocitiesPassBins), stream, pos, vel, counts, rows,
+                                  sources, edges2, edge_stride, max_bodies, bins, weight, bins_out, systems);
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -3113,6 +3364,12 @@ struct BatchAnalysis {
     std::vector<double> shape_aps_host;               // the last call's: the copy's source until the stream is idle
     DeviceArray<double> shape_frames;                 // [n_systems][6]: centre, velocity
     std::vector<double> shape_frames_host;            // the last call's
+    DeviceArray<BatchPairVelocitiesSystem> pair_velocities_systems;  // [n_systems]
+    DeviceArray<BatchPairVelocitiesBin> pair_velocities_bins;        // [n_systems][bins] of the largest call that asked for them
+    DeviceArray<unsigned char> pair_velocities_rows;                 // [n_systems][max_bodies], the device copy of `rows`
+    DeviceArray<unsigned char> pair_velocities_sources;              // [n_systems][max_bodies], the device copy of `sources`
+    DeviceArray<float> pair_velocities_edges2;                       // one set or [n_systems] sets of padded squared edges
+    std::vector<float> pair_velocities_edges2_host;                  // the last call's: the copy's source until the stream is idle
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -3840,6 +4097,61 @@ int nbody_batch_shape(nbody_batch *b, const float *d_pos, const float *d_vel, in
     BATCH_TRY(b, copy_out(b, systems_out, a->shape_systems, B));
     BATCH_TRY(b, copy_out(b, apertures_out, a->shape_apertures, records));
     BATCH_TRY(b, copy_out(b, bodies_out, a->shape_bodies, slots));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_pair_velocities(nbody_batch *b, const float *d_pos, const float *d_vel, int bins, const float *edges, int per_system,
+                                const unsigned char *rows, const unsigned char *sources, int weight,
+                                nbody_batch_pair_velocities_system *systems_out, nbody_batch_pair_velocities_bin *bins_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: batch is NULL");
+    if (!d_pos || !d_vel || !edges || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: NULL argument");
+    if (bins < 1 || bins > NBODY_BATCH_PAIR_VELOCITIES_MAX_BINS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: bins must be 1 ... 32");
+    if (weight != NBODY_BATCH_WEIGHT_MASS && weight != NBODY_BATCH_WEIGHT_NUMBER)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: weight must be NBODY_BATCH_WEIGHT_MASS or NBODY_BATCH_WEIGHT_NUMBER");
+    const size_t B = (size_t)b->n_systems, slots = B * (size_t)b->max_bodies, sets = per_system ? B : 1;
+    const size_t given = (size_t)bins + 1, padded = (size_t)pair_velocities_padded_edges(bins, kPairVelocitiesPassBins);
+    for (size_t s = 0; s < sets; ++s) {
+        const float *e = edges + s * given;
+        const std::string which = per_system ? " of system " + std::to_string(s) : std::string(" of all systems");
+        for (size_t t = 0; t < given; ++t) {
+            if (!correlation_edge_valid(e[t]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: edge " + std::to_string(t) + which + " must be finite and >= 0");
+            if (t > 0 && !(e[t] > e[t - 1]))
+                return bfail(b, NBODY_ERR_INVALID, "nbody_batch_pair_velocities: edge " + std::to_string(t) + which +
+                                                       " is not above edge " + std::to_string(t - 1) + ": the edges must be strictly ascending");
+        }
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->pair_velocities_edges2_host.resize(sets * padded);
+    for (size_t s = 0; s < sets; ++s)
+        for (size_t t = 0; t < padded; ++t)  // e2: one fp32 product; from `bins` on copies of the last edge
+            a->pair_velocities_edges2_host[s * padded + t] = correlation_edge2(edges[s * given + (t < given ? t : given - 1)]);
+    const size_t records = bins_out ? B * (size_t)bins : 0;
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->pair_velocities_systems.ensure(B));
+    BATCH_TRY(b, a->pair_velocities_edges2.ensure(sets * padded));
+    BATCH_TRY(b, a->pair_velocities_rows.ensure(rows ? slots : 0));
+    BATCH_TRY(b, a->pair_velocities_sources.ensure(sources ? slots : 0));
+    BATCH_TRY(b, a->pair_velocities_bins.ensure(records));
+    BATCH_TRY(b, hipMemcpyAsync(a->pair_velocities_edges2.ptr, a->pair_velocities_edges2_host.data(), sizeof(float) * sets * padded,
+                                hipMemcpyHostToDevice, b->stream));
+    if (rows)
+        BATCH_TRY(b, hipMemcpyAsync(a->pair_velocities_rows.ptr, rows, slots, hipMemcpyHostToDevice, b->stream));
+    if (sources)
+        BATCH_TRY(b, hipMemcpyAsync(a->pair_velocities_sources.ptr, sources, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, launch_batch_pair_velocities(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel),
+                                              b->counts_dev.ptr, rows ? a->pair_velocities_rows.ptr : nullptr,
+                                              sources ? a->pair_velocities_sources.ptr : nullptr, a->pair_velocities_edges2.ptr,
+                                              per_system ? (int)padded : 0, (int)b->n_systems, (int)b->max_bodies, bins, weight,
+                                              bins_out ? a->pair_velocities_bins.ptr : nullptr, a->pair_velocities_systems.ptr, b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->pair_velocities_systems, B));
+    BATCH_TRY(b, copy_out(b, bins_out, a->pair_velocities_bins, records));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

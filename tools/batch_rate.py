@@ -162,7 +162,15 @@ the call with the aperture records, with the per-body masks too and with the per
 batch, plus the same iteration in numpy (einsum and numpy.linalg.eigh), measured on the first --subset systems and extrapolated
 to B, which the line says: all synchronous calls, wall clock, alternated after a warm-up of every call, medians of at least 15
 and spreads.  The line gives the passes of the slowest system, which sets the launch's time, and the converged q and s of the
-timed systems are asserted to be numpy's to 1e-2 (another order of summation, another eigensolver) before a line is printed."""
+timed systems are asserted to be numpy's to 1e-2 (another order of summation, another eigensolver) before a line is printed.
+
+--pair-velocities: instead, the pair velocity statistics (BatchedSystem.pair_velocities).  For n x B = 1024 x 1024, 4096 x 256 and
+256 x 4096 (or --cases), one line per case and number of bins (8 and 32 logarithmic bins from 0.05 to 10) on Plummer spheres: the
+lean call (bins=False), the call with the bin records, correlation() at the same bins in the same run, and what the call
+replaces -- positions.cpu() plus velocities.cpu(), measured on the whole batch, plus a numpy walk of all ordered pairs
+(numpy.histogram with weights per sum), measured once on the first --subset systems and extrapolated to B, which the line says:
+all synchronous calls, wall clock, alternated after a warm-up of every device call, medians and spreads.  The counts are asserted to be
+correlation()'s, and on the timed systems the sums to be numpy's to 1e-9 of their absolute addends, before a line is printed."""
 import argparse
 import json
 import os
@@ -228,6 +236,8 @@ ap.add_argument("--surface", action="store_true", help="surface_map() at 16 x 16
                 "records, against the download plus one numpy.histogram2d per system, radial_profile() and pairs(), wall clock")
 ap.add_argument("--shape", action="store_true", help="shape() at four apertures, reduced, with and without the aperture and body "
                 "records, against the download plus the iteration in numpy (timed on --subset systems) and radial_profile(), wall clock")
+ap.add_argument("--pair-velocities", action="store_true", help="pair_velocities() at 8 and 32 bins, lean and with the bin records, "
+                "against correlation() at the same bins and the download plus a numpy pair walk (timed on --subset systems), wall clock")
 args = ap.parse_args()
 
 
@@ -1522,6 +1532,92 @@ def shape_lines():
         print(json.dumps(line), flush=True)
 
 
+def host_pair_walk(p, v, edges):
+    """What pair_velocities() replaces, for one system: all ordered pairs in numpy, nine weighted histograms."""
+    x, u = p[:, :3].astype(np.float64), v[:, :3].astype(np.float64)
+    d, w = x[None, :, :] - x[:, None, :], u[None, :, :] - u[:, None, :]
+    keep = ~np.eye(len(x), dtype=bool)
+    s, rv, v2 = (d * d).sum(-1)[keep], (d * w).sum(-1)[keep], (w * w).sum(-1)[keep]
+    r = np.sqrt(s)
+    vr = rv / r
+    words = (np.ones_like(r), r, s, rv, vr, vr * vr, np.maximum(v2 - vr * vr, 0.0), np.sqrt(v2), v2)
+    return np.stack([np.histogram(r, bins=edges, weights=word)[0] for word in words], axis=1)
+
+
+def pair_velocities_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    terms = ("weight", "r1", "r2", "rv", "vr1", "vr2", "vt2", "v1", "v2")
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        few = min(args.subset, B)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            for bins in (8, 32):
+                edges = np.geomspace(0.05, 10.0, bins + 1).astype(np.float32)
+
+                def download():
+                    return batch.positions.cpu().numpy(), batch.velocities.cpu().numpy()
+
+                def host_walk():
+                    """The host's part of what the call replaces, on the first `few` systems only."""
+                    return [host_pair_walk(P[s], V[s], edges.astype(np.float64)) for s in range(few)]
+
+                calls = {"lean": lambda: batch.pair_velocities(edges, bins=False),
+                         "records": lambda: batch.pair_velocities(edges),
+                         "correlation": lambda: batch.correlation(edges),
+                         "download": download,
+                         "host_walk_subset": host_walk}
+                for name, fn in calls.items():                      # the first calls allocate the records and set the kernels' LDS limits
+                    if name != "host_walk_subset":
+                        wall(fn)
+                times = {name: [] for name in calls}
+                found = {}
+                for round_ in range(args.repeats):                  # alternated; the numpy walk, seconds long and on no GPU, once
+                    for name, fn in calls.items():
+                        if name == "host_walk_subset" and round_ > 0:
+                            continue
+                        t, out = wall(fn)
+                        times[name].append(t)
+                        found[name] = out
+                med = {name: statistics.median(ts) for name, ts in times.items()}
+                res, host = found["records"], found["host_walk_subset"]
+                assert found["lean"].systems.tobytes() == res.systems.tobytes()
+                assert np.array_equal(res.count, found["correlation"].counts) and np.array_equal(res.above, found["correlation"].above)
+                for s in range(few):                                # the same sums in another order; pairs on an edge's rounding aside
+                    if np.array_equal(host[s][:, 0], res.count[s]):
+                        for c, word in enumerate(terms):
+                            scale = np.abs(host[s][:, c]) + host[s][:, 8] + host[s][:, 2]
+                            assert (np.abs(res.bin_records[word][s] - host[s][:, c]) <= 1e-9 * scale).all(), (s, word)
+                replaced = med["download"] + med["host_walk_subset"] * B / few
+                line = {"n": n, "B": B, "bins": bins, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"), "repeats": args.repeats,
+                        "pairs_in_bins_share": round(float(res.count.sum() / res.pairs.sum()), 4),
+                        "records_megabytes": round(B * bins * 96 / 1e6, 3), "download_megabytes": round(2 * B * n * 16 / 1e6, 2),
+                        "records_crc32": zlib.crc32(res.bin_records.tobytes()), "host_systems_timed": few,
+                        "host_walk_ms_per_system": round(med["host_walk_subset"] / few, 3),
+                        "replaced_ms_extrapolated_to_B": round(replaced, 2)}
+                for name in calls:
+                    line[name + "_ms"] = round(med[name], 3)
+                for name in ("lean", "records"):
+                    line[name + "_over_correlation"] = round(med[name] / med["correlation"], 3)
+                    line[name + "_over_replaced"] = round(med[name] / replaced, 6)
+                for name in calls:
+                    line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+                print(json.dumps(line), flush=True)
+
+
+if args.pair_velocities:
+    pair_velocities_lines()
+    sys.exit(0)
 if args.shape:
     shape_lines()
     sys.exit(0)
