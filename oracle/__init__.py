@@ -4,6 +4,12 @@ PARITY UNPINNED -- see the header of ``nbody_oracle.c``: the reference has no te
 vectors for this path and cannot be built here, so this restatement is pinned by analytic known
 answers only.
 
+Two functions restate the reference's VERSION 3 step.  ``step_v3_tiled`` (with ``accel_v3_tiled``) sums the way
+``cal_acc_advanced`` does -- per 256 x 256 block a fresh row sum per thread and a fresh column sum per column in the staggered
+order, block sums then added in ascending block number: one legal, deterministic execution order of the reference's atomics,
+and the partner the HIP path is held to.  ``step_v3`` sums each body as ONE ascending fp32 chain: the single-chain upper
+envelope of what fp32 summation costs, not an order the reference takes.
+
 Importers allowed: ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of
 ``bench.py``.  Nothing under ``n_body_problem_amd/`` imports this package.
 """
@@ -57,8 +63,16 @@ def lib() -> ctypes.CDLL:
         L.oracle_step_kdk_f32.restype = _c_int
         L.oracle_step_f64.argtypes = [_f64p, _f64p, _c_int, ctypes.c_double, ctypes.c_double, _c_int, _c_int]
         L.oracle_step_f64.restype = _c_int
-        L.oracle_step_v3.argtypes = [_f32p, _f32p, _c_int, _c_int]
+        L.oracle_step_v3.argtypes = [_f32p, _f32p, _c_int, _c_int, _c_int]
         L.oracle_step_v3.restype = _c_int
+        L.oracle_step_v3_tiled.argtypes = [_f32p, _f32p, _c_int, _c_int, _c_int]
+        L.oracle_step_v3_tiled.restype = _c_int
+        L.oracle_accel_v3_tiled.argtypes = [_f32p, _c_int, _f32p, _c_int]
+        L.oracle_accel_v3_tiled.restype = _c_int
+        L.oracle_v3_tiled_blocks.argtypes = [_c_int]
+        L.oracle_v3_tiled_blocks.restype = _c_int
+        L.oracle_v3_tiled_visits.argtypes = [_c_int, _c_int, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")]
+        L.oracle_v3_tiled_visits.restype = _c_int
         L.oracle_step_v2_serial.argtypes = [_f32p, _f32p, _c_int, _c_int]
         L.oracle_step_v2_serial.restype = None
         L.oracle_pair_v3.argtypes = [_f32p, _f32p, _f32p]
@@ -189,13 +203,58 @@ def update_f32(pos, vel, acc3, dt, i0=0, i1=None):
     lib().oracle_update_f32(pos, vel, _f32(acc3), i0, i1, float(dt))
 
 
-def step_v3(pos, vel, nsteps=1):
-    """The reference's VERSION 3 with its own constants (dt=0.008, effective eps=1e-2), deterministic order."""
+def step_v3(pos, vel, nsteps=1, threads=None):
+    """VERSION 3's pair terms and constants (dt=0.008, effective eps=1e-2) with every body summed as ONE ascending fp32
+    chain: the single-chain upper envelope, not the reference's association (that is ``step_v3_tiled``).  The thread count
+    changes no bit."""
     p = _f32(pos).reshape(-1, 4).copy()
     v = _f32(vel).reshape(-1, 4).copy()
-    if lib().oracle_step_v3(p, v, p.shape[0], int(nsteps)) != 0:
+    if lib().oracle_step_v3(p, v, p.shape[0], int(nsteps), threads or host_threads()) != 0:
         raise MemoryError("oracle_step_v3")
     return p, v
+
+
+def _v3_tiled_rc(rc, what, n):
+    if rc == -2:
+        raise ValueError(f"{what}: {n} bodies is not 256 k + 1, the reference's padded count (kernel.cu:260-278)")
+    if rc != 0:
+        raise MemoryError(what)
+
+
+def step_v3_tiled(pos, vel, nsteps=1, threads=None):
+    """The reference's VERSION 3 with its own constants and its own two-level summation (``cal_acc_advanced``,
+    kernel.cu:640-661, 703-774): block sums of at most 256 staggered terms, added in ascending block number -- one legal
+    order of its float atomics.  The body count must be 256 k + 1; the thread count changes no bit."""
+    p = _f32(pos).reshape(-1, 4).copy()
+    v = _f32(vel).reshape(-1, 4).copy()
+    _v3_tiled_rc(-2 if p.shape[0] == 0 else lib().oracle_step_v3_tiled(p, v, p.shape[0], int(nsteps), threads or host_threads()),
+                 "step_v3_tiled", p.shape[0])
+    return p, v
+
+
+def accel_v3_tiled(pos, threads=None) -> np.ndarray:
+    """The summed fp32 accelerations of one force pass of ``step_v3_tiled``: (n, 3) float32."""
+    p = _f32(pos).reshape(-1, 4)
+    out = np.zeros((p.shape[0], 3), dtype=np.float32)
+    _v3_tiled_rc(-2 if p.shape[0] == 0 else lib().oracle_accel_v3_tiled(p, p.shape[0], out, threads or host_threads()),
+                 "accel_v3_tiled", p.shape[0])
+    return out
+
+
+def v3_tiled_blocks(n) -> int:
+    """How many 256 x 256 blocks the reference launches for n = 256 k + 1 bodies: k (k + 1) / 2."""
+    rc = lib().oracle_v3_tiled_blocks(int(n))
+    _v3_tiled_rc(min(rc, 0), "v3_tiled_blocks", n)
+    return rc
+
+
+def v3_tiled_visits(n, block) -> np.ndarray:
+    """The (row, column) pairs block ``block`` visits, in the order the force pass itself walks them: (visits, 2) int32."""
+    out = np.zeros((65536, 2), dtype=np.int32)
+    rc = lib().oracle_v3_tiled_visits(int(n), int(block), out)
+    if rc < 0:
+        raise ValueError(f"v3_tiled_visits: {n} bodies is not 256 k + 1, or it has no block {block}")
+    return out[:rc]
 
 
 def step_v2_serial(pos, vel, nsteps=1):

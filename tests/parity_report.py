@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
-"""Measured parity on the reference's own inputs (tests/golden: galaxy_20K.bin, k17hp.snap, k17c.snap, stars_8192.dat), the reference's
-way: padded to roundup(n, 256) + 1 (kernel.cu:260-278), dt = 0.008, VERSION 3's effective softening 1e-2 (kernel.cu:63-66,
-665-692), K frames of the bracket kernel.cu:1225-1242.
+"""Measured parity on the reference's own inputs (tests/golden: galaxy_20K.bin, k17hp.snap, k17c.snap, stars_8192.dat, stars.dat),
+the reference's way: padded to roundup(n, 256) + 1 (kernel.cu:260-278), dt = 0.008, VERSION 3's effective softening 1e-2
+(kernel.cu:63-66, 665-692), K frames of the bracket kernel.cu:1225-1242.
 
-For every input, force mode and body order: the HIP path's state against the fp64 truth (oracle.step_f64) and against the
-oracle's literal restatement of VERSION 3 in the reference's fp32 order (oracle.step_v3), next to the error of that
-restatement itself against the fp64 truth -- the number the GPU has to stay below to be "no worse than the reference order".
+For every input, force mode and body order, the HIP path's state against three CPU results: VERSION 3 restated in the
+reference's own tile order (oracle.step_v3_tiled: 256 x 256 blocks, fresh sums per block, blocks added in ascending number --
+one legal order of its atomics, and the partner of the stated 1e-5), the fp64 truth (oracle.step_f64), and VERSION 3 summed
+as one ascending fp32 chain per body (oracle.step_v3: the upper envelope, no order the reference takes).  Per input, next
+to them: tile order and chain against the truth, and the wall time of each CPU path at oracle.host_threads() threads (the
+chain also on one thread, as it ran before it was threaded).
 rel = max_i |x_i - ref_i|_inf / max_i |ref_i|_inf over the real bodies.  Run on an MI355X; the output is
-committed under profiles/ and quoted in README.md / DESIGN.md next to the 1e-5 tolerance.
+committed as profiles/parity_tile_order.txt and quoted in README.md / DESIGN.md next to the 1e-5 tolerance.
 """
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,25 +39,41 @@ def run(ppos, pvel, frames, mode, order):
         return s.download()
 
 
+def timed(fn, *args, **kw):
+    t0 = time.perf_counter()
+    out = fn(*args, **kw)
+    return out, time.perf_counter() - t0
+
+
 def main():
     oracle.build()
     golden = os.path.join(ROOT, "tests", "golden")
-    print(f"{'input':16s} {'frames':>6s} {'mode':10s} {'order':7s} | {'pos vs f64':>10s} {'vel vs f64':>10s} | "
-          f"{'pos vs v3':>10s} {'vel vs v3':>10s} | oracle v3 vs f64: pos, vel")
-    for name, frame_list in (("galaxy_20K.bin", (1, 10)), ("k17hp.snap", (1, 10)), ("k17c.snap", (3,)), ("stars_8192.dat", (1, 2))):
+    err = rel_state_error
+    print(f"oracle threads: {oracle.host_threads()}; every entry: positions / velocities")
+    for name, frame_list in (("galaxy_20K.bin", (1, 10)), ("k17hp.snap", (1, 10)), ("k17c.snap", (3,)), ("stars_8192.dat", (1,)),
+                             ("stars.dat", (1,))):
         pos, vel = ds.read_any(os.path.join(golden, name))
         ppos, pvel = nb.pad_reference_style(pos, vel)
         n = pos.shape[0]
         for frames in frame_list:
-            p3, v3 = oracle.step_v3(ppos, pvel, nsteps=frames)
-            p64, v64 = oracle.step_f64(ppos, pvel, nb.TIME_TICK, nb.SOFTENING_VERSION3, nsteps=frames)
-            ref = (rel_state_error(p3[:n], p64[:n]), rel_state_error(v3[:n], v64[:n]))
+            (pt, vt), t_tiled = timed(oracle.step_v3_tiled, ppos, pvel, nsteps=frames)
+            (p3, v3), t_chain = timed(oracle.step_v3, ppos, pvel, nsteps=frames)
+            (p1, v1), t_chain1 = timed(oracle.step_v3, ppos, pvel, nsteps=frames, threads=1)
+            assert np.array_equal(p1, p3) and np.array_equal(v1, v3)
+            (p64, v64), t_f64 = timed(oracle.step_f64, ppos, pvel, nb.TIME_TICK, nb.SOFTENING_VERSION3, nsteps=frames)
+            print(f"\n{name}: {n} bodies padded to {ppos.shape[0]} ({oracle.v3_tiled_blocks(ppos.shape[0])} blocks), {frames} frame(s)")
+            print(f"  tile order vs truth {err(pt[:n], p64[:n]):.3e} / {err(vt[:n], v64[:n]):.3e} | single chain vs truth "
+                  f"{err(p3[:n], p64[:n]):.3e} / {err(v3[:n], v64[:n]):.3e} | tile order vs chain {err(pt[:n], p3[:n]):.3e} / "
+                  f"{err(vt[:n], v3[:n]):.3e}")
+            print(f"  CPU seconds: tile order {t_tiled:.2f}, single chain {t_chain:.2f} (one thread, the same bits: {t_chain1:.2f}), "
+                  f"fp64 truth {t_f64:.2f}")
+            print(f"  {'mode':10s} {'order':7s} | {'HIP vs tile order':>21s} | {'HIP vs truth':>21s} | {'HIP vs single chain':>21s}")
             for mode in ("one_sided", "pair_once"):
                 for order in ("given", "morton"):
                     p, v = run(ppos, pvel, frames, mode, order)
-                    print(f"{name:16s} {frames:6d} {mode:10s} {order:7s} | {rel_state_error(p[:n], p64[:n]):10.3e} "
-                          f"{rel_state_error(v[:n], v64[:n]):10.3e} | {rel_state_error(p[:n], p3[:n]):10.3e} "
-                          f"{rel_state_error(v[:n], v3[:n]):10.3e} | {ref[0]:.3e}, {ref[1]:.3e}", flush=True)
+                    print(f"  {mode:10s} {order:7s} | {err(p[:n], pt[:n]):10.3e} {err(v[:n], vt[:n]):10.3e} | "
+                          f"{err(p[:n], p64[:n]):10.3e} {err(v[:n], v64[:n]):10.3e} | {err(p[:n], p3[:n]):10.3e} "
+                          f"{err(v[:n], v3[:n]):10.3e}", flush=True)
 
 
 if __name__ == "__main__":
