@@ -565,6 +565,8 @@ int nbody_batch_momentum(nbody_batch *b, const float *d_positions_xyzm, const fl
 #include "nbody_batch_shape.h"
 /* pair velocities: per system and each of up to 32 bins of separation the count and nine fp64 sums over the ordered pairs (row, source) of the bin -- separation, radial velocity and its square, tangential and whole relative velocity -- every sum over the columns in ascending index, then over blocks of 64 rows, then over the blocks */
 #include "nbody_batch_pair_velocities.h"
+/* mutual gravity: per system and ordered pair (a, b) of up to 8 labelled sets of its bodies what set b does to set a -- potential energy, net force, torque and Clausius virial about a centre, power in a frame -- every sum over the sources in ascending index, then over blocks of 64 rows of the set, then over the blocks */
+#include "nbody_batch_mutual_gravity.h"
 
 #ifdef __cplusplus
 }

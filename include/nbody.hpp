@@ -908,6 +908,34 @@ public:
               "nbody_batch_pair_velocities");
         return s;
     }
+    // Mutual gravity of labelled sets (nbody_batch_mutual_gravity.h): for every system and ordered pair (a, b) of `sets` (1 ... 8)
+    // sets what set b does to set a -- potential, force, torque, virial, power -- as fp64 sums in a pinned order.  labels:
+    // numSystems x maxBodies bytes (host), a value below sets or NBODY_BATCH_MUTUAL_GRAVITY_NO_SET.  centre, velocity: empty
+    // for zeros, or numSystems x 3 doubles (host).  Returns the per-system records; matrix, where given, is resized to
+    // numSystems x sets x sets and takes the entries (entry (a, b) of system s at (s * sets + a) * sets + b); nullptr skips
+    // that copy.  Changes nothing the handle keeps.
+    std::vector<nbody_batch_mutual_gravity_system> mutualGravity(const float *dPositions, const float *dVelocities, int sets,
+                                                                 const std::vector<unsigned char> &labels,
+                                                                 std::vector<nbody_batch_mutual_gravity_entry> *matrix,
+                                                                 float softening = 0.f, const std::vector<double> &centre = {},
+                                                                 const std::vector<double> &velocity = {})
+    {
+        if (sets < 1 || sets > NBODY_BATCH_MUTUAL_GRAVITY_MAX_SETS)
+            throw std::invalid_argument("nbody::Batch::mutualGravity: sets must be 1 ... 8");
+        if (labels.size() != (size_t)systems_ * (size_t)maxBodies_)
+            throw std::invalid_argument("nbody::Batch::mutualGravity: one label byte per slot");
+        if (!centre.empty() && centre.size() != 3 * (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::mutualGravity: three centre words per system, or none");
+        if (!velocity.empty() && velocity.size() != 3 * (size_t)systems_)
+            throw std::invalid_argument("nbody::Batch::mutualGravity: three velocity words per system, or none");
+        std::vector<nbody_batch_mutual_gravity_system> s((size_t)systems_);
+        if (matrix)
+            matrix->resize((size_t)systems_ * (size_t)(sets * sets));
+        check(nbody_batch_mutual_gravity(b_, dPositions, dVelocities, sets, labels.data(), softening, centre.empty() ? nullptr : centre.data(),
+                                         velocity.empty() ? nullptr : velocity.data(), s.data(), matrix ? matrix->data() : nullptr),
+              "nbody_batch_mutual_gravity");
+        return s;
+    }
     // per system {kinetic, potential, total} and {px, py, pz, mass}
     std::vector<System::Energy> energy(const float *dPositions, const float *dVelocities, float softening)
     {

@@ -9,7 +9,7 @@ from .initial_conditions import plummer, uniform_cube, pad_reference_style, padd
 from ._lib import NBodyError  # noqa: F401
 from .system import (NBodySystem, initialize, step, default_split_len, TIME_TICK, SOFTENING_VERSION3,  # noqa: F401
                      SOFTENING_VERSION1, BLOCK_SIZE, pair_once_split_len, morton_order)
-from .batch import BatchedSystem, EvolveResult, StopResult, MergeResult, FateResult, AccretionResult, PairResult, StructureResult, MemberResult, HierarchyResult, GravityResult, GRAVITY_RECORD_DTYPE, BatchGroups, SpanResult, NeighbourResult, CorrelationResult, CORRELATION_SYSTEM_DTYPE, ContactsResult, CONTACT_SYSTEM_DTYPE, CONTACT_BODY_DTYPE, CONTACT_DTYPE, ApproachesResult, APPROACH_SYSTEM_DTYPE, APPROACH_BODY_DTYPE, APPROACH_DTYPE, RadialProfileResult, RADIAL_SYSTEM_DTYPE, RADIAL_SHELL_DTYPE, RADIAL_BODY_DTYPE, SurfaceMapResult, SURFACE_SYSTEM_DTYPE, SURFACE_CELL_DTYPE, SURFACE_BODY_DTYPE, ShapeResult, SHAPE_SYSTEM_DTYPE, SHAPE_APERTURE_DTYPE, SHAPE_BODY_DTYPE, PairVelocityResult, PAIR_VELOCITIES_SYSTEM_DTYPE, PAIR_VELOCITIES_BIN_DTYPE, HIERARCHY_NODE_DTYPE, HIERARCHY_BODY_DTYPE, HIERARCHY_SYSTEM_DTYPE, BATCH_MAX_BODIES  # noqa: F401
+from .batch import BatchedSystem, EvolveResult, StopResult, MergeResult, FateResult, AccretionResult, PairResult, StructureResult, MemberResult, HierarchyResult, GravityResult, GRAVITY_RECORD_DTYPE, BatchGroups, SpanResult, NeighbourResult, CorrelationResult, CORRELATION_SYSTEM_DTYPE, ContactsResult, CONTACT_SYSTEM_DTYPE, CONTACT_BODY_DTYPE, CONTACT_DTYPE, ApproachesResult, APPROACH_SYSTEM_DTYPE, APPROACH_BODY_DTYPE, APPROACH_DTYPE, RadialProfileResult, RADIAL_SYSTEM_DTYPE, RADIAL_SHELL_DTYPE, RADIAL_BODY_DTYPE, SurfaceMapResult, SURFACE_SYSTEM_DTYPE, SURFACE_CELL_DTYPE, SURFACE_BODY_DTYPE, ShapeResult, SHAPE_SYSTEM_DTYPE, SHAPE_APERTURE_DTYPE, SHAPE_BODY_DTYPE, PairVelocityResult, PAIR_VELOCITIES_SYSTEM_DTYPE, PAIR_VELOCITIES_BIN_DTYPE, MutualGravityResult, MUTUAL_GRAVITY_SYSTEM_DTYPE, MUTUAL_GRAVITY_ENTRY_DTYPE, HIERARCHY_NODE_DTYPE, HIERARCHY_BODY_DTYPE, HIERARCHY_SYSTEM_DTYPE, BATCH_MAX_BODIES  # noqa: F401
 
 __all__ = ["NBodySystem", "initialize", "step", "default_split_len", "plummer", "uniform_cube",
            "pad_reference_style", "padded_count", "NBodyError", "TIME_TICK", "SOFTENING_VERSION3",
@@ -22,4 +22,5 @@ __all__ = ["NBodySystem", "initialize", "step", "default_split_len", "plummer", 
            "RadialProfileResult", "RADIAL_SYSTEM_DTYPE", "RADIAL_SHELL_DTYPE", "RADIAL_BODY_DTYPE",
            "SurfaceMapResult", "SURFACE_SYSTEM_DTYPE", "SURFACE_CELL_DTYPE", "SURFACE_BODY_DTYPE",
            "ShapeResult", "SHAPE_SYSTEM_DTYPE", "SHAPE_APERTURE_DTYPE", "SHAPE_BODY_DTYPE",
-           "PairVelocityResult", "PAIR_VELOCITIES_SYSTEM_DTYPE", "PAIR_VELOCITIES_BIN_DTYPE"]
+           "PairVelocityResult", "PAIR_VELOCITIES_SYSTEM_DTYPE", "PAIR_VELOCITIES_BIN_DTYPE",
+           "MutualGravityResult", "MUTUAL_GRAVITY_SYSTEM_DTYPE", "MUTUAL_GRAVITY_ENTRY_DTYPE"]

@@ -618,6 +618,29 @@ _PAIR_VELOCITIES_PROTOTYPES = {
 }
 
 
+BATCH_MUTUAL_GRAVITY_MAX_SETS = 8
+BATCH_MUTUAL_GRAVITY_NO_SET = 255
+
+
+class BatchMutualGravityEntry(ctypes.Structure):
+    """``nbody_batch_mutual_gravity_entry`` of include/nbody_batch_mutual_gravity.h."""
+    _fields_ = [("pairs", ctypes.c_longlong), ("potential", c_double), ("force", c_double * 3), ("torque", c_double * 3),
+                ("virial", c_double), ("power", c_double)]
+
+
+class BatchMutualGravitySystem(ctypes.Structure):
+    """``nbody_batch_mutual_gravity_system`` of include/nbody_batch_mutual_gravity.h."""
+    _fields_ = [("sets", c_int), ("selected", c_int), ("left_out", c_int), ("unmeasured", c_int), ("pairs", ctypes.c_longlong),
+                ("coincident", ctypes.c_longlong), ("members", c_int * 8), ("mass", c_double * 8)]
+
+
+#: the entry point of include/nbody_batch_mutual_gravity.h (mutual gravity of labelled sets of batched ensembles), which nbody.h includes
+_MUTUAL_GRAVITY_PROTOTYPES = {
+    "nbody_batch_mutual_gravity": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(ctypes.c_ubyte), c_float, POINTER(c_double),
+                                           POINTER(c_double), POINTER(BatchMutualGravitySystem), POINTER(BatchMutualGravityEntry)]),
+}
+
+
 class MultiConfig(ctypes.Structure):
     """``nbody_multi_config`` of include/nbody.h."""
     _fields_ = [("n_bodies", c_int64), ("split_len", c_int64), ("force_mode", c_int), ("integrator", c_int),
@@ -650,7 +673,7 @@ def load() -> ctypes.CDLL:
                 list(_NEIGHBOURS_PROTOTYPES.items()) + list(_CORRELATION_PROTOTYPES.items()) + \
                 list(_CONTACTS_PROTOTYPES.items()) + list(_APPROACHES_PROTOTYPES.items()) + list(_RADIAL_PROTOTYPES.items()) + \
                 list(_SURFACE_PROTOTYPES.items()) + list(_SHAPE_PROTOTYPES.items()) + \
-                list(_PAIR_VELOCITIES_PROTOTYPES.items()):
+                list(_PAIR_VELOCITIES_PROTOTYPES.items()) + list(_MUTUAL_GRAVITY_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -776,6 +799,11 @@ def shape_names():
 def pair_velocities_names():
     """The entry point of nbody_batch_pair_velocities.h."""
     return list(_PAIR_VELOCITIES_PROTOTYPES)
+
+
+def mutual_gravity_names():
+    """The entry point of nbody_batch_mutual_gravity.h."""
+    return list(_MUTUAL_GRAVITY_PROTOTYPES)
 
 
 def check(status: int, ctx=None) -> None:

@@ -153,6 +153,13 @@ PAIR_VELOCITIES_BIN_DTYPE = np.dtype([("count", np.int64), ("approaching", np.in
                                      [(name, np.float64) for name in ("weight", "r1", "r2", "rv", "vr1", "vr2", "vt2", "v1", "v2")])
 assert PAIR_VELOCITIES_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairVelocitiesSystem) == 56
 assert PAIR_VELOCITIES_BIN_DTYPE.itemsize == ctypes.sizeof(_lib.BatchPairVelocitiesBin) == 96
+#: the records of :meth:`BatchedSystem.mutual_gravity`: numpy's views of ``nbody_batch_mutual_gravity_system`` and ``_entry``
+MUTUAL_GRAVITY_SYSTEM_DTYPE = np.dtype([("sets", np.int32), ("selected", np.int32), ("left_out", np.int32), ("unmeasured", np.int32),
+                                        ("pairs", np.int64), ("coincident", np.int64), ("members", np.int32, 8), ("mass", np.float64, 8)])
+MUTUAL_GRAVITY_ENTRY_DTYPE = np.dtype([("pairs", np.int64), ("potential", np.float64), ("force", np.float64, 3), ("torque", np.float64, 3),
+                                       ("virial", np.float64), ("power", np.float64)])
+assert MUTUAL_GRAVITY_SYSTEM_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMutualGravitySystem) == 128
+assert MUTUAL_GRAVITY_ENTRY_DTYPE.itemsize == ctypes.sizeof(_lib.BatchMutualGravityEntry) == 80
 
 WEIGHTS = {"mass": _lib.BATCH_WEIGHT_MASS, "number": _lib.BATCH_WEIGHT_NUMBER}
 
@@ -1318,6 +1325,74 @@ class BatchedSystem:
             out.ctypes.data_as(ctypes.POINTER(_lib.BatchPairVelocitiesBin)) if bins else None), self._h)
         return PairVelocityResult(systems, out, e, weight)
 
+    def mutual_gravity(self, labels, sets=None, softening: float = 0.0, centre=None, velocity=None,
+                       matrix: bool = True) -> "MutualGravityResult":
+        """What the parts of every system do to each other (``include/nbody_batch_mutual_gravity.h`` states the rules): for
+        every ordered pair ``(a, b)`` of up to 8 disjoint sets of bodies the potential energy between them, the net force of
+        ``b`` on ``a``, its torque and Clausius virial about ``centre`` and the power it puts into ``a`` in the frame moving
+        with ``velocity``, as fp64 pair sums on the device from the current state in a pinned order (waits for the queued
+        work).  ``labels`` is ``(B, max_bodies)`` integers (numpy or torch): a value ``a`` in ``[0, sets)`` puts the body in set
+        ``a`` and any negative value leaves it out -- ``groups().label``, ``members().member`` or a mask as integers all do --
+        or a tuple of ``(B, max_bodies)`` boolean masks, mask ``a`` being set ``a`` (overlapping masks are refused).  ``sets``
+        (1 ... 8) defaults to ``max(label) + 1``.  ``centre`` and ``velocity`` are what :meth:`radial_profile` takes: ``None``
+        (zeros), ``(3,)``, ``(B, 3)``, for ``centre`` also a :class:`StructureResult` or ``"density"``.  ``softening`` follows
+        :meth:`energy`'s rule.  Only bodies below the count take part, whatever the massive counts; a labelled body with a NaN
+        or infinite word is taken out and counted in ``unmeasured``.  ``matrix=False`` skips the entries on their way to the
+        host: the per-system words are the same bits.  Changes nothing: an :meth:`evolve` after it is bit for bit the
+        :meth:`evolve` without it."""
+        B, n = self.num_systems, self.max_bodies
+        if isinstance(labels, (tuple, list)) and len(labels) and np.asarray(
+                labels[0].detach().cpu().numpy() if hasattr(labels[0], "detach") else labels[0]).dtype == np.bool_:
+            labels = MutualGravityResult.labels_from_masks(*labels)
+        if hasattr(labels, "detach"):  # a torch tensor
+            labels = labels.detach().cpu().numpy()
+        lab = np.asarray(labels)
+        if lab.dtype == np.bool_ or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"labels must be integers or a tuple of bool masks, not {lab.dtype}")
+        if lab.shape != (B, n):
+            raise ValueError(f"labels must have shape ({B}, {n}), got {tuple(lab.shape)}")
+        lab = lab.astype(np.int64)
+        top = int(lab.max()) if lab.size else -1
+        if sets is None:
+            sets = max(top + 1, 1)
+        sets = int(sets)
+        if not 1 <= sets <= _lib.BATCH_MUTUAL_GRAVITY_MAX_SETS:
+            raise ValueError(f"sets must be 1 ... {_lib.BATCH_MUTUAL_GRAVITY_MAX_SETS}, not {sets}")
+        if top >= sets:
+            s, i = np.argwhere(lab >= sets)[0]
+            raise ValueError(f"the label {lab[s, i]} of body {i} of system {s} must be below sets ({sets}) or negative")
+        wire = np.ascontiguousarray(np.where(lab < 0, _lib.BATCH_MUTUAL_GRAVITY_NO_SET, lab).astype(np.uint8))
+
+        def frame(name, value):
+            if value is None:
+                return None
+            if hasattr(value, "detach"):
+                value = value.detach().cpu().numpy()
+            v = np.asarray(value, dtype=np.float64)
+            if v.shape == (3,):
+                v = np.broadcast_to(v, (B, 3))
+            if v.shape != (B, 3):
+                raise ValueError(f"{name} must have shape (3,) or ({B}, 3), got {tuple(v.shape)}")
+            return np.ascontiguousarray(v)
+
+        if isinstance(centre, str):
+            if centre != "density":
+                raise ValueError(f"centre must be an array, a StructureResult or 'density', not {centre!r}")
+            centre = self.structure(bodies=False).centre
+        elif isinstance(centre, StructureResult):
+            centre = centre.centre
+        c, v0 = frame("centre", centre), frame("velocity", velocity)
+        systems = np.zeros(B, dtype=MUTUAL_GRAVITY_SYSTEM_DTYPE)
+        out = np.zeros((B, sets, sets), dtype=MUTUAL_GRAVITY_ENTRY_DTYPE) if matrix else None
+        dbl = ctypes.POINTER(ctypes.c_double)
+        self._use_current_stream()
+        _check(self._lib, self._lib.nbody_batch_mutual_gravity(
+            self._h, _ptr(self.positions), _ptr(self.velocities), sets, wire.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+            float(softening), c.ctypes.data_as(dbl) if c is not None else None, v0.ctypes.data_as(dbl) if v0 is not None else None,
+            systems.ctypes.data_as(ctypes.POINTER(_lib.BatchMutualGravitySystem)),
+            out.ctypes.data_as(ctypes.POINTER(_lib.BatchMutualGravityEntry)) if matrix else None), self._h)
+        return MutualGravityResult(systems, out, sets)
+
     def _source_mass(self) -> np.ndarray:
         """``(B,)`` float64: the mass of all sources of :meth:`members` -- :meth:`momentum`'s mass, and with massive counts the
         fp64 sum of the massive bodies' mass words alone."""
@@ -2415,6 +2490,126 @@ class PairVelocityResult:
                 f"below={self.below.tolist()}, above={self.above.tolist()}, unmeasured={self.unmeasured.tolist()})")
 
 
+class MutualGravityResult:
+    """What :meth:`BatchedSystem.mutual_gravity` summed.  ``entries`` is ``(B, K, K)`` of ``MUTUAL_GRAVITY_ENTRY_DTYPE``
+    (``None`` without ``matrix``), entry ``[s, a, b]`` what set ``b`` does to set ``a`` in system ``s``, and each of its words a
+    view of that name: ``pairs`` (int64), ``potential``, ``virial``, ``power`` (``(B, K, K)`` float64), ``force`` and
+    ``torque`` (``(B, K, K, 3)``).  Per system (``(B,)`` arrays): ``selected``, ``left_out``, ``unmeasured``, ``total_pairs``,
+    ``coincident``; ``members`` (``(B, K)`` int32) and ``mass`` (``(B, K)`` float64).  ``systems`` is the records themselves,
+    ``sets`` is ``K``.  The derived quantities are NaN where a set is empty."""
+
+    WORDS = ("pairs", "potential", "force", "torque", "virial", "power")
+
+    def __init__(self, systems, entries, sets):
+        self.systems, self.entries, self.sets = systems, entries, int(sets)
+        for name in ("selected", "left_out", "unmeasured", "coincident"):
+            setattr(self, name, np.ascontiguousarray(systems[name]))
+        self.total_pairs = np.ascontiguousarray(systems["pairs"])
+        self.members = np.ascontiguousarray(systems["members"][:, :self.sets])
+        self.mass = np.ascontiguousarray(systems["mass"][:, :self.sets])
+        for name in self.WORDS:
+            setattr(self, name, None if entries is None else entries[name])
+
+    def _need_matrix(self):
+        if self.entries is None:
+            raise ValueError("this needs the entries: call mutual_gravity(matrix=True)")
+
+    def _set(self, a):
+        if not 0 <= int(a) < self.sets:
+            raise ValueError(f"set must be 0 ... {self.sets - 1}, not {a}")
+        return int(a)
+
+    def _where_both(self, a, b, value):
+        full = (self.members[:, a] > 0) & (self.members[:, b] > 0)
+        return np.where(full.reshape(full.shape + (1,) * (value.ndim - 1)), value, np.nan)
+
+    def _others(self, a, word):
+        self._need_matrix()
+        a = self._set(a)
+        value = sum((word[:, a, b] for b in range(self.sets) if b != a), np.zeros_like(word[:, a, a]))
+        return np.where((self.members[:, a] > 0).reshape((-1,) + (1,) * (value.ndim - 1)), value, np.nan)
+
+    def interaction_energy(self, a, b) -> np.ndarray:
+        """``(B,)``: the potential energy between sets ``a`` and ``b != a``, ``potential[:, a, b]`` (``potential[:, b, a]`` is
+        the same sum in another order)."""
+        self._need_matrix()
+        a, b = self._set(a), self._set(b)
+        if a == b:
+            raise ValueError("interaction_energy is between two different sets: self_energy(a) is the energy of one")
+        return self._where_both(a, b, self.potential[:, a, b])
+
+    def self_energy(self, a) -> np.ndarray:
+        """``(B,)``: the potential energy of set ``a`` in its own field, ``potential[:, a, a] / 2`` (every unordered pair was
+        summed twice)."""
+        self._need_matrix()
+        a = self._set(a)
+        return self._where_both(a, a, self.potential[:, a, a] / 2.0)
+
+    def total_potential_energy(self) -> np.ndarray:
+        """``(B,)``: the potential energy of all selected bodies, the sum of all entries' ``potential`` halved; NaN where no
+        body is selected."""
+        self._need_matrix()
+        return np.where(self.selected > 0, self.potential.sum(axis=(1, 2)) / 2.0, np.nan)
+
+    def force_on(self, a) -> np.ndarray:
+        """``(B, 3)``: the net force of all other sets on set ``a``."""
+        return self._others(a, self.force)
+
+    def torque_on(self, a) -> np.ndarray:
+        """``(B, 3)``: the torque of all other sets on set ``a`` about the centre."""
+        return self._others(a, self.torque)
+
+    def power_into(self, a) -> np.ndarray:
+        """``(B,)``: the rate at which all other sets do work on set ``a`` in the frame of ``velocity``."""
+        return self._others(a, self.power)
+
+    def acceleration_of(self, a) -> np.ndarray:
+        """``(B, 3)``: the acceleration of the centre of mass of set ``a`` by all other sets, ``force_on(a) / mass[:, a]``;
+        NaN where the set's mass is 0."""
+        force = self.force_on(a)
+        m = self.mass[:, self._set(a)]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((m != 0)[:, None], force / np.where(m != 0, m, 1.0)[:, None], np.nan)
+
+    def two_body_energy(self, a, b, centres, velocities) -> np.ndarray:
+        """``(B,)``: the orbital energy of sets ``a`` and ``b`` as two point masses and nothing else:
+        ``mu |v_a - v_b|^2 / 2 - M_a M_b / |x_a - x_b|`` with ``mu = M_a M_b / (M_a + M_b)`` from ``mass``.  ``centres`` and
+        ``velocities`` are ``(B, K, 3)``: where each set is and how it moves, by the caller's choice (no softening enters).
+        It knows nothing of the sets' extent: compare it with :meth:`interaction_energy`, which sums over the bodies."""
+        a, b = self._set(a), self._set(b)
+        x, v = np.asarray(centres, np.float64), np.asarray(velocities, np.float64)
+        want = (self.mass.shape[0], self.sets, 3)
+        if x.shape != want or v.shape != want:
+            raise ValueError(f"centres and velocities must have shape {want}, got {tuple(x.shape)} and {tuple(v.shape)}")
+        ma, mb = self.mass[:, a], self.mass[:, b]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mu = ma * mb / (ma + mb)
+            r = np.sqrt(((x[:, a] - x[:, b]) ** 2).sum(axis=1))
+            w2 = ((v[:, a] - v[:, b]) ** 2).sum(axis=1)
+            return self._where_both(a, b, 0.5 * mu * w2 - ma * mb / r)
+
+    @staticmethod
+    def labels_from_masks(*masks) -> np.ndarray:
+        """``(B, max_bodies)`` int64 labels from boolean masks of that shape (numpy or torch): mask ``a`` is set ``a``, a
+        body in no mask is -1.  Overlapping masks are refused."""
+        if not masks:
+            raise ValueError("labels_from_masks needs at least one mask")
+        ms = [np.asarray(m.detach().cpu().numpy() if hasattr(m, "detach") else m) for m in masks]
+        for m in ms:
+            if m.dtype != np.bool_ or m.shape != ms[0].shape:
+                raise ValueError("the masks must be bool arrays of one shape")
+        if (np.sum([m.astype(np.int64) for m in ms], axis=0) > 1).any():
+            raise ValueError("the masks overlap: a body is in one set at most")
+        labels = np.full(ms[0].shape, -1, np.int64)
+        for a, m in enumerate(ms):
+            labels[m] = a
+        return labels
+
+    def __repr__(self):
+        return (f"MutualGravityResult(sets={self.sets}, members={self.members.tolist()}, pairs={self.total_pairs.tolist()}, "
+                f"coincident={self.coincident.tolist()}, unmeasured={self.unmeasured.tolist()})")
+
+
 class HierarchyResult:
     """What :meth:`BatchedSystem.hierarchy` found.  Per system (``(B,)`` int32 arrays): ``nodes`` (made), ``roots`` (live at the
     end, leaves only), ``levels`` (evaluated), ``singles``, ``binaries``, ``triples``, ``higher`` (roots with 1, 2, 3 and >= 4
@@ -2474,4 +2669,4 @@ class HierarchyResult:
                 f"levels={self.levels.tolist()}, converged={self.converged.tolist()})")
 
 
-__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "ApproachesResult", "APPROACH_SYSTEM_DTYPE", "APPROACH_BODY_DTYPE", "APPROACH_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step", "PairVelocityResult", "PAIR_VELOCITIES_SYSTEM_DTYPE", "PAIR_VELOCITIES_BIN_DTYPE"]
+__all__ = ["BatchedSystem", "EvolveResult", "StopResult", "MergeResult", "FateResult", "AccretionResult", "PairResult", "StructureResult", "MemberResult", "HierarchyResult", "GravityResult", "GRAVITY_RECORD_DTYPE", "BatchGroups", "GROUP_BODY_DTYPE", "GROUP_RECORD_DTYPE", "GROUP_SYSTEM_DTYPE", "SpanResult", "SPAN_SYSTEM_DTYPE", "SPAN_EDGE_DTYPE", "SPAN_BODY_DTYPE", "NeighbourResult", "NEIGHBOUR_SYSTEM_DTYPE", "NEIGHBOUR_BODY_DTYPE", "CorrelationResult", "CORRELATION_SYSTEM_DTYPE", "ContactsResult", "CONTACT_SYSTEM_DTYPE", "CONTACT_BODY_DTYPE", "CONTACT_DTYPE", "ApproachesResult", "APPROACH_SYSTEM_DTYPE", "APPROACH_BODY_DTYPE", "APPROACH_DTYPE", "WEIGHTS", "MERGE_EVENT_DTYPE", "PAIR_RECORD_DTYPE", "STRUCTURE_BODY_DTYPE", "STRUCTURE_SYSTEM_DTYPE", "MEMBER_BODY_DTYPE", "MEMBER_SYSTEM_DTYPE", "HIERARCHY_NODE_DTYPE", "HIERARCHY_BODY_DTYPE", "HIERARCHY_SYSTEM_DTYPE", "BATCH_MAX_BODIES", "INTEGRATORS", "FIELD_KINDS", "interactions_per_step", "PairVelocityResult", "PAIR_VELOCITIES_SYSTEM_DTYPE", "PAIR_VELOCITIES_BIN_DTYPE", "MutualGravityResult", "MUTUAL_GRAVITY_SYSTEM_DTYPE", "MUTUAL_GRAVITY_ENTRY_DTYPE"]

@@ -28,6 +28,7 @@ HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_
            os.path.join(CSRC, "nbody_batch_contacts_math.h"), os.path.join(CSRC, "nbody_batch_approaches_math.h"),
            os.path.join(CSRC, "nbody_batch_radial_math.h"), os.path.join(CSRC, "nbody_batch_surface_math.h"),
            os.path.join(CSRC, "nbody_batch_shape_math.h"), os.path.join(CSRC, "nbody_batch_pair_velocities_math.h"),
+           os.path.join(CSRC, "nbody_batch_mutual_gravity_math.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_evolve.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_stop.h"),
@@ -51,7 +52,8 @@ HEADERS = [os.path.join(CSRC, "nbody_kernels.h"), os.path.join(CSRC, "nbody_sym_
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_radial.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_surface.h"),
            os.path.join(PKG_DIR, "..", "include", "nbody_batch_shape.h"),
-           os.path.join(PKG_DIR, "..", "include", "nbody_batch_pair_velocities.h")]
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_pair_velocities.h"),
+           os.path.join(PKG_DIR, "..", "include", "nbody_batch_mutual_gravity.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result"]

@@ -1,6 +1,6 @@
 // nbody_batch_analysis.hip -- what a batched ensemble (nbody_batch.hip) can be asked about a state: bound pairs, cluster
 // structure, bound members, gravity at points, hierarchies, groups, spanning trees, neighbours, pair-separation counts, contact
-// lists, approach lists, radial profiles, surface maps, shapes, pair velocity statistics, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_surface.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
+// lists, approach lists, radial profiles, surface maps, shapes, pair velocity statistics, mutual gravity of labelled sets, energy and momentum (include/nbody.h, nbody_batch_pairs.h ... nbody_batch_surface.h).  Every kernel here is a sibling of the force kernels -- one workgroup per system,
 // the columns broadcast from LDS, rows in registers -- that reads the caller's state and writes only records of its own: no
 // integrator reads what these calls keep (BatchAnalysis below), and no call here touches a cache, a level or a report of the
 // integrators.  The arithmetic of each kernel is in its HIP-free header (nbody_batch_*_math.h, nbody_batch_pairs_elements.h).
@@ -12,6 +12,7 @@
 #include "nbody_batch_handle.h"
 #include "nbody_batch_hierarchy_math.h"
 #include "nbody_batch_members_math.h"
+#include "nbody_batch_mutual_gravity_math.h"
 #include "nbody_batch_neighbours_math.h"
 #include "nbody_batch_pair_velocities_math.h"
 #include "nbody_batch_pairs_elements.h"
@@ -3214,6 +3215,224 @@ hipError_t launch_batch_pair_velocities(const float4 *pos, const float4 *vel, co
                                   sources, edges2, edge_stride, max_bodies, bins, weight, bins_out, systems);
 }
 
+// ---- mutual gravity (include/nbody_batch_mutual_gravity.h): per system and ordered pair (a, b) of labelled sets, what set b
+// does to set a -- potential, force, torque, virial and power as fp64 sums in the header's pinned order.  A sibling of
+// batch_pair_velocities_kernel at a fraction of its registers: one workgroup per system sorts the bodies by set into LDS, so
+// that the sources of a set are a contiguous range in ascending body index and a block of 64 rows holds rows of one set; a wave
+// takes a row block and walks every set's range as a broadcast column loop.  It reads the state and writes only the handle's
+// records.
+
+static_assert(sizeof(BatchMutualGravityEntry) == sizeof(nbody_batch_mutual_gravity_entry) && sizeof(nbody_batch_mutual_gravity_entry) == 80 &&
+                  offsetof(BatchMutualGravityEntry, pairs) == offsetof(nbody_batch_mutual_gravity_entry, pairs) &&
+                  offsetof(BatchMutualGravityEntry, potential) == offsetof(nbody_batch_mutual_gravity_entry, potential) &&
+                  offsetof(BatchMutualGravityEntry, force) == offsetof(nbody_batch_mutual_gravity_entry, force) &&
+                  offsetof(BatchMutualGravityEntry, torque) == offsetof(nbody_batch_mutual_gravity_entry, torque) &&
+                  offsetof(BatchMutualGravityEntry, virial) == offsetof(nbody_batch_mutual_gravity_entry, virial) &&
+                  offsetof(BatchMutualGravityEntry, power) == offsetof(nbody_batch_mutual_gravity_entry, power) &&
+                  offsetof(nbody_batch_mutual_gravity_entry, potential) == 8 && offsetof(nbody_batch_mutual_gravity_entry, force) == 16 &&
+                  offsetof(nbody_batch_mutual_gravity_entry, torque) == 40 && offsetof(nbody_batch_mutual_gravity_entry, virial) == 64 &&
+                  offsetof(nbody_batch_mutual_gravity_entry, power) == 72,
+              "nbody_batch_mutual_gravity_math.h mirrors the entry of nbody_batch_mutual_gravity.h");
+static_assert(sizeof(BatchMutualGravitySystem) == sizeof(nbody_batch_mutual_gravity_system) && sizeof(nbody_batch_mutual_gravity_system) == 128 &&
+                  offsetof(BatchMutualGravitySystem, sets) == offsetof(nbody_batch_mutual_gravity_system, sets) &&
+                  offsetof(BatchMutualGravitySystem, selected) == offsetof(nbody_batch_mutual_gravity_system, selected) &&
+                  offsetof(BatchMutualGravitySystem, left_out) == offsetof(nbody_batch_mutual_gravity_system, left_out) &&
+                  offsetof(BatchMutualGravitySystem, unmeasured) == offsetof(nbody_batch_mutual_gravity_system, unmeasured) &&
+                  offsetof(BatchMutualGravitySystem, pairs) == offsetof(nbody_batch_mutual_gravity_system, pairs) &&
+                  offsetof(BatchMutualGravitySystem, coincident) == offsetof(nbody_batch_mutual_gravity_system, coincident) &&
+                  offsetof(BatchMutualGravitySystem, members) == offsetof(nbody_batch_mutual_gravity_system, members) &&
+                  offsetof(BatchMutualGravitySystem, mass) == offsetof(nbody_batch_mutual_gravity_system, mass) &&
+                  offsetof(nbody_batch_mutual_gravity_system, pairs) == 16 && offsetof(nbody_batch_mutual_gravity_system, coincident) == 24 &&
+                  offsetof(nbody_batch_mutual_gravity_system, members) == 32 && offsetof(nbody_batch_mutual_gravity_system, mass) == 64,
+              "nbody_batch_mutual_gravity_math.h mirrors the system record of nbody_batch_mutual_gravity.h");
+static_assert(kMutualGravityMaxSets == NBODY_BATCH_MUTUAL_GRAVITY_MAX_SETS && kMutualGravityNoSet == NBODY_BATCH_MUTUAL_GRAVITY_NO_SET,
+              "nbody_batch_mutual_gravity_math.h mirrors the limits of nbody_batch_mutual_gravity.h");
+static_assert(sizeof(MutualGravityColumn) == sizeof(float4), "a column is one 16-byte read");
+
+// The workgroup: batch_shape's, held to NBODY_BATCH_MUTUAL_GRAVITY_MAX_THREADS lanes.  A lane holds one row, four accumulators
+// and nine addends, so every shape up to 1024 lanes fits its registers (DESIGN.md 3.6 has the compiler's figures); the units of
+// work -- the row blocks of all sets -- go round the waves, so fewer waves cost no pass.
+#ifndef NBODY_BATCH_MUTUAL_GRAVITY_MAX_THREADS
+#define NBODY_BATCH_MUTUAL_GRAVITY_MAX_THREADS 1024
+#endif
+constexpr int kMutualGravityMaxThreads = NBODY_BATCH_MUTUAL_GRAVITY_MAX_THREADS;
+inline int mutual_gravity_threads(int threads) { return threads < kMutualGravityMaxThreads ? threads : kMutualGravityMaxThreads; }
+
+// The set of body i of the system (i below the count): its label, unless one of its seven words is not finite.  p and v take
+// the body's words.
+__device__ inline int mutual_gravity_body(const float4 *pos, const float4 *vel, const unsigned char *labels, size_t at, int sets, float4 &p,
+                                          float4 &v, bool &labelled)
+{
+    p = pos[at];
+    v = vel[at];
+    const int label = labels[at];
+    labelled = mutual_gravity_labelled(label, sets);
+    return mutual_gravity_set(label, sets, mutual_gravity_measured(p.x, p.y, p.z, p.w, v.x, v.y, v.z));
+}
+
+// LDS: cols[slot] = {x, y, z, m} of the body sorted into `slot`, one broadcast ds_read_b128 per column, 64 KiB at 4096 bodies;
+// behind it the partials of every unit, sets x 9 doubles each (41 KiB at 4096 bodies in 8 sets), and order[slot], the body of
+// the slot, through which a row finds its velocity (16 KiB).  The sort: chunk c is bodies 64 c ... 64 c + 63, one wave at a
+// time; the ballot of "my set is a" gives the chunk's count and every lane's rank, a lane per set walks the prefix over the
+// chunks, and a second walk over the chunks places the bodies.  Unlabelled and unmeasured bodies get no slot.  Then unit u --
+// block u - unit_start[a] of set a -- goes to wave u mod waves: lane l holds rank 64 k + l of the set, walks the range of every
+// set b with four accumulators, forms the nine addends and six shuffles per sum make the block's partial; after the barrier
+// lane (a, b, k) adds the partials of set a's blocks in ascending order.  The order of the header is that of body indices, so
+// neither the workgroup's shape nor which wave took which unit shows in a record.
+// frames holds {centre, velocity} of every system, six doubles.
+__global__ __launch_bounds__(kMutualGravityMaxThreads) void batch_mutual_gravity_kernel(
+    const float4 *__restrict__ pos, const float4 *__restrict__ vel, const int *__restrict__ counts, const unsigned char *__restrict__ labels,
+    const double *__restrict__ frames, int max_bodies, int sets, double e2, BatchMutualGravityEntry *__restrict__ entries,
+    BatchMutualGravitySystem *__restrict__ systems)
+{
+    extern __shared__ float4 sorted[];
+    __shared__ int chunk_count[kMutualGravityMaxChunks * kMutualGravityMaxSets], chunk_offset[kMutualGravityMaxChunks * kMutualGravityMaxSets];
+    __shared__ int members[kMutualGravityMaxSets], start[kMutualGravityMaxSets + 1], unit_start[kMutualGravityMaxSets + 1];
+    __shared__ int tally[3];  // selected, left out, unmeasured
+    __shared__ unsigned int coincident_total;
+    MutualGravityColumn *cols = reinterpret_cast<MutualGravityColumn *>(sorted);
+    double *partials = reinterpret_cast<double *>(sorted + max_bodies);  // [unit][sets][9]
+    int *order = reinterpret_cast<int *>(partials + (size_t)mutual_gravity_max_units(max_bodies, sets) * sets * kMutualGravityTerms);
+    const int n = counts[blockIdx.x] < max_bodies ? counts[blockIdx.x] : max_bodies;
+    const int tid = threadIdx.x, T = blockDim.x, lane = tid & (kMutualGravityBlock - 1), wave = tid / kMutualGravityBlock;
+    const int waves = T / kMutualGravityBlock, chunks = mutual_gravity_chunks(n);
+    const size_t base = (size_t)blockIdx.x * (size_t)max_bodies;
+    if (tid < 3)
+        tally[tid] = 0;
+    if (tid == 0)
+        coincident_total = 0;
+    __syncthreads();
+    // The counts of every chunk and set, and who is selected, left out and unmeasured.
+    for (int c = wave; c < chunks; c += waves) {  // the same for every lane of the wave
+        const int i = c * kMutualGravityBlock + lane;
+        const bool below = i < n;
+        bool labelled = false;
+        int set = -1;
+        if (below) {
+            float4 p, v;
+            set = mutual_gravity_body(pos, vel, labels, base + i, sets, p, v, labelled);
+        }
+        const int selected = mutual_gravity_chunk_count(__builtin_amdgcn_ballot_w64(set >= 0));
+        const int left_out = mutual_gravity_chunk_count(__builtin_amdgcn_ballot_w64(below && !labelled));
+        const int unmeasured = mutual_gravity_chunk_count(__builtin_amdgcn_ballot_w64(labelled && set < 0));
+        for (int a = 0; a < sets; ++a) {
+            const int count = mutual_gravity_chunk_count(__builtin_amdgcn_ballot_w64(set == a));
+            if (lane == 0)
+                chunk_count[c * kMutualGravityMaxSets + a] = count;
+        }
+        if (lane == 0) {  // integers: the order of the additions does not matter
+            atomicAdd(&tally[0], selected);
+            atomicAdd(&tally[1], left_out);
+            atomicAdd(&tally[2], unmeasured);
+        }
+    }
+    __syncthreads();
+    if (tid < sets)
+        members[tid] = mutual_gravity_prefix(chunk_count, chunks, tid, chunk_offset);
+    __syncthreads();
+    if (tid == 0)
+        mutual_gravity_starts(members, sets, start, unit_start);
+    __syncthreads();
+    // The bodies into their slots.
+    for (int c = wave; c < chunks; c += waves) {
+        const int i = c * kMutualGravityBlock + lane;
+        bool labelled = false;
+        int set = -1;
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+        if (i < n)
+            set = mutual_gravity_body(pos, vel, labels, base + i, sets, p, v, labelled);
+        for (int a = 0; a < sets; ++a) {
+            const unsigned long long mask = __builtin_amdgcn_ballot_w64(set == a);
+            if (set == a) {
+                const int slot = mutual_gravity_slot(start, chunk_offset, c, a, mutual_gravity_chunk_rank(mask, lane));
+                sorted[slot] = p;
+                order[slot] = i;
+            }
+        }
+    }
+    __syncthreads();  // the image is in place
+    const double *frame = frames + (size_t)blockIdx.x * 6;
+    const double centre[3] = {frame[0], frame[1], frame[2]}, velocity[3] = {frame[3], frame[4], frame[5]};
+    const int units = unit_start[sets];
+    unsigned int coincident = 0;
+    for (int u = wave; u < units; u += waves) {  // the same for every lane of the wave
+        const int a = mutual_gravity_unit_set(unit_start, u);
+        const int rank = (u - unit_start[a]) * kMutualGravityBlock + lane, slot = start[a] + rank;
+        const bool present = rank < members[a];
+        MutualGravityRow row = mutual_gravity_row(0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f);
+        if (present) {
+            const float4 p = sorted[slot], v = vel[base + order[slot]];
+            row = mutual_gravity_row(p.x, p.y, p.z, p.w, v.x, v.y, v.z);
+        }
+        for (int b = 0; b < sets; ++b) {
+            MutualGravitySums sums;
+            mutual_gravity_clear(sums);
+            const int last = start[b + 1];
+#pragma unroll 1
+            for (int j = start[b]; j < last; ++j)  // wave-uniform addresses: broadcast LDS reads
+                mutual_gravity_step(sums, coincident, present && j != slot, row, cols[j], e2);
+            double w[kMutualGravityTerms];
+            mutual_gravity_addends(present, row, sums, centre, velocity, w);
+            // The block's partial of every sum: the halving tree over the 64 addends, the result in lane 0.
+#pragma unroll
+            for (int k = 0; k < kMutualGravityTerms; ++k)
+                for (int off = kMutualGravityBlock / 2; off > 0; off >>= 1)
+                    w[k] = pair_velocities_tree_step(w[k], __shfl_down(w[k], off, kMutualGravityBlock));
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < kMutualGravityTerms; ++k)
+                    partials[((size_t)u * sets + b) * kMutualGravityTerms + k] = w[k];
+            }
+        }
+    }
+    coincident = pair_velocities_wave_total(coincident);
+    if (lane == 0 && coincident)
+        atomicAdd(&coincident_total, coincident);
+    __syncthreads();  // every partial is in
+    BatchMutualGravityEntry *out = entries + (size_t)blockIdx.x * (size_t)(sets * sets);
+    for (int word = tid; word < sets * sets * kMutualGravityTerms; word += T) {
+        const int k = word % kMutualGravityTerms, b = word / kMutualGravityTerms % sets, a = word / (kMutualGravityTerms * sets);
+        mutual_gravity_store(out + a * sets + b, k,
+                             mutual_gravity_total(partials, unit_start[a], unit_start[a + 1] - unit_start[a], sets, b, k));
+    }
+    for (int e = tid; e < sets * sets; e += T)
+        out[e].pairs = mutual_gravity_pairs(members[e / sets], members[e % sets], e / sets == e % sets);
+    if (tid < kMutualGravityMaxSets) {
+        systems[blockIdx.x].members[tid] = tid < sets ? members[tid] : 0;
+        systems[blockIdx.x].mass[tid] = tid < sets ? mutual_gravity_mass(cols, start[tid], start[tid + 1]) : 0.0;
+    }
+    if (tid == 0) {
+        long long pairs = 0;
+        for (int e = 0; e < sets * sets; ++e)
+            pairs += mutual_gravity_pairs(members[e / sets], members[e % sets], e / sets == e % sets);
+        systems[blockIdx.x].sets = sets;
+        systems[blockIdx.x].selected = tally[0];
+        systems[blockIdx.x].left_out = tally[1];
+        systems[blockIdx.x].unmeasured = tally[2];
+        systems[blockIdx.x].pairs = pairs;
+        systems[blockIdx.x].coincident = (long long)coincident_total;
+    }
+}
+
+// The dynamic LDS of one launch: the sorted columns, the partials of every unit, the body of every slot.
+inline size_t mutual_gravity_lds_bytes(int max_bodies, int sets)
+{
+    return sizeof(float4) * (size_t)max_bodies + sizeof(double) * (size_t)mutual_gravity_max_units(max_bodies, sets) * (size_t)(sets * kMutualGravityTerms) +
+           sizeof(int) * (size_t)max_bodies;
+}
+
+// One launch over all systems.
+hipError_t launch_batch_mutual_gravity(const float4 *pos, const float4 *vel, const int *counts, const unsigned char *labels,
+                                       const double *frames, int n_systems, int max_bodies, int sets, double e2,
+                                       BatchMutualGravityEntry *entries, BatchMutualGravitySystem *systems, hipStream_t stream)
+{
+    if (max_bodies > kMutualGravityMaxChunks * kMutualGravityBlock)
+        return hipErrorInvalidValue;  // the chunk counts are laid out for 4096 bodies
+    const int threads = mutual_gravity_threads(batch_shape(max_bodies).threads);
+    return launch_analysis_kernel(batch_mutual_gravity_kernel, n_systems, threads, mutual_gravity_lds_bytes(max_bodies, sets), stream, pos, vel,
+                                  counts, labels, frames, max_bodies, sets, e2, entries, systems);
+}
+
 // ---- diagnostics: per system {kinetic, potential, px, py, pz, mass} (fp32 pair terms, fp64 sums), nbody_energy's and
 // nbody_momentum's definitions.  Not the hot path: one workgroup per system, one row per thread at a time.
 constexpr int kDiagThreads = 256;  // kDiagValues: nbody_batch_handle.h, whose handle holds the results
@@ -3370,6 +3589,11 @@ struct BatchAnalysis {
     DeviceArray<unsigned char> pair_velocities_sources;              // [n_systems][max_bodies], the device copy of `sources`
     DeviceArray<float> pair_velocities_edges2;                       // one set or [n_systems] sets of padded squared edges
     std::vector<float> pair_velocities_edges2_host;                  // the last call's: the copy's source until the stream is idle
+    DeviceArray<BatchMutualGravitySystem> mutual_gravity_systems;  // [n_systems]
+    DeviceArray<BatchMutualGravityEntry> mutual_gravity_entries;   // [n_systems][sets][sets] of the largest call so far
+    DeviceArray<unsigned char> mutual_gravity_labels;              // [n_systems][max_bodies], the device copy of `labels`
+    DeviceArray<double> mutual_gravity_frames;                     // [n_systems][6]: centre, velocity
+    std::vector<double> mutual_gravity_frames_host;                // the last call's: the copy's source until the stream is idle
 };
 
 // Every member frees itself, in one walk that no new array can be left out of.
@@ -4152,6 +4376,57 @@ int nbody_batch_pair_velocities(nbody_batch *b, const float *d_pos, const float 
                                               bins_out ? a->pair_velocities_bins.ptr : nullptr, a->pair_velocities_systems.ptr, b->stream));
     BATCH_TRY(b, copy_out(b, systems_out, a->pair_velocities_systems, B));
     BATCH_TRY(b, copy_out(b, bins_out, a->pair_velocities_bins, records));
+    BATCH_TRY(b, hipStreamSynchronize(b->stream));
+    return NBODY_OK;
+}
+
+int nbody_batch_mutual_gravity(nbody_batch *b, const float *d_pos, const float *d_vel, int sets, const unsigned char *labels, float softening,
+                               const double *centre, const double *velocity, nbody_batch_mutual_gravity_system *systems_out,
+                               nbody_batch_mutual_gravity_entry *matrix_out)
+{
+    if (!b)
+        return bfail(nullptr, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: batch is NULL");
+    if (!d_pos || !d_vel || !labels || !systems_out)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: NULL argument");
+    if (sets < 1 || sets > NBODY_BATCH_MUTUAL_GRAVITY_MAX_SETS)
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: sets must be 1 ... 8");
+    if (!batch_softening_ok(softening))
+        return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: softening must be finite, 0 or >= NBODY_MIN_SOFTENING (1e-9)");
+    const size_t B = (size_t)b->n_systems, n = (size_t)b->max_bodies, slots = B * n;
+    for (size_t k = 0; k < slots; ++k)
+        if (!mutual_gravity_label_valid(labels[k], sets))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: the label " + std::to_string((int)labels[k]) + " of body " +
+                                                   std::to_string(k % n) + " of system " + std::to_string(k / n) + " must be below sets (" +
+                                                   std::to_string(sets) + ") or 255");
+    for (size_t k = 0; k < 3 * B; ++k) {
+        if (centre && !radial_finite(centre[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: the centre of system " + std::to_string(k / 3) + " must be finite");
+        if (velocity && !radial_finite(velocity[k]))
+            return bfail(b, NBODY_ERR_INVALID, "nbody_batch_mutual_gravity: the velocity of system " + std::to_string(k / 3) + " must be finite");
+    }
+    BatchAnalysis *a = nullptr;
+    BATCH_TRY(b, batch_analysis(b, a));
+    a->mutual_gravity_frames_host.resize(B * 6);
+    for (size_t s = 0; s < B; ++s)
+        for (size_t c = 0; c < 3; ++c) {
+            a->mutual_gravity_frames_host[s * 6 + c] = centre ? centre[3 * s + c] : 0.0;
+            a->mutual_gravity_frames_host[s * 6 + 3 + c] = velocity ? velocity[3 * s + c] : 0.0;
+        }
+    const size_t records = B * (size_t)(sets * sets);
+    BATCH_TRY(b, hipSetDevice(b->device));
+    BATCH_TRY(b, a->mutual_gravity_systems.ensure(B));
+    BATCH_TRY(b, a->mutual_gravity_entries.ensure(records));
+    BATCH_TRY(b, a->mutual_gravity_labels.ensure(slots));
+    BATCH_TRY(b, a->mutual_gravity_frames.ensure(B * 6));
+    BATCH_TRY(b, hipMemcpyAsync(a->mutual_gravity_labels.ptr, labels, slots, hipMemcpyHostToDevice, b->stream));
+    BATCH_TRY(b, hipMemcpyAsync(a->mutual_gravity_frames.ptr, a->mutual_gravity_frames_host.data(), sizeof(double) * B * 6, hipMemcpyHostToDevice,
+                                b->stream));
+    BATCH_TRY(b, launch_batch_mutual_gravity(reinterpret_cast<const float4 *>(d_pos), reinterpret_cast<const float4 *>(d_vel), b->counts_dev.ptr,
+                                             a->mutual_gravity_labels.ptr, a->mutual_gravity_frames.ptr, (int)b->n_systems, (int)b->max_bodies,
+                                             sets, mutual_gravity_e2(softening), a->mutual_gravity_entries.ptr, a->mutual_gravity_systems.ptr,
+                                             b->stream));
+    BATCH_TRY(b, copy_out(b, systems_out, a->mutual_gravity_systems, B));
+    BATCH_TRY(b, copy_out(b, matrix_out, a->mutual_gravity_entries, matrix_out ? records : 0));
     BATCH_TRY(b, hipStreamSynchronize(b->stream));
     return NBODY_OK;
 }

@@ -170,7 +170,15 @@ lean call (bins=False), the call with the bin records, correlation() at the same
 replaces -- positions.cpu() plus velocities.cpu(), measured on the whole batch, plus a numpy walk of all ordered pairs
 (numpy.histogram with weights per sum), measured once on the first --subset systems and extrapolated to B, which the line says:
 all synchronous calls, wall clock, alternated after a warm-up of every device call, medians and spreads.  The counts are asserted to be
-correlation()'s, and on the timed systems the sums to be numpy's to 1e-9 of their absolute addends, before a line is printed."""
+correlation()'s, and on the timed systems the sums to be numpy's to 1e-9 of their absolute addends, before a line is printed.
+
+--mutual-gravity: instead, the mutual gravity of labelled sets (BatchedSystem.mutual_gravity).  For n x B = 1024 x 1024, 4096 x 256
+and 256 x 4096 (or --cases), one line per case and number of sets (K = 2 and 8, body i in set i mod K, softening --eps) on Plummer
+spheres: the call with the matrix and without it (matrix=False), pair_velocities() at 8 bins on the same state in the same run, and
+what the call replaces -- positions.cpu() plus velocities.cpu(), measured on the whole batch, plus a numpy walk of all ordered
+pairs resolved by set, measured once on the first --subset systems and extrapolated to B, which the line says: all synchronous
+calls, wall clock, alternated after a warm-up of every device call, medians and spreads.  On the timed systems every word is
+asserted to be numpy's to 1e-9 of the potential's size before a line is printed."""
 import argparse
 import json
 import os
@@ -238,6 +246,8 @@ ap.add_argument("--shape", action="store_true", help="shape() at four apertures,
                 "records, against the download plus the iteration in numpy (timed on --subset systems) and radial_profile(), wall clock")
 ap.add_argument("--pair-velocities", action="store_true", help="pair_velocities() at 8 and 32 bins, lean and with the bin records, "
                 "against correlation() at the same bins and the download plus a numpy pair walk (timed on --subset systems), wall clock")
+ap.add_argument("--mutual-gravity", action="store_true", help="mutual_gravity() at 2 and 8 sets, with and without the matrix, against "
+                "pair_velocities() at 8 bins and the download plus a numpy pair walk by set (timed on --subset systems), wall clock")
 args = ap.parse_args()
 
 
@@ -1615,6 +1625,100 @@ def pair_velocities_lines():
                 print(json.dumps(line), flush=True)
 
 
+def host_mutual_walk(p, v, labels, sets, eps):
+    """What mutual_gravity() replaces, for one system: all ordered pairs in numpy, summed by the sets of row and source."""
+    x, u, m = p[:, :3].astype(np.float64), v[:, :3].astype(np.float64), p[:, 3].astype(np.float64)
+    d = x[None, :, :] - x[:, None, :]
+    s2 = (d * d).sum(-1) + eps * eps
+    np.fill_diagonal(s2, np.inf)
+    inv = 1.0 / np.sqrt(s2)
+    phi = m[None, :] * inv
+    acc = (phi * inv * inv)[:, :, None] * d
+    out = np.zeros((sets, sets, 9))
+    for b in range(sets):
+        source = labels == b
+        P, f = phi[:, source].sum(1), m[:, None] * acc[:, source].sum(1)
+        words = np.concatenate([(-m * P)[:, None], f, np.cross(x, f), (x * f).sum(1)[:, None], (u * f).sum(1)[:, None]], axis=1)
+        for a in range(sets):
+            out[a, b] = words[labels == a].sum(0)
+    return out
+
+
+def mutual_gravity_lines():
+    import time
+    import zlib
+    cases = args.cases if args.cases != [f"{n}x{b}" for n, b in CASES] else ["1024x1024", "4096x256", "256x4096"]
+    for case in cases:
+        n, B = (int(x) for x in case.lower().split("x"))
+        P, V = ensemble(n, B)
+        few = min(args.subset, B)
+        edges = np.geomspace(0.05, 10.0, 9).astype(np.float32)
+        with nb.BatchedSystem(B, n) as batch:
+            batch.set_state(P, V)
+
+            def wall(fn):
+                batch.sync()
+                t0 = time.perf_counter()
+                out = fn()
+                return (time.perf_counter() - t0) * 1e3, out
+
+            for sets in (2, 8):
+                labels = np.tile(np.arange(n) % sets, (B, 1))
+
+                def download():
+                    return batch.positions.cpu().numpy(), batch.velocities.cpu().numpy()
+
+                def host_walk():
+                    """The host's part of what the call replaces, on the first `few` systems only."""
+                    return [host_mutual_walk(P[s], V[s], labels[s], sets, args.eps) for s in range(few)]
+
+                calls = {"matrix": lambda: batch.mutual_gravity(labels, sets=sets, softening=args.eps),
+                         "lean": lambda: batch.mutual_gravity(labels, sets=sets, softening=args.eps, matrix=False),
+                         "pair_velocities8": lambda: batch.pair_velocities(edges),
+                         "download": download,
+                         "host_walk_subset": host_walk}
+                for name, fn in calls.items():                      # the first calls allocate the records and set the kernels' LDS limits
+                    if name != "host_walk_subset":
+                        wall(fn)
+                times = {name: [] for name in calls}
+                found = {}
+                for round_ in range(args.repeats):                  # alternated; the numpy walk, seconds long and on no GPU, once
+                    for name, fn in calls.items():
+                        if name == "host_walk_subset" and round_ > 0:
+                            continue
+                        t, out = wall(fn)
+                        times[name].append(t)
+                        found[name] = out
+                med = {name: statistics.median(ts) for name, ts in times.items()}
+                res, host = found["matrix"], found["host_walk_subset"]
+                assert found["lean"].systems.tobytes() == res.systems.tobytes()
+                assert (res.selected == n).all() and int(res.total_pairs[0]) == n * (n - 1)
+                for s in range(few):                                # the same sums in another order
+                    got = np.concatenate([res.potential[s][..., None], res.force[s], res.torque[s], res.virial[s][..., None],
+                                          res.power[s][..., None]], axis=-1)
+                    scale = np.abs(host[s][:, :, :1]) * (1.0 + np.abs(P[s, :, :3]).max() + np.abs(V[s, :, :3]).max()) / args.eps
+                    assert (np.abs(got - host[s]) <= 1e-9 * scale).all(), s
+                replaced = med["download"] + med["host_walk_subset"] * B / few
+                pairs = float(res.total_pairs.sum())
+                line = {"n": n, "B": B, "sets": sets, "softening": args.eps, "library": os.environ.get("NBODY_AMD_LIBRARY", "in-tree"),
+                        "repeats": args.repeats, "pairs": int(pairs), "pairs_per_ns_matrix": round(pairs / (med["matrix"] * 1e6), 3),
+                        "matrix_megabytes": round(B * sets * sets * 80 / 1e6, 3), "download_megabytes": round(2 * B * n * 16 / 1e6, 2),
+                        "matrix_crc32": zlib.crc32(res.entries.tobytes()), "host_systems_timed": few,
+                        "host_walk_ms_per_system": round(med["host_walk_subset"] / few, 3),
+                        "replaced_ms_extrapolated_to_B": round(replaced, 2)}
+                for name in calls:
+                    line[name + "_ms"] = round(med[name], 3)
+                for name in ("matrix", "lean"):
+                    line[name + "_over_pair_velocities8"] = round(med[name] / med["pair_velocities8"], 3)
+                    line[name + "_over_replaced"] = round(med[name] / replaced, 6)
+                for name in calls:
+                    line[name + "_spread"] = round((max(times[name]) - min(times[name])) / med[name], 4)
+                print(json.dumps(line), flush=True)
+
+
+if args.mutual_gravity:
+    mutual_gravity_lines()
+    sys.exit(0)
 if args.pair_velocities:
     pair_velocities_lines()
     sys.exit(0)
